@@ -25,6 +25,8 @@ Besides the bench line the same JSON carries (skipped with --no-legs):
     launch from two `rocprofv3 --pmc` child passes that run BEFORE this process touches the GPU;
   * `cpu_baseline`: the numpy oracle on the host cores, a pool of worker processes over utterances (N = 1, before the GPU is touched).
 `--workload cfg3 | cfg4 | cfg5` makes that configuration the (only) timed workload of the run.
+`--dump-outputs DIR` writes the waveforms the timed workload computed in its last timed step to DIR/audio.npy (rank 0; the inputs and weights
+are seeded, so two builds run with the same arguments can be compared output for output).
 """
 from __future__ import annotations
 
@@ -213,6 +215,31 @@ def timed_steps(ctx: Ctx, step, steps: int, warmup: int, after_warmup=None) -> f
     return ctx.max_over_ranks(time.perf_counter() - t0)
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs: at most this much array data in all (below 64 MB with the .npy headers)
+
+
+def dump_outputs(dirname: str, arrays) -> dict:
+    """--dump-outputs DIR: write what the timed path returned in its last step as DIR/<name>.npy (float32), outside the timed region.
+    When the arrays hold more than DUMP_BYTES in all, each is replaced by the same seeded sample of its flattened elements (indices drawn
+    with a fixed seed from its size alone, ascending), so two builds run with the same arguments can be compared element for element."""
+    import numpy as np
+
+    host = {n: np.ascontiguousarray(a.detach().float().cpu().numpy() if hasattr(a, "detach") else a, dtype=np.float32) for n, a in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(dirname, exist_ok=True)
+    info = {"dir": os.path.abspath(dirname), "arrays": {}}
+    for name, a in host.items():
+        rec = {"shape": list(a.shape), "dtype": "float32", "sampled": total > DUMP_BYTES}
+        if total > DUMP_BYTES:
+            keep = max(1, a.size * DUMP_BYTES // total)
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, keep))
+            a = a.reshape(-1)[idx]
+            rec.update(sample_seed=0, sample_elements=int(a.size))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        info["arrays"][name] = rec
+    return info
+
+
 def device_identity(device) -> str:
     import torch
 
@@ -293,6 +320,10 @@ def run_cfg2(ctx: Ctx, args, traffic, traffic_note):
 
     elapsed = timed_steps(ctx, step, args.steps, args.warmup, after_warmup=model.check_status)
     assert all(bool(torch.isfinite(a).all()) for a in bufs)
+    dumped = None
+    if args.dump_outputs and ctx.rank == 0:  # the last timed step's waveforms as the caller receives them (N > 1: the global batch collected on rank 0)
+        last = col.recv if col is not None else bufs[(k[0] - 1) % len(bufs)]
+        dumped = dump_outputs(args.dump_outputs, {"audio": last.reshape(B * ctx.world, 75 * t4)})
     step_ms_per_rank = ctx.gather_objects(round(1e3 * ctx.local_elapsed / args.steps, 4)) if hasattr(ctx, "local_elapsed") else None
     collect_ms = col.collect_ms() if col is not None else None
     utts = ctx.world * B * args.steps
@@ -323,6 +354,8 @@ def run_cfg2(ctx: Ctx, args, traffic, traffic_note):
             "ms_per_step_per_rank": step_ms_per_rank,  # every rank's own wall time over the timed steps (value uses the MAX)
         },
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if not args.pmc_child:
         out["roofline"] = roofline_leg(ctx, args, model, lambda: model.frame_path(seg, inp["asr"], inp["pitch"], inp["energy"], inp["style"], inp["prior_noise"],
                                                                                  inp["src_noise"], inp["init_phase"], batch_scope=True, out=audio),
@@ -526,6 +559,9 @@ def run_sharded(ctx: Ctx, args, name: str, steps: int, warmup: int, n_utt: int =
 
     elapsed = timed_steps(ctx, step, steps, warmup, after_warmup=model.check_status)
     assert bool(torch.isfinite(audio).all())
+    dumped = None
+    if args.dump_outputs and ctx.rank == 0 and args.workload == name:  # the timed workload (not a leg): every utterance's waveform, in global order
+        dumped = dump_outputs(args.dump_outputs, {"audio": torch.cat([col.utterance(i) for i in range(n_utt)]) if col is not None else audio})
     rows_all = [sum(frames[i] for i in p) for p in parts]
     audio_seconds = steps * sum(frames) * 75 / SR
     out = {
@@ -547,6 +583,8 @@ def run_sharded(ctx: Ctx, args, name: str, steps: int, warmup: int, n_utt: int =
                             "point-to-point collection of the waveforms on rank 0 per step") if ctx.world > 1 else "single GPU",
         },
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     model.close()
     return out
 
@@ -616,6 +654,9 @@ def run_cfg3(ctx: Ctx, args, steps: int, warmup: int):
         elapsed = ctx.max_over_ranks(time.perf_counter() - t0)
         state["waves"] = outs[-1]
     assert all(bool(torch.isfinite(x).all()) for x in state["waves"])
+    dumped = None
+    if args.dump_outputs and ctx.rank == 0 and args.workload == "cfg3":  # before stage_times() reuses the lanes: rank 0's waveforms, concatenated
+        dumped = dump_outputs(args.dump_outputs, {"audio": torch.cat([x.reshape(-1) for x in state["waves"]])})
     # stage split (one extra call, events on the caller's stream): phoneme-rate part = everything before the frame path
     syn.stage_times(toks, noise)  # (the caller's own lane may not have run yet when the batches went through map()'s lanes: its workspaces are sized by this call)
     t = syn.stage_times(toks, noise)
@@ -647,6 +688,8 @@ def run_cfg3(ctx: Ctx, args, steps: int, warmup: int):
             "stage_note": "one serialised call with events between the stages; in the timed steps the phoneme-rate side streams overlap",
         },
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     eng.close()
     return out
 
@@ -733,7 +776,13 @@ def parse_args(argv=None):
                     help="cfg2 (default, the bench line + legs): 8 x 3 s per GPU, weak scaling; cfg3: the full chain at 64 x 50 tokens per GPU; cfg4 / cfg5: BASELINE's "
                          "sharded configs, one fixed global batch partitioned over the ranks (strong scaling)")
     ap.add_argument("--utterances", type=int, default=0, help="cfg4 / cfg5: override the global batch size (rehearsals on one GPU)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the waveforms the timed workload computed in its last step to DIR/audio.npy (float32; above 60 MB "
+                         "a fixed seeded sample of them); the inputs are seeded, so runs with the same arguments can be compared output for output")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def main():
