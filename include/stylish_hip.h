@@ -74,11 +74,20 @@ int stts_finalize_weights(stts_ctx* ctx, int which);
  * in fp32; norms, gates, style projections, FFTs and every non-contraction kernel stay fp32.
  * The PHONEME-RATE predictors (text encoders, style encoders, duration and pitch / energy predictors) always run in fp32:
  * durations are integers (bit-exact against the fp32 reference in every mode) and those stages are latency-bound.
- * F32, how the fp32 products are formed (round 4): every fp32 operand is the EXACT sum of three bf16 numbers (8 + 8 + 8 significand
- * bits), so x * w is nine bf16 x bf16 products, each exact in fp32; the frame-rate contractions run the six largest on the bf16
- * matrix cores with fp32 accumulation (the three dropped terms are <= 2^-23 |x w|, 2^-27 |x w| rms, zero-mean: below the
- * rounding of the fp32 accumulation that both forms share).  Nothing is rounded to 16 bits: results agree with the
- * f32 matrix cores' to fp32 accumulation noise (tests/test_hip_split_fp32.py measures both against float64).
+ * F32, how the fp32 products are formed (round 4): every finite fp32 operand with |x| >= 2^-110 is the EXACT sum of three bf16 numbers
+ * (8 + 8 + 8 significand bits; from 0x7F7F8000 up the top term is 0x7F7F, not a rounding to Inf), so x * w is nine bf16 x bf16 products,
+ * each exact in fp32; the frame-rate contractions run the six largest on the bf16 matrix cores with fp32 accumulation (the three dropped
+ * terms are <= 2^-23 |x w|, 2^-27 |x w| rms, zero-mean: below the rounding of the fp32 accumulation that both forms share).  Nothing is
+ * rounded to 16 bits: results agree with the f32 matrix cores' to fp32 accumulation noise (tests/test_hip_split_fp32.py,
+ * tests/test_hip_split_fp32_edges.py: one exposed product per output, every tile and variant, against float64).  The domain:
+ *  - |x| < 2^-110: the low terms are bf16 subnormals (step 2^-133), so an operand is off by at most 2^-134 - an absolute error of
+ *    2^-134 |w| per product; v_mfma_f32_32x32x16_bf16 keeps bf16 subnormal inputs (measured: 2^40 * 2^-130 = 2^-90 exactly);
+ *  - +-Inf is split (0, 0, +-Inf): its only nonzero term meets the other operand's top term, so products are IEEE's (+-Inf, NaN for
+ *    Inf * 0) except Inf * Inf (NaN) and Inf times an fp32 subnormal below 2^-134 (its top term is 0: NaN); NaN stays NaN;
+ *  - the Winograd forms (the k = 3 / 7 convs of long calls): a non-finite input turns its whole F(6, k) group of outputs NaN, and the
+ *    transforms can overflow where the direct form would not (inputs near FLT_MAX);
+ *  - pad columns of an activation (channels between the real count and the 32-aligned row width) must hold finite values: they meet
+ *    zero weights, and Inf or NaN times zero is NaN.
  * F32_NATIVE keeps every fp32 contraction on v_mfma_f32_32x32x2_f32 (rounds 1-3; also process-wide with STTS_NO_X3=1). */
 enum { STTS_PREC_F32 = 0, STTS_PREC_BF16 = 1, STTS_PREC_F16 = 2, STTS_PREC_F32_NATIVE = 3 };
 int stts_set_precision(stts_ctx* ctx, int precision);
@@ -267,6 +276,14 @@ int stts_op_mrf_block(stts_ctx* ctx, void* stream, const char* prefix, int n_utt
 /* F.conv1d(stride 1, zero pad (k-1)/2*dil) on time-major rows; w is the reference layout [cout, cin, k] on the HOST. */
 int stts_op_conv1d(void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, const float* x, int ldx, int cin,
                    const float* w_host, const float* bias_host, int cout, int k, int dil, int act, float* y, int ldy, int force_tile, int precision);
+/* The fp32 contraction variants stts_op_conv1d does not reach (precision STTS_PREC_F32 or _F32_NATIVE, no activation):
+ * F.conv1d over the channel concatenation [x, x2] (w [cout, cin + cin2, k]; x2 may be null) as two segments of one launch;
+ * an input affine of x staged with the tile, x' = lrelu_slope(x * scale + shift) with aff_host [n_utt][2][ldx] (scale 0: pad column;
+ * xaff_mode 1 = scale / shift, 2 = the scale-only form: shift 0, slope 1, cin == ldx, no x2; 0 = none, aff_host null);
+ * presplit 1: the activations are split into the three bf16 planes of the split-fp32 form before the contraction (tiles 25 - 28). */
+int stts_op_conv1d_x3(void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, const float* x, int ldx, int cin,
+                      const float* x2, int ldx2, int cin2, const float* w_host, const float* bias_host, int cout, int k, int dil, const float* aff_host,
+                      int xaff_mode, float slope, int presplit, float* y, int ldy, int force_tile, int precision);
 /* AdaptiveDecoderBlock.forward (models/ada_norm.py:166-182) with weights named `prefix` + reference keys. */
 int stts_op_adain_block(stts_ctx* ctx, void* stream, const char* prefix, int n_utt, const int32_t* seg_off_host,
                         const int32_t* seg_off_dev, const float* x, int ldx, int cin, int cout, const float* style, float* y, int ldy,

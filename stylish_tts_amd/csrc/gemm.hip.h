@@ -174,16 +174,29 @@ __device__ __forceinline__ u32x2 pack4_16(const f32x4 v) {
   }
   return r;
 }
-// exact three-term bf16 split of four fp32 values: v = p0 + p1 + p2 (each u32x2 = four bf16 in channel order)
+// exact three-term bf16 split of four fp32 values: v = p0 + p1 + p2 (each u32x2 = four bf16 in channel order).  Exact for every finite
+// |v| >= 2^-110 (below, the low terms run out of bf16 subnormal bits: off by <= 2^-134).  The top term is the RNE bf16 of v clamped to
+// +-0x7F7F7FFF, the largest fp32 whose bf16 is finite: from 0x7F7F8000 up it would round to Inf (remainder -Inf, a NaN split); clamped, the
+// top term is 0x7F7F and the 16 bits below go to the two remainders.  +-Inf is split (0, 0, +-Inf): the infinite term enters only the product
+// x2 w0, so x * w is IEEE's +-Inf whenever the other operand's top term is nonzero and finite (Inf * 0 stays NaN, as in IEEE).  NaN stays NaN.
+// split3_host agrees bit for bit on every non-NaN value (for a NaN it keeps a NaN top term, v_med3_f32 returns -0x7F7F7FFF: NaN either way).
 __device__ __forceinline__ void split3_bf16(const f32x4 v, u32x2& p0, u32x2& p1, u32x2& p2) {
   typedef __bf16 b2 __attribute__((ext_vector_type(2)));
   typedef float f2 __attribute__((ext_vector_type(2)));
   auto pk = [](float a, float b) { const f2 t = {a, b}; return __builtin_bit_cast(unsigned, __builtin_convertvector(t, b2)); };  // v_cvt_pk_bf16_f32 (RNE)
   auto lo = [](unsigned u) { return __uint_as_float(u << 16); };
   auto hi = [](unsigned u) { return __uint_as_float(u & 0xffff0000u); };
-  p0.x = pk(v.x, v.y); p0.y = pk(v.z, v.w);
-  const float r0 = v.x - lo(p0.x), r1 = v.y - hi(p0.x), r2 = v.z - lo(p0.y), r3 = v.w - hi(p0.y);  // exact
-  p1.x = pk(r0, r1); p1.y = pk(r2, r3);
+  const float tmax = __uint_as_float(0x7f7f7fffu);
+  bool inf[4];
+  float f[4];  // v with +-Inf replaced by 0: the upper terms of +-Inf are 0
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    inf[e] = __builtin_isinf(v[e]);                                      // v_cmp_class_f32
+    f[e] = __builtin_amdgcn_fmed3f(inf[e] ? 0.0f : v[e], -tmax, tmax);   // v_cndmask + v_med3_f32
+  }
+  p0.x = pk(f[0], f[1]); p0.y = pk(f[2], f[3]);
+  const float r0 = v.x - lo(p0.x), r1 = v.y - hi(p0.x), r2 = v.z - lo(p0.y), r3 = v.w - hi(p0.y);  // exact (+-Inf: +-Inf)
+  p1.x = pk(inf[0] ? 0.0f : r0, inf[1] ? 0.0f : r1); p1.y = pk(inf[2] ? 0.0f : r2, inf[3] ? 0.0f : r3);
   p2.x = pk(r0 - lo(p1.x), r1 - hi(p1.x)); p2.y = pk(r2 - lo(p1.y), r3 - hi(p1.y));                 // exact remainders, representable in bf16
 }
 template <int PREC>
@@ -1507,6 +1520,7 @@ inline int launch_conv_gemm(hipStream_t st, const GemmArgs& a, int epi, int npad
     }
   }
   STTS_CHECK(!(a.x16 && (tile == 8 || tile == 11 || tile == 13 || a.xaff)), "conv_gemm: 16-bit activation rows need a plain register-staged tile");
+  STTS_CHECK(!(a.xaff && (tile == 11 || tile == 13)), "conv_gemm: the input affine lives on the register staging path (not tiles 11 / 13)");
   STTS_CHECK(!((tile == 14 || tile == 15) && (a.prec == PREC_F32 || epi != EPI_STORE)), "conv_gemm: tiles 14 / 15 are for 16-bit operand store launches");
   STTS_CHECK(!((tile >= 16 && tile <= 18) && (a.prec == PREC_F32 || epi != EPI_STORE || !a.x16)), "conv_gemm: tiles 16 - 18 are for 16-bit activation rows, store epilogue");
   STTS_CHECK((tile != 14 && tile != 16) || npad % 256 == 0, "conv_gemm: tiles 14 / 16 need cout padded to 256");

@@ -279,9 +279,18 @@ inline float bf16_to_f32(unsigned short h) {
   memcpy(&f, &u, 4);
   return f;
 }
-// exact three-term bf16 split of an fp32 value (gemm.hip.h, PREC_X3): f = p0 + p1 + p2, every term the RNE bf16 of what is left
+// exact three-term bf16 split of an fp32 value (gemm.hip.h split3_bf16, PREC_X3): f = p0 + p1 + p2, every term the RNE bf16 of what is left;
+// the top term that of f clamped to +-0x7F7F7FFF (finite from 0x7F7F8000 up, where it would round to Inf); +-Inf is (0, 0, +-Inf); NaN stays NaN
 inline void split3_host(float f, unsigned short* p0, unsigned short* p1, unsigned short* p2) {
-  *p0 = f32_to_bf16(f);
+  if (std::isinf(f)) {
+    *p0 = *p1 = 0;
+    *p2 = f32_to_bf16(f);
+    return;
+  }
+  const unsigned tbits = 0x7f7f7fffu;
+  float tmax;
+  memcpy(&tmax, &tbits, 4);
+  *p0 = f32_to_bf16(f != f ? f : std::fmin(std::fmax(f, -tmax), tmax));
   const float r1 = f - bf16_to_f32(*p0);
   *p1 = f32_to_bf16(r1);
   *p2 = f32_to_bf16(r1 - bf16_to_f32(*p1));

@@ -66,6 +66,73 @@ int stts_op_conv1d(void* stream, int n_utt, const int32_t* seg_off_host, const i
   API_END
 }
 
+// The contraction variants a plain conv does not reach: F.conv1d over the channel concatenation [x, x2] (w [cout, cin + cin2, k]) as two
+// segments of one launch (MSEG), an input affine on x staged with the tile (XAFF: x' = lrelu_slope(x * scale + shift), aff_host
+// [n_utt][2][ldx], scale 0 marks a pad column; xaff_mode 2 = the scale-only instantiation: shift 0, slope 1, cin a multiple of 32, no x2),
+// and activations split into three bf16 planes by launch_split_rows before the contraction (presplit: tiles 25 - 28).
+int stts_op_conv1d_x3(void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, const float* x, int ldx, int cin,
+                      const float* x2, int ldx2, int cin2, const float* w_host, const float* bias_host, int cout, int k, int dil, const float* aff_host,
+                      int xaff_mode, float slope, int presplit, float* y, int ldy, int force_tile, int precision) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(ldx % 32 == 0 && ldx >= cin && (!x2 || (ldx2 % 32 == 0 && ldx2 >= cin2 && cin2 > 0)), "op_conv1d_x3: ldx must be a multiple of 32 covering cin");
+  STTS_CHECK(precision == 0 || precision == 3, "op_conv1d_x3: precision must be STTS_PREC_F32 or _F32_NATIVE");
+  STTS_CHECK(xaff_mode >= 0 && xaff_mode <= 2 && (xaff_mode == 0) == (aff_host == nullptr), "op_conv1d_x3: xaff_mode 1 / 2 need the affine table");
+  STTS_CHECK(xaff_mode != 2 || (!x2 && cin == ldx && slope == 1.0f), "op_conv1d_x3: the scale-only affine is single-segment, cin == ldx, slope 1");
+  STTS_CHECK(!presplit || (precision == 0 && xaff_mode == 0), "op_conv1d_x3: pre-split planes are a split-fp32 form without an input affine");
+  stts_ctx tmp;
+  tmp.prec = 0;
+  tmp.allow_x3 = precision != 3;
+  struct FreeAll {
+    stts_ctx& t;
+    hipStream_t st;
+    ~FreeAll() {
+      (void)hipStreamSynchronize(st);
+      for (void* p : t.allocs) (void)hipFree(p);
+    }
+  } free_all{tmp, st};
+  const int ctot = cin + (x2 ? cin2 : 0);
+  HostTensor w;
+  w.shape = {cout, ctot, k};
+  w.data.assign(w_host, w_host + (size_t)cout * ctot * k);
+  HostTensor b;
+  b.shape = {cout};
+  if (bias_host) b.data.assign(bias_host, bias_host + cout);
+  Seg s{n_utt, seg_off_host, seg_off_dev};
+  PackedConv pc0, pc1;
+  STTS_TRY(pack_rows(&tmp, w, bias_host ? &b : nullptr, plain_rows(cout), 0, cin, round_up(cin, 32), cout, &pc0));
+  if (x2) STTS_TRY(pack_rows(&tmp, w, nullptr, plain_rows(cout), cin, cin2, round_up(cin2, 32), cout, &pc1));
+  GemmArgs a = gemm_args(s);
+  set_seg(a, 0, x, ldx, 0, pc0, (k - 1) / 2, dil);
+  if (x2) set_seg(a, 1, x2, ldx2, 0, pc1, (k - 1) / 2, dil);
+  a.N = cout; a.bias = pc0.bias; a.Y = y; a.ldy = ldy; a.act = 0;
+  if (xaff_mode) {
+    std::vector<float> aff(aff_host, aff_host + (size_t)n_utt * 2 * ldx);
+    float* d = nullptr;
+    STTS_TRY(dev_upload(&tmp, aff, &d));
+    a.xaff = d;
+    a.ld_xaff = ldx;
+    a.xaff_slope = slope;
+    a.xaff_scale_only = xaff_mode == 2;
+  }
+  if (presplit) {  // every segment's rows -> three bf16 planes (pad columns included: they are finite and meet zero weights)
+    for (int i = 0; i < a.nseg; ++i) {
+      const long plane = (long)s.rows() * a.seg[i].ldx;
+      unsigned short* p = nullptr;
+      STTS_HIP(hipMalloc(&p, 3 * plane * sizeof(unsigned short)));
+      tmp.allocs.push_back(p);
+      launch_split_rows(st, a.seg[i].X, a.seg[i].ldx, a.seg[i].ldx, p, a.seg[i].ldx, plane, s.rows());
+      a.seg[i].X = reinterpret_cast<const float*>(p);
+      a.seg[i].x_plane = plane;
+    }
+    a.x16 = 1;
+  }
+  STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, pc0.npad, n_utt, s.max_len(), force_tile));
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
 static int op_scratch(Arena& a, const Seg& s, int kc, int cout, float** act1, float** h, float** act2, float** ss, float** sty, int ld_sty) {
   const long R = s.rows();
   const int n_utt = s.n_utt;

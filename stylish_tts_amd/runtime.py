@@ -227,6 +227,23 @@ class HipModel:
                                            self.PRECISIONS[precision or self.precision]))
         return y
 
+    def op_conv1d_x3(self, seg: Segments, x, cin, w: np.ndarray, bias: Optional[np.ndarray], dil=1, x2=None, cin2=0, aff: Optional[np.ndarray] = None,
+                     xaff_mode=0, slope=1.0, presplit=False, force_tile=0, precision: Optional[str] = None):
+        """stts_op_conv1d_x3: the fp32 contraction with a second input segment x2 (w [cout, cin + cin2, k]), an input affine of x
+        (aff [n_utt, 2, ldx] scale / shift rows, xaff_mode 1 or 2) or pre-split activation planes."""
+        cout, _, k = w.shape
+        ldy = (cout + 31) // 32 * 32
+        y = torch.zeros(seg.rows, ldy, dtype=torch.float32, device=self.device)
+        w = np.ascontiguousarray(w, np.float32)
+        b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+        a = None if aff is None else np.ascontiguousarray(aff, np.float32)
+        _lib.check(self.lib.stts_op_conv1d_x3(_stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(x), x.shape[1], cin,
+                                              None if x2 is None else _ptr(x2), 0 if x2 is None else x2.shape[1], cin2, w.ctypes.data_as(C.c_void_p),
+                                              None if b is None else b.ctypes.data_as(C.c_void_p), cout, k, dil,
+                                              None if a is None else a.ctypes.data_as(C.c_void_p), xaff_mode, slope, int(presplit), _ptr(y), ldy,
+                                              force_tile, self.PRECISIONS[precision or self.precision]))
+        return y
+
     def op_adain_block(self, prefix: str, seg: Segments, x, cin, cout, style):
         y = self._f32(seg.rows, cout)
         ws = self.workspace(seg)
