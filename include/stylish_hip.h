@@ -296,6 +296,15 @@ int stts_op_adain_block(stts_ctx* ctx, void* stream, const char* prefix, int n_u
 int stts_op_attention(void* stream, int n_utt, const int32_t* q_off_host, const int32_t* q_off_dev, const int32_t* k_off_host,
                       const int32_t* k_off_dev, const float* q, const float* k, const float* v, float* o, int heads, int kc,
                       const int32_t* band_centre, int window, int kernel);
+/* The vocoder's STFT / iSTFT at a geometry (n_fft, win, vocoder hop h = hop_length / 4; the rules of stts_finalize_weights) without a model.
+ * Utterance u has seg_off[u+1] - seg_off[u] frames and h samples per frame, packed.  generic 0: the kernels the engine would run (the
+ * specialised ones at 2048 / 1200 / 75), 1: the run-time-geometry kernels always.
+ * stft: sig -> spec = |X|, phase = atan2 [frames, ld] time-major (bins 0 .. n_fft/2, zeros up to ld).
+ * istft: logamp, phase [frames, ld] -> audio = tanh(iSTFT(exp(logamp) e^{i phase})) over frames 0 .. T4 (the last repeats row T4 - 1). */
+int stts_op_stft_geom(void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, int n_fft, int win, int h, const float* sig,
+                      float* spec, float* phase, int ld, int generic);
+int stts_op_istft_geom(void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, int n_fft, int win, int h, const float* logamp,
+                       const float* phase, int ld, float* audio, int generic);
 /* Tuning aid (tools/gemm_bench.py): average time of `iters` back-to-back contraction launches on synthetic data.
  * tile: 0 = the launcher's own choice; tune bits: 128 bf16 operands, 256 fp16 operands; only in a library built with
  * -DSTTS_GEMM_TRACE: 2/4/8/16 K-loop ablations (results invalid, timing only), 64 block-timeline trace. */

@@ -98,6 +98,8 @@ TEST_SIGNATURES = {
     "stts_op_conv1d_x3": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I, C.c_float, _I, _P, _I, _I, _I]),
     "stts_op_adain_block": (_I, [_P, _P, C.c_char_p, _I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _SZ]),
     "stts_op_attention": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I]),
+    "stts_op_stft_geom": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I]),
+    "stts_op_istft_geom": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I]),
 }
 
 _lib = None

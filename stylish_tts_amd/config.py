@@ -14,6 +14,7 @@ import io
 import json
 from typing import Any, Mapping
 
+import numpy as np
 import yaml
 
 
@@ -117,6 +118,31 @@ def validate(cfg: Record) -> Record:
     if cfg.hop_length % 4 != 0:
         raise ValueError("hop_length must be divisible by 4 (vocoder runs at hop/4)")
     return cfg
+
+
+def geometry(cfg) -> tuple:
+    """The vocoder's STFT geometry of a model config: (n_fft, win_length, h, bins, specialised), h = hop_length / 4 the vocoder hop and
+    specialised True for the model.yml default 2048 / 1200 / 300 (the engine's specialised kernels).  Raises ValueError naming the rule a
+    geometry breaks; the engine's finalize applies the same rules (csrc/signal_geom.hip.h: signal_geometry)."""
+    n_fft, win, hop, sr = int(cfg.n_fft), int(cfg.win_length), int(cfg.hop_length), cfg.sample_rate
+    if n_fft <= 0 or n_fft & (n_fft - 1):
+        raise ValueError(f"n_fft {n_fft} is not a power of two")
+    if not 256 <= n_fft <= 4096:
+        raise ValueError(f"n_fft {n_fft} is outside [256, 4096]")
+    if not 1 <= win <= n_fft:
+        raise ValueError(f"win_length {win} is outside [1, n_fft = {n_fft}]")
+    if hop <= 0 or hop % 4:
+        raise ValueError(f"hop_length {hop} is not a positive multiple of 4 (the vocoder runs at hop / 4)")
+    if not sr > 0:
+        raise ValueError(f"sample_rate {sr} is not positive")
+    h, lo = hop // 4, (n_fft - win) // 2
+    # NOLA over one period of the overlap-add envelope, torch.istft's threshold (the window in fp32, as the engine's table)
+    w = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(win) / win)).astype(np.float32).astype(np.float64)
+    env = np.zeros(h)
+    np.add.at(env, (lo + np.arange(win)) % h, w * w)
+    if not env.min() > 1e-11:
+        raise ValueError(f"NOLA: the overlap-add envelope of Hann({win})^2 at hop {h} reaches {env.min():.3g} (must exceed 1e-11)")
+    return n_fft, win, h, n_fft // 2 + 1, (n_fft, win, hop) == (2048, 1200, 300)
 
 
 def load_model_config(src: Any = None) -> Record:

@@ -29,6 +29,7 @@ int stts_ctx_create(const stts_model_dims* dims, int device, stts_ctx** out) {
   stts_ctx* c = new stts_ctx();
   c->d = *dims;
   c->device = device;
+  c->force_generic_signal = getenv("STTS_SIGNAL_GENERIC") && atoi(getenv("STTS_SIGNAL_GENERIC")) != 0;  // comparisons: signal_geom.hip.h kernels at 2048 / 1200 / 300 too
   void* p = nullptr;
   STTS_HIP(hipMalloc(&p, 256));
   STTS_HIP(hipMemset(p, 0, 256));
@@ -128,7 +129,7 @@ int stts_check_status(stts_ctx* c, void* stream) {
     STTS_HIP(hipMemset(c->d_err, 0, sizeof(int)));
     std::string msg;
     if (e & 2) msg += "text encoder: token id outside [0, tokens); ";
-    if (e & 4) msg += "harmonic source: an utterance is too short for the STFT's reflect padding (needs more than " + std::to_string(kNfft / 2) + " samples); ";
+    if (e & 4) msg += "harmonic source: an utterance is too short for the STFT's reflect padding (needs more than " + std::to_string(c->d.n_fft / 2) + " samples); ";
     if (e & 1) msg += "harmonic source: a frame is voiced (f0 > 10 Hz) but no f0 exceeds 20 Hz (reference raises: models/generator.py:285); ";
     if (e & ~7) msg += "unknown device error bits " + std::to_string(e & ~7) + "; ";
     msg.resize(msg.size() - 2);
@@ -141,7 +142,7 @@ int stts_check_status(stts_ctx* c, void* stream) {
 int stts_har_ld(const stts_ctx* c) {
   if (!c) return 0;
   if (c->amp_prior.kc) return har_ld(c);  // the generator is packed: the prior convs' input width
-  return round_up(kBins, c->prec != PREC_F32 ? 64 : 32);  // before: what finalize_frame will pad the bins to in this precision (kc_align)
+  return round_up(c->d.n_fft / 2 + 1, c->prec != PREC_F32 ? 64 : 32);  // before: what finalize_frame will pad the bins to in this precision (kc_align)
 }
 
 size_t stts_frame_workspace_bytes(const stts_ctx* c, int64_t rows, int n_utt, int max_len) { return frame_workspace_bytes(c, rows, n_utt, max_len); }
@@ -181,7 +182,7 @@ int stts_harmonic_stft(stts_ctx* c, void* stream, int n_utt, const int32_t* seg_
                        float* har_phase, int ld_har, void* ws, size_t ws_bytes) {
   API_BEGIN
   SEG_CHECK(STTS_W_GENERATOR);
-  STTS_CHECK(ld_har >= kBins, "ld_har %d < %d", ld_har, kBins);
+  STTS_CHECK(ld_har >= c->geom.bins, "ld_har %d < %d", ld_har, c->geom.bins);
   Arena a(ws, ws_bytes);
   return harmonic_stft(c, st, s, pitch, src_noise, init_phase, batch_scope, prior_signal_out, har_spec, har_phase, ld_har, a);
   API_END
@@ -193,7 +194,7 @@ int stts_vocoder_forward(stts_ctx* c, void* stream, int n_utt, const int32_t* se
   API_BEGIN
   SEG_CHECK(STTS_W_GENERATOR);
   STTS_CHECK(ld_mel % 4 == 0 && ld_har % 32 == 0 && ld_har >= har_ld(c), "har/mel leading dimension: ld_har must be a multiple of 32 covering %d columns (the prior convs' packed input width)", har_ld(c));
-  STTS_CHECK(!logamp_out || ld_lp >= kBins, "ld_lp too small");
+  STTS_CHECK(!logamp_out || ld_lp >= c->geom.bins, "ld_lp too small");
   Arena a(ws, ws_bytes);
   return vocoder_forward(c, st, s, mel, ld_mel, style, har_spec, har_phase, ld_har, audio_out, logamp_out, phase_out, ld_lp, a);
   API_END

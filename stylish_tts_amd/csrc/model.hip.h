@@ -13,6 +13,7 @@
 #include "gemm.hip.h"
 #include "gemm16.hip.h"
 #include "signal.hip.h"
+#include "signal_geom.hip.h"
 #include "phoneme.hip.h"
 #include "wn_layer.hip.h"
 #include "wn_layer_small.hip.h"
@@ -160,6 +161,10 @@ struct stts_ctx {
   bool allow_x3 = true;  // false: STTS_PREC_F32_NATIVE - fp32 contractions on the f32 matrix cores only
   bool pack_x3 = true;  // fp32 mode: pack_rows also writes the three bf16 planes of every weight (split-fp32 contractions, gemm.hip.h PREC_X3); off while the phoneme-rate / CFM models are packed
   int kc_align = 32;  // input channels of a packed conv are padded to this (64 while the frame path is packed for a 16-bit mode: conv_gemm16_kernel's K tile)
+  // STFT geometry of the frame path (set by finalize_frame from d.n_fft / win_length / hop_length); STTS_SIGNAL_GENERIC=1 at context
+  // creation: the run-time-geometry kernels (signal_geom.hip.h) at the default geometry too, for comparisons
+  stts::SignalGeom geom;
+  bool force_generic_signal = false;
   // shared tables
   float* hann = nullptr;      // periodic Hann(win)
   float2* twiddle = nullptr;  // exp(-2 pi i m / n_fft), m < n_fft/2
@@ -605,8 +610,9 @@ inline int pack_wn_fused(stts_ctx* c, const std::string& q, const HostTensor& pm
 // ------------------------------------------------------------------------------------------------
 inline int finalize_frame(stts_ctx* c, int which) {
   const stts_model_dims& d = c->d;
-  STTS_CHECK(d.n_fft == kNfft && d.win_length == kWin && d.hop_length / 4 == kHop && d.sample_rate == 24000,
-             "this build is specialised for n_fft 2048 / win 1200 / hop 300 / 24 kHz (model.yml defaults)");
+  // STFT geometry: 2048 / 1200 / 300 runs the specialised kernels of signal.hip.h, every other supported one those of signal_geom.hip.h
+  STTS_TRY(signal_geometry(d.n_fft, d.win_length, d.hop_length, d.sample_rate, c->force_generic_signal, &c->geom));
+  const SignalGeom& geo = c->geom;
   // channel sizes come from the model config (lib/config_loader.py:369-414); what the kernels need: 16-byte rows and column
   // offsets (multiples of 32 for the concatenated widths) and the generator reading the decoder's width
   STTS_CHECK(d.style_dim > 0 && d.style_dim % 4 == 0 && d.inter_dim > 0 && d.inter_dim % 4 == 0, "style_dim / inter_dim must be multiples of 4");
@@ -625,14 +631,13 @@ inline int finalize_frame(stts_ctx* c, int which) {
   // tables
   c->cur_tag = 0;
   if (!c->hann) {
-    std::vector<float> h(kWin);
-    for (int i = 0; i < kWin; ++i) h[i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * i / kWin));
+    std::vector<float> h;
+    std::vector<double2> tw64;
+    signal_tables(geo.n_fft, geo.win, &h, &tw64);
     STTS_TRY(dev_upload(c, h, &c->hann));
-    std::vector<float2> tw(kNfft / 2);
-    for (int i = 0; i < kNfft / 2; ++i) tw[i] = make_float2((float)cos(2.0 * M_PI * i / kNfft), (float)-sin(2.0 * M_PI * i / kNfft));
+    std::vector<float2> tw(geo.n_fft / 2);
+    for (int i = 0; i < geo.n_fft / 2; ++i) tw[i] = make_float2((float)cos(2.0 * M_PI * i / geo.n_fft), (float)-sin(2.0 * M_PI * i / geo.n_fft));
     STTS_TRY(dev_upload(c, tw, &c->twiddle));
-    std::vector<double2> tw64(kNfft / 2);
-    for (int i = 0; i < kNfft / 2; ++i) tw64[i] = make_double2(cos(2.0 * M_PI * i / kNfft), -sin(2.0 * M_PI * i / kNfft));
     STTS_TRY(dev_upload(c, tw64, &c->twiddle64));
   }
   // decoder (models/decoder.py:6-45)
@@ -712,28 +717,29 @@ inline int finalize_frame(stts_ctx* c, int which) {
     c->gen_style.K = d.style_dim;
     const std::string g = sp + "generator.";
     const int h = d.gen_hidden, hp = h / 2;
-    STTS_TRY(pack_plain(c, g + "amp_prior_conv", true, 0, kBins, &c->amp_prior));
-    STTS_TRY(pack_plain(c, g + "phase_prior_conv", true, 0, kBins, &c->phase_prior));
+    STTS_TRY(pack_plain(c, g + "amp_prior_conv", true, 0, geo.bins, &c->amp_prior));
+    STTS_TRY(pack_plain(c, g + "phase_prior_conv", true, 0, geo.bins, &c->phase_prior));
     for (int q = 0; q < 2; ++q) c->wino_prior[q] = c->wino_out[q] = WinoConv();
     if (c->prec == PREC_F32) {
       for (int q = 0; q < 2; ++q) {
         const std::string nm = g + (q == 0 ? "amp_prior_conv" : "phase_prior_conv");
         HostTensor wq;
         STTS_TRY(get_weight(c, nm, &wq));
-        if (wq.shape[2] == 7) STTS_TRY(pack_winograd(c, wq, find(c, nm + ".bias"), 0, kBins, hp, &c->wino_prior[q]));
+        if (wq.shape[2] == 7) STTS_TRY(pack_winograd(c, wq, find(c, nm + ".bias"), 0, geo.bins, hp, &c->wino_prior[q]));
       }
     }
     STTS_TRY(pack_plain(c, g + "projector", true, 0, d.gen_input, &c->proj_mel));
     STTS_TRY(pack_plain(c, g + "projector", false, d.gen_input, hp, &c->proj_la));
     STTS_TRY(pack_plain(c, g + "projector", false, d.gen_input + hp, hp, &c->proj_ph));
-    // output convs: n_fft/2 + 1 = 8*128 + 1 channels -> GEMM for the first 1024, a dot-product kernel for the last
+    // output convs: n_fft/2 + 1 = 8*128 + 1 channels -> GEMM for the first 1024, a dot-product kernel for the last (other geometries: n_fft/2 =
+    // 128 .. 2048 GEMM channels, the same split)
     for (int which = 0; which < 2; ++which) {
       const std::string nm = g + (which == 0 ? "amp_output_conv" : "phase_output_conv");
       HostTensor w;
       STTS_TRY(get_weight(c, nm, &w));
       STTS_GET(b, nm + ".bias");
-      const int nmain = kBins - 1, ci = (int)w.shape[1], kk = (int)w.shape[2];
-      STTS_CHECK((int)w.shape[0] == kBins && ci == h + hp, "%s: unexpected shape", nm.c_str());
+      const int nmain = geo.bins - 1, ci = (int)w.shape[1], kk = (int)w.shape[2];
+      STTS_CHECK((int)w.shape[0] == geo.bins && ci == h + hp, "%s: unexpected shape", nm.c_str());
       STTS_TRY(pack_rows(c, w, b, plain_rows(nmain), 0, ci, round_up(ci, 32), nmain, which == 0 ? &c->amp_out : &c->phase_out));
       if (c->prec == PREC_F32 && kk == 7) STTS_TRY(pack_winograd(c, w, b, 0, ci, nmain, &c->wino_out[which]));
       std::vector<float> last((size_t)kk * ci);
@@ -1806,14 +1812,22 @@ inline int harmonic_stft(stts_ctx* c, hipStream_t st, const Seg& s, const float*
   const long R = s.rows();
   double* prefix = ws.get<double>(R);
   float* stats = ws.get<float>(2 * s.n_utt);
-  float* sig = prior_out ? prior_out : ws.get<float>(R * kHop);
+  const SignalGeom& g = c->geom;
+  float* sig = prior_out ? prior_out : ws.get<float>(R * g.h);
   STTS_CHECK(ws.ok, "harmonic_stft: workspace too small");
-  STTS_CHECK(ld >= kBins && ld <= 64 * ((kBins + 63) / 64), "harmonic_stft: row stride %d outside [%d, %d]", ld, kBins, 64 * ((kBins + 63) / 64));
+  if (g.generic) STTS_CHECK(ld >= g.bins, "harmonic_stft: row stride %d < %d bins", ld, g.bins);
+  else STTS_CHECK(ld >= kBins && ld <= 64 * ((kBins + 63) / 64), "harmonic_stft: row stride %d outside [%d, %d]", ld, kBins, 64 * ((kBins + 63) / 64));
   STTS_DRY_RETURN(ws);
   if (!s.cap)  // (capacity segments: pcph_kernel checks the real lengths and raises the device error word 4)
     for (int u = 0; u < s.n_utt; ++u)
-      STTS_CHECK((long)(s.host[u + 1] - s.host[u]) * kHop > kNfft / 2, "utterance %d too short for reflect padding (%d frames; need > %d samples)", u,
-                 s.host[u + 1] - s.host[u], kNfft / 2);
+      STTS_CHECK((long)(s.host[u + 1] - s.host[u]) * g.h > g.n_fft / 2, "utterance %d too short for reflect padding (%d frames; need > %d samples)", u,
+                 s.host[u + 1] - s.host[u], g.n_fft / 2);
+  if (g.generic) {
+    STTS_TRY(launch_pcph_geom(st, g, s.n_utt, s.dev, R, s.max_len(), pitch, noise, init_phase, batch_scope, prefix, stats, sig, c->d_err));
+    STTS_TRY(launch_stft_geom(st, g, s.n_utt, s.dev, R, s.max_len(), sig, c->hann, c->twiddle64, har_spec, har_phase, ld, out16));
+    STTS_HIP(hipGetLastError());
+    return 0;
+  }
   STTS_LAUNCH_PROF("pcph_prep_kernel", (size_t)R * 12, pcph_prep_kernel, dim3(s.n_utt), dim3(256), st, pitch, s.dev, prefix, stats);
   STTS_LAUNCH_PROF("pcph_kernel", (size_t)R * kHop * 8, pcph_kernel, dim3(std::min(1024, ceil_div(s.max_len() * kHop, 256)), s.n_utt), dim3(256), st, pitch, s.dev, s.n_utt,
                      prefix, stats, noise, init_phase, batch_scope, sig, c->d_err);
@@ -1850,7 +1864,7 @@ inline int prior_conv(stts_ctx* c, hipStream_t st, const Seg& s, int which, cons
   a.N = hp; a.bias = w.bias;
   if (vocoder_rows16(c, s.rows())) {
     STTS_CHECK((har16 || har_is16) && ld_har % 8 == 0, "prior_conv: 16-bit mode needs the rounded-copy scratch");
-    if (!har_is16) launch_cast_rows(st, c->prec, har, ld_har, kBins, har16, ld_har, s.rows());
+    if (!har_is16) launch_cast_rows(st, c->prec, har, ld_har, c->geom.bins, har16, ld_har, s.rows());
     a.seg[0].X = har_is16 ? har : reinterpret_cast<const float*>(har16);
     a.x16 = 1;
     a.Y = nullptr; a.Y16 = reinterpret_cast<unsigned short*>(head); a.ldy16 = hc; a.ycol16 = h;
@@ -1868,7 +1882,8 @@ inline int vocoder_body(stts_ctx* c, hipStream_t st, const Seg& s, const float* 
   const stts_model_dims& d = c->d;
   const long R = s.rows();
   const int h = d.gen_hidden, hp = h / 2, hc = h + hp, inter = d.gen_inter, ml = s.max_len();
-  const int ldlp = round_up(kBins, 32);
+  const SignalGeom& geo = c->geom;
+  const int ldlp = round_up(geo.bins, 32);
   float* xa = ws.get<float>(R * h);
   float* xb = ws.get<float>(R * h);
   float* dw = ws.get<float>(R * h);
@@ -1889,7 +1904,7 @@ inline int vocoder_body(stts_ctx* c, hipStream_t st, const Seg& s, const float* 
   //  than the staging they save)
   const int p16 = (c->prec != PREC_F32 && vocoder_rows16(c, R)) ? c->prec : 0;
   unsigned short* mel16 = (p16 && !mel16_in) ? ws.get<unsigned short>(R * round_up(d.gen_input, 32)) : nullptr;
-  float* yw = ws.get<float>((R + s.n_utt) * kWin);
+  float* yw = ws.get<float>((R + s.n_utt) * geo.win);
   WinoScratch wino;
   if (c->wino_out[0].ready && c->wino_out[1].ready) wino.p = ws.get<float>(wino_scratch_floats(s, c->wino_out[0]));
   STTS_CHECK(ws.ok, "vocoder: workspace too small");
@@ -1976,13 +1991,13 @@ inline int vocoder_body(stts_ctx* c, hipStream_t st, const Seg& s, const float* 
     GemmArgs a = gemm_args(s);
     set_seg(a, 0, headA, hc, 0, c->amp_out);
     a.x16 = p16 != 0;
-    a.N = kBins - 1; a.bias = c->amp_out.bias; a.Y = la; a.ldy = ldl;
+    a.N = geo.bins - 1; a.bias = c->amp_out.bias; a.Y = la; a.ldy = ldl;
     if (wino) STTS_TRY(run_winograd(st, s, headA, hc, c->wino_out[0], la, ldl, ACT_NONE, nullptr, 0, 1.0f, wino));
     else STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, c->amp_out.npad, s.n_utt, ml));
     GemmArgs b = gemm_args(s);
     set_seg(b, 0, headP, hc, 0, c->phase_out);
     b.x16 = p16 != 0;
-    b.N = kBins - 1; b.bias = c->phase_out.bias; b.Y = ph; b.ldy = ldl;
+    b.N = geo.bins - 1; b.bias = c->phase_out.bias; b.Y = ph; b.ldy = ldl;
     if (wino) STTS_TRY(run_winograd(st, s, headP, hc, c->wino_out[1], ph, ldl, ACT_NONE, nullptr, 0, 1.0f, wino));
     else STTS_TRY(launch_conv_gemm(st, b, EPI_STORE, c->phase_out.npad, s.n_utt, ml));
     const int kk = c->amp_out.ntaps;
@@ -1990,9 +2005,14 @@ inline int vocoder_body(stts_ctx* c, hipStream_t st, const Seg& s, const float* 
     const ChanConvSet sa{headA, c->nyq_w[0], c->nyq_b[0], la}, sp{headP, c->nyq_w[1], c->nyq_b[1], ph};
     const dim3 cg((unsigned)ceil_div(ml, 4 * kChanRows), 2, s.n_utt);
     const size_t cb = (size_t)2 * R * (hc * (p16 ? 2 : 4) + 4);
-    if (p16 == PREC_BF16) STTS_LAUNCH_PROF("single_channel_conv_kernel", cb, single_channel_conv_kernel<PREC_BF16>, cg, dim3(256), st, sa, sp, hc, hc, s.dev, kk, ldl, kBins - 1);
-    else if (p16 == PREC_F16) STTS_LAUNCH_PROF("single_channel_conv_kernel", cb, single_channel_conv_kernel<PREC_F16>, cg, dim3(256), st, sa, sp, hc, hc, s.dev, kk, ldl, kBins - 1);
-    else STTS_LAUNCH_PROF("single_channel_conv_kernel", cb, single_channel_conv_kernel<0>, cg, dim3(256), st, sa, sp, hc, hc, s.dev, kk, ldl, kBins - 1);
+    if (p16 == PREC_BF16) STTS_LAUNCH_PROF("single_channel_conv_kernel", cb, single_channel_conv_kernel<PREC_BF16>, cg, dim3(256), st, sa, sp, hc, hc, s.dev, kk, ldl, geo.bins - 1);
+    else if (p16 == PREC_F16) STTS_LAUNCH_PROF("single_channel_conv_kernel", cb, single_channel_conv_kernel<PREC_F16>, cg, dim3(256), st, sa, sp, hc, hc, s.dev, kk, ldl, geo.bins - 1);
+    else STTS_LAUNCH_PROF("single_channel_conv_kernel", cb, single_channel_conv_kernel<0>, cg, dim3(256), st, sa, sp, hc, hc, s.dev, kk, ldl, geo.bins - 1);
+  }
+  if (geo.generic) {
+    STTS_TRY(launch_istft_geom(st, geo, s.n_utt, s.dev, R, ml, la, ph, ldl, c->hann, c->twiddle64, yw, audio));
+    STTS_HIP(hipGetLastError());
+    return 0;
   }
   STTS_LAUNCH_PROF("istft_frames_kernel", (size_t)R * 2 * kBins * 4, istft_frames_kernel, dim3((ml + 1 + kFftWaves - 1) / kFftWaves, s.n_utt), dim3(64 * kFftWaves), st, la, ph, ldl, s.dev, c->hann, c->twiddle64, yw);
   STTS_LAUNCH_PROF("istft_ola_kernel", (size_t)R * kHop * 4, istft_ola_kernel, dim3(std::min(1024, ceil_div(ml * kHop, 256)), s.n_utt), dim3(256), st, yw, s.dev, c->hann, audio);
@@ -2024,7 +2044,7 @@ inline int vocoder_forward(stts_ctx* c, hipStream_t st, const Seg& s, const floa
 }
 
 // row stride of the harmonic spectra: the prior convs' packed input width (1056; 1088 in the 16-bit modes)
-inline int har_ld(const stts_ctx* c) { return std::max(round_up(kBins, 32), c->amp_prior.kc); }
+inline int har_ld(const stts_ctx* c) { return std::max(round_up(c->d.n_fft / 2 + 1, 32), c->amp_prior.kc); }
 
 inline int frame_path(stts_ctx* c, hipStream_t st, const Seg& s, const float* asr, int ld_asr, const float* pitch, const float* energy,
                       const float* style, const float* prior_noise, const float* src_noise, const float* init_phase, int batch_scope,
@@ -2040,7 +2060,7 @@ inline int frame_path(stts_ctx* c, hipStream_t st, const Seg& s, const float* as
   float* headP = top.get<float>(R * hc);
   const int ldm16 = round_up(c->d.gen_input, 32);
   unsigned short* mel16 = (c->prec != PREC_F32 && vocoder_rows16(c, R) && c->d.gen_input == dh) ? top.get<unsigned short>(R * ldm16) : nullptr;
-  const size_t side_bytes = (size_t)R * (sizeof(double) + kHop * sizeof(float)) + 4096 + 8 * s.n_utt;
+  const size_t side_bytes = (size_t)R * (sizeof(double) + c->geom.h * sizeof(float)) + 4096 + 8 * s.n_utt;
   const size_t side_off = top.used;
   char* side_ws = top.get<char>(side_bytes);
   // (side stream, below: the prior convs then need scratch of their own - the decoder uses the stage region at the same time)

@@ -182,6 +182,79 @@ int stts_op_attention(void* stream, int n_utt, const int32_t* q_off_host, const 
   API_END
 }
 
+// The vocoder's STFT / iSTFT kernels at a geometry (n_fft, win, hop 4h) without a model: the launches of harmonic_stft / vocoder_body, with
+// this geometry's tables.  generic 0: the kernels the engine picks (signal.hip.h at 2048 / 1200 / 300), 1: signal_geom.hip.h always.
+struct GeomOpTables {
+  stts_ctx tmp;  // only for allocation bookkeeping
+  hipStream_t st;
+  SignalGeom g;
+  float* hann = nullptr;
+  double2* tw64 = nullptr;
+  explicit GeomOpTables(hipStream_t s) : st(s) {}
+  int init(int n_fft, int win, int h, int generic) {
+    STTS_TRY(signal_geometry(n_fft, win, 4 * h, 24000, generic != 0, &g));
+    std::vector<float> hw;
+    std::vector<double2> tw;
+    signal_tables(n_fft, win, &hw, &tw);
+    STTS_TRY(dev_upload(&tmp, hw, &hann));
+    STTS_TRY(dev_upload(&tmp, tw, &tw64));
+    return 0;
+  }
+  ~GeomOpTables() {  // every exit path waits for the stream and frees the temporaries
+    (void)hipStreamSynchronize(st);
+    for (void* p : tmp.allocs) (void)hipFree(p);
+  }
+};
+
+int stts_op_stft_geom(void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, int n_fft, int win, int h, const float* sig,
+                      float* spec, float* phase, int ld, int generic) {
+  API_BEGIN
+  STTS_CHECK(n_utt > 0 && seg_off_host && seg_off_dev && sig && spec && phase, "null / empty argument");
+  hipStream_t st = (hipStream_t)stream;
+  GeomOpTables t(st);
+  STTS_TRY(t.init(n_fft, win, h, generic));
+  const SignalGeom& g = t.g;
+  Seg s{n_utt, seg_off_host, seg_off_dev};
+  for (int u = 0; u < n_utt; ++u)
+    STTS_CHECK((long)(seg_off_host[u + 1] - seg_off_host[u]) * h > n_fft / 2, "op_stft_geom: utterance %d too short for reflect padding", u);
+  if (g.generic) {
+    STTS_CHECK(ld >= g.bins, "op_stft_geom: ld %d < %d bins", ld, g.bins);
+    STTS_TRY(launch_stft_geom(st, g, n_utt, seg_off_dev, s.rows(), s.max_len(), sig, t.hann, t.tw64, spec, phase, ld, 0));
+  } else {
+    STTS_CHECK(ld >= kBins && ld <= 64 * ((kBins + 63) / 64), "op_stft_geom: ld %d outside [%d, %d]", ld, kBins, 64 * ((kBins + 63) / 64));
+    hipLaunchKernelGGL(stft_kernel, dim3(ceil_div(s.max_len(), kFftWaves), n_utt), dim3(64 * kFftWaves), 0, st, sig, seg_off_dev, t.hann, t.tw64, spec, phase, ld, 0);
+  }
+  STTS_HIP(hipGetLastError());
+  return 0;
+  API_END
+}
+
+// logamp / phase [frames, ld] (bins 0 .. n_fft/2) -> audio, h samples per frame (tanh of the normalised overlap-add, as the vocoder)
+int stts_op_istft_geom(void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, int n_fft, int win, int h, const float* logamp,
+                       const float* phase, int ld, float* audio, int generic) {
+  API_BEGIN
+  STTS_CHECK(n_utt > 0 && seg_off_host && seg_off_dev && logamp && phase && audio, "null / empty argument");
+  hipStream_t st = (hipStream_t)stream;
+  GeomOpTables t(st);
+  STTS_TRY(t.init(n_fft, win, h, generic));
+  const SignalGeom& g = t.g;
+  STTS_CHECK(ld >= g.bins, "op_istft_geom: ld %d < %d bins", ld, g.bins);
+  Seg s{n_utt, seg_off_host, seg_off_dev};
+  float* yw = nullptr;
+  STTS_HIP(hipMalloc(&yw, (size_t)(s.rows() + n_utt) * g.win * sizeof(float)));
+  t.tmp.allocs.push_back(yw);
+  if (g.generic) {
+    STTS_TRY(launch_istft_geom(st, g, n_utt, seg_off_dev, s.rows(), s.max_len(), logamp, phase, ld, t.hann, t.tw64, yw, audio));
+  } else {
+    const int ml = s.max_len();
+    hipLaunchKernelGGL(istft_frames_kernel, dim3(ceil_div(ml + 1, kFftWaves), n_utt), dim3(64 * kFftWaves), 0, st, logamp, phase, ld, seg_off_dev, t.hann, t.tw64, yw);
+    hipLaunchKernelGGL(istft_ola_kernel, dim3(std::min(1024, ceil_div(ml * kHop, 256)), n_utt), dim3(256), 0, st, yw, seg_off_dev, t.hann, audio);
+  }
+  STTS_HIP(hipGetLastError());
+  return 0;
+  API_END
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ kernel microbench

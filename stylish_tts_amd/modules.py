@@ -164,9 +164,9 @@ def _durations_from_alignment(alignment: torch.Tensor, lengths, dev):
     return dur, T
 
 
-def draw_noise(B: int, T4: int, dev, flow_dim: int = 128):
-    """The reference's three draws (models/flow.py:314; models/generator.py:272,306) with torch's generator."""
-    return dict(prior_noise=torch.randn(B, flow_dim, T4, device=dev), src_noise=torch.randn(B, 1, 75 * T4, device=dev),
+def draw_noise(B: int, T4: int, dev, flow_dim: int = 128, h: int = 75):
+    """The reference's three draws (models/flow.py:314; models/generator.py:272,306) with torch's generator; h = hop_length / 4."""
+    return dict(prior_noise=torch.randn(B, flow_dim, T4, device=dev), src_noise=torch.randn(B, 1, h * T4, device=dev),
                 init_phase=torch.rand(1, 1, device=dev))
 
 
@@ -307,18 +307,19 @@ class Generator(HipModule):
         cfg = cfg or load_model_config()
         super().__init__(params.generator_spec("", cfg), cfg, engine)
         self.n_bins = n_fft // 2 + 1
+        self.hop4 = hop_length // 4
 
     def forward(self, *, mel, style, pitch, energy=None, noise=None):
         eng = self.engine
         B, _, T4 = mel.shape
         seg = Segments([T4] * B, eng.device)
-        nz = noise or draw_noise(B, T4, eng.device)
+        nz = noise or draw_noise(B, T4, eng.device, h=self.hop4)
         spec, phase = eng.harmonic_stft(seg, _f(pitch, eng.device).reshape(-1), _f(torch.as_tensor(nz["src_noise"]), eng.device).reshape(-1),
                                         _f(torch.as_tensor(nz["init_phase"]), eng.device).reshape(-1), batch_scope=True)
         audio, la, ph = eng.vocoder(seg, eng.to_time_major(_f(mel, eng.device)), _f(style, eng.device), spec, phase, return_spec=True)
         eng.check_status()
         rep = lambda t: torch.cat([t, t[:, :, -1:]], dim=2)  # F.pad(..., mode="replicate") (generator.py:425-426)  # noqa: E731
-        return DecoderPrediction(audio=audio.reshape(B, 1, 75 * T4), magnitude=rep(eng.to_channel_major(la, B, self.n_bins, T4)),
+        return DecoderPrediction(audio=audio.reshape(B, 1, self.hop4 * T4), magnitude=rep(eng.to_channel_major(la, B, self.n_bins, T4)),
                                  phase=rep(eng.to_channel_major(ph, B, self.n_bins, T4)))
 
 
@@ -344,11 +345,12 @@ class SpeechPredictor(HipModule):
         pk = lambda t: torch.cat([_f(t, eng.device)[b, : T[b]] for b in range(B)])  # noqa: E731
         p4, e4 = eng.upsample4(st, st4, pk(pitch)), eng.upsample4(st, st4, pk(energy))
         equal = len(set(T)) == 1
-        nz = noise or draw_noise(B, 4 * max(T), eng.device)
+        h, nb = self.cfg.hop_length // 4, self.cfg.n_fft // 2 + 1
+        nz = noise or draw_noise(B, 4 * max(T), eng.device, h=h)
         pn = _f(torch.as_tensor(nz["prior_noise"]), eng.device)
         sn = _f(torch.as_tensor(nz["src_noise"]), eng.device)
         pn_tm = torch.cat([pn[b, :, : 4 * T[b]].t() for b in range(B)]).contiguous()
-        sn_flat = torch.cat([sn[b, 0, : 300 * T[b]] for b in range(B)]).contiguous()
+        sn_flat = torch.cat([sn[b, 0, : 4 * h * T[b]] for b in range(B)]).contiguous()
         ip = _f(torch.as_tensor(nz["init_phase"]), eng.device).reshape(-1)
         x = eng.decoder(st4, asr, p4, e4, style)
         mel = eng.prior_flow(st4, x, style, pn_tm)
@@ -358,9 +360,9 @@ class SpeechPredictor(HipModule):
         if equal:
             T4 = 4 * T[0]
             rep = lambda t: torch.cat([t, t[:, :, -1:]], dim=2)  # noqa: E731
-            return DecoderPrediction(audio=audio.reshape(B, 1, 75 * T4), magnitude=rep(eng.to_channel_major(la, B, 1025, T4)),
-                                     phase=rep(eng.to_channel_major(ph, B, 1025, T4)))
-        return DecoderPrediction(audio=[audio[75 * st4.host[b] : 75 * st4.host[b + 1]] for b in range(B)], magnitude=None, phase=None)
+            return DecoderPrediction(audio=audio.reshape(B, 1, h * T4), magnitude=rep(eng.to_channel_major(la, B, nb, T4)),
+                                     phase=rep(eng.to_channel_major(ph, B, nb, T4)))
+        return DecoderPrediction(audio=[audio[h * st4.host[b] : h * st4.host[b + 1]] for b in range(B)], magnitude=None, phase=None)
 
 
 class STFT(torch.nn.Module):

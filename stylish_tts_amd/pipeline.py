@@ -170,7 +170,7 @@ class Synthesizer:
         # 4. frame path.  Explicit noise is indexed by the REAL packed rows (as the outputs are): only its first rows are read.
         R = st4.rows
         if noise is None:
-            noise = dict(prior_noise=torch.randn(R, 128, device=dev), src_noise=torch.randn(R * 75, device=dev),
+            noise = dict(prior_noise=torch.randn(R, 128, device=dev), src_noise=torch.randn(R * eng.hop4, device=dev),
                          init_phase=torch.rand(1, device=dev))
         if ev:
             ev[1].record(main)
@@ -194,7 +194,7 @@ class Synthesizer:
         if self._adapt:
             want = 1.25 * max(t / max(n, 1) for t, n in zip(T, L))
             self._ratio = min(float(self.MAX_FRAMES_PER_TOKEN), max(self._ratio, 2.0 * float(np.ceil(want / 2.0))))
-        off = np.concatenate([[0], np.cumsum(T)]) * (4 * 75)
+        off = np.concatenate([[0], np.cumsum(T)]) * (4 * eng.hop4)  # hop_length samples per mel frame
         waves = [audio[int(off[i]) : int(off[i + 1])] for i in range(len(L))]
         if return_details:
             Tm = int(sum(T))

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import load_model_config
+from .config import geometry, load_model_config
 
 N_BINS_LD = 1056  # 1025 bins padded to a multiple of 32 floats (spectrum rows of an fp32 engine; HipModel.har_ld is the engine's own stride)
 
@@ -84,6 +84,10 @@ class HipModel:
             raise RuntimeError("HipModel needs a GPU (MI355X); there is no CPU fallback in the product path")
         self.lib = _lib.load()
         self.cfg = cfg if cfg is not None else load_model_config()
+        # STFT geometry (ValueError naming the broken rule before any device work): h = vocoder hop (samples per row of the frame path),
+        # n_bins = n_fft / 2 + 1, ld_lp = the row stride of logamp / phase outputs (N_BINS_LD at the default geometry)
+        self.n_fft, self.win_length, self.hop4, self.n_bins, _ = geometry(self.cfg)
+        self.ld_lp = (self.n_bins + 31) // 32 * 32
         self.device = torch.device("cuda", device)
         self._dims = _lib.dims_from_config(self.cfg)
         h = C.c_void_p()
@@ -178,7 +182,7 @@ class HipModel:
     def harmonic_stft(self, seg: Segments, pitch, src_noise, init_phase, batch_scope=True, return_signal=False):
         spec = self._f32(seg.rows, self.har_ld)
         phase = self._f32(seg.rows, self.har_ld)
-        sig = self._f32(seg.rows * 75) if return_signal else None
+        sig = self._f32(seg.rows * self.hop4) if return_signal else None
         ws = self.workspace(seg)
         _lib.check(self.lib.stts_harmonic_stft(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(pitch), _ptr(src_noise),
                                                _ptr(init_phase), int(batch_scope), _ptr(sig), _ptr(spec), _ptr(phase), self.har_ld, _ptr(ws),
@@ -186,17 +190,17 @@ class HipModel:
         return (spec, phase, sig) if return_signal else (spec, phase)
 
     def vocoder(self, seg: Segments, mel, style, har_spec, har_phase, return_spec=False):
-        audio = self._f32(seg.rows * 75)
-        la = self._f32(seg.rows, N_BINS_LD) if return_spec else None
-        ph = self._f32(seg.rows, N_BINS_LD) if return_spec else None
+        audio = self._f32(seg.rows * self.hop4)
+        la = self._f32(seg.rows, self.ld_lp) if return_spec else None
+        ph = self._f32(seg.rows, self.ld_lp) if return_spec else None
         ws = self.workspace(seg)
         _lib.check(self.lib.stts_vocoder_forward(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(mel), mel.shape[1], _ptr(style),
-                                                 _ptr(har_spec), _ptr(har_phase), har_spec.shape[1], _ptr(audio), _ptr(la), _ptr(ph), N_BINS_LD,
+                                                 _ptr(har_spec), _ptr(har_phase), har_spec.shape[1], _ptr(audio), _ptr(la), _ptr(ph), self.ld_lp,
                                                  _ptr(ws), ws.numel()))
         return (audio, la, ph) if return_spec else audio
 
     def frame_path(self, seg: Segments, asr, pitch, energy, style, prior_noise, src_noise, init_phase, batch_scope=True, out=None):
-        audio = out if out is not None else self._f32(seg.rows * 75)
+        audio = out if out is not None else self._f32(seg.rows * self.hop4)
         ws = self.workspace(seg)
         _lib.check(self.lib.stts_frame_path(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(asr), asr.shape[1], _ptr(pitch),
                                             _ptr(energy), _ptr(style), _ptr(prior_noise), _ptr(src_noise), _ptr(init_phase), int(batch_scope),
@@ -264,6 +268,22 @@ class HipModel:
         _lib.check(self.lib.stts_op_mrf_block(self.ctx, _stream(), prefix.encode(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(x), x.shape[1], channels,
                                               kernel, _ptr(style), _ptr(y), channels, _ptr(ws), ws.numel()))
         return y
+
+    # ------------------------------------------------------------------ vocoder STFT kernels at any geometry (test surface)
+    def op_stft_geom(self, seg: Segments, sig: torch.Tensor, n_fft: int, win: int, h: int, generic: bool = True):
+        """sig: packed samples, h per row -> spec, phase [rows, round_up(n_fft/2 + 1, 32)] (stts_op_stft_geom)."""
+        ld = (n_fft // 2 + 1 + 31) // 32 * 32
+        spec, phase = self._f32(seg.rows, ld), self._f32(seg.rows, ld)
+        _lib.check(self.lib.stts_op_stft_geom(_stream(), seg.n, seg.host_ptr, _ptr(seg.dev), n_fft, win, h, _ptr(sig), _ptr(spec), _ptr(phase), ld,
+                                              int(generic)))
+        return spec, phase
+
+    def op_istft_geom(self, seg: Segments, logamp: torch.Tensor, phase: torch.Tensor, n_fft: int, win: int, h: int, generic: bool = True):
+        """logamp, phase [rows, ld] -> audio [rows * h] (stts_op_istft_geom: tanh of the iSTFT with the replicated last frame)."""
+        audio = self._f32(seg.rows * h)
+        _lib.check(self.lib.stts_op_istft_geom(_stream(), seg.n, seg.host_ptr, _ptr(seg.dev), n_fft, win, h, _ptr(logamp), _ptr(phase), logamp.shape[1],
+                                               _ptr(audio), int(generic)))
+        return audio
 
     # ------------------------------------------------------------------ conv-form STFT of the ONNX export (models/stft.py)
     def conv_stft_transform(self, seg_frames: Segments, wave: torch.Tensor, hop: int):
