@@ -63,7 +63,9 @@ enum {
   STTS_W_PITCH_ENERGY = 128, /* pitch_energy_predictor.*                                   models/pitch_energy_predictor.py */
   STTS_W_FRAME_PATH = 7,
   STTS_W_ALL = 255,
-  STTS_W_CFM = 256           /* cfm_mel_decoder.* (finalized by stts_cfm_finalize, not part of STTS_W_ALL)  models/cfm/cfm_mel_decoder.py */
+  STTS_W_CFM = 256,          /* cfm_mel_decoder.* (finalized by stts_cfm_finalize, not part of STTS_W_ALL)  models/cfm/cfm_mel_decoder.py */
+  STTS_W_HUBERT = 512,       /* hubert_speech_predictor.{phone_encoder, style_encoder} (not part of STTS_W_ALL) models/speech_predictor.py:132-148 */
+  STTS_W_HUBERT_PE = 1024    /* hubert_pitch_energy_predictor.* (not part of STTS_W_ALL)   models/pitch_energy_predictor.py:124-191 */
 };
 int stts_finalize_weights(stts_ctx* ctx, int which);
 /* Operand precision of the FRAME-RATE Conv1d / Linear contractions (call before the first stts_finalize_weights).
@@ -234,6 +236,32 @@ int stts_cfm_estimator(stts_ctx* ctx, void* stream, int n_utt, const int32_t* se
                        const float* asr, int ld_asr, const float* f0, const float* n_curve, const int32_t* curve_off_host,
                        const int32_t* curve_off_dev, const float* spk_emb, const float* t, const float* sine_noise, float* out, int ld_out,
                        void* workspace, size_t workspace_bytes);
+
+/* ---- HuBERT voice conversion (the reference's hubert_acoustic models, train/stage_type.py:907-1015).  Inputs are HuBERT features at the
+ * mel-frame rate as packed time-major rows feats [rows_T, ld_feats] (ld_feats a multiple of 4 covering hubert.hidden_dim padded to 32, pad
+ * columns finite) with off_T[n_utt+1] row offsets, and wespeaker embeddings spk_emb [n_utt, ld >= speaker_embedder.hidden_dim].  The HuBERT
+ * and speaker widths are taken from the weights (phone_emb / phone_quant, style_encoder.0).  Statistics are per utterance over its own
+ * frames (the reference at B = 1).  These stages always run fp32, whatever stts_set_precision chose; the frame path that follows
+ * (stts_frame_path, on the hubert_speech_predictor's decoder .. generator weights loaded under "speech_predictor.") follows it. */
+size_t stts_hubert_workspace_bytes(const stts_ctx* ctx, int64_t rows_T, int n_utt, int max_len);
+/* Speaker styles: hubert_speech_predictor.style_encoder (Linear -> Mish -> Linear -> Mish -> Linear, models/speech_predictor.py:137-147,
+ * dropout = identity) -> style_out [n_utt, 64], and hubert_pitch_energy_predictor.style_encoder (one Linear, models/pitch_energy_predictor.py:139)
+ * -> pe_style_out [n_utt, 64].  Either output may be null (its component need not be finalized).  An utterance's rows are the same bit
+ * for bit alone and in any batch (fixed-order split-K sums, no atomics). */
+int stts_speaker_style(stts_ctx* ctx, void* stream, int n_utt, const float* spk_emb, int ld, float* style_out, float* pe_style_out, void* ws,
+                       size_t ws_bytes);
+/* HubertEncoder.forward with input_cond_dim=None (models/hubert_encoder.py:36-47, called at models/speech_predictor.py:211-213):
+ * phone_emb (1x1) at T rows, repeat_interleave(4) (the two commute), the transformer Encoder (models/text_encoder.py:332-393) at 4T rows
+ * masked by 4 x lengths.  feats (offsets off_T) -> asr_out [4 rows_T, ld_asr >= inter_dim] = the decoder input of stts_frame_path
+ * (offsets 4 x off_T).  Heads of 16 / 32 / 40 / 64 / 96 / 128 / 160 channels take any length; others at most 1024 positions (4T). */
+int stts_hubert_encoder_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_T_host, const int32_t* off_T_dev, const float* feats,
+                                int ld_feats, float* asr_out, int ld_asr, void* ws, size_t ws_bytes);
+/* HubertPitchEnergyPredictor.forward (models/pitch_energy_predictor.py:176-191): phone_quant (1x1), ProsodyEncoder (3 layers), two chains of
+ * 3 AdaptiveDecoderBlocks + 1x1 projections.  feats, pe_style [n_utt, 64] (stts_speaker_style) -> f0_out, energy_out [rows_T]; optional
+ * prosody_tap [rows_T, inter_dim + style_dim]. */
+int stts_hubert_pitch_energy_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_T_host, const int32_t* off_T_dev, const float* feats,
+                                     int ld_feats, const float* pe_style, float* f0_out, float* energy_out, float* prosody_tap, void* ws,
+                                     size_t ws_bytes);
 
 /* Layout bridge for the nn.Module shims: reference [B, C, T] (equal T) <-> time-major rows. */
 int stts_to_time_major(void* stream, const float* x_bct, int B, int C, int T, float* y, int ldy);

@@ -79,6 +79,10 @@ SIGNATURES = {
     "stts_set_precision": (_I, [_P, _I]),
     "stts_upsample4": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     "stts_euler_step": (_I, [_P, _P, _P, C.c_float, C.c_int64]),
+    "stts_hubert_workspace_bytes": (_SZ, [_P, C.c_int64, _I, _I]),
+    "stts_speaker_style": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _SZ]),
+    "stts_hubert_encoder_forward": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _SZ]),
+    "stts_hubert_pitch_energy_forward": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ]),
     "stts_cfm_finalize": (_I, [_P, _P]),
     "stts_cfm_workspace_bytes": (_SZ, [_P, _I64, _I]),
     "stts_cfm_estimator": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _SZ]),

@@ -145,6 +145,27 @@ def geometry(cfg) -> tuple:
     return n_fft, win, h, n_fft // 2 + 1, (n_fft, win, hop) == (2048, 1200, 300)
 
 
+def hubert_dims(cfg) -> tuple:
+    """(hubert.hidden_dim, speaker_embedder.hidden_dim): the feature widths of the voice-conversion models (models/models.py:92-101,
+    models/hubert_encoder.py:9-11).  Raises ValueError naming a missing or non-positive width."""
+    out = []
+    for section in ("hubert", "speaker_embedder"):
+        node = cfg.get(section)
+        v = node.get("hidden_dim") if node is not None else None
+        if v is None:
+            raise ValueError(f"model config: missing key '{section}.hidden_dim'")
+        if isinstance(v, bool) or int(v) != v or int(v) <= 0:
+            raise ValueError(f"{section}.hidden_dim {v} is not a positive integer")
+        out.append(int(v))
+    return tuple(out)
+
+
+def check_width(what: str, got: int, key: str, expected: int) -> None:
+    """ValueError naming the width when an input's feature width is not the configured one."""
+    if int(got) != int(expected):
+        raise ValueError(f"{what} has width {int(got)}; {key} is {int(expected)}")
+
+
 def load_model_config(src: Any = None) -> Record:
     """Accepts None (reference default), a path, an open file, a YAML/JSON string or a dict."""
     if src is None:

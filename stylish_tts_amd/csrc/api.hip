@@ -2,6 +2,7 @@
 // (which includes every kernel header) into libstylish_hip.so for gfx950.
 #include "model.hip.h"
 #include "cfm.hip.h"
+#include "hubert.hip.h"
 
 using namespace stts;
 
@@ -113,6 +114,19 @@ int stts_finalize_weights(stts_ctx* c, int which) {
     c->prec = saved_prec;
     STTS_TRY(rc);
     c->ready |= ph;
+  }
+  const int hb = which & (STTS_W_HUBERT | STTS_W_HUBERT_PE);
+  if (hb) {
+    if (!c->hubert) c->hubert = std::make_shared<HubertModel>();
+    // fp32 on the f32 matrix cores whatever the precision, as the phoneme-rate predictors above
+    const int saved_prec = c->prec;
+    c->prec = PREC_F32;
+    c->pack_x3 = false;
+    const int rc = finalize_hubert(c, static_cast<HubertModel*>(c->hubert.get()), hb);
+    c->pack_x3 = true;
+    c->prec = saved_prec;
+    STTS_TRY(rc);
+    c->ready |= hb;
   }
   STTS_HIP(hipDeviceSynchronize());
   return 0;
@@ -545,6 +559,57 @@ int stts_profile_report(void* stream, char* json, size_t cap) {
   STTS_CHECK(out.size() + 1 <= cap, "profile report needs %zu bytes", out.size() + 1);
   memcpy(json, out.c_str(), out.size() + 1);
   return 0;
+  API_END
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ HuBERT voice conversion (hubert.hip.h)
+extern "C" {
+
+#define HB_CHECK(mask)                                                               \
+  STTS_CHECK(c && c->hubert && (c->ready & (mask)) == (mask), "weights for this stage are not finalized (need components 0x%x, have 0x%x)", (mask), c ? c->ready : 0); \
+  STTS_HIP(hipSetDevice(c->device));                                                 \
+  HubertModel& H = *static_cast<HubertModel*>(c->hubert.get());                      \
+  hipStream_t st = (hipStream_t)stream
+
+size_t stts_hubert_workspace_bytes(const stts_ctx* c, int64_t rows_T, int n_utt, int max_len) { return c ? hubert_workspace_bytes(c, rows_T, n_utt, max_len) : 0; }
+
+int stts_speaker_style(stts_ctx* c, void* stream, int n_utt, const float* spk_emb, int ld, float* style_out, float* pe_style_out, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  HB_CHECK((style_out ? STTS_W_HUBERT : 0) | (pe_style_out ? STTS_W_HUBERT_PE : 0));
+  STTS_CHECK(n_utt > 0 && spk_emb, "speaker_style: bad argument");
+  Arena a(ws, ws_bytes);
+  return speaker_style(c, H, st, n_utt, spk_emb, ld, style_out, pe_style_out, a);
+  API_END
+}
+
+int stts_hubert_encoder_forward(stts_ctx* c, void* stream, int n_utt, const int32_t* off_T_host, const int32_t* off_T_dev, const float* feats, int ld_feats,
+                                float* asr_out, int ld_asr, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  HB_CHECK(STTS_W_HUBERT);
+  STTS_TRY(seg_ok(n_utt, off_T_host, off_T_dev));
+  STTS_CHECK(feats && asr_out, "hubert_encoder: null argument");
+  STTS_CHECK(ld_feats >= round_up(H.sp.hubert_dim, 32) && ld_feats % 4 == 0, "feature rows: ld_feats %d must be a multiple of 4 covering %d columns (hubert.hidden_dim %d padded to 32)",
+             ld_feats, round_up(H.sp.hubert_dim, 32), H.sp.hubert_dim);
+  STTS_CHECK(ld_asr >= H.sp.enc.C, "ld_asr too small");
+  Seg s{n_utt, off_T_host, off_T_dev};
+  Arena a(ws, ws_bytes);
+  return hubert_encoder_forward(c, H, st, s, feats, ld_feats, asr_out, ld_asr, a);
+  API_END
+}
+
+int stts_hubert_pitch_energy_forward(stts_ctx* c, void* stream, int n_utt, const int32_t* off_T_host, const int32_t* off_T_dev, const float* feats, int ld_feats,
+                                     const float* pe_style, float* f0_out, float* energy_out, float* prosody_tap, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  HB_CHECK(STTS_W_HUBERT_PE);
+  STTS_TRY(seg_ok(n_utt, off_T_host, off_T_dev));
+  STTS_CHECK(feats && pe_style && f0_out && energy_out, "hubert_pitch_energy: null argument");
+  STTS_CHECK(ld_feats >= round_up(H.pe.hubert_dim, 32) && ld_feats % 4 == 0, "feature rows: ld_feats %d must be a multiple of 4 covering %d columns (hubert.hidden_dim %d padded to 32)",
+             ld_feats, round_up(H.pe.hubert_dim, 32), H.pe.hubert_dim);
+  Seg s{n_utt, off_T_host, off_T_dev};
+  Arena a(ws, ws_bytes);
+  return hubert_pitch_energy_forward(c, H, st, s, feats, ld_feats, pe_style, f0_out, energy_out, prosody_tap, a);
   API_END
 }
 

@@ -95,6 +95,24 @@ inline int pack_stacked(stts_ctx* c, const std::vector<std::string>& names, Pack
   return pack_rows(c, w, &b, plain_rows((int)w.shape[0]), 0, cin, round_up(cin, 32), (int)w.shape[0], out);
 }
 
+// the transformer Encoder's layers (models/text_encoder.py:332-393) under prefix p (".../encoder."); W->C, heads, n_layers, filter set
+inline int pack_encoder_layers(stts_ctx* c, const std::string& p, TextEncW* W) {
+  for (int i = 0; i < W->n_layers; ++i) {
+    const std::string a = p + "attn_layers." + std::to_string(i) + ".";
+    const std::string f = p + "ffn_layers." + std::to_string(i) + ".";
+    TextEncW::Layer& L = W->layer[i];
+    STTS_TRY(pack_stacked(c, {a + "conv_q", a + "conv_k", a + "conv_v"}, &L.qkv));
+    STTS_TRY(pack_plain(c, a + "conv_o", true, 0, W->C, &L.o));
+    STTS_TRY(pack_plain(c, f + "conv_1", true, 0, W->C, &L.f1));
+    STTS_TRY(pack_plain(c, f + "conv_2", true, 0, W->filter, &L.f2));
+    STTS_TRY(upload_vec(c, p + "norm_layers_1." + std::to_string(i) + ".gamma", &L.g1));
+    STTS_TRY(upload_vec(c, p + "norm_layers_1." + std::to_string(i) + ".beta", &L.b1));
+    STTS_TRY(upload_vec(c, p + "norm_layers_2." + std::to_string(i) + ".gamma", &L.g2));
+    STTS_TRY(upload_vec(c, p + "norm_layers_2." + std::to_string(i) + ".beta", &L.b2));
+  }
+  return 0;
+}
+
 inline int pack_text_encoder(stts_ctx* c, const std::string& p, int inter, TextEncW* W) {
   const stts_model_dims& d = c->d;
   W->C = d.te_hidden; W->inter = inter; W->heads = d.te_heads; W->n_layers = d.te_layers; W->ffk = d.te_kernel; W->filter = d.te_filter;
@@ -108,19 +126,7 @@ inline int pack_text_encoder(stts_ctx* c, const std::string& p, int inter, TextE
     STTS_TRY(upload_vec(c, p + "prenet.norm_layers." + si + ".beta", &W->pre_b[i]));
   }
   STTS_TRY(pack_plain(c, p + "prenet.proj", true, 0, W->C, &W->pre_proj));
-  for (int i = 0; i < W->n_layers; ++i) {
-    const std::string a = p + "encoder.attn_layers." + std::to_string(i) + ".";
-    const std::string f = p + "encoder.ffn_layers." + std::to_string(i) + ".";
-    TextEncW::Layer& L = W->layer[i];
-    STTS_TRY(pack_stacked(c, {a + "conv_q", a + "conv_k", a + "conv_v"}, &L.qkv));
-    STTS_TRY(pack_plain(c, a + "conv_o", true, 0, W->C, &L.o));
-    STTS_TRY(pack_plain(c, f + "conv_1", true, 0, W->C, &L.f1));
-    STTS_TRY(pack_plain(c, f + "conv_2", true, 0, W->filter, &L.f2));
-    STTS_TRY(upload_vec(c, p + "encoder.norm_layers_1." + std::to_string(i) + ".gamma", &L.g1));
-    STTS_TRY(upload_vec(c, p + "encoder.norm_layers_1." + std::to_string(i) + ".beta", &L.b1));
-    STTS_TRY(upload_vec(c, p + "encoder.norm_layers_2." + std::to_string(i) + ".gamma", &L.g2));
-    STTS_TRY(upload_vec(c, p + "encoder.norm_layers_2." + std::to_string(i) + ".beta", &L.b2));
-  }
+  STTS_TRY(pack_encoder_layers(c, p + "encoder.", W));
   STTS_TRY(pack_plain(c, p + "proj_m", true, 0, W->C, &W->proj_m));
   W->ready = true;
   return 0;
@@ -321,6 +327,24 @@ inline void run_rope(hipStream_t st, const Seg& s, float* X, int ldx, int col0, 
                      ldx, col0, col1, heads, kc, d, s.dev);
 }
 
+// ------------------------------------------------------------------------------------------------ Encoder.forward (the layer loop)
+// models/text_encoder.py:375-393 in place on x [rows, C]; scratch t [rows, C], qkv [rows, 3C], att [rows, C], ff [rows, filter].
+// Shared by TextEncoder (after its embedding and prenet) and HubertEncoder (after phone_emb, at 4 rows per feature frame).
+inline int encoder_layers_forward(hipStream_t st, const TextEncW& W, const Seg& s, float* x, float* t, float* qkv, float* att, float* ff) {
+  const int C = W.C;
+  const int kc = C / W.heads;
+  for (int i = 0; i < W.n_layers; ++i) {
+    const TextEncW::Layer& L = W.layer[i];
+    STTS_TRY(gemm_store(st, s, x, C, 0, L.qkv, qkv, 3 * C, 0));
+    run_rope(st, s, qkv, 3 * C, 0, W.heads, kc, C);  // q and k blocks of the fused q|k|v buffer
+    STTS_TRY(run_attention(st, s, s, qkv, 3 * C, 0, qkv, 3 * C, C, qkv, 3 * C, 2 * C, att, C, W.heads, kc, nullptr, 0));
+    STTS_TRY(gemm_ln(st, s, att, C, L.o, t, C, x, C, C, 1e-4f, 0, nullptr, LnOut{x, C, 0, L.g1, L.b1, 0, 0}, ACT_NONE));
+    STTS_TRY(gemm_store(st, s, x, C, 0, L.f1, ff, W.filter, 0, ACT_RELU));
+    STTS_TRY(gemm_ln(st, s, ff, W.filter, L.f2, t, C, x, C, C, 1e-4f, 0, nullptr, LnOut{x, C, 0, L.g2, L.b2, 0, 0}, ACT_NONE));
+  }
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ TextEncoder.forward
 // tokens [rows] int64 -> mu [rows, inter] (proj_m output), optional x [rows, C] (last hidden layer).
 inline int text_encoder_forward(stts_ctx* c, hipStream_t st, const TextEncW& W, const Seg& s, const long* tokens, float* mu, int ld_mu, float* x_out,
@@ -344,16 +368,7 @@ inline int text_encoder_forward(stts_ctx* c, hipStream_t st, const TextEncW& W, 
   }
   STTS_TRY(gemm_store(st, s, h, C, 0, W.pre_proj, t, C, 0, ACT_NONE, x, C));
   std::swap(x, t);  // x = x_org + proj(h)
-  const int kc = C / W.heads;
-  for (int i = 0; i < W.n_layers; ++i) {
-    const TextEncW::Layer& L = W.layer[i];
-    STTS_TRY(gemm_store(st, s, x, C, 0, L.qkv, qkv, 3 * C, 0));
-    run_rope(st, s, qkv, 3 * C, 0, W.heads, kc, C);  // q and k blocks of the fused q|k|v buffer
-    STTS_TRY(run_attention(st, s, s, qkv, 3 * C, 0, qkv, 3 * C, C, qkv, 3 * C, 2 * C, att, C, W.heads, kc, nullptr, 0));
-    STTS_TRY(gemm_ln(st, s, att, C, L.o, t, C, x, C, C, 1e-4f, 0, nullptr, LnOut{x, C, 0, L.g1, L.b1, 0, 0}, ACT_NONE));
-    STTS_TRY(gemm_store(st, s, x, C, 0, L.f1, ff, W.filter, 0, ACT_RELU));
-    STTS_TRY(gemm_ln(st, s, ff, W.filter, L.f2, t, C, x, C, C, 1e-4f, 0, nullptr, LnOut{x, C, 0, L.g2, L.b2, 0, 0}, ACT_NONE));
-  }
+  STTS_TRY(encoder_layers_forward(st, W, s, x, t, qkv, att, ff));
   if (x_out) STTS_HIP(hipMemcpyAsync(x_out, x, R * C * sizeof(float), hipMemcpyDeviceToDevice, st));
   STTS_TRY(gemm_store(st, s, x, C, 0, W.proj_m, mu, ld_mu, 0));
   return 0;

@@ -11,6 +11,8 @@ Reference classes mirrored (paths relative to /root/reference/src/stylish_tts/tr
   Generator              models/generator.py:340-438
   SpeechPredictor        models/speech_predictor.py:13-129
   ExportModel            models/export_model.py:5-45
+  HubertSpeechPredictor       models/speech_predictor.py:132-251
+  HubertPitchEnergyPredictor  models/pitch_energy_predictor.py:124-191
 
 Differences, all additive: forward() of the stochastic modules takes an optional ``noise`` dict with the three draws
 the reference takes from the global torch generator (``prior_noise`` [B,128,4T], ``src_noise`` [B,1,300T],
@@ -27,10 +29,11 @@ import numpy as np
 import torch
 
 from . import params
-from .config import Record, load_model_config
+from .config import Record, check_width, hubert_dims, load_model_config
 from .runtime import HipModel, Segments
 
 W_DECODER, W_FLOW, W_GENERATOR, W_SPEECH_TEXT, W_DURATION, W_PE_TEXT, W_PE_STYLE, W_PITCH_ENERGY = 1, 2, 4, 8, 16, 32, 64, 128
+W_HUBERT, W_HUBERT_PE = 512, 1024  # hubert_speech_predictor.{phone_encoder, style_encoder}; hubert_pitch_energy_predictor.*
 
 _ENGINES: Dict[int, HipModel] = {}
 
@@ -118,13 +121,17 @@ class HipModule(torch.nn.Module):
         each component last, and a shim whose weights are not the packed ones re-binds before it runs."""
         eng = self._engine
         owners = eng.__dict__.setdefault("_owners", {})
-        bits = [1 << i for i in range(8) if self.components >> i & 1]
+        bits = [1 << i for i in range(self.components.bit_length()) if self.components >> i & 1]
         if self._dirty or any(owners.get(b) is not self for b in bits):
-            eng.load_state_dict(self.module_name, self._store, prefix=self.key_prefix)
+            self._load_into(eng)
             eng.finalize(self.components)  # releases the previous packing of these components (stts_finalize_weights)
             for b in bits:
                 owners[b] = self
             self._dirty = False
+
+
+    def _load_into(self, eng: HipModel):
+        eng.load_state_dict(self.module_name, self._store, prefix=self.key_prefix)
 
 
 # ------------------------------------------------------------------------------------------------ helpers
@@ -427,8 +434,114 @@ class ExportModel(torch.nn.Module):
         return prediction.audio.reshape(-1)
 
 
-def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int] = None):
-    """The five modules of the inference composition (models/models.py:32-63, :79-101), optionally with synthetic weights."""
+def _hubert_cfg(cfg, hubert_dim: int, spk_dim: int):
+    c2 = Record(cfg)
+    c2["hubert"] = Record(dict(cfg.get("hubert") or {}, hidden_dim=hubert_dim))
+    c2["speaker_embedder"] = Record(dict(cfg.get("speaker_embedder") or {}, hidden_dim=spk_dim))
+    hubert_dims(c2)
+    return c2
+
+
+def _pack_curve(x: torch.Tensor, L, dev) -> torch.Tensor:
+    x = _f(torch.as_tensor(x), dev)
+    return torch.cat([x[b, : L[b]] for b in range(len(L))]).contiguous()
+
+
+def _unpack_curve(x: torch.Tensor, seg: Segments, P: int, equal: bool):
+    if equal:
+        return x.reshape(seg.n, P)
+    return [x[seg.host[b] : seg.host[b + 1]] for b in range(seg.n)]
+
+
+def _check_feats(cfg, phones: torch.Tensor, spk_emb: torch.Tensor, hubert_dim: int, spk_dim: int):
+    if phones.dim() != 3:
+        raise ValueError(f"HuBERT features must be [B, {hubert_dim}, T], got shape {tuple(phones.shape)}")
+    check_width("HuBERT features", phones.shape[1], "hubert.hidden_dim", hubert_dim)
+    if spk_emb.dim() != 2:
+        raise ValueError(f"speaker embeddings must be [B, {spk_dim}], got shape {tuple(spk_emb.shape)}")
+    check_width("speaker embedding", spk_emb.shape[1], "speaker_embedder.hidden_dim", spk_dim)
+    if spk_emb.shape[0] != phones.shape[0]:
+        raise ValueError(f"{spk_emb.shape[0]} speaker embeddings for {phones.shape[0]} utterances")
+
+
+class HubertPitchEnergyPredictor(HipModule):
+    """models/pitch_energy_predictor.py:124-191: HuBERT features [B, hubert_dim, T] + speaker embedding [B, spk_dim] -> F0, N [B, T]
+    (ragged lengths: lists of [T_b]).  Statistics per utterance over its own frames (the reference at B = 1)."""
+
+    module_name, components = "hubert_pitch_energy_predictor", W_HUBERT_PE
+
+    def __init__(self, hubert_dim, spk_dim, style_dim, inter_dim, style_config, pitch_energy_config, cfg=None, engine=None):
+        cfg = _hubert_cfg(cfg or load_model_config(), hubert_dim, spk_dim)
+        if style_dim != cfg.style_dim or inter_dim != cfg.inter_dim:
+            raise ValueError(f"style_dim / inter_dim ({style_dim}, {inter_dim}) must be the model config's ({cfg.style_dim}, {cfg.inter_dim})")
+        super().__init__(params.hubert_pitch_energy_predictor_spec(cfg), cfg, engine)
+        self.hubert_dim, self.spk_dim = int(hubert_dim), int(spk_dim)
+
+    def forward(self, phones, phone_lengths, spk_emb):
+        _check_feats(self.cfg, phones, spk_emb, self.hubert_dim, self.spk_dim)
+        eng = self.engine
+        L = [int(v) for v in torch.as_tensor(phone_lengths).tolist()]
+        seg = Segments(L, eng.device)
+        _, pe_style = eng.speaker_style(_f(spk_emb, eng.device), style=False)
+        f0, en = eng.hubert_pitch_energy(seg, _pack_rows(eng, phones, L), pe_style)
+        equal = len(set(L)) == 1 and L[0] == phones.shape[2]
+        return _unpack_curve(f0, seg, L[0], equal), _unpack_curve(en, seg, L[0], equal)
+
+
+class HubertSpeechPredictor(HipModule):
+    """models/speech_predictor.py:132-251 (inference: audio_gt=None).  The phone_encoder and style_encoder are this module's own
+    component (W_HUBERT); its decoder, prior_encoder, flow, post_flow and generator run on the engine's frame path, whose weights are
+    re-bound from this module whenever another shim (SpeechPredictor, Decoder, Generator) packed them last."""
+
+    module_name, components = "hubert_speech_predictor", W_DECODER | W_FLOW | W_GENERATOR | W_HUBERT
+    _OWN = ("phone_encoder.", "style_encoder.")
+
+    def __init__(self, model_config=None, engine=None):
+        cfg = model_config if model_config is not None else load_model_config()
+        self.hubert_dim, self.spk_dim = hubert_dims(cfg)
+        super().__init__(params.hubert_speech_predictor_spec(cfg), cfg, engine)
+
+    def _load_into(self, eng: HipModel):
+        own = OrderedDict((k, v) for k, v in self._store.items() if k.startswith(self._OWN))
+        frame = OrderedDict((k, v) for k, v in self._store.items() if not k.startswith(self._OWN))
+        eng.load_state_dict(self.module_name, own)
+        eng.load_state_dict("speech_predictor", frame)  # the names the frame path is packed from (include/stylish_hip.h, STTS_W_DECODER..)
+
+    def forward(self, phones, phone_lengths, spk_emb, pitch, energy, audio_gt=None, noise=None):
+        if audio_gt is not None:
+            raise NotImplementedError("audio_gt (posterior encoder, training only: speech_predictor.py:225-232) is outside the inference hot path")
+        _check_feats(self.cfg, phones, spk_emb, self.hubert_dim, self.spk_dim)
+        eng = self.engine
+        L = [int(v) for v in torch.as_tensor(phone_lengths).tolist()]
+        B = len(L)
+        st = Segments(L, eng.device)
+        st4 = st.scaled(4)
+        asr = eng.hubert_encoder(st, _pack_rows(eng, phones, L))
+        style, _ = eng.speaker_style(_f(spk_emb, eng.device), pe_style=False)
+        p4, e4 = eng.upsample4(st, st4, _pack_curve(pitch, L, eng.device)), eng.upsample4(st, st4, _pack_curve(energy, L, eng.device))
+        h, nb = self.cfg.hop_length // 4, self.cfg.n_fft // 2 + 1
+        nz = noise or draw_noise(B, 4 * max(L), eng.device, flow_dim=self.cfg.decoder.hidden_dim // 4, h=h)
+        pn = _f(torch.as_tensor(nz["prior_noise"]), eng.device)
+        sn = _f(torch.as_tensor(nz["src_noise"]), eng.device)
+        pn_tm = torch.cat([pn[b, :, : 4 * L[b]].t() for b in range(B)]).contiguous()
+        sn_flat = torch.cat([sn[b, 0, : 4 * h * L[b]] for b in range(B)]).contiguous()
+        ip = _f(torch.as_tensor(nz["init_phase"]), eng.device).reshape(-1)
+        x = eng.decoder(st4, asr, p4, e4, style)
+        mel = eng.prior_flow(st4, x, style, pn_tm)
+        spec, phase = eng.harmonic_stft(st4, p4, sn_flat, ip, batch_scope=True)
+        audio, la, ph = eng.vocoder(st4, mel, style, spec, phase, return_spec=True)
+        eng.check_status()
+        if len(set(L)) == 1 and L[0] == phones.shape[2]:
+            T4 = 4 * L[0]
+            rep = lambda t: torch.cat([t, t[:, :, -1:]], dim=2)  # noqa: E731
+            return DecoderPrediction(audio=audio.reshape(B, 1, h * T4), magnitude=rep(eng.to_channel_major(la, B, nb, T4)),
+                                     phase=rep(eng.to_channel_major(ph, B, nb, T4)))
+        return DecoderPrediction(audio=[audio[h * st4.host[b] : h * st4.host[b + 1]] for b in range(B)], magnitude=None, phase=None)
+
+
+def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int] = None, hubert: bool = False):
+    """The five modules of the inference composition (models/models.py:32-63, :79-101), optionally with synthetic weights.
+    hubert=True adds the voice-conversion pair hubert_speech_predictor / hubert_pitch_energy_predictor (models/models.py:92-101)."""
     cfg = cfg or load_model_config()
     m = dict(
         speech_predictor=SpeechPredictor(cfg, engine=engine),
@@ -439,6 +552,11 @@ def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int]
         pe_text_encoder=TextEncoder(inter_dim=cfg.pitch_energy_predictor.inter_dim, config=cfg.text_encoder, cfg=cfg, engine=engine),
         pe_text_style_encoder=TextStyleEncoder(cfg.pitch_energy_predictor.inter_dim, cfg.style_dim, cfg.style_encoder, cfg=cfg, engine=engine),
     )
+    if hubert:
+        hd, sd = hubert_dims(cfg)
+        m["hubert_speech_predictor"] = HubertSpeechPredictor(cfg, engine=engine)
+        m["hubert_pitch_energy_predictor"] = HubertPitchEnergyPredictor(hd, sd, cfg.style_dim, cfg.inter_dim, cfg.style_encoder, cfg.pitch_energy_predictor,
+                                                                        cfg=cfg, engine=engine)
     if synthetic_seed is not None:
         for mod in m.values():
             mod.load_synthetic(synthetic_seed)

@@ -250,6 +250,56 @@ def speech_predictor_spec(cfg) -> Spec:
     return s
 
 
+def encoder_spec(p: str, c: int, filter_channels: int, kernel_size: int, n: int) -> Spec:
+    """The transformer Encoder (models/text_encoder.py:332-393), registration order."""
+    s: Spec = []
+    for i in range(n):
+        s += _attn(p + f"attn_layers.{i}.", c)
+    for i in range(n):
+        s += [(p + f"norm_layers_1.{i}.gamma", (c,), "ln_g"), (p + f"norm_layers_1.{i}.beta", (c,), "ln_b")]
+    for i in range(n):
+        s += _conv(p + f"ffn_layers.{i}.conv_1", filter_channels, c, kernel_size)
+        s += _conv(p + f"ffn_layers.{i}.conv_2", c, filter_channels, kernel_size)
+    for i in range(n):
+        s += [(p + f"norm_layers_2.{i}.gamma", (c,), "ln_g"), (p + f"norm_layers_2.{i}.beta", (c,), "ln_b")]
+    return s
+
+
+def hubert_speech_predictor_spec(cfg) -> Spec:
+    """HubertSpeechPredictor (models/speech_predictor.py:132-201) minus the training-only posterior encoder.  Its phone_encoder is
+    HubertEncoder without input_cond_dim (models/hubert_encoder.py:7-34): phone_emb + Encoder at inter_dim channels."""
+    hid = cfg.decoder.hidden_dim
+    fh = hid // 4
+    te, sd = cfg.text_encoder, cfg.style_dim
+    s: Spec = _conv("phone_encoder.phone_emb", cfg.inter_dim, cfg.hubert.hidden_dim, 1)
+    s += encoder_spec("phone_encoder.encoder.", cfg.inter_dim, te.filter_channels, te.kernel_size, te.layers)
+    s += _linear("style_encoder.0", 4 * sd, cfg.speaker_embedder.hidden_dim)
+    s += _linear("style_encoder.3", 2 * sd, 4 * sd)
+    s += _linear("style_encoder.6", sd, 2 * sd)
+    s += decoder_spec("decoder.", cfg.inter_dim, sd, hid, cfg.decoder.residual_dim)
+    s += [("prior_encoder.proj_mean.weight", (fh, hid), "w"), ("prior_encoder.proj_mean.bias", (fh,), "b")]
+    s += [("prior_encoder.proj_logstd.weight", (fh, hid), "w_tiny"), ("prior_encoder.proj_logstd.bias", (fh,), "b")]
+    s += flow_spec("flow.", fh, fh, 5, 4, 8, sd)
+    s += _linear("post_flow", hid, fh)
+    s += generator_spec("generator.", cfg)
+    return s
+
+
+def hubert_pitch_energy_predictor_spec(cfg) -> Spec:
+    """HubertPitchEnergyPredictor (models/pitch_energy_predictor.py:124-174), as build_model constructs it (models/models.py:94-101)."""
+    inter, st = cfg.inter_dim, cfg.style_dim
+    c = inter + st
+    s: Spec = _conv("phone_quant", inter, cfg.hubert.hidden_dim, 1)
+    s += _linear("style_encoder", st, cfg.speaker_embedder.hidden_dim)
+    s += prosody_encoder_spec("prosody_encoder.", st, inter, 3)
+    for br in ("F0", "N"):
+        for i in range(3):
+            s += adaptive_decoder_block_spec(f"{br}.{i}", c, c, st)
+    s += [("F0_proj.weight", (1, c, 1), "w_f0"), ("F0_proj.bias", (1,), "b_f0")]
+    s += [("N_proj.weight", (1, c, 1), "w"), ("N_proj.bias", (1,), "b")]
+    return s
+
+
 def adaptive_generator_block_spec(p: str, channels: int, k: int, style: int) -> Spec:
     """AdaptiveGeneratorBlock (MRF + Snake; models/ada_norm.py:11-120).  Not executed by any
     runnable reference path; inventoried for the standalone block only."""
@@ -272,6 +322,12 @@ MODULE_SPECS = {
     "pitch_energy_predictor": pitch_energy_predictor_spec,
     "pe_text_encoder": lambda cfg: text_encoder_spec("", cfg, cfg.pitch_energy_predictor.inter_dim),
     "pe_text_style_encoder": lambda cfg: text_style_encoder_spec("", cfg, cfg.pitch_energy_predictor.inter_dim),
+}
+
+# the voice-conversion models (models/models.py:92-101): known to module_spec, kept out of MODULE_SPECS (the text-to-speech composition)
+HUBERT_MODULE_SPECS = {
+    "hubert_speech_predictor": hubert_speech_predictor_spec,
+    "hubert_pitch_energy_predictor": hubert_pitch_energy_predictor_spec,
 }
 
 
@@ -326,7 +382,7 @@ def cfm_mel_decoder_spec(dims=None) -> Spec:
 
 
 def module_spec(module: str, cfg) -> Spec:
-    return MODULE_SPECS[module](cfg)
+    return (MODULE_SPECS[module] if module in MODULE_SPECS else HUBERT_MODULE_SPECS[module])(cfg)
 
 
 # ----------------------------------------------------------------------------

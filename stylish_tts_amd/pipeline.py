@@ -200,3 +200,75 @@ class Synthesizer:
             Tm = int(sum(T))
             return waves, dict(durations=dur, frames=T, pitch=f0[:Tm], energy=en[:Tm], style=style, capacities=list(caps))
         return waves
+
+
+class VoiceConverter:
+    """The reference's voice-conversion path (the hubert_acoustic models, train/stage_type.py:907-1015) on one engine: HuBERT features of
+    the source speech + a wespeaker embedding of the target speaker -> waveforms.  HubertPitchEnergyPredictor predicts F0 / energy from
+    the features and the target embedding (unless the caller gives them), then HubertSpeechPredictor renders the features with that
+    prosody in the target's style.
+
+    The engine must hold the weights of both models: hubert_speech_predictor.{phone_encoder, style_encoder} and
+    hubert_pitch_energy_predictor.* finalized as STTS_W_HUBERT | STTS_W_HUBERT_PE, and the hubert_speech_predictor's decoder .. generator
+    as the frame path (``modules.HubertSpeechPredictor`` binds them; pass the shims as ``modules`` to have them re-bound before each call).
+    One packed ragged batch per call; the frame counts are known up front, so nothing is read back by the host before the audio."""
+
+    host_syncs_per_call = 0  # reads of device data by the host between the pitch predictor and the frame path
+
+    def __init__(self, engine: HipModel, modules: Sequence[torch.nn.Module] = ()):
+        from .config import hubert_dims
+
+        self.eng = engine
+        self.cfg = engine.cfg
+        self.hubert_dim, self.spk_dim = hubert_dims(self.cfg)
+        self._modules = list(modules)
+
+    @torch.no_grad()
+    def convert(self, features, lengths, spk_emb, pitch=None, energy=None, noise: Optional[Dict[str, torch.Tensor]] = None,
+                return_details: bool = False):
+        """features [B, hubert_dim, T] (mel-frame rate, zero padded past lengths[b]), spk_emb [B, spk_dim]; optional pitch / energy
+        [B, T] replace the predicted curves; noise: the packed draws of ``Synthesizer`` (prior_noise [4 sum T, 128], src_noise
+        [4 sum T * hop / 4], init_phase [1]).  -> list of B float waveforms (hop_length samples per frame)."""
+        from .config import check_width
+        from .modules import _pack_curve, _pack_rows, _f
+
+        eng, dev = self.eng, self.eng.device
+        for m in self._modules:
+            _ = m.engine  # re-bind if another shim packed these components last
+        if features.dim() != 3:
+            raise ValueError(f"HuBERT features must be [B, {self.hubert_dim}, T], got shape {tuple(features.shape)}")
+        check_width("HuBERT features", features.shape[1], "hubert.hidden_dim", self.hubert_dim)
+        check_width("speaker embedding", spk_emb.shape[-1], "speaker_embedder.hidden_dim", self.spk_dim)
+        L = [int(v) for v in torch.as_tensor(lengths).tolist()]
+        if len(L) != features.shape[0] or spk_emb.shape[0] != len(L) or min(L) <= 0 or max(L) > features.shape[2]:
+            raise ValueError(f"lengths {L} do not describe features of shape {tuple(features.shape)} / {spk_emb.shape[0]} speaker embeddings")
+        if (pitch is None) != (energy is None):
+            raise ValueError("give both pitch and energy, or neither")
+        st = Segments(L, dev)
+        st4 = st.scaled(4)
+        feats = _pack_rows(eng, features, L)
+        style, pe_style = eng.speaker_style(_f(spk_emb, dev), pe_style=pitch is None)
+        if pitch is None:
+            f0, en = eng.hubert_pitch_energy(st, feats, pe_style)
+        else:
+            f0, en = _pack_curve(pitch, L, dev), _pack_curve(energy, L, dev)
+        asr = eng.hubert_encoder(st, feats)
+        p4, e4 = eng.upsample4(st, st4, f0), eng.upsample4(st, st4, en)
+        R = st4.rows
+        if noise is None:
+            noise = dict(prior_noise=torch.randn(R, self.cfg.decoder.hidden_dim // 4, device=dev), src_noise=torch.randn(R * eng.hop4, device=dev),
+                         init_phase=torch.rand(1, device=dev))
+        audio = eng.frame_path(st4, asr, p4, e4, style, noise["prior_noise"], noise["src_noise"], noise["init_phase"], batch_scope=False)
+        eng.check_status()
+        waves = [audio[eng.hop4 * st4.host[b] : eng.hop4 * st4.host[b + 1]] for b in range(len(L))]
+        if return_details:
+            return waves, dict(pitch=f0, energy=en, style=style, pe_style=pe_style, asr=asr)
+        return waves
+
+    def convert_int16(self, features, lengths, spk_emb, pitch=None, energy=None, noise=None, out_prefix: Optional[str] = None):
+        """convert() as int16 samples; with ``out_prefix`` also written as ``<prefix>_<i>.wav`` (like ``Synthesizer.infer``)."""
+        samples = [to_int16(w) for w in self.convert(features, lengths, spk_emb, pitch, energy, noise)]
+        if out_prefix is not None:
+            for i, smp in enumerate(samples):
+                write_wav(f"{out_prefix}_{i}.wav", smp, self.cfg.sample_rate)
+        return samples

@@ -366,3 +366,40 @@ class HipModel:
         y = self._f32(seg_t4.rows)
         _lib.check(self.lib.stts_upsample4(self.ctx, _stream(), seg_t.n, seg_t.host_ptr, _ptr(seg_t.dev), _ptr(seg_t4.dev), _ptr(x), _ptr(y)))
         return y
+
+    # ------------------------------------------------------------------ HuBERT voice conversion (packed feature frames)
+    def _hb_ws(self, rows_T: int, n_utt: int, max_len: int) -> torch.Tensor:
+        """Grow-only workspace of the HuBERT stages, shared with the phoneme stages' (same stream discipline)."""
+        need = int(self.lib.stts_hubert_workspace_bytes(self.ctx, rows_T, n_utt, max_len))
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        with self._ws_lock:
+            ws = self._pws.get(key)
+            if ws is None or ws.numel() < need:
+                ws = self._pws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def speaker_style(self, spk_emb: torch.Tensor, style: bool = True, pe_style: bool = True):
+        """spk_emb [n_utt, ld >= speaker_embedder.hidden_dim] -> (style, pe_style) [n_utt, style_dim] each (None where not asked)."""
+        n = spk_emb.shape[0]
+        s = self._f32(n, self.cfg.style_dim) if style else None
+        p = self._f32(n, self.cfg.style_dim) if pe_style else None
+        ws = self._hb_ws(0, n, 1)
+        _lib.check(self.lib.stts_speaker_style(self.ctx, _stream(), n, _ptr(spk_emb), spk_emb.shape[1], _ptr(s), _ptr(p), _ptr(ws), ws.numel()))
+        return s, p
+
+    def hubert_encoder(self, seg: Segments, feats: torch.Tensor) -> torch.Tensor:
+        """feats [rows_T, ld] packed feature frames -> asr [4 rows_T, inter_dim] (decoder input at the vocoder-frame rate)."""
+        asr = self._f32(4 * seg.rows, self.cfg.inter_dim)
+        ws = self._hb_ws(seg.rows, seg.n, seg.max_len)
+        _lib.check(self.lib.stts_hubert_encoder_forward(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(feats), feats.shape[1], _ptr(asr),
+                                                        asr.shape[1], _ptr(ws), ws.numel()))
+        return asr
+
+    def hubert_pitch_energy(self, seg: Segments, feats: torch.Tensor, pe_style: torch.Tensor, taps: bool = False):
+        """feats [rows_T, ld], pe_style [n_utt, style_dim] -> f0, energy [rows_T] (+ prosody tap [rows_T, inter_dim + style_dim])."""
+        f0, en = self._f32(seg.rows), self._f32(seg.rows)
+        pros = self._f32(seg.rows, self.cfg.inter_dim + self.cfg.style_dim) if taps else None
+        ws = self._hb_ws(seg.rows, seg.n, seg.max_len)
+        _lib.check(self.lib.stts_hubert_pitch_energy_forward(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(feats), feats.shape[1],
+                                                             _ptr(pe_style), _ptr(f0), _ptr(en), _ptr(pros), _ptr(ws), ws.numel()))
+        return (f0, en, pros) if taps else (f0, en)
