@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — utterances/s and RTF of the Stylish-TTS inference hot path on MI355X (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 The bench line (`value`): BASELINE cfg2 — one step = one pass of `stts_frame_path` (Decoder → PriorEncoder + reverse flow +
 post_flow → harmonic source → STFT → vocoder body → iSTFT → tanh) over 8 synthetic LJSpeech-shaped utterances of 3.0 s per GPU
@@ -13,7 +13,9 @@ child processes (stylish_tts_amd/launcher.py), relays rank 0's JSON line and exi
 weights once; per step every rank runs its shard and the waveforms are collected on rank 0 (exact-size point-to-point transfers)
 inside the timed region.  Rank 0 prints ONE JSON line.
 
-Besides the bench line the same JSON carries (skipped with --no-legs):
+A plain run does only what the bench line needs: it compiles the library if it is stale, builds the weights and inputs, runs the W warm-up
+and the K timed steps, writes --dump-outputs if asked and prints the line.  Everything else it can measure runs only with --full, in the
+same JSON line (each part can be left out again with --no-legs / --no-traffic / --no-cpu-baseline):
   * `legs.cfg4_strong` / `legs.cfg5_strong`: BASELINE configs[3] / [4] as ONE fixed global batch (256 utterances of 0.25-10 s in fp32;
     512 segments of 10 s with fp16 operands) partitioned over the ranks by frame count — the strong-scaling numbers;
   * `legs.cfg3_full_chain`: BASELINE configs[2] — tokens → waveform through the whole chain (duration + pitch/energy predictors in
@@ -24,7 +26,7 @@ Besides the bench line the same JSON carries (skipped with --no-legs):
     bandwidth-bound kernels against 8 TB/s with their algorithmic bytes; `traffic`: HBM-side bytes per contraction
     launch from two `rocprofv3 --pmc` child passes that run BEFORE this process touches the GPU;
   * `cpu_baseline`: the numpy oracle on the host cores, a pool of worker processes over utterances (N = 1, before the GPU is touched).
-`--workload cfg3 | cfg4 | cfg5` makes that configuration the (only) timed workload of the run.
+`--workload cfg3 | cfg4 | cfg5` makes that configuration the (only) timed workload of the run (cfg3's phoneme-rate / frame-rate split: --full).
 `--dump-outputs DIR` writes the waveforms the timed workload computed in its last timed step to DIR/audio.npy (rank 0; the inputs and weights
 are seeded, so two builds run with the same arguments can be compared output for output).
 """
@@ -337,7 +339,7 @@ def run_cfg2(ctx: Ctx, args, traffic, traffic_note):
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32" if args.precision == "f32_native" else args.precision, "data": "synthetic",
         "arithmetic": {"f32": "fp32: every activation and weight is the exact sum of three bf16 terms; the frame-rate contractions of the decoder and the vocoder form each fp32 product from the six "
                               "largest bf16 x bf16 cross terms on the bf16 matrix cores, fp32 accumulate (nothing is rounded to 16 bits; error against float64 at or below the f32 matrix cores', "
-                              "tests/test_hip_split_fp32.py); the flow, norms, gates, FFTs: fp32 on v_mfma_f32 / VALU.  legs.cfg2_f32_matrix_cores = the same step with v_mfma_f32 only",
+                              "tests/test_hip_split_fp32.py); the flow, norms, gates, FFTs: fp32 on v_mfma_f32 / VALU.  legs.cfg2_f32_matrix_cores (--full) = the same step with v_mfma_f32 only",
                        "f32_native": "fp32 on the f32 matrix cores (v_mfma_f32_32x32x2_f32) for every contraction"}.get(args.precision, f"{args.precision} matrix-core operands, fp32 accumulate"),
         "config": {
             "workload": ("cfg2: " if is_cfg2 else "side experiment: ") + f"LJSpeech-shaped batch={B} x {args.mel_frames / 80:.1f} s per GPU (T={args.mel_frames} mel frames, {t4 * 75} samples @24 kHz) "
@@ -356,7 +358,7 @@ def run_cfg2(ctx: Ctx, args, traffic, traffic_note):
     }
     if dumped is not None:
         out["dumped_outputs"] = dumped
-    if not args.pmc_child:
+    if args.full and not args.pmc_child:
         out["roofline"] = roofline_leg(ctx, args, model, lambda: model.frame_path(seg, inp["asr"], inp["pitch"], inp["energy"], inp["style"], inp["prior_noise"],
                                                                                  inp["src_noise"], inp["init_phase"], batch_scope=True, out=audio),
                                        1e3 * elapsed / args.steps, traffic, traffic_note)
@@ -657,13 +659,8 @@ def run_cfg3(ctx: Ctx, args, steps: int, warmup: int):
     dumped = None
     if args.dump_outputs and ctx.rank == 0 and args.workload == "cfg3":  # before stage_times() reuses the lanes: rank 0's waveforms, concatenated
         dumped = dump_outputs(args.dump_outputs, {"audio": torch.cat([x.reshape(-1) for x in state["waves"]])})
-    # stage split (one extra call, events on the caller's stream): phoneme-rate part = everything before the frame path
-    syn.stage_times(toks, noise)  # (the caller's own lane may not have run yet when the batches went through map()'s lanes: its workspaces are sized by this call)
-    t = syn.stage_times(toks, noise)
     utts = ctx.world * B * steps
     audio_seconds = ctx.world * steps * sum(frames) * 300 / SR
-    ph_gflop = PHONEME_GFLOP_PER_TOKEN * P * B
-    fr_gflop = FRAME_MFLOP * 1e-3 * R4
     out = {
         "metric": "utterances_per_sec", "value": round(utts / elapsed, 3), "unit": "utt/s",
         "rtf": elapsed / audio_seconds, "realtime_x": audio_seconds / elapsed, "n_gpus": ctx.world, "steps": steps, "warmup": warmup,
@@ -678,7 +675,16 @@ def run_cfg3(ctx: Ctx, args, steps: int, warmup: int):
             "host_syncs_between_duration_and_frame_path": syn.host_syncs_per_call,
             "batches_in_flight": W, "capacity_retries": syn.capacity_retries,
         },
-        "roofline": {
+    }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if args.full:
+        # stage split (one extra call, events on the caller's stream): phoneme-rate part = everything before the frame path
+        syn.stage_times(toks, noise)  # (the caller's own lane may not have run yet when the batches went through map()'s lanes: its workspaces are sized by this call)
+        t = syn.stage_times(toks, noise)
+        ph_gflop = PHONEME_GFLOP_PER_TOKEN * P * B
+        fr_gflop = FRAME_MFLOP * 1e-3 * R4
+        out["roofline"] = {
             "phoneme_rate": {"ms": round(t["phoneme_ms"], 3), "gflop": round(ph_gflop, 1), "tflops": round(ph_gflop / t["phoneme_ms"], 2), "peak": FP32_MFMA_PEAK_TFLOPS,
                              "frac": round(ph_gflop / t["phoneme_ms"] / FP32_MFMA_PEAK_TFLOPS, 4), "dtype": "f32",
                              "note": "SURVEY.md 8d: ~3.6 GFLOP per 50-token utterance; latency-bound (hundreds of small launches)"},
@@ -686,10 +692,7 @@ def run_cfg3(ctx: Ctx, args, steps: int, warmup: int):
                            "frac": round(fr_gflop / t["frame_ms"] / MFMA_PEAK_TFLOPS[precision], 4), "dtype": precision,
                            "note": "SURVEY.md 8d: 74.1 MFLOP per hop-75 frame, whole stts_frame_path (contractions + bandwidth-bound kernels) against the dense 16-bit MFMA peak"},
             "stage_note": "one serialised call with events between the stages; in the timed steps the phoneme-rate side streams overlap",
-        },
-    }
-    if dumped is not None:
-        out["dumped_outputs"] = dumped
+        }
     eng.close()
     return out
 
@@ -753,7 +756,10 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the timed workload: cpu_baseline, roofline + rocprofv3 --pmc traffic, the legs (cfg2), cfg3's stage split; "
+                         "a run without it only sets up, warms up, times the steps, dumps (--dump-outputs) and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--batch", type=int, default=8, help="utterances per GPU per step (BASELINE cfg2 = 8; other values are side experiments)")
     ap.add_argument("--mel-frames", type=int, default=240, help="mel frames per utterance (cfg2 = 240 = 3.0 s)")
     ap.add_argument("--precision", choices=["f32", "f32_native", "bf16", "f16"], default="f32",
@@ -761,19 +767,19 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-utts", type=int, default=256, help="utterances the CPU baseline times (bounded sample: ~10-30 s of host work)")
     ap.add_argument("--cpu-threads", type=int, default=2, help="BLAS threads per CPU-baseline worker process")
     ap.add_argument("--cpu-workers", type=int, default=0, help="CPU-baseline worker processes (0: fill the one-GPU box's share of 16 cores)")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc child passes (roofline.traffic = null)")
-    ap.add_argument("--no-legs", action="store_true", help="only the bench line (no cfg3 / cfg4 / cfg5 legs)")
-    ap.add_argument("--legs", default="f32mfma,cfg4,cfg5,cfg3", help="comma-separated legs run after the bench line")
+    ap.add_argument("--no-traffic", action="store_true", help="--full without the two rocprofv3 --pmc child passes (roofline.traffic = null)")
+    ap.add_argument("--no-legs", action="store_true", help="--full without the legs (no f32mfma / cfg3 / cfg4 / cfg5)")
+    ap.add_argument("--legs", default="f32mfma,cfg4,cfg5,cfg3", help="comma-separated legs run after the bench line (--full)")
     ap.add_argument("--leg-steps", type=int, default=5)
     ap.add_argument("--leg-warmup", type=int, default=2)
     ap.add_argument("--cfg3-batch", type=int, default=64)
     ap.add_argument("--cfg3-tokens", type=int, default=50)
     ap.add_argument("--cfg3-workers", type=int, default=4, help="cfg3: batches in flight (Synthesizer.map); 1 = one call after the other (measured: 1: 15.7 ms per batch, 2: 16.2, 3: 14.1, 4: 13.6)")
-    ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # the counter passes run this script with the legs off
+    ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)  # the counter passes run this script without --full
     ap.add_argument("--plumbing-check", action="store_true", help=argparse.SUPPRESS)  # CPU test of the N > 1 launcher + collection (no GPU, no metric)
     ap.add_argument("--fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--workload", choices=["cfg2", "cfg3", "cfg4", "cfg5"], default="cfg2",
-                    help="cfg2 (default, the bench line + legs): 8 x 3 s per GPU, weak scaling; cfg3: the full chain at 64 x 50 tokens per GPU; cfg4 / cfg5: BASELINE's "
+                    help="cfg2 (default, the bench line; + legs with --full): 8 x 3 s per GPU, weak scaling; cfg3: the full chain at 64 x 50 tokens per GPU; cfg4 / cfg5: BASELINE's "
                          "sharded configs, one fixed global batch partitioned over the ranks (strong scaling)")
     ap.add_argument("--utterances", type=int, default=0, help="cfg4 / cfg5: override the global batch size (rehearsals on one GPU)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -818,7 +824,7 @@ def main():
         entry.compile()  # file-locked: with several ranks one compiles, the others wait
     cpu = None
     traffic, traffic_note = None, "not measured (--no-traffic / multi-GPU run / another workload)"
-    if world == 1 and not args.pmc_child and args.workload == "cfg2":
+    if args.full and world == 1 and not args.pmc_child and args.workload == "cfg2":
         if not args.no_cpu_baseline:
             try:
                 cpu = cpu_baseline(args, 4 * args.mel_frames)  # worker processes, before the GPU is touched
@@ -849,7 +855,7 @@ def main():
         out = run_cfg2(ctx, args, traffic, traffic_note)
         if cpu is not None:
             out["cpu_baseline"] = cpu
-        if not args.no_legs and not args.pmc_child and (args.batch, args.mel_frames, args.precision) == (8, 240, "f32"):
+        if args.full and not args.no_legs and not args.pmc_child and (args.batch, args.mel_frames, args.precision) == (8, 240, "f32"):
             legs = {}
             for leg in [x for x in args.legs.split(",") if x]:
                 t0 = time.perf_counter()

@@ -10,12 +10,12 @@ set -eo pipefail
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_round
 rm -rf "$O" && mkdir -p "$O"
-cd "$R" && python3 bench.py > "$O/bench.json" 2> "$O/bench.err"
-python3 bench.py --batch 1 --no-cpu-baseline --no-traffic > "$O/bench_b1.json" 2>> "$O/bench.err"
-python3 bench.py --batch 64 --precision bf16 --no-cpu-baseline --no-traffic > "$O/bench_cfg3_bf16.json" 2>> "$O/bench.err"
-python3 bench.py --batch 16 --mel-frames 800 --precision f16 --no-cpu-baseline --no-traffic > "$O/bench_cfg5_f16.json" 2>> "$O/bench.err"
+cd "$R" && python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err"
+python3 bench.py --batch 1 --full --no-cpu-baseline --no-traffic > "$O/bench_b1.json" 2>> "$O/bench.err"
+python3 bench.py --batch 64 --precision bf16 --full --no-cpu-baseline --no-traffic > "$O/bench_cfg3_bf16.json" 2>> "$O/bench.err"
+python3 bench.py --batch 16 --mel-frames 800 --precision f16 --full --no-cpu-baseline --no-traffic > "$O/bench_cfg5_f16.json" 2>> "$O/bench.err"
 python3 bench.py --workload cfg4 --steps 3 --warmup 1 > "$O/bench_cfg4_n1.json" 2>> "$O/bench.err"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d "$O/trace" -o trace --output-format csv -- python3 "$R/bench.py" --no-cpu-baseline --no-traffic > "$O/trace.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$O/trace" -o trace --output-format csv -- python3 "$R/bench.py" --full --no-cpu-baseline --no-traffic > "$O/trace.log" 2>&1
 rm -f "$O"/trace/*kernel_trace.csv  # per-dispatch rows (tens of MB): the stats file is what gets committed
 ls -R "$O" | head -30

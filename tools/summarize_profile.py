@@ -19,7 +19,7 @@ for r in sorted(rows, key=lambda r: -float(r["TotalDurationNs"])):
     if t / tot > 0.002:
         lines.append(f"| `{n}` | {c / steps:.1f} | {t / 1e6 / steps:.3f} | {t / c / 1e3:.1f} | {100 * t / tot:.1f} % |")
 summary = {
-    "source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline (20 timed + 3 warm-up + 3 profiled steps)",
+    "source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline (20 timed + 3 warm-up + 3 profiled steps)",
     "steps_in_trace": steps,
     "gpu_busy_ms_per_step": tot / 1e6 / steps,
     "contraction_kernels": "conv_gemm_f32<*> + wn_fused_kernel / wn_layer_kernel (+ winograd_input/output_kernel of the Winograd-form convs)",
