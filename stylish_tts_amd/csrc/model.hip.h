@@ -1548,6 +1548,19 @@ inline int prior_flow_forward(stts_ctx* c, hipStream_t st, const Seg& s, const f
     if (force == -1) blockx3_rt = 0;
   }
   auto wptr = [&](const PackedConv& pc) -> const void* { return c->prec != PREC_F32 ? (const void*)pc.W16 : (const void*)pc.W; };
+  // experiments / tests: wn_fused_x3_kernel with 4 waves per block (default: eight, wn_fused_x3.hip.h); read on every call like STTS_WN_X3
+  const int x3_waves = getenv("STTS_WN_X3_WAVES") ? atoi(getenv("STTS_WN_X3_WAVES")) : 8;
+  // diagnostics (tests/test_hip_flow_layers.py; read on every call, needs z_flow_out): STTS_WN_DEBUG = +-k stops after WaveNet layer k = 4 (7 - f) + i + 1
+  // and hands back h after that layer (+k) or `out` (-k); k = 0: the first coupling layer's h_0 = pre(z).  After a coupling layer's last WaveNet layer
+  // (i = 3; the fused kernels keep the finished `out` on chip) +k hands back the next coupling layer's h_0 = pre(z) (the last coupling layer, f = 0: z) and
+  // -k the whole z, its coupled half updated.  wn_block_x3_kernel (one launch per coupling layer) answers k = 0 and the i = 3 numbers only.
+  const bool dbg_on = getenv("STTS_WN_DEBUG") && z_flow_out;
+  const int dbg_n = dbg_on ? atoi(getenv("STTS_WN_DEBUG")) : -1000;
+  auto dbg_hand_back = [&](const float* src) -> int {
+    STTS_HIP(hipGetLastError());  // (a launch error of the last kernel is reported, not hidden by the early return)
+    STTS_HIP(hipMemcpyAsync(z_flow_out, src, R * fh * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return 0;
+  };
   float* blk_in = hf;  // wn_block16_kernel: the coupling layer's h_0 (ping-pongs between hf and hf2)
   for (int f = 7; f >= 0; --f) {
     const FlowLayerW& L = c->flow[f];
@@ -1559,6 +1572,7 @@ inline int prior_flow_forward(stts_ctx* c, hipStream_t st, const Seg& s, const f
       set_seg(a, 0, z, fh, p * half, L.pre);
       a.N = fh; a.bias = L.pre.bias; a.Y = hf; a.ldy = fh;
       STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, L.pre.npad, s.n_utt, ml));
+      if (dbg_n == 4 * (7 - f)) return dbg_hand_back(hf);  // k = 0, or the previous coupling layer's +k at i = 3
       for (int i = 0; i < 4; ++i) {
         GemmArgs g = gemm_args(s);
         set_seg(g, 0, hf, fh, 0, L.in[i]);
@@ -1572,11 +1586,13 @@ inline int prior_flow_forward(stts_ctx* c, hipStream_t st, const Seg& s, const f
         r.D1 = outf; r.ldd1 = fh; r.acc1 = i > 0;           // out (+)= rs[fh:] ; last layer: all of rs
         r.nsplit = L.rs[i].N == 2 * fh ? fh : 0;
         STTS_TRY(launch_conv_gemm(st, r, EPI_SPLIT_ACC, L.rs[i].npad, s.n_utt, ml));
+        if (i < 3 && (dbg_n == 4 * (7 - f) + i + 1 || dbg_n == -(4 * (7 - f) + i + 1))) return dbg_hand_back(dbg_n > 0 ? hf : outf);
       }
       GemmArgs q = gemm_args(s);
       set_seg(q, 0, outf, fh, 0, L.proj);
       q.N = half; q.bias = L.proj.bias; q.Z = z; q.ldz = fh; q.zcol0 = (1 - p) * half;
       STTS_TRY(launch_conv_gemm(st, q, EPI_COUPLE, L.proj.npad, s.n_utt, ml));
+      if (dbg_n == -(4 * (7 - f) + 4) || (f == 0 && dbg_n == 4 * 7 + 4)) return dbg_hand_back(z);
       continue;
     }
     if (f == 7) {  // later blocks get their `pre` from the tail of the previous block's last WaveNet launch
@@ -1584,6 +1600,7 @@ inline int prior_flow_forward(stts_ctx* c, hipStream_t st, const Seg& s, const f
       set_seg(a, 0, z, fh, p * half, L.pre);
       a.N = fh; a.bias = L.pre.bias; a.Y = hf; a.ldy = fh;
       STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, L.pre.npad, s.n_utt, ml));
+      if (dbg_n == 0) return dbg_hand_back(hf);
     }
     if (blockx3_rt) {
       // ---- split fp32: one launch for the whole coupling layer; reads h_0 = pre(z0) from `blk_in`, writes the next coupling layer's h_0 to the other buffer
@@ -1617,6 +1634,7 @@ inline int prior_flow_forward(stts_ctx* c, hipStream_t st, const Seg& s, const f
       const dim3 bgrid(ceil_div(ml, out_rows), s.n_utt);
       if (blockx3_rt == 3) STTS_LAUNCH_TIMED((wn_block_x3_kernel<3>), bgrid, dim3(64 * kWnWaves), st, e0, e1, ba);
       else STTS_LAUNCH_TIMED((wn_block_x3_kernel<4>), bgrid, dim3(64 * kWnWaves), st, e0, e1, ba);
+      if (dbg_n == 4 * (7 - f) + 4 || dbg_n == -(4 * (7 - f) + 4)) return dbg_hand_back(dbg_n > 0 && f > 0 ? blk_out : z);
       blk_in = blk_out;
       STTS_HIP(hipGetLastError());
       continue;
@@ -1706,7 +1724,6 @@ inline int prior_flow_forward(stts_ctx* c, hipStream_t st, const Seg& s, const f
 #ifdef STTS_WN_TRACE
         xa.dbg = wn_trace_buffer((f * 4 + i), (long)fgrid.x * fgrid.y);
 #endif
-        static const int x3_waves = getenv("STTS_WN_X3_WAVES") ? atoi(getenv("STTS_WN_X3_WAVES")) : 8;  // experiments: 4 waves per block (default: eight, wn_fused_x3.hip.h)
         const bool eight = x3_waves != 4;
 #define STTS_WNX3(RT_)                                                                                                                  \
   do {                                                                                                                                   \
@@ -1778,13 +1795,8 @@ inline int prior_flow_forward(stts_ctx* c, hipStream_t st, const Seg& s, const f
       else if (c->prec == PREC_BF16) STTS_LAUNCH_TIMED(wn_layer_kernel<PREC_BF16>, wgrid, dim3(1024), st, e0, e1, w);
       else if (c->prec == PREC_F16) STTS_LAUNCH_TIMED(wn_layer_kernel<PREC_F16>, wgrid, dim3(1024), st, e0, e1, w);
       else STTS_LAUNCH_TIMED(wn_layer_kernel<PREC_F32>, wgrid, dim3(1024), st, e0, e1, w);
-      if (const char* dbgs = getenv("STTS_WN_DEBUG")) {  // diagnostics: stop after launch #n and hand back h (n > 0) or out (n < 0)
-        const int n = atoi(dbgs), k = (7 - f) * 4 + i + 1;
-        if (z_flow_out && (n == k || n == -k)) {
-          STTS_HIP(hipMemcpyAsync(z_flow_out, n > 0 ? (i < 3 ? hnext : hf) : outf, R * fh * sizeof(float), hipMemcpyDeviceToDevice, st));
-          return 0;
-        }
-      }
+      if (dbg_n == 4 * (7 - f) + i + 1 || dbg_n == -(4 * (7 - f) + i + 1))  // diagnostics (above); layer 3 wrote the next h_0 to hf (w.Hpre)
+        return dbg_hand_back(i < 3 ? (dbg_n > 0 ? hnext : outf) : (dbg_n > 0 && f > 0 ? hf : z));
       std::swap(hcur, hnext);
     }
     STTS_HIP(hipGetLastError());
