@@ -65,7 +65,9 @@ enum {
   STTS_W_ALL = 255,
   STTS_W_CFM = 256,          /* cfm_mel_decoder.* (finalized by stts_cfm_finalize, not part of STTS_W_ALL)  models/cfm/cfm_mel_decoder.py */
   STTS_W_HUBERT = 512,       /* hubert_speech_predictor.{phone_encoder, style_encoder} (not part of STTS_W_ALL) models/speech_predictor.py:132-148 */
-  STTS_W_HUBERT_PE = 1024    /* hubert_pitch_energy_predictor.* (not part of STTS_W_ALL)   models/pitch_energy_predictor.py:124-191 */
+  STTS_W_HUBERT_PE = 1024,   /* hubert_pitch_energy_predictor.* (not part of STTS_W_ALL)   models/pitch_energy_predictor.py:124-191 */
+  STTS_W_PE_MEL_STYLE = 2048, /* pe_mel_style_encoder.* (not part of STTS_W_ALL)            models/models.py:57-62 */
+  STTS_W_CFM_PITCH = 4096    /* cfm_pitch_predictor.spk_emb.* (not part of STTS_W_ALL)     models/cfm/cfm_pitch_predictor.py:25-27 */
 };
 int stts_finalize_weights(stts_ctx* ctx, int which);
 /* Operand precision of the FRAME-RATE Conv1d / Linear contractions (call before the first stts_finalize_weights).
@@ -262,6 +264,24 @@ int stts_hubert_encoder_forward(stts_ctx* ctx, void* stream, int n_utt, const in
 int stts_hubert_pitch_energy_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_T_host, const int32_t* off_T_dev, const float* feats,
                                      int ld_feats, const float* pe_style, float* f0_out, float* energy_out, float* prosody_tap, void* ws,
                                      size_t ws_bytes);
+
+/* ---- MelStyleEncoder (models/mel_style_encoder.py:120-151): mel -> style vector, as pe_mel_style_encoder (which = STTS_W_PE_MEL_STYLE,
+ * models/models.py:57-62) or as cfm_pitch_predictor.spk_emb (which = STTS_W_CFM_PITCH, models/cfm/cfm_pitch_predictor.py:25-27).
+ * Input: the normalised mel as packed time-major rows mel [rows_T, ld >= n_mels] with seg_off[n_utt+1] row offsets; output
+ * style_out [n_utt, style_dim].  Dims come from the weights (shared.0 gives n_mels; n_mels must be a multiple of 2^downsamplings with at least
+ * 5 rows after them, 40 for the model.yml encoders); spectral norm is folded at finalize from the stored weight_u / weight_v (eval mode).
+ * An utterance shorter than the 5 x 5 conv allows (33 mel frames with three downsamplings) is an error, as the reference fails there.
+ * seg_off_host and seg_off_dev must hold the SAME offsets (no STTS_SEG_CAPACITY upper bounds): buffers, grids and the length check are
+ * planned from the host copy, the kernels index with the device copy.
+ * Each utterance is the reference at B = 1, the same bits alone and in any batch.  Always fp32 (the f32 matrix cores), whatever
+ * stts_set_precision chose: the 16-bit modes give the same bits as f32. */
+size_t stts_mel_style_workspace_bytes(stts_ctx* ctx, int which, int64_t rows_T, int n_utt);
+int stts_mel_style_forward(stts_ctx* ctx, void* stream, int which, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, const float* mel,
+                           int ld, float* style_out, void* ws, size_t ws_bytes);
+/* The same, also writing the four ResBlk outputs to block_taps one after the other, each [rows of its level][round_up(cout, 16)]
+ * channels-last (row (off_l[u] + t) * F_l + f, F_l = n_mels / 2^l, off_l the per-level time offsets, T halved rounding up). */
+int stts_mel_style_forward_taps(stts_ctx* ctx, void* stream, int which, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev,
+                                const float* mel, int ld, float* style_out, float* block_taps, void* ws, size_t ws_bytes);
 
 /* Layout bridge for the nn.Module shims: reference [B, C, T] (equal T) <-> time-major rows. */
 int stts_to_time_major(void* stream, const float* x_bct, int B, int C, int T, float* y, int ldy);

@@ -3,6 +3,7 @@
 #include "model.hip.h"
 #include "cfm.hip.h"
 #include "hubert.hip.h"
+#include "mel_style.hip.h"
 
 using namespace stts;
 
@@ -127,6 +128,12 @@ int stts_finalize_weights(stts_ctx* c, int which) {
     c->prec = saved_prec;
     STTS_TRY(rc);
     c->ready |= hb;
+  }
+  const int ms = which & (STTS_W_PE_MEL_STYLE | STTS_W_CFM_PITCH);
+  if (ms) {
+    if (!c->mel_style) c->mel_style = std::make_shared<MelStyleModel>();
+    STTS_TRY(finalize_mel_style(c, static_cast<MelStyleModel*>(c->mel_style.get()), ms));  // fp32 whatever the precision (mel_style.hip.h)
+    c->ready |= ms;
   }
   STTS_HIP(hipDeviceSynchronize());
   return 0;
@@ -610,6 +617,52 @@ int stts_hubert_pitch_energy_forward(stts_ctx* c, void* stream, int n_utt, const
   Seg s{n_utt, off_T_host, off_T_dev};
   Arena a(ws, ws_bytes);
   return hubert_pitch_energy_forward(c, H, st, s, feats, ld_feats, pe_style, f0_out, energy_out, prosody_tap, a);
+  API_END
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ MelStyleEncoder (mel_style.hip.h)
+extern "C" {
+
+static int mel_style_get(stts_ctx* c, int which, const MelStyleW** E) {
+  STTS_CHECK(c && (which == STTS_W_PE_MEL_STYLE || which == STTS_W_CFM_PITCH), "mel_style: `which` must be STTS_W_PE_MEL_STYLE or STTS_W_CFM_PITCH");
+  STTS_CHECK(c->mel_style && (c->ready & which) == which, "weights for this stage are not finalized (need components 0x%x, have 0x%x)", which, c->ready);
+  *E = &static_cast<MelStyleModel*>(c->mel_style.get())->enc[which == STTS_W_PE_MEL_STYLE ? 0 : 1];
+  return 0;
+}
+
+size_t stts_mel_style_workspace_bytes(stts_ctx* c, int which, int64_t rows_T, int n_utt) {
+  const MelStyleW* E = nullptr;
+  if (mel_style_get(c, which, &E) != 0) return 0;
+  return mel_style_workspace_bytes(*E, rows_T, n_utt);
+}
+
+static int mel_style_entry(stts_ctx* c, void* stream, int which, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, const float* mel,
+                           int ld, float* style_out, float* taps, void* ws, size_t ws_bytes) {
+  const MelStyleW* E = nullptr;
+  STTS_TRY(mel_style_get(c, which, &E));
+  STTS_TRY(seg_ok(n_utt, seg_off_host, seg_off_dev));
+  STTS_CHECK(mel && style_out, "mel_style: null argument");
+  STTS_CHECK(ld >= E->n_mels, "mel rows: ld %d < n_mels %d", ld, E->n_mels);
+  STTS_HIP(hipSetDevice(c->device));
+  Seg s{n_utt, seg_off_host, seg_off_dev};
+  Arena a(ws, ws_bytes);
+  return mel_style_forward(*E, (hipStream_t)stream, s, mel, ld, style_out, E->style_dim, taps, a);
+}
+
+int stts_mel_style_forward(stts_ctx* c, void* stream, int which, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, const float* mel, int ld,
+                           float* style_out, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  return mel_style_entry(c, stream, which, n_utt, seg_off_host, seg_off_dev, mel, ld, style_out, nullptr, ws, ws_bytes);
+  API_END
+}
+
+int stts_mel_style_forward_taps(stts_ctx* c, void* stream, int which, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, const float* mel,
+                                int ld, float* style_out, float* block_taps, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  STTS_CHECK(block_taps, "mel_style: null block_taps");
+  return mel_style_entry(c, stream, which, n_utt, seg_off_host, seg_off_dev, mel, ld, style_out, block_taps, ws, ws_bytes);
   API_END
 }
 

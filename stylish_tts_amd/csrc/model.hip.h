@@ -193,6 +193,7 @@ struct stts_ctx {
   std::shared_ptr<void> phoneme;  // stts::PhonemeModel (phoneme_model.hip.h)
   std::shared_ptr<void> cfm;      // stts::CfmModel (cfm.hip.h)
   std::shared_ptr<void> hubert;   // stts::HubertModel (hubert.hip.h)
+  std::shared_ptr<void> mel_style;  // stts::MelStyleModel (mel_style.hip.h)
 };
 
 namespace stts {

@@ -13,6 +13,7 @@ Reference classes mirrored (paths relative to /root/reference/src/stylish_tts/tr
   ExportModel            models/export_model.py:5-45
   HubertSpeechPredictor       models/speech_predictor.py:132-251
   HubertPitchEnergyPredictor  models/pitch_energy_predictor.py:124-191
+  MelStyleEncoder             models/mel_style_encoder.py:120-151
 
 Differences, all additive: forward() of the stochastic modules takes an optional ``noise`` dict with the three draws
 the reference takes from the global torch generator (``prior_noise`` [B,128,4T], ``src_noise`` [B,1,300T],
@@ -29,11 +30,12 @@ import numpy as np
 import torch
 
 from . import params
-from .config import Record, check_width, hubert_dims, load_model_config
+from .config import DEFAULT_MODEL, Record, check_width, hubert_dims, load_model_config
 from .runtime import HipModel, Segments
 
 W_DECODER, W_FLOW, W_GENERATOR, W_SPEECH_TEXT, W_DURATION, W_PE_TEXT, W_PE_STYLE, W_PITCH_ENERGY = 1, 2, 4, 8, 16, 32, 64, 128
 W_HUBERT, W_HUBERT_PE = 512, 1024  # hubert_speech_predictor.{phone_encoder, style_encoder}; hubert_pitch_energy_predictor.*
+W_PE_MEL_STYLE, W_CFM_PITCH = 2048, 4096  # pe_mel_style_encoder.*; cfm_pitch_predictor.spk_emb.*
 
 _ENGINES: Dict[int, HipModel] = {}
 
@@ -539,9 +541,93 @@ class HubertSpeechPredictor(HipModule):
         return DecoderPrediction(audio=[audio[h * st4.host[b] : h * st4.host[b + 1]] for b in range(B)], magnitude=None, phase=None)
 
 
-def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int] = None, hubert: bool = False):
+def mel_style_levels(n_mels: int, skip_downsamples: bool):
+    """(number of "half" downsamplings, the shortest mel the encoder takes).  The reference needs n_mels to halve exactly at every level
+    (an odd F gives mismatched shortcut / residual shapes) and 5 x 5 positions left for shared.6 (models/mel_style_encoder.py:139)."""
+    n_down = 3 if skip_downsamples else 4
+    if n_mels % (1 << n_down) or (n_mels >> n_down) < 5:
+        raise ValueError(f"MelStyleEncoder: n_mels = {n_mels} must be a multiple of {1 << n_down} and at least {5 << n_down}")
+    t_min = 1
+    while True:
+        t = t_min
+        for _ in range(n_down):
+            t = (t + 1) // 2
+        if t >= 5:
+            return n_down, t_min
+        t_min += 1
+
+
+def mel_style_tap_shapes(dim_in: int, max_conv_dim: int, skip_downsamples: bool, lengths):
+    """[(rows, ld, cout, F, per-utterance T)] of the four ResBlk taps of stts_mel_style_forward_taps (channels-last, ld = cout padded to 16)."""
+    out, c, F, T = [], dim_in, dim_in, [int(x) for x in lengths]
+    for i in range(4):
+        co = min(2 * c, max_conv_dim)
+        if not (i == 3 and skip_downsamples):
+            F, T = F // 2, [(t + 1) // 2 for t in T]
+        out.append((F * sum(T), (co + 15) // 16 * 16, co, F, T))
+        c = co
+    return out
+
+
+class MelStyleEncoder(HipModule):
+    """models/mel_style_encoder.py:120-151: x [B, 1, n_mels, T] -> style [B, style_dim].  ``lengths`` (optional, [B] mel frames) runs a
+    ragged batch: each utterance gets what the reference gives it alone; without it the batch is dense and equals the reference on it.
+    The engine slot is ``component``: "pe_mel_style_encoder" (models/models.py:57-62) or "cfm_pitch_predictor.spk_emb"
+    (models/cfm/cfm_pitch_predictor.py:25-27); the dims come from the weights."""
+
+    _SLOTS = {"pe_mel_style_encoder": ("pe_mel_style_encoder", "", W_PE_MEL_STYLE),
+              "cfm_pitch_predictor.spk_emb": ("cfm_pitch_predictor", "spk_emb.", W_CFM_PITCH)}
+
+    def __init__(self, dim_in=48, style_dim=48, max_conv_dim=384, skip_downsamples=False, cfg=None, engine=None, component="pe_mel_style_encoder"):
+        if component not in self._SLOTS:
+            raise ValueError(f"component must be one of {sorted(self._SLOTS)}")
+        self.module_name, self.key_prefix, self.components = self._SLOTS[component]
+        self.dim_in, self.style_dim, self.max_conv_dim, self.skip_downsamples = int(dim_in), int(style_dim), int(max_conv_dim), bool(skip_downsamples)
+        self.n_down, self.min_frames = mel_style_levels(self.dim_in, self.skip_downsamples)
+        super().__init__(params.mel_style_encoder_spec(self.dim_in, self.style_dim, self.max_conv_dim, self.skip_downsamples), cfg or load_model_config(), engine)
+
+    def _load_into(self, eng: HipModel):
+        eng.load_state_dict(self.module_name, self._store, prefix=self.key_prefix)
+
+    def _lengths(self, x, lengths):
+        if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] != self.dim_in:
+            raise ValueError(f"MelStyleEncoder input must be [B, 1, {self.dim_in}, T], got shape {tuple(x.shape)}")
+        B, T = x.shape[0], x.shape[3]
+        L = [T] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).tolist()]
+        if len(L) != B or any(t < 1 or t > T for t in L):
+            raise ValueError(f"lengths {L} do not fit a batch of {B} x {T} frames")
+        return L
+
+    def forward(self, x, lengths=None):
+        return self.run(x, lengths)[0]
+
+    def run(self, x, lengths=None, taps: bool = False):
+        """(style, taps or None); taps = the four ResBlk outputs as lists of per-utterance [cout, F, T] tensors."""
+        L = self._lengths(x, lengths)
+        eng = self.engine
+        seg = Segments(L, eng.device)
+        xd = _f(x, eng.device)[:, 0]  # [B, F, T]
+        mel = torch.cat([xd[b, :, : L[b]].t() for b in range(len(L))]).contiguous()  # packed time-major rows [sum T, n_mels]
+        if not taps:
+            return eng.mel_style(self.components, seg, mel, self.style_dim), None
+        shapes = mel_style_tap_shapes(self.dim_in, self.max_conv_dim, self.skip_downsamples, L)
+        style, flat = eng.mel_style(self.components, seg, mel, self.style_dim, tap_floats=sum(r * ld for r, ld, *_ in shapes))
+        out, o = [], 0
+        for rows, ld, co, F, T in shapes:
+            blk = flat[o : o + rows * ld].view(rows, ld)[:, :co]
+            o += rows * ld
+            per, r0 = [], 0
+            for t in T:
+                per.append(blk[r0 : r0 + t * F].reshape(t, F, co).permute(2, 1, 0))
+                r0 += t * F
+            out.append(per)
+        return style, out
+
+
+def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int] = None, hubert: bool = False, mel_style: bool = False):
     """The five modules of the inference composition (models/models.py:32-63, :79-101), optionally with synthetic weights.
-    hubert=True adds the voice-conversion pair hubert_speech_predictor / hubert_pitch_energy_predictor (models/models.py:92-101)."""
+    hubert=True adds the voice-conversion pair hubert_speech_predictor / hubert_pitch_energy_predictor (models/models.py:92-101);
+    mel_style=True adds pe_mel_style_encoder (models/models.py:57-62)."""
     cfg = cfg or load_model_config()
     m = dict(
         speech_predictor=SpeechPredictor(cfg, engine=engine),
@@ -557,6 +643,9 @@ def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int]
         m["hubert_speech_predictor"] = HubertSpeechPredictor(cfg, engine=engine)
         m["hubert_pitch_energy_predictor"] = HubertPitchEnergyPredictor(hd, sd, cfg.style_dim, cfg.inter_dim, cfg.style_encoder, cfg.pitch_energy_predictor,
                                                                         cfg=cfg, engine=engine)
+    if mel_style:
+        ms = Record(cfg.get("mel_style_encoder") or DEFAULT_MODEL["mel_style_encoder"])  # model.yml section, config.DEFAULT_MODEL when absent
+        m["pe_mel_style_encoder"] = MelStyleEncoder(cfg.n_mels, cfg.style_dim, ms.max_channels, ms.skip_downsample, cfg=cfg, engine=engine)
     if synthetic_seed is not None:
         for mod in m.values():
             mod.load_synthetic(synthetic_seed)

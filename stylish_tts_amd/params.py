@@ -381,8 +381,46 @@ def cfm_mel_decoder_spec(dims=None) -> Spec:
     return s
 
 
+def _sn_conv(p: str, cout: int, cin: int, k: int, bias: bool = True, groups: int = 1) -> Spec:
+    """torch.nn.utils.spectral_norm(Conv2d) keys: bias, weight_orig, then the buffers weight_u [cout] and weight_v [cin / groups * k * k]."""
+    s: Spec = [(p + ".bias", (cout,), "b")] if bias else []
+    return s + [(p + ".weight_orig", (cout, cin // groups, k, k), "w"), (p + ".weight_u", (cout,), "sn_u"), (p + ".weight_v", (cin // groups * k * k,), "sn_v")]
+
+
+def mel_style_encoder_spec(dim_in: int, style_dim: int, max_conv_dim: int, skip_downsamples: bool, p: str = "") -> Spec:
+    """MelStyleEncoder (models/mel_style_encoder.py:120-151): shared.0 conv, shared.1-4 ResBlk (:68-117; LearnedDownSample "half" registered
+    before conv1 / conv2 / conv1x1), shared.6 the 5 x 5 conv, unshared.  Every conv is spectral-normed."""
+    s: Spec = _sn_conv(p + "shared.0", dim_in, 1, 3)
+    c = dim_in
+    for i in range(4):
+        co = min(2 * c, max_conv_dim)
+        q = p + f"shared.{i + 1}."
+        if not (i == 3 and skip_downsamples):
+            s += _sn_conv(q + "downsample_res.conv", c, c, 3, groups=c)
+        s += _sn_conv(q + "conv1", c, c, 3) + _sn_conv(q + "conv2", co, c, 3)
+        if c != co:
+            s += _sn_conv(q + "conv1x1", co, c, 1, bias=False)
+        c = co
+    return s + _sn_conv(p + "shared.6", c, c, 5) + _linear(p + "unshared", style_dim, c)
+
+
+def pe_mel_style_encoder_spec(cfg) -> Spec:
+    """pe_mel_style_encoder (models/models.py:57-62); model.yml's mel_style_encoder section (max_channels 384, skip_downsample True)."""
+    from .config import DEFAULT_MODEL, Record
+
+    ms = Record(cfg.get("mel_style_encoder") or DEFAULT_MODEL["mel_style_encoder"])  # model.yml section, config.DEFAULT_MODEL when absent
+    return mel_style_encoder_spec(cfg.n_mels, cfg.style_dim, ms.max_channels, ms.skip_downsample)
+
+
+# the mel style encoders (models/models.py:57-62): known to module_spec, outside the text-to-speech composition
+MEL_STYLE_MODULE_SPECS = {"pe_mel_style_encoder": pe_mel_style_encoder_spec}
+
+
 def module_spec(module: str, cfg) -> Spec:
-    return (MODULE_SPECS[module] if module in MODULE_SPECS else HUBERT_MODULE_SPECS[module])(cfg)
+    for table in (MODULE_SPECS, HUBERT_MODULE_SPECS, MEL_STYLE_MODULE_SPECS):
+        if module in table:
+            return table[module](cfg)
+    raise KeyError(module)
 
 
 # ----------------------------------------------------------------------------
@@ -481,9 +519,40 @@ def synth_tensor(name: str, shape: Tuple[int, ...], kind: str, seed: int = 0) ->
     return v.astype(np.float32).reshape(shape)
 
 
+def spectral_uv(w: np.ndarray, name: str, seed: int = 0, iters: int = 64):
+    """(u, v) of a spectral-norm layer: float64 power iteration on w.view(cout, -1) from a hashed start, as
+    torch.nn.utils.spectral_norm's training steps converge to (normalize with eps 1e-12).  iters=1 gives one step, not converged."""
+    m = np.asarray(w, np.float64).reshape(w.shape[0], -1)
+    v = hash_normal(name + "#sn_v0", m.shape[1], seed).astype(np.float64)
+    v /= max(np.linalg.norm(v), 1e-12)
+    for _ in range(max(1, iters)):
+        u = m @ v
+        u /= max(np.linalg.norm(u), 1e-12)
+        v = m.T @ u
+        v /= max(np.linalg.norm(v), 1e-12)
+    return u.astype(np.float32), v.astype(np.float32)
+
+
+def fold_spectral_norm(w_orig: np.ndarray, u: np.ndarray, v: np.ndarray) -> np.ndarray:
+    """torch.nn.utils.spectral_norm's eval-mode weight W_orig / (u . (W_orig.view(cout, -1) @ v)) from the stored u and v, in float64
+    (the fold the engine does at finalize: csrc/mel_style.hip.h, spectral_norm_weight)."""
+    w = np.asarray(w_orig, np.float64)
+    sigma = float(np.asarray(u, np.float64) @ (w.reshape(w.shape[0], -1) @ np.asarray(v, np.float64)))
+    return w / sigma
+
+
 def synth_state_dict(spec: Spec, seed: int = 0, prefix: str = "") -> "OrderedDict[str, np.ndarray]":
-    """prefix keys the hash (e.g. the module name) so equal-named tensors of different modules differ."""
-    return OrderedDict((name, synth_tensor(prefix + name, shape, kind, seed)) for name, shape, kind in spec)
+    """prefix keys the hash (e.g. the module name) so equal-named tensors of different modules differ.  Spectral-norm buffers
+    (kinds sn_u / sn_v) are the converged singular vectors of their layer's weight_orig (spectral_uv)."""
+    out: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for name, shape, kind in spec:
+        if kind in ("sn_u", "sn_v"):
+            base = name[: -len(".weight_u")]
+            u, v = spectral_uv(out[base + ".weight_orig"], prefix + base, seed)
+            out[name] = u if kind == "sn_u" else v
+        else:
+            out[name] = synth_tensor(prefix + name, shape, kind, seed)
+    return out
 
 
 def spec_shapes(spec: Spec) -> Dict[str, Tuple[int, ...]]:

@@ -403,3 +403,25 @@ class HipModel:
         _lib.check(self.lib.stts_hubert_pitch_energy_forward(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(feats), feats.shape[1],
                                                              _ptr(pe_style), _ptr(f0), _ptr(en), _ptr(pros), _ptr(ws), ws.numel()))
         return (f0, en, pros) if taps else (f0, en)
+
+    # ------------------------------------------------------------------ MelStyleEncoder (packed mel frames)
+    def mel_style(self, which: int, seg: Segments, mel: torch.Tensor, style_dim: int, tap_floats: int = 0):
+        """mel [rows_T, ld >= n_mels] packed time-major -> style [n_utt, style_dim] of the encoder `which` (STTS_W_PE_MEL_STYLE /
+        STTS_W_CFM_PITCH); tap_floats > 0 also returns the four ResBlk outputs, flat (include/stylish_hip.h, stts_mel_style_forward_taps)."""
+        need = int(self.lib.stts_mel_style_workspace_bytes(self.ctx, which, seg.rows, seg.n))
+        if need == 0:
+            _lib.check(1)  # the weights of `which` are not finalized: the library's message
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        with self._ws_lock:
+            wsd = self.__dict__.setdefault("_mws", {})
+            ws = wsd.get(key)
+            if ws is None or ws.numel() < need:
+                ws = wsd[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        out = self._f32(seg.n, style_dim)
+        args = (self.ctx, _stream(), which, seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(mel), mel.shape[1], _ptr(out))
+        if tap_floats:
+            taps = self._f32(tap_floats)
+            _lib.check(self.lib.stts_mel_style_forward_taps(*args, _ptr(taps), _ptr(ws), ws.numel()))
+            return out, taps
+        _lib.check(self.lib.stts_mel_style_forward(*args, _ptr(ws), ws.numel()))
+        return out
