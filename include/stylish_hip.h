@@ -67,7 +67,8 @@ enum {
   STTS_W_HUBERT = 512,       /* hubert_speech_predictor.{phone_encoder, style_encoder} (not part of STTS_W_ALL) models/speech_predictor.py:132-148 */
   STTS_W_HUBERT_PE = 1024,   /* hubert_pitch_energy_predictor.* (not part of STTS_W_ALL)   models/pitch_energy_predictor.py:124-191 */
   STTS_W_PE_MEL_STYLE = 2048, /* pe_mel_style_encoder.* (not part of STTS_W_ALL)            models/models.py:57-62 */
-  STTS_W_CFM_PITCH = 4096    /* cfm_pitch_predictor.spk_emb.* (not part of STTS_W_ALL)     models/cfm/cfm_pitch_predictor.py:25-27 */
+  STTS_W_CFM_PITCH = 4096,   /* cfm_pitch_predictor.spk_emb.* (not part of STTS_W_ALL)     models/cfm/cfm_pitch_predictor.py:25-27 */
+  STTS_W_CFM_PITCH_NET = 8192 /* cfm_pitch_predictor.{asr_emb, blocks, out_proj} (in_proj.* is accepted and ignored; not part of STTS_W_ALL) */
 };
 int stts_finalize_weights(stts_ctx* ctx, int which);
 /* Operand precision of the FRAME-RATE Conv1d / Linear contractions (call before the first stts_finalize_weights).
@@ -282,6 +283,23 @@ int stts_mel_style_forward(stts_ctx* ctx, void* stream, int which, int n_utt, co
  * channels-last (row (off_l[u] + t) * F_l + f, F_l = n_mels / 2^l, off_l the per-level time offsets, T halved rounding up). */
 int stts_mel_style_forward_taps(stts_ctx* ctx, void* stream, int which, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev,
                                 const float* mel, int ld, float* style_out, float* block_taps, void* ws, size_t ws_bytes);
+
+/* ---- CfmPitchPredictor's frame-rate network (models/cfm/cfm_pitch_predictor.py:12-51), component STTS_W_CFM_PITCH_NET: asr_emb (1x1,
+ * Mish, 1x1), four generator ConvNeXt blocks (256 / 1024 channels, k = 7) conditioned on the speaker style, out_proj (256 -> 1).
+ * Input: asr features as packed time-major rows asr [rows_T, ld_asr >= asr_dim, ld_asr % 4 == 0] with off_T[n_utt+1] row offsets (the
+ * pitch-frame rate), and spk_style [n_utt, 256] = stts_mel_style_forward(STTS_W_CFM_PITCH) of the reference mel (any stream).
+ * Output: out_normed [rows_T] (the normed F0, packed by the real lengths).  out_hz (or null) [rows_T] = denorm_f0_zscore of it
+ * (train/stage_type.py:801-829): clamp(2^(x * f0_log2_std + f0_log2_mean), 50, 1200), 0 where uv[row] > 0 (uv [rows_T] or null).
+ * The log2 statistics are the training set's (not in the checkpoint).  GRN's norm runs over each utterance's own rows: every utterance
+ * is the reference at B = 1.  off_T_host / off_T_dev must hold the same offsets.  Always fp32, whatever stts_set_precision chose. */
+size_t stts_cfm_pitch_workspace_bytes(stts_ctx* ctx, int64_t rows_T, int n_utt);
+int stts_cfm_pitch_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_T_host, const int32_t* off_T_dev, const float* asr, int ld_asr,
+                           const float* spk_style, float* out_normed, float* out_hz, float f0_log2_mean, float f0_log2_std, const float* uv, void* ws,
+                           size_t ws_bytes);
+/* The same, also writing taps [5][rows_T][256]: the asr_emb output, then the output of each ConvNeXt block. */
+int stts_cfm_pitch_forward_taps(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_T_host, const int32_t* off_T_dev, const float* asr, int ld_asr,
+                                const float* spk_style, float* out_normed, float* out_hz, float f0_log2_mean, float f0_log2_std, const float* uv,
+                                float* taps, void* ws, size_t ws_bytes);
 
 /* Layout bridge for the nn.Module shims: reference [B, C, T] (equal T) <-> time-major rows. */
 int stts_to_time_major(void* stream, const float* x_bct, int B, int C, int T, float* y, int ldy);

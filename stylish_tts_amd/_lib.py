@@ -86,6 +86,9 @@ SIGNATURES = {
     "stts_mel_style_workspace_bytes": (_SZ, [_P, _I, _I64, _I]),
     "stts_mel_style_forward": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _SZ]),
     "stts_mel_style_forward_taps": (_I, [_P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _SZ]),
+    "stts_cfm_pitch_workspace_bytes": (_SZ, [_P, _I64, _I]),
+    "stts_cfm_pitch_forward": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, C.c_float, C.c_float, _P, _P, _SZ]),
+    "stts_cfm_pitch_forward_taps": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _SZ]),
     "stts_cfm_finalize": (_I, [_P, _P]),
     "stts_cfm_workspace_bytes": (_SZ, [_P, _I64, _I]),
     "stts_cfm_estimator": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _SZ]),

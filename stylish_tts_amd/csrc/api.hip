@@ -4,6 +4,7 @@
 #include "cfm.hip.h"
 #include "hubert.hip.h"
 #include "mel_style.hip.h"
+#include "cfm_pitch.hip.h"
 
 using namespace stts;
 
@@ -134,6 +135,18 @@ int stts_finalize_weights(stts_ctx* c, int which) {
     if (!c->mel_style) c->mel_style = std::make_shared<MelStyleModel>();
     STTS_TRY(finalize_mel_style(c, static_cast<MelStyleModel*>(c->mel_style.get()), ms));  // fp32 whatever the precision (mel_style.hip.h)
     c->ready |= ms;
+  }
+  if (which & STTS_W_CFM_PITCH_NET) {
+    if (!c->cfm_pitch) c->cfm_pitch = std::make_shared<CfmPitchNetW>();
+    // fp32 on the f32 matrix cores whatever the precision, as the HuBERT front ends above (cfm_pitch.hip.h)
+    const int saved_prec = c->prec;
+    c->prec = PREC_F32;
+    c->pack_x3 = false;
+    const int rc = finalize_cfm_pitch_net(c, static_cast<CfmPitchNetW*>(c->cfm_pitch.get()));
+    c->pack_x3 = true;
+    c->prec = saved_prec;
+    STTS_TRY(rc);
+    c->ready |= STTS_W_CFM_PITCH_NET;
   }
   STTS_HIP(hipDeviceSynchronize());
   return 0;
@@ -663,6 +676,58 @@ int stts_mel_style_forward_taps(stts_ctx* c, void* stream, int which, int n_utt,
   API_BEGIN
   STTS_CHECK(block_taps, "mel_style: null block_taps");
   return mel_style_entry(c, stream, which, n_utt, seg_off_host, seg_off_dev, mel, ld, style_out, block_taps, ws, ws_bytes);
+  API_END
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ CfmPitchPredictor (cfm_pitch.hip.h)
+extern "C" {
+
+static int cfm_pitch_get(stts_ctx* c, const CfmPitchNetW** W) {
+  STTS_CHECK(c && c->cfm_pitch && (c->ready & STTS_W_CFM_PITCH_NET), "weights for this stage are not finalized (need components 0x%x, have 0x%x)",
+             STTS_W_CFM_PITCH_NET, c ? c->ready : 0);
+  *W = static_cast<const CfmPitchNetW*>(c->cfm_pitch.get());
+  return 0;
+}
+
+size_t stts_cfm_pitch_workspace_bytes(stts_ctx* c, int64_t rows_T, int n_utt) {
+  const CfmPitchNetW* W = nullptr;
+  if (cfm_pitch_get(c, &W) != 0) return 0;
+  return cfm_pitch_workspace_bytes(*W, rows_T, n_utt);
+}
+
+static int cfm_pitch_entry(stts_ctx* c, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* asr, int ld_asr,
+                           const float* spk_style, float* out_normed, float* out_hz, float mean, float stdv, const float* uv, float* taps, void* ws,
+                           size_t ws_bytes) {
+  const CfmPitchNetW* W = nullptr;
+  STTS_TRY(cfm_pitch_get(c, &W));
+  STTS_TRY(seg_ok(n_utt, off_host, off_dev));
+  STTS_CHECK(asr && spk_style && out_normed && ws, "cfm_pitch: null argument");
+  STTS_CHECK(ld_asr >= W->asr_dim && ld_asr % 4 == 0, "asr rows: ld %d must be >= asr_dim %d and a multiple of 4", ld_asr, W->asr_dim);
+  STTS_CHECK(!out_hz || (std::isfinite(mean) && std::isfinite(stdv)), "cfm_pitch: the F0 log2 statistics must be finite");
+  STTS_HIP(hipSetDevice(c->device));
+  Seg s{n_utt, off_host, off_dev};
+  Arena a(ws, ws_bytes);
+  return cfm_pitch_forward(*W, (hipStream_t)stream, s, asr, ld_asr, spk_style, out_normed, out_hz, mean, stdv, out_hz ? uv : nullptr, taps, a);
+}
+
+int stts_cfm_pitch_forward(stts_ctx* c, void* stream, int n_utt, const int32_t* off_T_host, const int32_t* off_T_dev, const float* asr, int ld_asr,
+                           const float* spk_style, float* out_normed, float* out_hz, float f0_log2_mean, float f0_log2_std, const float* uv, void* ws,
+                           size_t ws_bytes) {
+  API_BEGIN
+  return cfm_pitch_entry(c, stream, n_utt, off_T_host, off_T_dev, asr, ld_asr, spk_style, out_normed, out_hz, f0_log2_mean, f0_log2_std, uv, nullptr, ws,
+                         ws_bytes);
+  API_END
+}
+
+int stts_cfm_pitch_forward_taps(stts_ctx* c, void* stream, int n_utt, const int32_t* off_T_host, const int32_t* off_T_dev, const float* asr, int ld_asr,
+                                const float* spk_style, float* out_normed, float* out_hz, float f0_log2_mean, float f0_log2_std, const float* uv,
+                                float* taps, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  STTS_CHECK(taps, "cfm_pitch: null taps");
+  return cfm_pitch_entry(c, stream, n_utt, off_T_host, off_T_dev, asr, ld_asr, spk_style, out_normed, out_hz, f0_log2_mean, f0_log2_std, uv, taps, ws,
+                         ws_bytes);
   API_END
 }
 

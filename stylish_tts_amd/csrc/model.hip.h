@@ -194,6 +194,7 @@ struct stts_ctx {
   std::shared_ptr<void> cfm;      // stts::CfmModel (cfm.hip.h)
   std::shared_ptr<void> hubert;   // stts::HubertModel (hubert.hip.h)
   std::shared_ptr<void> mel_style;  // stts::MelStyleModel (mel_style.hip.h)
+  std::shared_ptr<void> cfm_pitch;  // stts::CfmPitchNetW (cfm_pitch.hip.h)
 };
 
 namespace stts {
@@ -434,6 +435,37 @@ inline int pack_winograd(stts_ctx* c, const HostTensor& w, const HostTensor* bia
   out->pad = (r - 1) / 2;
   out->ready = true;
   return 0;
+}
+
+// one ConvNeXtBlock with an AdaptiveLayerNorm (models/generator.py:441-499) at h channels and a k-tap depthwise conv; its norm.fc goes into `table`
+inline int pack_convnext_block(stts_ctx* c, const std::string& q, int h, int k, StyleTable* table, ConvNextW* o) {
+  ConvNextW& B = *o;
+  STTS_GET(dw, q + "dwconv.weight");
+  STTS_GET(db, q + "dwconv.bias");
+  STTS_CHECK(dw->shape.size() == 3 && dw->shape[0] == h && dw->shape[1] == 1 && dw->shape[2] == k, "%sdwconv: expected [%d, 1, %d]", q.c_str(), h, k);
+  B.K = k;
+  std::vector<float> wt((size_t)B.K * h);
+  for (int ch = 0; ch < h; ++ch)
+    for (int kk = 0; kk < B.K; ++kk) wt[(size_t)kk * h + ch] = dw->data[(size_t)ch * B.K + kk];
+  STTS_TRY(dev_upload(c, wt, &B.dw_wt));
+  STTS_TRY(dev_upload(c, db->data, &B.dw_b));
+  STTS_TRY(add_style(c, table, q + "norm", h, &B.norm));
+  STTS_TRY(pack_plain(c, q + "pwconv1", true, 0, h, &B.pw1));
+  // pwconv2 with GRN's beta folded into the bias: W2 (U*s + beta) + b2 = (W2*s) U + (W2 beta + b2)
+  HostTensor w2;
+  STTS_TRY(get_weight(c, q + "pwconv2", &w2));
+  STTS_GET(b2, q + "pwconv2.bias");
+  STTS_GET(gg, q + "grn.gamma");
+  STTS_GET(gb, q + "grn.beta");
+  HostTensor b2f = *b2;
+  const int ci = (int)w2.shape[1];
+  for (int r = 0; r < (int)w2.shape[0]; ++r) {
+    double s = 0;
+    for (int kk = 0; kk < ci; ++kk) s += (double)w2.data[(size_t)r * ci + kk] * gb->data[kk];
+    b2f.data[r] = (float)((double)b2->data[r] + s);
+  }
+  STTS_TRY(pack_rows(c, w2, &b2f, plain_rows((int)w2.shape[0]), 0, ci, round_up(ci, 32), (int)w2.shape[0], &B.pw2));
+  return dev_upload(c, gg->data, &B.grn_gamma);
 }
 
 inline int pack_adain_block(stts_ctx* c, const std::string& p, int cin, int cout, StyleTable* table, AdainBlockW* o) {
@@ -751,36 +783,7 @@ inline int finalize_frame(stts_ctx* c, int which) {
       c->nyq_b[which] = b->data[nmain];
     }
     const int ks[4] = {31, 15, 7, 3};
-    for (int i = 0; i < 4; ++i) {
-      const std::string q = g + "convnext." + std::to_string(i) + ".";
-      ConvNextW& B = c->cnx[i];
-      STTS_GET(dw, q + "dwconv.weight");
-      STTS_GET(db, q + "dwconv.bias");
-      STTS_CHECK(dw->shape[2] == ks[i], "convnext.%d dwconv kernel %lld != %d", i, (long long)dw->shape[2], ks[i]);
-      B.K = ks[i];
-      std::vector<float> wt((size_t)B.K * h);
-      for (int ch = 0; ch < h; ++ch)
-        for (int k = 0; k < B.K; ++k) wt[(size_t)k * h + ch] = dw->data[(size_t)ch * B.K + k];
-      STTS_TRY(dev_upload(c, wt, &B.dw_wt));
-      STTS_TRY(dev_upload(c, db->data, &B.dw_b));
-      STTS_TRY(add_style(c, &c->gen_style, q + "norm", h, &B.norm));
-      STTS_TRY(pack_plain(c, q + "pwconv1", true, 0, h, &B.pw1));
-      // pwconv2 with GRN's beta folded into the bias: W2 (U*s + beta) + b2 = (W2*s) U + (W2 beta + b2)
-      HostTensor w2;
-      STTS_TRY(get_weight(c, q + "pwconv2", &w2));
-      STTS_GET(b2, q + "pwconv2.bias");
-      STTS_GET(gg, q + "grn.gamma");
-      STTS_GET(gb, q + "grn.beta");
-      HostTensor b2f = *b2;
-      const int ci = (int)w2.shape[1];
-      for (int r = 0; r < (int)w2.shape[0]; ++r) {
-        double s = 0;
-        for (int k = 0; k < ci; ++k) s += (double)w2.data[(size_t)r * ci + k] * gb->data[k];
-        b2f.data[r] = (float)((double)b2->data[r] + s);
-      }
-      STTS_TRY(pack_rows(c, w2, &b2f, plain_rows((int)w2.shape[0]), 0, ci, round_up(ci, 32), (int)w2.shape[0], &B.pw2));
-      STTS_TRY(dev_upload(c, gg->data, &B.grn_gamma));
-    }
+    for (int i = 0; i < 4; ++i) STTS_TRY(pack_convnext_block(c, g + "convnext." + std::to_string(i) + ".", h, ks[i], &c->gen_style, &c->cnx[i]));
     STTS_TRY(add_style(c, &c->gen_style, g + "amp_final_layer_norm", h, &c->head_amp));
     STTS_TRY(add_style(c, &c->gen_style, g + "phase_final_layer_norm", h, &c->head_phase));
     STTS_TRY(upload_table(c, &c->gen_style));
@@ -1861,6 +1864,77 @@ inline int ln_launch(hipStream_t st, const float* X, int ldx, int C, long n_rows
   return 0;
 }
 
+// Scratch of convnext_block_forward: dw / nrm [rows, h], U [rows, inter], part [n_utt * ss_stride, inter] (GRN sums of squares per 32-row
+// sub-tile, ss_stride >= ceil(max_len / 32)), gscale [n_utt, inter], w2u [n_utt, pw2.npad * inter] (per-utterance GRN-scaled pwconv2),
+// row_utt [rows] (read only when the block does not fit dwconv_ln_kernel).
+struct ConvNextScratch {
+  float *dw, *nrm, *U, *part;
+  int ss_stride;
+  float *gscale, *w2u;
+  const int* row_utt;
+};
+
+// One ConvNeXtBlock with an AdaptiveLayerNorm (models/generator.py:441-499) over packed rows: nxt = cur + block(cur, style).  sty / lds:
+// the block's style table rows (its norm slot); p16: the 16-bit operand mode of the frame path (0: fp32).  Used by the vocoder
+// (vocoder_body) and by CfmPitchPredictor (cfm_pitch.hip.h).
+inline int convnext_block_forward(hipStream_t st, const Seg& s, const ConvNextW& B, int h, int inter, const float* sty, int lds, int p16, const float* cur,
+                                  float* nxt, const ConvNextScratch& sc) {
+  const long R = s.rows();
+  const int ml = s.max_len();
+  float *dw = sc.dw, *nrm = sc.nrm, *U = sc.U, *part = sc.part, *gscale = sc.gscale, *w2u = sc.w2u;
+  const int ss_stride = sc.ss_stride;
+  const int* row_utt = sc.row_utt;
+  if (h <= kDwLnMaxC && h % 4 == 0 && (B.K == 3 || B.K == 7 || B.K == 15 || B.K == 31)) {
+    // depthwise conv + adaptive LayerNorm in one launch (the [rows, h] intermediate never reaches HBM)
+    // (32-row blocks for the long kernels - half the halo re-reads, two blocks per CU - measured no faster at B = 64: 64 vs 58 us)
+    const dim3 fg(ceil_div(ml, 16), s.n_utt);
+    const size_t fb = (size_t)R * h * (4 + (p16 ? 2 : 4));
+#define STTS_DWLN(KK) STTS_LAUNCH_PROF("dwconv_ln_kernel", fb, (dwconv_ln_kernel<KK, 16>), fg, dim3(256), st, cur, h, h, s.dev, B.dw_wt, B.dw_b, 1e-6f, sty, lds, B.norm.col0, nrm, h, p16)
+    if (B.K == 3) STTS_DWLN(3);
+    else if (B.K == 7) STTS_DWLN(7);
+    else if (B.K == 15) STTS_DWLN(15);
+    else STTS_DWLN(31);
+#undef STTS_DWLN
+  } else {
+    STTS_CHECK(row_utt, "convnext_block_forward: this block needs the row -> utterance table");
+    STTS_LAUNCH_PROF("dwconv_kernel", (size_t)R * h * 2 * 4, (dwconv_kernel<31>), dim3(ceil_div(h, 64), ceil_div(ml, 64), s.n_utt), dim3(256), st, cur, h, dw, h, h, s.dev, B.dw_wt,
+                       B.dw_b, B.K, (int)ACT_NONE);
+    LnOut o0{nrm, h, 0, sty, nullptr, lds, B.norm.col0, p16}, o1{};
+    STTS_TRY(ln_launch(st, dw, h, h, R, row_utt, 1e-6f, 1, 1, o0, o1, ACT_NONE, LnIn{}, s.rows_dev()));
+  }
+  GemmArgs a = gemm_args(s);
+  set_seg(a, 0, nrm, h, 0, B.pw1);
+  a.N = inter; a.bias = B.pw1.bias; a.act = ACT_SILU;
+  a.x16 = p16 != 0;
+  if (p16) { a.Y = nullptr; a.Y16 = reinterpret_cast<unsigned short*>(U); a.ldy16 = inter; }  // GRN's sums of squares come from the fp32 values
+  else { a.Y = U; a.ldy = inter; }
+  a.sumsq_part = part; a.ld_ss = inter; a.ss_stride = ss_stride;
+  STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, B.pw1.npad, s.n_utt, ml));
+  STTS_LAUNCH_PROF("grn_gx_kernel", (size_t)s.n_utt * ss_stride * inter * 4, grn_gx_kernel, dim3(ceil_div(inter, 32), s.n_utt), dim3(256), st, part, inter, ss_stride, s.dev, inter, gscale, inter);
+  GemmArgs b = gemm_args(s);
+  set_seg(b, 0, U, inter, 0, B.pw2);
+  if (B.pw2.prec == PREC_F32 && B.pw2.w16_plane > 0 && x3_enabled()) {
+    // split fp32: GRN's per-(utterance, channel) factor scales the ACTIVATION while pwconv2's tile is staged (the contraction's input affine with
+    // slope 1) instead of a per-utterance copy of the weight: the shared split planes of W stay valid and the scale_weight pass is gone
+    hipLaunchKernelGGL(grn_xaff_kernel, dim3(s.n_utt), dim3(256), 0, st, gscale, inter, B.grn_gamma, w2u, B.pw2.kc, inter);
+    b.xaff = w2u;
+    b.ld_xaff = B.pw2.kc;
+    b.xaff_slope = 1.0f;
+    static const bool no_scale_only = getenv("STTS_XAFF_GENERAL") != nullptr;  // experiments: the general scale / shift / slope form
+    b.xaff_scale_only = B.pw2.kc == inter && !no_scale_only;  // (no pad column: every staged value is a written one)
+  } else {
+    launch_scale_weight(st, dim3(128, s.n_utt), B.pw2.prec, B.pw2.W, gscale, inter, B.grn_gamma, w2u, B.pw2.npad, B.pw2.kc);
+    b.seg[0].W = w2u;
+    b.seg[0].W16 = reinterpret_cast<const unsigned short*>(w2u);
+    b.seg[0].w16_plane = 0;
+    b.seg[0].w_utt_stride = (long)B.pw2.npad * B.pw2.kc;
+  }
+  b.x16 = p16 != 0;
+  b.N = h; b.bias = B.pw2.bias; b.Y = nxt; b.ldy = h; b.R = cur; b.ldr = h;
+  STTS_TRY(launch_conv_gemm(st, b, EPI_STORE, B.pw2.npad, s.n_utt, ml));
+  return 0;
+}
+
 // prior convs (generator.py:412-413) write straight into the concat slots [h, h+hp) of the two head inputs.  The two
 // convs are independent (and independent of decoder/flow), so the caller may put them on different streams.
 inline bool vocoder_rows16(const stts_ctx* c, long rows) { return c->prec != PREC_F32 && rows >= rows16_threshold(); }
@@ -1945,55 +2019,9 @@ inline int vocoder_body(stts_ctx* c, hipStream_t st, const Seg& s, const float* 
   }
   float* cur = xa;
   float* nxt = xb;
+  const ConvNextScratch cs{dw, nrm, U, part, ss_stride, gscale, w2u, row_utt};
   for (int i = 0; i < 4; ++i) {
-    const ConvNextW& B = c->cnx[i];
-    if (h <= kDwLnMaxC && h % 4 == 0 && (B.K == 3 || B.K == 7 || B.K == 15 || B.K == 31)) {
-      // depthwise conv + adaptive LayerNorm in one launch (the [rows, h] intermediate never reaches HBM)
-      // (32-row blocks for the long kernels - half the halo re-reads, two blocks per CU - measured no faster at B = 64: 64 vs 58 us)
-      const dim3 fg(ceil_div(ml, 16), s.n_utt);
-      const size_t fb = (size_t)R * h * (4 + (p16 ? 2 : 4));
-#define STTS_DWLN(KK) STTS_LAUNCH_PROF("dwconv_ln_kernel", fb, (dwconv_ln_kernel<KK, 16>), fg, dim3(256), st, cur, h, h, s.dev, B.dw_wt, B.dw_b, 1e-6f, sty, lds, B.norm.col0, nrm, h, p16)
-      if (B.K == 3) STTS_DWLN(3);
-      else if (B.K == 7) STTS_DWLN(7);
-      else if (B.K == 15) STTS_DWLN(15);
-      else STTS_DWLN(31);
-#undef STTS_DWLN
-    } else {
-      STTS_LAUNCH_PROF("dwconv_kernel", (size_t)R * h * 2 * 4, (dwconv_kernel<31>), dim3(ceil_div(h, 64), ceil_div(ml, 64), s.n_utt), dim3(256), st, cur, h, dw, h, h, s.dev, B.dw_wt,
-                         B.dw_b, B.K, (int)ACT_NONE);
-      LnOut o0{nrm, h, 0, sty, nullptr, lds, B.norm.col0, p16}, o1{};
-      STTS_TRY(ln_launch(st, dw, h, h, R, row_utt, 1e-6f, 1, 1, o0, o1, ACT_NONE, LnIn{}, s.rows_dev()));
-    }
-    GemmArgs a = gemm_args(s);
-    set_seg(a, 0, nrm, h, 0, B.pw1);
-    a.N = inter; a.bias = B.pw1.bias; a.act = ACT_SILU;
-    a.x16 = p16 != 0;
-    if (p16) { a.Y = nullptr; a.Y16 = reinterpret_cast<unsigned short*>(U); a.ldy16 = inter; }  // GRN's sums of squares come from the fp32 values
-    else { a.Y = U; a.ldy = inter; }
-    a.sumsq_part = part; a.ld_ss = inter; a.ss_stride = ss_stride;
-    STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, B.pw1.npad, s.n_utt, ml));
-    STTS_LAUNCH_PROF("grn_gx_kernel", (size_t)s.n_utt * ss_stride * inter * 4, grn_gx_kernel, dim3(ceil_div(inter, 32), s.n_utt), dim3(256), st, part, inter, ss_stride, s.dev, inter, gscale, inter);
-    GemmArgs b = gemm_args(s);
-    set_seg(b, 0, U, inter, 0, B.pw2);
-    if (B.pw2.prec == PREC_F32 && B.pw2.w16_plane > 0 && x3_enabled()) {
-      // split fp32: GRN's per-(utterance, channel) factor scales the ACTIVATION while pwconv2's tile is staged (the contraction's input affine with
-      // slope 1) instead of a per-utterance copy of the weight: the shared split planes of W stay valid and the scale_weight pass is gone
-      hipLaunchKernelGGL(grn_xaff_kernel, dim3(s.n_utt), dim3(256), 0, st, gscale, inter, B.grn_gamma, w2u, B.pw2.kc, inter);
-      b.xaff = w2u;
-      b.ld_xaff = B.pw2.kc;
-      b.xaff_slope = 1.0f;
-      static const bool no_scale_only = getenv("STTS_XAFF_GENERAL") != nullptr;  // experiments: the general scale / shift / slope form
-      b.xaff_scale_only = B.pw2.kc == inter && !no_scale_only;  // (no pad column: every staged value is a written one)
-    } else {
-    launch_scale_weight(st, dim3(128, s.n_utt), B.pw2.prec, B.pw2.W, gscale, inter, B.grn_gamma, w2u, B.pw2.npad, B.pw2.kc);
-    b.seg[0].W = w2u;
-    b.seg[0].W16 = reinterpret_cast<const unsigned short*>(w2u);
-    b.seg[0].w16_plane = 0;
-    b.seg[0].w_utt_stride = (long)B.pw2.npad * B.pw2.kc;
-    }
-    b.x16 = p16 != 0;
-    b.N = h; b.bias = B.pw2.bias; b.Y = nxt; b.ldy = h; b.R = cur; b.ldr = h;
-    STTS_TRY(launch_conv_gemm(st, b, EPI_STORE, B.pw2.npad, s.n_utt, ml));
+    STTS_TRY(convnext_block_forward(st, s, c->cnx[i], h, inter, sty, lds, p16, cur, nxt, cs));
     std::swap(cur, nxt);
   }
   // two AdaLN heads (eps 1e-5) into columns [0,512) of the head inputs (generator.py:417-423)

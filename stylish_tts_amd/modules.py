@@ -14,6 +14,7 @@ Reference classes mirrored (paths relative to /root/reference/src/stylish_tts/tr
   HubertSpeechPredictor       models/speech_predictor.py:132-251
   HubertPitchEnergyPredictor  models/pitch_energy_predictor.py:124-191
   MelStyleEncoder             models/mel_style_encoder.py:120-151
+  CfmPitchPredictor           models/cfm/cfm_pitch_predictor.py:12-51 (+ norm_f0_zscore / denorm_f0_zscore, train/stage_type.py:783-829)
 
 Differences, all additive: forward() of the stochastic modules takes an optional ``noise`` dict with the three draws
 the reference takes from the global torch generator (``prior_noise`` [B,128,4T], ``src_noise`` [B,1,300T],
@@ -36,6 +37,7 @@ from .runtime import HipModel, Segments
 W_DECODER, W_FLOW, W_GENERATOR, W_SPEECH_TEXT, W_DURATION, W_PE_TEXT, W_PE_STYLE, W_PITCH_ENERGY = 1, 2, 4, 8, 16, 32, 64, 128
 W_HUBERT, W_HUBERT_PE = 512, 1024  # hubert_speech_predictor.{phone_encoder, style_encoder}; hubert_pitch_energy_predictor.*
 W_PE_MEL_STYLE, W_CFM_PITCH = 2048, 4096  # pe_mel_style_encoder.*; cfm_pitch_predictor.spk_emb.*
+W_CFM_PITCH_NET = 8192  # cfm_pitch_predictor.{asr_emb, blocks, out_proj}
 
 _ENGINES: Dict[int, HipModel] = {}
 
@@ -624,10 +626,108 @@ class MelStyleEncoder(HipModule):
         return style, out
 
 
-def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int] = None, hubert: bool = False, mel_style: bool = False):
+def norm_f0_zscore(f0, uv, log_f0_mean, log_f0_std):
+    """train/stage_type.py:783-798 for numpy arrays and torch tensors: (log2(f0 + 1e-8) - mean) / std, 0 where uv > 0."""
+    is_torch = isinstance(f0, torch.Tensor)
+    log_f0 = torch.log2(f0 + 1e-8) if is_torch else np.log2(f0 + 1e-8)
+    normed = (log_f0 - log_f0_mean) / log_f0_std
+    if uv is not None:
+        normed[uv > 0] = 0
+    return normed
+
+
+def denorm_f0_zscore(normed_f0, uv, log_f0_mean, log_f0_std, min_hz=50, max_hz=1200):
+    """train/stage_type.py:801-829 for numpy arrays and torch tensors: clamp(2^(x * std + mean), min_hz, max_hz), 0 where uv > 0.
+    log_f0_mean / log_f0_std are the training set's log2 F0 statistics (train/train_context.py:209-214), not part of a checkpoint."""
+    f0 = 2 ** (normed_f0 * log_f0_std + log_f0_mean)
+    f0 = f0.clamp(min=min_hz, max=max_hz) if isinstance(f0, torch.Tensor) else np.clip(f0, a_min=min_hz, a_max=max_hz)
+    if uv is not None:
+        f0[uv > 0] = 0
+    return f0
+
+
+class CfmPitchPredictor(HipModule):
+    """models/cfm/cfm_pitch_predictor.py:12-51: forward(asr [B, asr_dim, T], mel [B, n_mels, Tm]) -> normed F0 [B, 1, T].  The speaker
+    branch (spk_emb, a MelStyleEncoder) is engine component STTS_W_CFM_PITCH, the frame-rate network STTS_W_CFM_PITCH_NET; both load from
+    the reference's full state dict (in_proj is kept and ignored, as forward ignores it).  ``asr_lengths`` / ``mel_lengths`` (optional,
+    [B]) run a ragged batch: each utterance gets what the reference gives it alone, frames past asr_lengths[b] are 0; without them
+    the batch is dense and equals the reference on it."""
+
+    module_name = "cfm_pitch_predictor"
+    components = W_CFM_PITCH | W_CFM_PITCH_NET
+    hidden = 256
+
+    def __init__(self, asr_dim=768, n_mels=80, cfg=None, engine=None):
+        self.asr_dim, self.n_mels = int(asr_dim), int(n_mels)
+        self.min_mel_frames = mel_style_levels(self.n_mels, True)[1]
+        super().__init__(params.cfm_pitch_predictor_spec(self.asr_dim, self.n_mels), cfg or load_model_config(), engine)
+
+    def _load_into(self, eng: HipModel):
+        eng.load_state_dict(self.module_name, self._store)
+
+    def _lengths(self, asr, mel, asr_lengths, mel_lengths):
+        if asr.dim() != 3 or asr.shape[1] != self.asr_dim:
+            raise ValueError(f"CfmPitchPredictor asr must be [B, {self.asr_dim}, T], got shape {tuple(asr.shape)}")
+        if mel.dim() != 3 or mel.shape[1] != self.n_mels or mel.shape[0] != asr.shape[0]:
+            raise ValueError(f"CfmPitchPredictor mel must be [{asr.shape[0]}, {self.n_mels}, Tm], got shape {tuple(mel.shape)}")
+        B, T, Tm = asr.shape[0], asr.shape[2], mel.shape[2]
+        La = [T] * B if asr_lengths is None else [int(v) for v in torch.as_tensor(asr_lengths).tolist()]
+        Lm = [Tm] * B if mel_lengths is None else [int(v) for v in torch.as_tensor(mel_lengths).tolist()]
+        if len(La) != B or any(t < 1 or t > T for t in La):
+            raise ValueError(f"asr_lengths {La} do not fit a batch of {B} x {T} frames")
+        if len(Lm) != B or any(t < 1 or t > Tm for t in Lm):
+            raise ValueError(f"mel_lengths {Lm} do not fit a batch of {B} x {Tm} frames")
+        return La, Lm  # (mels below min_mel_frames are the engine's to reject, as for MelStyleEncoder)
+
+    def forward(self, asr, mel, asr_lengths=None, mel_lengths=None):
+        return self.run(asr, mel, asr_lengths, mel_lengths)[0]
+
+    def speaker_style(self, mel, mel_rows_lengths):
+        """spk_emb(mel) [B, 256] from packed inputs: (mel [B, n_mels, Tm], lengths)."""
+        eng = self.engine
+        sm = Segments(mel_rows_lengths, eng.device)
+        md = _f(mel, eng.device)
+        rows = torch.cat([md[b, :, : mel_rows_lengths[b]].t() for b in range(len(mel_rows_lengths))]).contiguous()
+        return eng.mel_style(W_CFM_PITCH, sm, rows, self.hidden)
+
+    def run(self, asr, mel, asr_lengths=None, mel_lengths=None, f0_log2_stats=None, uv=None, taps: bool = False):
+        """(normed [B, 1, T], hz [B, 1, T] or None, taps or None).  f0_log2_stats = (log2 mean, log2 std) also gives
+        denorm_f0_zscore(normed, uv, mean, std) from the same launch (uv [B, T] or [B, 1, T], > 0 = unvoiced); taps = the asr_emb
+        output and the four block outputs as lists of per-utterance [256, T_b] tensors."""
+        La, Lm = self._lengths(asr, mel, asr_lengths, mel_lengths)
+        eng = self.engine
+        dev = eng.device
+        B, T = asr.shape[0], asr.shape[2]
+        spk = self.speaker_style(mel, Lm)
+        sa = Segments(La, dev)
+        rows = _pack_rows(eng, asr, La)
+        uv_rows = None
+        if uv is not None:
+            u = torch.as_tensor(uv).to(dev, torch.float32).reshape(B, T)
+            uv_rows = torch.cat([u[b, : La[b]] for b in range(B)]).contiguous()
+        res = eng.cfm_pitch(sa, rows, spk, f0_log2_stats=f0_log2_stats, uv=uv_rows, taps=taps)
+        res = res if isinstance(res, tuple) else (res,)
+
+        def dense(x):
+            out = torch.zeros(B, 1, T, dtype=torch.float32, device=dev)
+            for b in range(B):
+                out[b, 0, : La[b]] = x[sa.host[b] : sa.host[b + 1]]
+            return out
+
+        normed = dense(res[0])
+        hz = dense(res[1]) if f0_log2_stats is not None else None
+        tp = None
+        if taps:
+            t = res[-1]
+            tp = [[t[k, sa.host[b] : sa.host[b + 1]].t() for b in range(B)] for k in range(5)]
+        return normed, hz, tp
+
+
+def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int] = None, hubert: bool = False, mel_style: bool = False,
+                            cfm_pitch: bool = False):
     """The five modules of the inference composition (models/models.py:32-63, :79-101), optionally with synthetic weights.
     hubert=True adds the voice-conversion pair hubert_speech_predictor / hubert_pitch_energy_predictor (models/models.py:92-101);
-    mel_style=True adds pe_mel_style_encoder (models/models.py:57-62)."""
+    mel_style=True adds pe_mel_style_encoder (models/models.py:57-62); cfm_pitch=True adds cfm_pitch_predictor (models/models.py:72-75)."""
     cfg = cfg or load_model_config()
     m = dict(
         speech_predictor=SpeechPredictor(cfg, engine=engine),
@@ -646,6 +746,8 @@ def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int]
     if mel_style:
         ms = Record(cfg.get("mel_style_encoder") or DEFAULT_MODEL["mel_style_encoder"])  # model.yml section, config.DEFAULT_MODEL when absent
         m["pe_mel_style_encoder"] = MelStyleEncoder(cfg.n_mels, cfg.style_dim, ms.max_channels, ms.skip_downsample, cfg=cfg, engine=engine)
+    if cfm_pitch:
+        m["cfm_pitch_predictor"] = CfmPitchPredictor(hubert_dims(cfg)[0], cfg.n_mels, cfg=cfg, engine=engine)
     if synthetic_seed is not None:
         for mod in m.values():
             mod.load_synthetic(synthetic_seed)

@@ -412,8 +412,32 @@ def pe_mel_style_encoder_spec(cfg) -> Spec:
     return mel_style_encoder_spec(cfg.n_mels, cfg.style_dim, ms.max_channels, ms.skip_downsample)
 
 
-# the mel style encoders (models/models.py:57-62): known to module_spec, outside the text-to-speech composition
-MEL_STYLE_MODULE_SPECS = {"pe_mel_style_encoder": pe_mel_style_encoder_spec}
+def cfm_pitch_predictor_spec(asr_dim: int, n_mels: int) -> Spec:
+    """CfmPitchPredictor (models/cfm/cfm_pitch_predictor.py:12-39), in the reference's state_dict() order: asr_emb, spk_emb (a
+    MelStyleEncoder(n_mels, 256, 1024, skip_downsamples=True)), four generator ConvNeXt blocks (256, 1024, style 256, k 7), the unused
+    in_proj, out_proj."""
+    h = 256
+    s: Spec = _conv("asr_emb.0", 4 * h, asr_dim, 1) + _conv("asr_emb.2", h, 4 * h, 1)
+    s += mel_style_encoder_spec(n_mels, h, 4 * h, True, p="spk_emb.")
+    for i in range(4):
+        q = f"blocks.{i}."
+        s += [(q + "dwconv.weight", (h, 1, 7), "w"), (q + "dwconv.bias", (h,), "b")]
+        s += _adain(q + "norm", h, h)
+        s += _linear(q + "pwconv1", 4 * h, h)
+        s += [(q + "grn.gamma", (1, 1, 4 * h), "grn"), (q + "grn.beta", (1, 1, 4 * h), "grn")]
+        s += _linear(q + "pwconv2", h, 4 * h)
+    return s + _conv("in_proj", h, 1, 1) + _conv("out_proj", 1, h, 1)
+
+
+def cfm_pitch_predictor_module_spec(cfg) -> Spec:
+    """cfm_pitch_predictor (models/models.py:72-75): asr_dim = hubert.hidden_dim, n_mels from the model config."""
+    from .config import hubert_dims
+
+    return cfm_pitch_predictor_spec(hubert_dims(cfg)[0], cfg.n_mels)
+
+
+# the mel style encoders (models/models.py:57-62) and the CFM pitch predictor: known to module_spec, outside the text-to-speech composition
+MEL_STYLE_MODULE_SPECS = {"pe_mel_style_encoder": pe_mel_style_encoder_spec, "cfm_pitch_predictor": cfm_pitch_predictor_module_spec}
 
 
 def module_spec(module: str, cfg) -> Spec:

@@ -225,10 +225,14 @@ class VoiceConverter:
 
     @torch.no_grad()
     def convert(self, features, lengths, spk_emb, pitch=None, energy=None, noise: Optional[Dict[str, torch.Tensor]] = None,
-                return_details: bool = False):
+                return_details: bool = False, ref_mel=None, ref_mel_lengths=None, f0_log2_stats=None, uv=None):
         """features [B, hubert_dim, T] (mel-frame rate, zero padded past lengths[b]), spk_emb [B, spk_dim]; optional pitch / energy
         [B, T] replace the predicted curves; noise: the packed draws of ``Synthesizer`` (prior_noise [4 sum T, 128], src_noise
-        [4 sum T * hop / 4], init_phase [1]).  -> list of B float waveforms (hop_length samples per frame)."""
+        [4 sum T * hop / 4], init_phase [1]).  -> list of B float waveforms (hop_length samples per frame).
+        ref_mel [B, n_mels, Tm] (normalised mel of the target speaker, ref_mel_lengths [B] optional): F0 comes from the CFM pitch predictor
+        (cfm_pitch_predictor: STTS_W_CFM_PITCH | STTS_W_CFM_PITCH_NET on this engine) on the same features, denormed on the device with
+        f0_log2_stats = (log2 mean, log2 std) of the training set, 0 where uv [B, T] > 0; energy is HubertPitchEnergyPredictor's unless
+        given."""
         from .config import check_width
         from .modules import _pack_curve, _pack_rows, _f
 
@@ -242,13 +246,33 @@ class VoiceConverter:
         L = [int(v) for v in torch.as_tensor(lengths).tolist()]
         if len(L) != features.shape[0] or spk_emb.shape[0] != len(L) or min(L) <= 0 or max(L) > features.shape[2]:
             raise ValueError(f"lengths {L} do not describe features of shape {tuple(features.shape)} / {spk_emb.shape[0]} speaker embeddings")
-        if (pitch is None) != (energy is None):
+        cfm = ref_mel is not None
+        if cfm:
+            if pitch is not None:
+                raise ValueError("give ref_mel (F0 from the CFM pitch predictor) or pitch, not both")
+            if f0_log2_stats is None:
+                raise ValueError("ref_mel needs f0_log2_stats = (log2 F0 mean, log2 F0 std) of the training set")
+            if ref_mel.dim() != 3 or ref_mel.shape[0] != len(L):
+                raise ValueError(f"ref_mel must be [{len(L)}, n_mels, Tm], got shape {tuple(ref_mel.shape)}")
+            Lm = [ref_mel.shape[2]] * len(L) if ref_mel_lengths is None else [int(v) for v in torch.as_tensor(ref_mel_lengths).tolist()]
+            if len(Lm) != len(L) or min(Lm) < 1 or max(Lm) > ref_mel.shape[2]:
+                raise ValueError(f"ref_mel_lengths {Lm} do not fit ref_mel of shape {tuple(ref_mel.shape)}")
+        elif (pitch is None) != (energy is None):
             raise ValueError("give both pitch and energy, or neither")
         st = Segments(L, dev)
         st4 = st.scaled(4)
         feats = _pack_rows(eng, features, L)
-        style, pe_style = eng.speaker_style(_f(spk_emb, dev), pe_style=pitch is None)
-        if pitch is None:
+        style, pe_style = eng.speaker_style(_f(spk_emb, dev), pe_style=energy is None)
+        if cfm:
+            from .modules import W_CFM_PITCH
+
+            md = _f(ref_mel, dev)
+            mel_rows = torch.cat([md[b, :, : Lm[b]].t() for b in range(len(L))]).contiguous()
+            spk = eng.mel_style(W_CFM_PITCH, Segments(Lm, dev), mel_rows, 256)
+            uv_rows = _pack_curve(uv, L, dev) if uv is not None else None
+            _, f0 = eng.cfm_pitch(st, feats, spk, f0_log2_stats=f0_log2_stats, uv=uv_rows)
+            en = eng.hubert_pitch_energy(st, feats, pe_style)[1] if energy is None else _pack_curve(energy, L, dev)
+        elif pitch is None:
             f0, en = eng.hubert_pitch_energy(st, feats, pe_style)
         else:
             f0, en = _pack_curve(pitch, L, dev), _pack_curve(energy, L, dev)

@@ -425,3 +425,36 @@ class HipModel:
             return out, taps
         _lib.check(self.lib.stts_mel_style_forward(*args, _ptr(ws), ws.numel()))
         return out
+
+    # ------------------------------------------------------------------ CfmPitchPredictor, frame-rate network (packed pitch frames)
+    def cfm_pitch(self, seg: Segments, asr_rows: torch.Tensor, spk_style: torch.Tensor, f0_log2_stats=None, uv: Optional[torch.Tensor] = None,
+                  taps: bool = False):
+        """asr_rows [rows_T, ld >= asr_dim] packed time-major, spk_style [n_utt, 256] (mel_style(W_CFM_PITCH)) -> normed F0 [rows_T];
+        with f0_log2_stats = (log2 mean, log2 std) also F0 in Hz [rows_T] (denorm_f0_zscore; uv [rows_T] > 0 -> 0), returned as
+        (normed, hz); taps=True appends [5, rows_T, 256] (asr_emb output, then each ConvNeXt block's).  include/stylish_hip.h,
+        stts_cfm_pitch_forward."""
+        need = int(self.lib.stts_cfm_pitch_workspace_bytes(self.ctx, seg.rows, seg.n))
+        if need == 0:
+            _lib.check(1)  # the weights are not finalized: the library's message
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        with self._ws_lock:
+            wsd = self.__dict__.setdefault("_cpws", {})
+            ws = wsd.get(key)
+            if ws is None or ws.numel() < need:
+                ws = wsd[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        normed = self._f32(seg.rows)
+        hz = self._f32(seg.rows) if f0_log2_stats is not None else None
+        mean, std = (float(f0_log2_stats[0]), float(f0_log2_stats[1])) if f0_log2_stats is not None else (0.0, 1.0)
+        if uv is not None:
+            uv = uv.to(self.device, torch.float32).contiguous()
+        spk = spk_style.to(self.device, torch.float32).contiguous()
+        args = (self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(asr_rows), asr_rows.shape[1], _ptr(spk), _ptr(normed),
+                _ptr(hz), mean, std, _ptr(uv))
+        out = [normed] + ([hz] if hz is not None else [])
+        if taps:
+            t = self._f32(5, seg.rows, 256)
+            _lib.check(self.lib.stts_cfm_pitch_forward_taps(*args, _ptr(t), _ptr(ws), ws.numel()))
+            out.append(t)
+        else:
+            _lib.check(self.lib.stts_cfm_pitch_forward(*args, _ptr(ws), ws.numel()))
+        return out[0] if len(out) == 1 else tuple(out)
