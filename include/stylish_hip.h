@@ -68,7 +68,8 @@ enum {
   STTS_W_HUBERT_PE = 1024,   /* hubert_pitch_energy_predictor.* (not part of STTS_W_ALL)   models/pitch_energy_predictor.py:124-191 */
   STTS_W_PE_MEL_STYLE = 2048, /* pe_mel_style_encoder.* (not part of STTS_W_ALL)            models/models.py:57-62 */
   STTS_W_CFM_PITCH = 4096,   /* cfm_pitch_predictor.spk_emb.* (not part of STTS_W_ALL)     models/cfm/cfm_pitch_predictor.py:25-27 */
-  STTS_W_CFM_PITCH_NET = 8192 /* cfm_pitch_predictor.{asr_emb, blocks, out_proj} (in_proj.* is accepted and ignored; not part of STTS_W_ALL) */
+  STTS_W_CFM_PITCH_NET = 8192, /* cfm_pitch_predictor.{asr_emb, blocks, out_proj} (in_proj.* is accepted and ignored; not part of STTS_W_ALL) */
+  STTS_W_SSL = 16384         /* hubert.model.* = AdaptiveHubert (finalized by stts_ssl_finalize, not part of STTS_W_ALL)      train/models/ssl.py:16-31 */
 };
 int stts_finalize_weights(stts_ctx* ctx, int which);
 /* Operand precision of the FRAME-RATE Conv1d / Linear contractions (call before the first stts_finalize_weights).
@@ -239,6 +240,40 @@ int stts_cfm_estimator(stts_ctx* ctx, void* stream, int n_utt, const int32_t* se
                        const float* asr, int ld_asr, const float* f0, const float* n_curve, const int32_t* curve_off_host,
                        const int32_t* curve_off_dev, const float* spk_emb, const float* t, const float* sine_noise, float* out, int ld_out,
                        void* workspace, size_t workspace_bytes);
+
+/* ---- AdaptiveHubert, the HuBERT content encoder of the voice-conversion stages (train/models/ssl.py:16-31, called as
+ * train.hubert(audio, time_dim), train/stage_type.py:685-688): the transformers HuBERT graph in eval mode with feat_extract_norm "group",
+ * do_stable_layer_norm false, conv_bias false and exact GELU, then F.interpolate(mode="nearest", size=time_dim) over the frames.  Its
+ * dimensions are the HubertConfig fields, hence this struct (conv lists: the first num_feat_extract_layers entries count).
+ * Weights: stts_load_weight(ctx, "hubert.<AdaptiveHubert state_dict key>", ...), i.e. "hubert.model.feature_extractor..." (the positional
+ * conv in either weight-norm spelling; masked_spec_embed and final_proj.* are accepted and ignored), then stts_ssl_finalize.
+ * wave: packed mono samples at hubert.sr, utterance u = [sample_off[u], sample_off[u + 1]); off_T: the time_dim of every utterance as row
+ * offsets of feats [rows_T, ld_feats] (ld_feats a multiple of 4 covering hidden_size padded to 32, pad columns written as zeros) - the
+ * layout stts_hubert_encoder_forward / stts_cfm_pitch_forward take.  Every statistic and every attention stays inside the utterance (the
+ * reference at B = 1); an utterance's rows are the same bit for bit alone and in any batch.  Always fp32, whatever stts_set_precision chose
+ * (dense contractions in the split-fp32 form, on the f32 matrix cores for STTS_PREC_F32_NATIVE; positional conv and attention on the f32 matrix cores).  An utterance shorter than the feature extractor's receptive field (400 samples for HuBERT-base), or a
+ * time_dim of 0, is an error status. */
+typedef struct stts_ssl_dims {
+  int32_t hidden_size, num_hidden_layers, num_attention_heads, intermediate_size, num_feat_extract_layers;
+  int32_t conv_dim[8], conv_kernel[8], conv_stride[8];
+  int32_t num_conv_pos_embeddings, num_conv_pos_embedding_groups;
+  float layer_norm_eps;
+} stts_ssl_dims;
+int stts_ssl_finalize(stts_ctx* ctx, const stts_ssl_dims* dims);
+/* frames of the feature extractor for an utterance of `samples` samples (0: too short, the reference raises) */
+int64_t stts_ssl_frames(const stts_ssl_dims* dims, int64_t samples);
+size_t stts_ssl_workspace_bytes(const stts_ctx* ctx, int n_utt, const int32_t* sample_off_host);
+int stts_ssl_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const float* wave,
+                     const int32_t* off_T_host, const int32_t* off_T_dev, float* feats, int ld_feats, void* ws, size_t ws_bytes);
+/* The same, plus intermediate rows for the tests (any may be null).  conv0 [rows0, conv_dim[0]]: layer 0 after GroupNorm + GELU, utterance u's
+ * frames from row conv0_off[u] on (conv0_off: device int32 [n_utt + 1]; rows0 = conv0_rows of stts_ssl_tap_rows); the others are packed at
+ * the utterances' frame counts: conv_last [frames, conv_dim[-1]], proj [frames, hidden] after the feature projection, pos after positional
+ * conv + LayerNorm, layers [num_hidden_layers][frames, hidden], hidden = the last hidden state. */
+int stts_ssl_forward_taps(stts_ctx* ctx, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const float* wave,
+                          const int32_t* off_T_host, const int32_t* off_T_dev, float* feats, int ld_feats, float* conv0, int32_t* conv0_off,
+                          float* conv_last, float* proj, float* pos, float* layers, float* hidden, void* ws, size_t ws_bytes);
+/* rows of the conv0 tap buffer of a call (its utterances start at multiples of the later strides' product) */
+int64_t stts_ssl_tap_rows(const stts_ssl_dims* dims, int n_utt, const int32_t* sample_off_host);
 
 /* ---- HuBERT voice conversion (the reference's hubert_acoustic models, train/stage_type.py:907-1015).  Inputs are HuBERT features at the
  * mel-frame rate as packed time-major rows feats [rows_T, ld_feats] (ld_feats a multiple of 4 covering hubert.hidden_dim padded to 32, pad

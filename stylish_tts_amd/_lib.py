@@ -89,6 +89,12 @@ SIGNATURES = {
     "stts_cfm_pitch_workspace_bytes": (_SZ, [_P, _I64, _I]),
     "stts_cfm_pitch_forward": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, C.c_float, C.c_float, _P, _P, _SZ]),
     "stts_cfm_pitch_forward_taps": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _SZ]),
+    "stts_ssl_finalize": (_I, [_P, _P]),
+    "stts_ssl_frames": (_I64, [_P, _I64]),
+    "stts_ssl_workspace_bytes": (_SZ, [_P, _I, _P]),
+    "stts_ssl_forward": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _SZ]),
+    "stts_ssl_forward_taps": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _SZ]),
+    "stts_ssl_tap_rows": (_I64, [_P, _I, _P]),
     "stts_cfm_finalize": (_I, [_P, _P]),
     "stts_cfm_workspace_bytes": (_SZ, [_P, _I64, _I]),
     "stts_cfm_estimator": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _SZ]),

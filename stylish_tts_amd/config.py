@@ -90,7 +90,8 @@ DEFAULT_MODEL = {
     },
     "pitch_energy_predictor": {"inter_dim": 256, "dropout": 0.2},
     # feature extractors whose OUTPUT WIDTHS size the flow-matching mel decoder (model.yml:68-74; the extractors themselves are given tensors)
-    "hubert": {"hidden_dim": 768},
+    # (hubert.sr and the optional hubert.arch - HubertConfig fields, base values when absent - shape the content encoder itself: hubert_ssl_config)
+    "hubert": {"hidden_dim": 768, "sr": 16000},
     "mel_style_encoder": {"max_channels": 384, "skip_downsample": True},
     "speaker_embedder": {"hidden_dim": 10240},
     # text symbols (model.yml:81-85); index = position in pad + punctuation + letters + letters_ipa
@@ -159,6 +160,19 @@ def hubert_dims(cfg) -> tuple:
             raise ValueError(f"{section}.hidden_dim {v} is not a positive integer")
         out.append(int(v))
     return tuple(out)
+
+
+def hubert_ssl_config(cfg) -> tuple:
+    """(hubert.sr, arch) of the HuBERT content encoder (model.yml:68-71): ``sr`` defaults to 16000, ``hubert.arch`` is an optional mapping of
+    transformers HubertConfig fields over the HuBERT-base values (hubert_ssl.ARCH_DEFAULTS).  Raises ValueError naming the field for an
+    unsupported graph, a non-positive rate, or an arch.hidden_size that is not hubert.hidden_dim."""
+    from .hubert_ssl import DEFAULT_SR, arch_from_model_config
+
+    a = arch_from_model_config(cfg)
+    sr = (cfg.get("hubert") or {}).get("sr", DEFAULT_SR)
+    if isinstance(sr, bool) or int(sr) != sr or int(sr) <= 0:
+        raise ValueError(f"hubert.sr {sr} is not a positive integer")
+    return int(sr), a
 
 
 def check_width(what: str, got: int, key: str, expected: int) -> None:

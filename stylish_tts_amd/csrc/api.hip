@@ -5,6 +5,7 @@
 #include "hubert.hip.h"
 #include "mel_style.hip.h"
 #include "cfm_pitch.hip.h"
+#include "ssl.hip.h"
 
 using namespace stts;
 
@@ -583,6 +584,112 @@ int stts_profile_report(void* stream, char* json, size_t cap) {
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ AdaptiveHubert (ssl.hip.h)
+static int ssl_dims_from(const stts_ssl_dims* dims, SslDims* d) {
+  STTS_CHECK(dims, "ssl: null dims");
+  STTS_CHECK(dims->num_feat_extract_layers >= 1 && dims->num_feat_extract_layers <= kSslMaxConv, "ssl: num_feat_extract_layers %d outside [1, %d]",
+             dims->num_feat_extract_layers, kSslMaxConv);
+  d->hidden = dims->hidden_size; d->layers = dims->num_hidden_layers; d->heads = dims->num_attention_heads; d->inter = dims->intermediate_size;
+  d->n_conv = dims->num_feat_extract_layers;
+  for (int i = 0; i < d->n_conv; ++i) {
+    d->conv_dim[i] = dims->conv_dim[i]; d->conv_k[i] = dims->conv_kernel[i]; d->conv_s[i] = dims->conv_stride[i];
+    STTS_CHECK(d->conv_k[i] >= 1 && d->conv_s[i] >= 1, "ssl: conv_kernel[%d] / conv_stride[%d] must be positive", i, i);
+  }
+  d->pos_k = dims->num_conv_pos_embeddings; d->pos_groups = dims->num_conv_pos_embedding_groups; d->eps = dims->layer_norm_eps;
+  return 0;
+}
+
+int stts_ssl_finalize(stts_ctx* c, const stts_ssl_dims* dims) {
+  API_BEGIN
+  STTS_CHECK(c && dims, "null argument");
+  STTS_HIP(hipSetDevice(c->device));
+  TagReset tag_reset{c};
+  c->ready &= ~STTS_W_SSL;
+  free_component_allocs(c, STTS_W_SSL);
+  SslDims d;
+  STTS_TRY(ssl_dims_from(dims, &d));
+  auto m = std::make_shared<SslW>();
+  c->cur_tag = STTS_W_SSL;
+  // fp32 whatever the precision, as the other voice-conversion front ends; the dense contractions in the split-fp32 form (weights packed with their
+  // three bf16 planes) unless the engine is STTS_PREC_F32_NATIVE (ssl.hip.h says which tile they run and why)
+  const int saved_prec = c->prec, saved_align = c->kc_align;
+  c->prec = PREC_F32;
+  c->kc_align = 32;
+  const int rc = finalize_ssl(c, d, m.get());
+  c->prec = saved_prec;
+  c->kc_align = saved_align;
+  c->cur_tag = 0;
+  if (rc) return rc;
+  c->ssl = m;
+  c->ready |= STTS_W_SSL;
+  STTS_HIP(hipDeviceSynchronize());
+  return 0;
+  API_END
+}
+
+int64_t stts_ssl_frames(const stts_ssl_dims* dims, int64_t samples) {
+  SslDims d;
+  if (ssl_dims_from(dims, &d) != 0 || samples < 0) return 0;
+  return ssl_frames_host(d, samples);
+}
+
+static int ssl_check_offsets(const SslDims& d, int n_utt, const int32_t* sample_off_host) {
+  STTS_CHECK(n_utt > 0 && sample_off_host && sample_off_host[0] == 0, "ssl: bad sample offsets");
+  for (int u = 0; u < n_utt; ++u) {
+    const long n = (long)sample_off_host[u + 1] - sample_off_host[u];
+    STTS_CHECK(n > 0 && ssl_frames_host(d, n) > 0, "ssl: utterance %d has %ld samples, fewer than one frame of the feature extractor needs", u, n);
+  }
+  return 0;
+}
+
+size_t stts_ssl_workspace_bytes(const stts_ctx* c, int n_utt, const int32_t* sample_off_host) {
+  if (!c || !c->ssl || !(c->ready & STTS_W_SSL)) return 0;
+  const SslW& M = *static_cast<const SslW*>(c->ssl.get());
+  if (ssl_check_offsets(M.d, n_utt, sample_off_host) != 0) return 0;
+  return ssl_workspace_bytes(M, n_utt, sample_off_host);
+}
+
+int64_t stts_ssl_tap_rows(const stts_ssl_dims* dims, int n_utt, const int32_t* sample_off_host) {
+  SslDims d;
+  if (ssl_dims_from(dims, &d) != 0 || ssl_check_offsets(d, n_utt, sample_off_host) != 0) return 0;
+  SslPlan P;
+  ssl_plan(d, n_utt, sample_off_host, &P);
+  return (int64_t)P.cap_off[n_utt] * ssl_geom(d).D[0];
+}
+
+static int ssl_entry(stts_ctx* c, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const float* wave,
+                     const int32_t* off_T_host, const int32_t* off_T_dev, float* feats, int ld_feats, const SslTaps* taps, void* ws, size_t ws_bytes) {
+  STTS_CHECK(c && c->ssl && (c->ready & STTS_W_SSL), "the AdaptiveHubert weights are not finalized (stts_ssl_finalize)");
+  const SslW& M = *static_cast<const SslW*>(c->ssl.get());
+  STTS_CHECK(sample_off_dev && wave && off_T_host && off_T_dev && feats && ws, "ssl: null argument");
+  STTS_TRY(ssl_check_offsets(M.d, n_utt, sample_off_host));
+  STTS_CHECK(off_T_host[0] == 0, "ssl: bad time_dim offsets");
+  for (int u = 0; u < n_utt; ++u) STTS_CHECK(off_T_host[u + 1] > off_T_host[u], "ssl: utterance %d has a time_dim of %d", u, off_T_host[u + 1] - off_T_host[u]);
+  STTS_CHECK(ld_feats >= round_up(M.d.hidden, 32) && ld_feats % 4 == 0, "feature rows: ld_feats %d must be a multiple of 4 covering %d columns (hidden_size %d padded to 32)",
+             ld_feats, round_up(M.d.hidden, 32), M.d.hidden);
+  STTS_HIP(hipSetDevice(c->device));
+  Seg sT{n_utt, off_T_host, off_T_dev};
+  Arena a(ws, ws_bytes);
+  return ssl_forward(M, (hipStream_t)stream, n_utt, sample_off_host, sample_off_dev, wave, sT, feats, ld_feats, taps, a);
+}
+
+int stts_ssl_forward(stts_ctx* c, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const float* wave,
+                     const int32_t* off_T_host, const int32_t* off_T_dev, float* feats, int ld_feats, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  return ssl_entry(c, stream, n_utt, sample_off_host, sample_off_dev, wave, off_T_host, off_T_dev, feats, ld_feats, nullptr, ws, ws_bytes);
+  API_END
+}
+
+int stts_ssl_forward_taps(stts_ctx* c, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const float* wave,
+                          const int32_t* off_T_host, const int32_t* off_T_dev, float* feats, int ld_feats, float* conv0, int32_t* conv0_off,
+                          float* conv_last, float* proj, float* pos, float* layers, float* hidden, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  SslTaps t;
+  t.conv0 = conv0; t.conv0_off = conv0_off; t.conv_last = conv_last; t.proj = proj; t.pos = pos; t.layers = layers; t.hidden = hidden;
+  return ssl_entry(c, stream, n_utt, sample_off_host, sample_off_dev, wave, off_T_host, off_T_dev, feats, ld_feats, &t, ws, ws_bytes);
+  API_END
+}
 
 // ------------------------------------------------------------------------------------------------ HuBERT voice conversion (hubert.hip.h)
 extern "C" {

@@ -195,6 +195,7 @@ struct stts_ctx {
   std::shared_ptr<void> hubert;   // stts::HubertModel (hubert.hip.h)
   std::shared_ptr<void> mel_style;  // stts::MelStyleModel (mel_style.hip.h)
   std::shared_ptr<void> cfm_pitch;  // stts::CfmPitchNetW (cfm_pitch.hip.h)
+  std::shared_ptr<void> ssl;        // stts::SslW (ssl.hip.h)
 };
 
 namespace stts {

@@ -38,6 +38,7 @@ W_DECODER, W_FLOW, W_GENERATOR, W_SPEECH_TEXT, W_DURATION, W_PE_TEXT, W_PE_STYLE
 W_HUBERT, W_HUBERT_PE = 512, 1024  # hubert_speech_predictor.{phone_encoder, style_encoder}; hubert_pitch_energy_predictor.*
 W_PE_MEL_STYLE, W_CFM_PITCH = 2048, 4096  # pe_mel_style_encoder.*; cfm_pitch_predictor.spk_emb.*
 W_CFM_PITCH_NET = 8192  # cfm_pitch_predictor.{asr_emb, blocks, out_proj}
+W_SSL = 16384  # hubert.model.* (AdaptiveHubert; finalized by stts_ssl_finalize)
 
 _ENGINES: Dict[int, HipModel] = {}
 
@@ -723,11 +724,99 @@ class CfmPitchPredictor(HipModule):
         return normed, hz, tp
 
 
+class AdaptiveHubert(HipModule):
+    """train/models/ssl.py:16-31: wave [B, samples] at ``hubert_sr`` -> HuBERT features [B, hidden, time_dim] (last_hidden_state resampled to
+    time_dim frames by F.interpolate's nearest rule).  ``hubert_path``: a LOCAL directory with config.json and model.safetensors (or
+    pytorch_model.bin); nothing is ever downloaded.  Without it ``config`` (HubertConfig fields, hubert_ssl.arch) shapes the network and
+    load_state_dict takes the reference's keys (``model.*``; masked_spec_embed and final_proj.* are stored and unused).
+    ``lengths`` (optional, [B] samples) runs a ragged batch: each utterance gets what the reference gives it alone (the reference's own
+    padded batch lets GroupNorm, the positional conv and the attention see the padding); without it the batch is dense and equals the
+    reference on it.  The reference resamples model_sr -> hubert_sr first; this shim takes audio that already is at hubert_sr."""
+
+    module_name = "hubert"
+    components = W_SSL
+
+    def __init__(self, hubert_path=None, model_sr: int = 24000, hubert_sr: int = 16000, config=None, cfg=None, engine=None):
+        from . import hubert_ssl
+
+        sd = None
+        if hubert_path is not None:
+            import json
+            import os
+
+            with open(os.path.join(hubert_path, "config.json"), "r", encoding="utf-8") as f:
+                config = json.load(f)
+            st = os.path.join(hubert_path, "model.safetensors")
+            if os.path.exists(st):
+                from safetensors.torch import load_file
+
+                sd = load_file(st)
+            else:
+                sd = torch.load(os.path.join(hubert_path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
+        self.arch = hubert_ssl.arch(config)
+        self.model_sr, self.sr = int(model_sr), int(hubert_sr)
+        self.hidden = self.arch["hidden_size"]
+        super().__init__(params.hubert_ssl_spec(self.arch), cfg or load_model_config(), engine)
+        if sd is not None:
+            self.load_state_dict({(k if k.startswith("model.") else "model." + k): v for k, v in sd.items()}, strict=False)
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        # older checkpoints spell the positional conv's weight norm weight_g / weight_v
+        q = "model.encoder.pos_conv_embed.conv."
+        sd = dict(state_dict)
+        if q + "weight_g" in sd:
+            sd[q + "parametrizations.weight.original0"] = sd.pop(q + "weight_g")
+            sd[q + "parametrizations.weight.original1"] = sd.pop(q + "weight_v")
+        return super().load_state_dict(sd, strict=strict, assign=assign)
+
+    def _bind(self):
+        eng = self._engine
+        owners = eng.__dict__.setdefault("_owners", {})
+        if self._dirty or owners.get(W_SSL) is not self:
+            self._load_into(eng)
+            eng.ssl_finalize(self.arch)
+            owners[W_SSL] = self
+            self._dirty = False
+
+    def frames(self, samples: int) -> int:
+        from . import hubert_ssl
+
+        return hubert_ssl.frames(samples, self.arch)
+
+    def _lengths(self, wave, lengths):
+        if wave.dim() != 2:
+            raise ValueError(f"AdaptiveHubert input must be [B, samples], got shape {tuple(wave.shape)}")
+        B, S = wave.shape
+        L = [S] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).tolist()]
+        if len(L) != B or any(n < 1 or n > S for n in L):
+            raise ValueError(f"lengths {L} do not fit a batch of {B} x {S} samples")
+        for n in L:
+            self.frames(n)  # ValueError below the receptive field, where the reference raises
+        return L
+
+    def packed(self, wave, time_dims, lengths=None, taps: bool = False):
+        """Packed rows [sum time_dims, ld] (the ``feats`` of the engine's HuBERT stages) for per-utterance ``time_dims``."""
+        L = self._lengths(wave, lengths)
+        T = [int(t) for t in time_dims]
+        if len(T) != len(L) or min(T) < 1:
+            raise ValueError(f"time_dim {T} must be one positive frame count per utterance")
+        eng = self.engine
+        wd = _f(wave, eng.device)
+        flat = torch.cat([wd[b, : L[b]] for b in range(len(L))]).contiguous()
+        return eng.hubert_ssl(Segments(L, eng.device), flat, Segments(T, eng.device), taps=taps)
+
+    def forward(self, wave, time_dim, lengths=None):
+        B, T = wave.shape[0], int(time_dim)
+        rows = self.packed(wave, [T] * B, lengths)
+        return rows[:, : self.hidden].reshape(B, T, self.hidden).permute(0, 2, 1).contiguous()
+
+
 def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int] = None, hubert: bool = False, mel_style: bool = False,
-                            cfm_pitch: bool = False):
+                            cfm_pitch: bool = False, ssl: bool = False):
     """The five modules of the inference composition (models/models.py:32-63, :79-101), optionally with synthetic weights.
     hubert=True adds the voice-conversion pair hubert_speech_predictor / hubert_pitch_energy_predictor (models/models.py:92-101);
-    mel_style=True adds pe_mel_style_encoder (models/models.py:57-62); cfm_pitch=True adds cfm_pitch_predictor (models/models.py:72-75)."""
+    mel_style=True adds pe_mel_style_encoder (models/models.py:57-62); cfm_pitch=True adds cfm_pitch_predictor (models/models.py:72-75);
+    ssl=True adds hubert, the AdaptiveHubert content encoder shaped by hubert.arch / hubert.sr (train/models/ssl.py:16-31)."""
     cfg = cfg or load_model_config()
     m = dict(
         speech_predictor=SpeechPredictor(cfg, engine=engine),
@@ -748,6 +837,11 @@ def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int]
         m["pe_mel_style_encoder"] = MelStyleEncoder(cfg.n_mels, cfg.style_dim, ms.max_channels, ms.skip_downsample, cfg=cfg, engine=engine)
     if cfm_pitch:
         m["cfm_pitch_predictor"] = CfmPitchPredictor(hubert_dims(cfg)[0], cfg.n_mels, cfg=cfg, engine=engine)
+    if ssl:
+        from .config import hubert_ssl_config
+
+        sr, a = hubert_ssl_config(cfg)
+        m["hubert"] = AdaptiveHubert(None, cfg.sample_rate, sr, config=a, cfg=cfg, engine=engine)
     if synthetic_seed is not None:
         for mod in m.values():
             mod.load_synthetic(synthetic_seed)

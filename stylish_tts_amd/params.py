@@ -437,6 +437,47 @@ def cfm_pitch_predictor_module_spec(cfg) -> Spec:
 
 
 # the mel style encoders (models/models.py:57-62) and the CFM pitch predictor: known to module_spec, outside the text-to-speech composition
+def hubert_ssl_spec(arch=None, weight_norm: str = "parametrizations", p: str = "model.") -> Spec:
+    """AdaptiveHubert.state_dict() (train/models/ssl.py:10-20): ``model.`` = transformers' HubertModel plus the reference's final_proj, in
+    registration order.  ``arch``: hubert_ssl.arch() fields (base when None); weight_norm "parametrizations" (original0 / original1, what
+    current torch registers) or "legacy" (weight_g / weight_v, older checkpoints).  The six un-normalised conv layers get kind w_gelu, which
+    undoes GELU's loss of scale so the features stay O(1) down the stack."""
+    from .hubert_ssl import ARCH_DEFAULTS
+
+    a = dict(ARCH_DEFAULTS if arch is None else arch)
+    h, inter = a["hidden_size"], a["intermediate_size"]
+    s: Spec = [(p + "masked_spec_embed", (h,), "b")]
+    cin = 1
+    for i, (c, k) in enumerate(zip(a["conv_dim"], a["conv_kernel"])):
+        q = p + f"feature_extractor.conv_layers.{i}"
+        s.append((q + ".conv.weight", (c, cin, k), "w_gelu" if i else "w_conv0"))
+        if i == 0:
+            s += [(q + ".layer_norm.weight", (c,), "ln_g"), (q + ".layer_norm.bias", (c,), "ln_b")]
+        cin = c
+    s += [(p + "feature_projection.layer_norm.weight", (cin,), "ln_g"), (p + "feature_projection.layer_norm.bias", (cin,), "ln_b")]
+    s += _linear(p + "feature_projection.projection", h, cin)
+    q = p + "encoder.pos_conv_embed.conv"
+    kpos, ci = a["num_conv_pos_embeddings"], h // a["num_conv_pos_embedding_groups"]
+    s.append((q + ".bias", (h,), "b"))
+    if weight_norm == "parametrizations":
+        s += [(q + ".parametrizations.weight.original0", (1, 1, kpos), "wn_g_pos"), (q + ".parametrizations.weight.original1", (h, ci, kpos), "wn_v")]
+    elif weight_norm == "legacy":
+        s += [(q + ".weight_g", (1, 1, kpos), "wn_g_pos"), (q + ".weight_v", (h, ci, kpos), "wn_v")]
+    else:
+        raise ValueError("weight_norm must be 'parametrizations' or 'legacy'")
+    s += [(p + "encoder.layer_norm.weight", (h,), "ln_g"), (p + "encoder.layer_norm.bias", (h,), "ln_b")]
+    for i in range(a["num_hidden_layers"]):
+        q = p + f"encoder.layers.{i}."
+        for nm, kind in (("k_proj", "w_qk"), ("v_proj", "w"), ("q_proj", "w_qk"), ("out_proj", "w")):
+            s += [(q + "attention." + nm + ".weight", (h, h), kind), (q + "attention." + nm + ".bias", (h,), "b")]
+        s += [(q + "layer_norm.weight", (h,), "ln_g"), (q + "layer_norm.bias", (h,), "ln_b")]
+        s += _linear(q + "feed_forward.intermediate_dense", inter, h)
+        s += _linear(q + "feed_forward.output_dense", h, inter)
+        s += [(q + "final_layer_norm.weight", (h,), "ln_g"), (q + "final_layer_norm.bias", (h,), "ln_b")]
+    s += _linear(p + "final_proj", a["classifier_proj_size"], h)
+    return s
+
+
 MEL_STYLE_MODULE_SPECS = {"pe_mel_style_encoder": pe_mel_style_encoder_spec, "cfm_pitch_predictor": cfm_pitch_predictor_module_spec}
 
 
@@ -499,6 +540,12 @@ def synth_tensor(name: str, shape: Tuple[int, ...], kind: str, seed: int = 0) ->
         v = u * 2.5 * np.sqrt(3.0 / fan_in)
     elif kind == "w_attn_o":
         v = u * 0.35 * np.sqrt(3.0 / fan_in)
+    elif kind == "w_gelu":  # a conv followed by GELU with no norm: E[gelu(x)^2] = 0.425 for unit x, so 1.55 keeps the scale
+        v = u * 1.55 * np.sqrt(3.0 / fan_in)
+    elif kind == "w_conv0":  # the waveform conv before the GroupNorm (any scale; O(1) outputs for unit-scale audio)
+        v = u * np.sqrt(3.0 / fan_in)
+    elif kind == "wn_g_pos":  # per-tap gain of the positional conv: the fold makes every tap's [cout, cin] slice this norm
+        v = 1.2 + 0.3 * u
     elif kind == "w_small":
         v = u * 0.5 * np.sqrt(3.0 / fan_in)
     elif kind == "w_tiny":

@@ -225,7 +225,7 @@ class VoiceConverter:
 
     @torch.no_grad()
     def convert(self, features, lengths, spk_emb, pitch=None, energy=None, noise: Optional[Dict[str, torch.Tensor]] = None,
-                return_details: bool = False, ref_mel=None, ref_mel_lengths=None, f0_log2_stats=None, uv=None):
+                return_details: bool = False, ref_mel=None, ref_mel_lengths=None, f0_log2_stats=None, uv=None, _packed_feats=None):
         """features [B, hubert_dim, T] (mel-frame rate, zero padded past lengths[b]), spk_emb [B, spk_dim]; optional pitch / energy
         [B, T] replace the predicted curves; noise: the packed draws of ``Synthesizer`` (prior_noise [4 sum T, 128], src_noise
         [4 sum T * hop / 4], init_phase [1]).  -> list of B float waveforms (hop_length samples per frame).
@@ -239,13 +239,16 @@ class VoiceConverter:
         eng, dev = self.eng, self.eng.device
         for m in self._modules:
             _ = m.engine  # re-bind if another shim packed these components last
-        if features.dim() != 3:
-            raise ValueError(f"HuBERT features must be [B, {self.hubert_dim}, T], got shape {tuple(features.shape)}")
-        check_width("HuBERT features", features.shape[1], "hubert.hidden_dim", self.hubert_dim)
-        check_width("speaker embedding", spk_emb.shape[-1], "speaker_embedder.hidden_dim", self.spk_dim)
         L = [int(v) for v in torch.as_tensor(lengths).tolist()]
-        if len(L) != features.shape[0] or spk_emb.shape[0] != len(L) or min(L) <= 0 or max(L) > features.shape[2]:
-            raise ValueError(f"lengths {L} do not describe features of shape {tuple(features.shape)} / {spk_emb.shape[0]} speaker embeddings")
+        check_width("speaker embedding", spk_emb.shape[-1], "speaker_embedder.hidden_dim", self.spk_dim)
+        if _packed_feats is None:
+            if features.dim() != 3:
+                raise ValueError(f"HuBERT features must be [B, {self.hubert_dim}, T], got shape {tuple(features.shape)}")
+            check_width("HuBERT features", features.shape[1], "hubert.hidden_dim", self.hubert_dim)
+            if len(L) != features.shape[0] or spk_emb.shape[0] != len(L) or min(L) <= 0 or max(L) > features.shape[2]:
+                raise ValueError(f"lengths {L} do not describe features of shape {tuple(features.shape)} / {spk_emb.shape[0]} speaker embeddings")
+        elif spk_emb.shape[0] != len(L) or min(L) <= 0 or _packed_feats.shape[0] != sum(L):
+            raise ValueError(f"lengths {L} do not describe {_packed_feats.shape[0]} packed feature rows / {spk_emb.shape[0]} speaker embeddings")
         cfm = ref_mel is not None
         if cfm:
             if pitch is not None:
@@ -261,7 +264,7 @@ class VoiceConverter:
             raise ValueError("give both pitch and energy, or neither")
         st = Segments(L, dev)
         st4 = st.scaled(4)
-        feats = _pack_rows(eng, features, L)
+        feats = _pack_rows(eng, features, L) if _packed_feats is None else _packed_feats
         style, pe_style = eng.speaker_style(_f(spk_emb, dev), pe_style=energy is None)
         if cfm:
             from .modules import W_CFM_PITCH
@@ -288,6 +291,25 @@ class VoiceConverter:
         if return_details:
             return waves, dict(pitch=f0, energy=en, style=style, pe_style=pe_style, asr=asr)
         return waves
+
+    @torch.no_grad()
+    def convert_audio(self, wave, sample_lengths, frames, spk_emb, ssl=None, **kw):
+        """Voice conversion from audio: wave [B, samples] at hubert.sr (zero padded past sample_lengths[b]), frames [B] = the mel-frame count
+        of every utterance (the reference's time_dim; an argument, so the host reads nothing back) -> HuBERT features on the engine
+        (``ssl``: the modules.AdaptiveHubert bound to this engine, or the one among this converter's modules) written as the packed rows
+        convert() consumes, then convert() with the same keywords (pitch, energy, noise, ref_mel, ...)."""
+        from .modules import AdaptiveHubert
+
+        if ssl is None:
+            ssl = next((m for m in self._modules if isinstance(m, AdaptiveHubert)), None)
+        if ssl is None:
+            raise ValueError("convert_audio needs an AdaptiveHubert: pass ssl= or list it among the converter's modules")
+        if ssl.hidden != self.hubert_dim:
+            raise ValueError(f"the content encoder has width {ssl.hidden}; hubert.hidden_dim is {self.hubert_dim}")
+        T = [int(v) for v in torch.as_tensor(frames).tolist()]
+        ssl._engine = ssl._engine or self.eng
+        feats = ssl.packed(wave, T, sample_lengths)
+        return self.convert(None, T, spk_emb, _packed_feats=feats, **kw)
 
     def convert_int16(self, features, lengths, spk_emb, pitch=None, energy=None, noise=None, out_prefix: Optional[str] = None):
         """convert() as int16 samples; with ``out_prefix`` also written as ``<prefix>_<i>.wav`` (like ``Synthesizer.infer``)."""

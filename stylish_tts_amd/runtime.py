@@ -458,3 +458,54 @@ class HipModel:
         else:
             _lib.check(self.lib.stts_cfm_pitch_forward(*args, _ptr(ws), ws.numel()))
         return out[0] if len(out) == 1 else tuple(out)
+
+    # ------------------------------------------------------------------ AdaptiveHubert, the HuBERT content encoder (packed waveforms)
+    def ssl_finalize(self, arch) -> None:
+        """Pack the weights loaded under "hubert." for the HubertConfig fields ``arch`` (hubert_ssl.arch); include/stylish_hip.h, stts_ssl_finalize."""
+        from . import hubert_ssl
+
+        self._ssl_arch = dict(arch)
+        self._ssl_dims = hubert_ssl.dims_struct(arch)
+        _lib.check(self.lib.stts_ssl_finalize(self.ctx, C.byref(self._ssl_dims)))
+
+    def hubert_ssl(self, seg_s: Segments, wave: torch.Tensor, seg_t: Segments, ld: Optional[int] = None, taps: bool = False):
+        """wave [sum samples] packed mono audio at hubert.sr (utterance offsets seg_s), seg_t: the time_dim of every utterance ->
+        feats [sum time_dim, ld] packed time-major rows (ld: hidden_size padded to 32 unless given; pad columns zero), the ``feats`` of
+        hubert_encoder / hubert_pitch_energy / cfm_pitch.  taps=True also returns a dict of intermediate rows (include/stylish_hip.h,
+        stts_ssl_forward_taps; "frames": the per-utterance frame counts).  Nothing is read back by the host."""
+        from . import hubert_ssl
+
+        if getattr(self, "_ssl_dims", None) is None:
+            _lib.check(self.lib.stts_ssl_forward(self.ctx, _stream(), 0, None, None, None, None, None, None, 0, None, 0))  # not finalized: the library's message
+        a = self._ssl_arch
+        H = a["hidden_size"]
+        ld = (H + 31) // 32 * 32 if ld is None else int(ld)
+        if seg_s.n != seg_t.n:
+            raise ValueError(f"{seg_s.n} utterances of audio but {seg_t.n} time_dim entries")
+        need = int(self.lib.stts_ssl_workspace_bytes(self.ctx, seg_s.n, seg_s.host_ptr))
+        if need == 0:
+            # too short an utterance (or bad offsets): let the entry point name it, it fails before any launch
+            need = 256
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        with self._ws_lock:
+            wsd = self.__dict__.setdefault("_sslws", {})
+            ws = wsd.get(key)
+            if ws is None or ws.numel() < need:
+                ws = wsd[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        wave = wave.to(self.device, torch.float32).contiguous()
+        if wave.dim() != 1 or wave.numel() != seg_s.rows:
+            raise ValueError(f"packed waveform of {wave.numel()} samples, the offsets describe {seg_s.rows}")
+        feats = self._f32(seg_t.rows, ld)
+        args = (self.ctx, _stream(), seg_s.n, seg_s.host_ptr, _ptr(seg_s.dev), _ptr(wave), seg_t.host_ptr, _ptr(seg_t.dev), _ptr(feats), ld)
+        if not taps:
+            _lib.check(self.lib.stts_ssl_forward(*args, _ptr(ws), ws.numel()))
+            return feats
+        fr = [hubert_ssl.frames(n, a) if n >= hubert_ssl.min_samples(a) else 0 for n in seg_s.lengths]
+        F, rows0 = sum(fr), int(self.lib.stts_ssl_tap_rows(C.byref(self._ssl_dims), seg_s.n, seg_s.host_ptr))
+        t = dict(conv0=self._f32(max(rows0, 1), a["conv_dim"][0]), conv0_off=torch.zeros(seg_s.n + 1, dtype=torch.int32, device=self.device),
+                 conv_last=self._f32(max(F, 1), a["conv_dim"][-1]), proj=self._f32(max(F, 1), H), pos=self._f32(max(F, 1), H),
+                 layers=self._f32(a["num_hidden_layers"], max(F, 1), H), hidden=self._f32(max(F, 1), H))
+        _lib.check(self.lib.stts_ssl_forward_taps(*args, _ptr(t["conv0"]), _ptr(t["conv0_off"]), _ptr(t["conv_last"]), _ptr(t["proj"]), _ptr(t["pos"]),
+                                                  _ptr(t["layers"]), _ptr(t["hidden"]), _ptr(ws), ws.numel()))
+        t["frames"] = fr
+        return feats, t
