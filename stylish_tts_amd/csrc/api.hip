@@ -34,12 +34,8 @@ int stts_ctx_create(const stts_model_dims* dims, int device, stts_ctx** out) {
   c->d = *dims;
   c->device = device;
   c->force_generic_signal = getenv("STTS_SIGNAL_GENERIC") && atoi(getenv("STTS_SIGNAL_GENERIC")) != 0;  // comparisons: signal_geom.hip.h kernels at 2048 / 1200 / 300 too
-  void* p = nullptr;
-  STTS_HIP(hipMalloc(&p, 256));
-  STTS_HIP(hipMemset(p, 0, 256));
-  c->d_err = (int*)p;
-  c->allocs.push_back(p);
-  c->alloc_tag.push_back(0);
+  PackScope scope(c, engine_mode(c));
+  STTS_TRY(dev_upload(c, std::vector<int>(64, 0), &c->d_err));
   *out = c;
   return 0;
   API_END
@@ -86,67 +82,52 @@ int stts_load_weight(stts_ctx* c, const char* name, const float* data, const int
   API_END
 }
 
-// every exit path of a finalize leaves the allocation tag at "context lifetime"
-struct TagReset {
-  stts_ctx* c;
-  ~TagReset() { c->cur_tag = 0; }
-};
-
+// Every finalize below has one shape: make sure the model object exists, open a PackScope with the component's packing mode, pack, and set the
+// `ready` bits on success.  The scope puts the mode back on every exit path; the engine's own precision (c->prec, c->allow_x3) is never touched.
 int stts_finalize_weights(stts_ctx* c, int which) {
   API_BEGIN
   STTS_CHECK(c, "null ctx");
   STTS_HIP(hipSetDevice(c->device));
-  TagReset tag_reset{c};
   // re-finalizing: the previous packing of these components goes away, and so do their `ready` bits - they come back only for
   // the components that finalize successfully below (a failed re-finalize must not leave a stage runnable on freed buffers)
   c->ready &= ~which;
   free_component_allocs(c, which);
-  if (which & (STTS_W_DECODER | STTS_W_FLOW | STTS_W_GENERATOR)) STTS_TRY(finalize_frame(c, which));
+  if (which & (STTS_W_DECODER | STTS_W_FLOW | STTS_W_GENERATOR)) {
+    // 16-bit operand modes: input channels padded to 64 (the K tile of conv_gemm16_kernel); the stages size their rows from the packed kc
+    PackScope scope(c, {c->prec, true, c->prec != PREC_F32 ? 64 : 32, 0});
+    STTS_TRY(finalize_frame(c, which));  // (sets its own `ready` bits)
+  }
   const int ph = which & (STTS_W_SPEECH_TEXT | STTS_W_DURATION | STTS_W_PE_TEXT | STTS_W_PE_STYLE | STTS_W_PITCH_ENERGY);
   if (ph) {
     if (!c->phoneme) c->phoneme = std::make_shared<PhonemeModel>();
     // the phoneme-rate predictors always run in fp32 (include/stylish_hip.h, stts_set_precision): durations are integers and must
     // equal the fp32 reference's bit for bit, and these stages are latency-bound (nothing to win from 16-bit operands)
     // (and on the f32 matrix cores, not the split-fp32 form: latency-bound launches, and per-utterance GRN weights in the style encoder)
-    const int saved_prec = c->prec;
-    c->prec = PREC_F32;
     static const bool phoneme_x3 = getenv("STTS_PHONEME_X3") && atoi(getenv("STTS_PHONEME_X3")) != 0;  // experiment: the split form for the phoneme-rate contractions too
-    c->pack_x3 = phoneme_x3;
-    const int rc = finalize_phoneme(c, static_cast<PhonemeModel*>(c->phoneme.get()), ph);
-    c->pack_x3 = true;
-    c->prec = saved_prec;
-    STTS_TRY(rc);
+    PackScope scope(c, {PREC_F32, phoneme_x3, 32, 0});
+    STTS_TRY(finalize_phoneme(c, static_cast<PhonemeModel*>(c->phoneme.get()), ph));
     c->ready |= ph;
   }
   const int hb = which & (STTS_W_HUBERT | STTS_W_HUBERT_PE);
   if (hb) {
     if (!c->hubert) c->hubert = std::make_shared<HubertModel>();
     // fp32 on the f32 matrix cores whatever the precision, as the phoneme-rate predictors above
-    const int saved_prec = c->prec;
-    c->prec = PREC_F32;
-    c->pack_x3 = false;
-    const int rc = finalize_hubert(c, static_cast<HubertModel*>(c->hubert.get()), hb);
-    c->pack_x3 = true;
-    c->prec = saved_prec;
-    STTS_TRY(rc);
+    PackScope scope(c, {PREC_F32, false, 32, 0});
+    STTS_TRY(finalize_hubert(c, static_cast<HubertModel*>(c->hubert.get()), hb));
     c->ready |= hb;
   }
   const int ms = which & (STTS_W_PE_MEL_STYLE | STTS_W_CFM_PITCH);
   if (ms) {
     if (!c->mel_style) c->mel_style = std::make_shared<MelStyleModel>();
-    STTS_TRY(finalize_mel_style(c, static_cast<MelStyleModel*>(c->mel_style.get()), ms));  // fp32 whatever the precision (mel_style.hip.h)
+    PackScope scope(c, engine_mode(c));  // (its packer reads only the tag: fp32 whatever the precision, mel_style.hip.h)
+    STTS_TRY(finalize_mel_style(c, static_cast<MelStyleModel*>(c->mel_style.get()), ms));
     c->ready |= ms;
   }
   if (which & STTS_W_CFM_PITCH_NET) {
     if (!c->cfm_pitch) c->cfm_pitch = std::make_shared<CfmPitchNetW>();
     // fp32 on the f32 matrix cores whatever the precision, as the HuBERT front ends above (cfm_pitch.hip.h)
-    const int saved_prec = c->prec;
-    c->prec = PREC_F32;
-    c->pack_x3 = false;
-    const int rc = finalize_cfm_pitch_net(c, static_cast<CfmPitchNetW*>(c->cfm_pitch.get()));
-    c->pack_x3 = true;
-    c->prec = saved_prec;
-    STTS_TRY(rc);
+    PackScope scope(c, {PREC_F32, false, 32, STTS_W_CFM_PITCH_NET});
+    STTS_TRY(finalize_cfm_pitch_net(c, static_cast<CfmPitchNetW*>(c->cfm_pitch.get())));
     c->ready |= STTS_W_CFM_PITCH_NET;
   }
   STTS_HIP(hipDeviceSynchronize());
@@ -177,18 +158,29 @@ int stts_check_status(stts_ctx* c, void* stream) {
 int stts_har_ld(const stts_ctx* c) {
   if (!c) return 0;
   if (c->amp_prior.kc) return har_ld(c);  // the generator is packed: the prior convs' input width
-  return round_up(c->d.n_fft / 2 + 1, c->prec != PREC_F32 ? 64 : 32);  // before: what finalize_frame will pad the bins to in this precision (kc_align)
+  return round_up(c->d.n_fft / 2 + 1, c->prec != PREC_F32 ? 64 : 32);  // before: what the frame path's packing mode will pad the bins to in this precision
 }
 
 size_t stts_frame_workspace_bytes(const stts_ctx* c, int64_t rows, int n_utt, int max_len) { return frame_workspace_bytes(c, rows, n_utt, max_len); }
 
-#define SEG_CHECK(mask)                                                              \
-  STTS_CHECK(c && (c->ready & (mask)) == (mask), "weights for this stage are not finalized (need components 0x%x, have 0x%x)", (mask), c ? c->ready : 0); \
-  STTS_CHECK(n_utt > 0 && seg_off_host && seg_off_dev && seg_off_host[0] == 0, "bad utterance offsets"); \
-  for (int _u = 0; _u < n_utt; ++_u) STTS_CHECK(seg_off_host[_u + 1] > seg_off_host[_u], "utterance %d is empty", _u); \
+// host offsets of n_utt utterances: present, starting at 0, none empty (`bad` / `empty`: the texts where they are not the utterance rows';
+// `empty` is formatted with the utterance and its length)
+static int seg_ok(int n_utt, const int32_t* h, const int32_t* d, const char* bad = "bad utterance offsets", const char* empty = "utterance %d is empty") {
+  STTS_CHECK(n_utt > 0 && h && d && h[0] == 0, "%s", bad);
+  for (int u = 0; u < n_utt; ++u) STTS_CHECK(h[u + 1] > h[u], empty, u, h[u + 1] - h[u]);
+  return 0;
+}
+
+// the opening of a stage entry point: its components (and the model object that holds them, `have`) are finalized; device and stream
+#define READY_CHECK(have, mask)                                                      \
+  STTS_CHECK(c && (have) && (c->ready & (mask)) == (mask), "weights for this stage are not finalized (need components 0x%x, have 0x%x)", (mask), c ? c->ready : 0); \
   STTS_HIP(hipSetDevice(c->device));                                                 \
-  Seg s{n_utt, seg_off_host, seg_off_dev};                                           \
   hipStream_t st = (hipStream_t)stream
+
+#define SEG_CHECK(mask)                                                              \
+  READY_CHECK(true, mask);                                                           \
+  STTS_TRY(seg_ok(n_utt, seg_off_host, seg_off_dev));                                \
+  Seg s{n_utt, seg_off_host, seg_off_dev}
 
 int stts_decoder_forward(stts_ctx* c, void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, const float* asr,
                          int ld_asr, const float* pitch, const float* energy, const float* style, float* x_out, int ld_x, void* ws,
@@ -299,19 +291,14 @@ int stts_cfm_finalize(stts_ctx* c, const stts_cfm_dims* dims) {
   API_BEGIN
   STTS_CHECK(c && dims, "null argument");
   STTS_HIP(hipSetDevice(c->device));
-  TagReset tag_reset{c};
   c->ready &= ~STTS_W_CFM;
   free_component_allocs(c, STTS_W_CFM);
   CfmDims d;
   d.feat = dims->feat_dim; d.asr = dims->asr_dim; d.spk = dims->spk_dim; d.hidden = dims->hidden_dim; d.emb = dims->emb_dim; d.depth = dims->depth;
   d.enc_blocks = dims->enc_blocks; d.dec_blocks = dims->dec_blocks; d.prev_depth = dims->prev_depth; d.post_depth = dims->post_depth; d.head_dim = dims->head_dim;
   auto m = std::make_shared<CfmModel>();
-  c->cur_tag = STTS_W_CFM;
-  c->pack_x3 = false;  // latency-bound estimator: f32 matrix cores
-  const int rc = finalize_cfm(c, d, m.get());
-  c->pack_x3 = true;
-  c->cur_tag = 0;
-  if (rc) return rc;
+  PackScope scope(c, {c->prec, false, 32, STTS_W_CFM});  // latency-bound estimator: f32 matrix cores
+  STTS_TRY(finalize_cfm(c, d, m.get()));
   c->cfm = m;
   c->ready |= STTS_W_CFM;
   STTS_HIP(hipDeviceSynchronize());
@@ -329,12 +316,8 @@ int stts_cfm_estimator(stts_ctx* c, void* stream, int n_utt, const int32_t* seg_
                        const float* spk_emb, const float* t, const float* sine_noise, float* out, int ld_out, void* ws, size_t ws_bytes) {
   API_BEGIN
   STTS_CHECK(c && c->cfm && (c->ready & STTS_W_CFM), "the CfmMelDecoder weights are not finalized (stts_cfm_finalize)");
-  STTS_CHECK(n_utt > 0 && seg_off_host && seg_off_dev && seg_off_host[0] == 0, "bad utterance offsets");
-  STTS_CHECK(curve_off_host && curve_off_dev && curve_off_host[0] == 0, "bad curve offsets");
-  for (int u = 0; u < n_utt; ++u) {
-    STTS_CHECK(seg_off_host[u + 1] > seg_off_host[u], "utterance %d is empty", u);
-    STTS_CHECK(curve_off_host[u + 1] > curve_off_host[u], "utterance %d has an empty F0 / N curve", u);
-  }
+  STTS_TRY(seg_ok(n_utt, seg_off_host, seg_off_dev));
+  STTS_TRY(seg_ok(n_utt, curve_off_host, curve_off_dev, "bad curve offsets", "utterance %d has an empty F0 / N curve"));
   STTS_CHECK(x && asr && f0 && n_curve && spk_emb && t && sine_noise && out && ws, "null tensor");
   STTS_HIP(hipSetDevice(c->device));
   Seg s{n_utt, seg_off_host, seg_off_dev};
@@ -363,16 +346,8 @@ int stts_to_channel_major(void* stream, const float* x, int ldx, int B, int C, i
 
 // ------------------------------------------------------------------------------------------------ phoneme-rate stages
 #define PH_CHECK(mask)                                                               \
-  STTS_CHECK(c && c->phoneme && (c->ready & (mask)) == (mask), "weights for this stage are not finalized (need components 0x%x, have 0x%x)", (mask), c ? c->ready : 0); \
-  STTS_HIP(hipSetDevice(c->device));                                                 \
-  PhonemeModel& M = *static_cast<PhonemeModel*>(c->phoneme.get());                   \
-  hipStream_t st = (hipStream_t)stream
-
-static int seg_ok(int n_utt, const int32_t* h, const int32_t* d) {
-  STTS_CHECK(n_utt > 0 && h && d && h[0] == 0, "bad utterance offsets");
-  for (int u = 0; u < n_utt; ++u) STTS_CHECK(h[u + 1] > h[u], "utterance %d is empty", u);
-  return 0;
-}
+  READY_CHECK(c->phoneme, mask);                                                     \
+  PhonemeModel& M = *static_cast<PhonemeModel*>(c->phoneme.get())
 
 size_t stts_phoneme_workspace_bytes(const stts_ctx* c, int64_t n_tokens, int64_t n_frames, int n_utt) {
   return phoneme_workspace_bytes(c, n_tokens, n_frames, n_utt);
@@ -457,7 +432,7 @@ int stts_duration_to_alignment(void* stream, const int32_t* dur, int n_tokens, i
 static int conv_stft_tables(stts_ctx* c) {
   if (c->hann) return 0;
   STTS_HIP(hipSetDevice(c->device));
-  c->cur_tag = 0;  // context-lifetime tables, whatever was finalized last
+  PackScope scope(c, engine_mode(c));  // context-lifetime tables
   std::vector<float> h(kWin);
   for (int i = 0; i < kWin; ++i) h[i] = (float)(0.5 - 0.5 * cos(2.0 * M_PI * i / kWin));
   STTS_TRY(dev_upload(c, h, &c->hann));
@@ -604,23 +579,15 @@ int stts_ssl_finalize(stts_ctx* c, const stts_ssl_dims* dims) {
   API_BEGIN
   STTS_CHECK(c && dims, "null argument");
   STTS_HIP(hipSetDevice(c->device));
-  TagReset tag_reset{c};
   c->ready &= ~STTS_W_SSL;
   free_component_allocs(c, STTS_W_SSL);
   SslDims d;
   STTS_TRY(ssl_dims_from(dims, &d));
   auto m = std::make_shared<SslW>();
-  c->cur_tag = STTS_W_SSL;
   // fp32 whatever the precision, as the other voice-conversion front ends; the dense contractions in the split-fp32 form (weights packed with their
   // three bf16 planes) unless the engine is STTS_PREC_F32_NATIVE (ssl.hip.h says which tile they run and why)
-  const int saved_prec = c->prec, saved_align = c->kc_align;
-  c->prec = PREC_F32;
-  c->kc_align = 32;
-  const int rc = finalize_ssl(c, d, m.get());
-  c->prec = saved_prec;
-  c->kc_align = saved_align;
-  c->cur_tag = 0;
-  if (rc) return rc;
+  PackScope scope(c, {PREC_F32, true, 32, STTS_W_SSL});
+  STTS_TRY(finalize_ssl(c, d, m.get()));
   c->ssl = m;
   c->ready |= STTS_W_SSL;
   STTS_HIP(hipDeviceSynchronize());
@@ -664,8 +631,7 @@ static int ssl_entry(stts_ctx* c, void* stream, int n_utt, const int32_t* sample
   const SslW& M = *static_cast<const SslW*>(c->ssl.get());
   STTS_CHECK(sample_off_dev && wave && off_T_host && off_T_dev && feats && ws, "ssl: null argument");
   STTS_TRY(ssl_check_offsets(M.d, n_utt, sample_off_host));
-  STTS_CHECK(off_T_host[0] == 0, "ssl: bad time_dim offsets");
-  for (int u = 0; u < n_utt; ++u) STTS_CHECK(off_T_host[u + 1] > off_T_host[u], "ssl: utterance %d has a time_dim of %d", u, off_T_host[u + 1] - off_T_host[u]);
+  STTS_TRY(seg_ok(n_utt, off_T_host, off_T_dev, "ssl: bad time_dim offsets", "ssl: utterance %d has a time_dim of %d"));
   STTS_CHECK(ld_feats >= round_up(M.d.hidden, 32) && ld_feats % 4 == 0, "feature rows: ld_feats %d must be a multiple of 4 covering %d columns (hidden_size %d padded to 32)",
              ld_feats, round_up(M.d.hidden, 32), M.d.hidden);
   STTS_HIP(hipSetDevice(c->device));
@@ -695,10 +661,8 @@ int stts_ssl_forward_taps(stts_ctx* c, void* stream, int n_utt, const int32_t* s
 extern "C" {
 
 #define HB_CHECK(mask)                                                               \
-  STTS_CHECK(c && c->hubert && (c->ready & (mask)) == (mask), "weights for this stage are not finalized (need components 0x%x, have 0x%x)", (mask), c ? c->ready : 0); \
-  STTS_HIP(hipSetDevice(c->device));                                                 \
-  HubertModel& H = *static_cast<HubertModel*>(c->hubert.get());                      \
-  hipStream_t st = (hipStream_t)stream
+  READY_CHECK(c->hubert, mask);                                                      \
+  HubertModel& H = *static_cast<HubertModel*>(c->hubert.get())
 
 size_t stts_hubert_workspace_bytes(const stts_ctx* c, int64_t rows_T, int n_utt, int max_len) { return c ? hubert_workspace_bytes(c, rows_T, n_utt, max_len) : 0; }
 

@@ -98,7 +98,6 @@ __global__ void STTS_CP_NO_PK __launch_bounds__(256) cp_out_kernel(const float* 
 // ------------------------------------------------------------------------------------------------ packing
 // dims from the weights: asr_dim = asr_emb.0's cin; hidden 256 / 1024 checked (models/cfm/cfm_pitch_predictor.py:14-19)
 inline int finalize_cfm_pitch_net(stts_ctx* c, CfmPitchNetW* W) {
-  c->cur_tag = STTS_W_CFM_PITCH_NET;
   *W = CfmPitchNetW();
   const std::string p = "cfm_pitch_predictor.";
   STTS_GET(e0, p + "asr_emb.0.weight");
@@ -126,7 +125,6 @@ inline int finalize_cfm_pitch_net(stts_ctx* c, CfmPitchNetW* W) {
   STTS_TRY(dev_upload(c, ow->data, &W->out_w));
   W->out_b = ob->data[0];
   W->ready = true;
-  c->cur_tag = 0;
   return 0;
 }
 

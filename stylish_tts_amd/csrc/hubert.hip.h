@@ -147,7 +147,7 @@ inline int upload_linear(stts_ctx* c, const std::string& p, int* out_n, int* in_
 inline int finalize_hubert(stts_ctx* c, HubertModel* M, int which) {
   const stts_model_dims& d = c->d;
   if (which & STTS_W_HUBERT) {
-    c->cur_tag = STTS_W_HUBERT;
+    c->pack.tag = STTS_W_HUBERT;
     HubertSpW& S = M->sp;
     S = HubertSpW();
     const std::string p = "hubert_speech_predictor.";
@@ -169,7 +169,7 @@ inline int finalize_hubert(stts_ctx* c, HubertModel* M, int which) {
     S.ready = true;
   }
   if (which & STTS_W_HUBERT_PE) {
-    c->cur_tag = STTS_W_HUBERT_PE;
+    c->pack.tag = STTS_W_HUBERT_PE;
     HubertPeW& P = M->pe;
     P = HubertPeW();
     const std::string p = "hubert_pitch_energy_predictor.";
@@ -194,7 +194,6 @@ inline int finalize_hubert(stts_ctx* c, HubertModel* M, int which) {
     P.n_b = nb->data[0];
     P.ready = true;
   }
-  c->cur_tag = 0;
   return 0;
 }
 

@@ -395,7 +395,7 @@ inline const char* mel_style_prefix(int which) { return which == STTS_W_PE_MEL_S
 
 // dims from the weight shapes: n_mels = shared.0's cout (dim_in = n_mels, models/models.py:57-62, cfm_pitch_predictor.py:25-27)
 inline int finalize_mel_style_one(stts_ctx* c, MelStyleW* E, int which) {
-  c->cur_tag = which;
+  c->pack.tag = which;
   *E = MelStyleW();
   const std::string p = mel_style_prefix(which);
   STTS_GET(w0, p + "shared.0.weight_orig");
@@ -445,7 +445,6 @@ inline int finalize_mel_style_one(stts_ctx* c, MelStyleW* E, int which) {
 inline int finalize_mel_style(stts_ctx* c, MelStyleModel* M, int which) {
   if (which & STTS_W_PE_MEL_STYLE) STTS_TRY(finalize_mel_style_one(c, &M->enc[0], STTS_W_PE_MEL_STYLE));
   if (which & STTS_W_CFM_PITCH) STTS_TRY(finalize_mel_style_one(c, &M->enc[1], STTS_W_CFM_PITCH));
-  c->cur_tag = 0;
   return 0;
 }
 

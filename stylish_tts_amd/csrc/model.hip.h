@@ -136,6 +136,14 @@ struct MrfW {
   StyleTable table;
 };
 
+// How the packers pack while a finalize runs: installed on stts_ctx::pack by a PackScope (below), never by hand.
+struct PackMode {
+  int prec;      // operand precision the weights are packed for (PREC_*); -1: no scope is open
+  bool x3;       // fp32: also the three bf16 planes of every weight (split-fp32 contractions, gemm.hip.h PREC_X3), where the engine allows them
+  int kc_align;  // input channels of a packed conv are padded to this (64 for the frame path in a 16-bit mode: conv_gemm16_kernel's K tile)
+  int tag;       // STTS_W_* component the allocations belong to (0: context lifetime); a finalize assigns it as it moves between components
+};
+
 }  // namespace stts
 
 struct stts_ctx {
@@ -144,7 +152,6 @@ struct stts_ctx {
   std::map<std::string, stts::HostTensor> host;
   std::vector<void*> allocs;
   std::vector<int> alloc_tag;  // STTS_W_* component a device allocation belongs to (0: context lifetime); same length as allocs
-  int cur_tag = 0;             // tag of the allocations made right now (set by the finalize sections)
   int* d_err = nullptr;
   // side streams of stts_frame_path (fp32, large batches): one per caller stream (several host threads may run the path on their own streams)
   struct SideLane {
@@ -157,10 +164,10 @@ struct stts_ctx {
   std::map<hipStream_t, SideLane> side_lanes;
   std::mutex side_mu;
   int ready = 0;  // STTS_W_* components finalized
+  // the engine's precision: written by stts_set_precision only, read by the stages (a finalize packs by `pack`, not by these)
   int prec = 0;   // contraction operand precision (stts::PREC_*), fixed before the first finalize
   bool allow_x3 = true;  // false: STTS_PREC_F32_NATIVE - fp32 contractions on the f32 matrix cores only
-  bool pack_x3 = true;  // fp32 mode: pack_rows also writes the three bf16 planes of every weight (split-fp32 contractions, gemm.hip.h PREC_X3); off while the phoneme-rate / CFM models are packed
-  int kc_align = 32;  // input channels of a packed conv are padded to this (64 while the frame path is packed for a 16-bit mode: conv_gemm16_kernel's K tile)
+  stts::PackMode pack{-1, true, 32, 0};  // what the packers read; valid only inside a stts::PackScope
   // STFT geometry of the frame path (set by finalize_frame from d.n_fft / win_length / hop_length); STTS_SIGNAL_GENERIC=1 at context
   // creation: the run-time-geometry kernels (signal_geom.hip.h) at the default geometry too, for comparisons
   stts::SignalGeom geom;
@@ -203,12 +210,26 @@ namespace stts {
 // ------------------------------------------------------------------------------------------------
 // small host utilities
 // ------------------------------------------------------------------------------------------------
+// Installs a packing mode for the lifetime of the scope and puts the previous one back on every exit path, an exception included.  Scopes nest.
+struct PackScope {
+  stts_ctx* c;
+  PackMode saved;
+  PackScope(stts_ctx* ctx, const PackMode& m) : c(ctx), saved(ctx->pack) { c->pack = m; }
+  ~PackScope() { c->pack = saved; }
+  PackScope(const PackScope&) = delete;
+  PackScope& operator=(const PackScope&) = delete;
+};
+// the mode of everything that is not a model finalize (context-lifetime tables, the test operators' on-demand packing)
+inline PackMode engine_mode(const stts_ctx* c) { return {c->prec, true, 32, 0}; }
+inline bool packs_x3(const stts_ctx* c) { return c->allow_x3 && c->pack.x3 && x3_enabled(); }
+
 template <typename T>
 inline int dev_upload(stts_ctx* c, const std::vector<T>& h, T** out) {
+  STTS_CHECK(c->pack.prec >= 0, "dev_upload outside a PackScope");
   void* p = nullptr;
   STTS_HIP(hipMalloc(&p, std::max<size_t>(h.size(), 1) * sizeof(T)));
   c->allocs.push_back(p);
-  c->alloc_tag.push_back(c->cur_tag);
+  c->alloc_tag.push_back(c->pack.tag);
   if (!h.empty()) STTS_HIP(hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
   *out = (T*)p;
   return 0;
@@ -313,6 +334,8 @@ inline unsigned short f32_to_f16(float f) {
 
 inline int pack_rows(stts_ctx* c, const HostTensor& w, const HostTensor* bias, const std::vector<int>& row_of, int cin_lo, int cin_n,
                      int kc, int N, PackedConv* out, float scale = 1.0f) {
+  STTS_CHECK(c->pack.prec >= 0, "pack_rows outside a PackScope");
+  const int prec = c->pack.prec;
   const int cin = (int)w.shape[1], k = (int)w.shape[2];
   const int npad = (int)row_of.size();
   std::vector<float> pw((size_t)npad * k * kc, 0.f), pb(npad, 0.f);
@@ -325,23 +348,18 @@ inline int pack_rows(stts_ctx* c, const HostTensor& w, const HostTensor* bias, c
   }
   STTS_TRY(dev_upload(c, pw, &out->W));
   STTS_TRY(dev_upload(c, pb, &out->bias));
-  out->prec = c->prec;
+  out->prec = prec;
   out->W16 = nullptr;
   out->w16_plane = 0;
-  if (c->prec != PREC_F32 || (c->allow_x3 && c->pack_x3 && x3_enabled())) {
-    const bool split = c->prec == PREC_F32;
+  if (prec != PREC_F32 || packs_x3(c)) {
+    const bool split = prec == PREC_F32;
     std::vector<unsigned short> h(pw.size() * (split ? 3 : 1));
     if (split) {
       out->w16_plane = (long)pw.size();
       for (size_t i = 0; i < pw.size(); ++i) split3_host(pw[i], &h[i], &h[pw.size() + i], &h[2 * pw.size() + i]);
     } else
-    for (size_t i = 0; i < pw.size(); ++i) h[i] = c->prec == PREC_BF16 ? f32_to_bf16(pw[i]) : f32_to_f16(pw[i]);
-    void* d = nullptr;
-    STTS_HIP(hipMalloc(&d, h.size() * sizeof(unsigned short)));
-    c->allocs.push_back(d);
-    c->alloc_tag.push_back(c->cur_tag);
-    STTS_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    out->W16 = (unsigned short*)d;
+    for (size_t i = 0; i < pw.size(); ++i) h[i] = prec == PREC_BF16 ? f32_to_bf16(pw[i]) : f32_to_f16(pw[i]);
+    STTS_TRY(dev_upload(c, h, &out->W16));
   }
   out->npad = npad;
   out->N = N;
@@ -376,7 +394,7 @@ inline int pack_plain(stts_ctx* c, const std::string& p, bool has_bias, int cin_
   const HostTensor* b = has_bias ? find(c, p + ".bias") : nullptr;
   if (has_bias && !b) return fail("missing weight '%s.bias'", p.c_str());
   if (cin_n < 0) cin_n = (int)w.shape[1] - cin_lo;
-  return pack_rows(c, w, b, plain_rows((int)w.shape[0]), cin_lo, cin_n, round_up(cin_n, c->kc_align), (int)w.shape[0], out, scale);
+  return pack_rows(c, w, b, plain_rows((int)w.shape[0]), cin_lo, cin_n, round_up(cin_n, c->pack.kc_align), (int)w.shape[0], out, scale);
 }
 
 inline int upload_table(stts_ctx* c, StyleTable* t) {
@@ -402,6 +420,7 @@ inline int add_style(stts_ctx* c, StyleTable* t, const std::string& p, int C, St
 inline int pack_winograd(stts_ctx* c, const HostTensor& w, const HostTensor* bias, int cin_lo, int cin_n, int cout_used, WinoConv* out) {
   static const bool disabled = getenv("STTS_NO_WINOGRAD") != nullptr;  // debugging aid: every conv then runs in its direct form
   if (disabled) return 0;  // out->ready stays false
+  STTS_CHECK(c->pack.prec >= 0, "pack_winograd outside a PackScope");
   const int cin = (int)w.shape[1], r = (int)w.shape[2];
   STTS_CHECK(wino_matrices(r, &out->mats), "winograd: unsupported kernel size %d (or self-check failed)", r);
   const int n = out->mats.n, npad = round_up(cout_used, 128), kc = round_up(cin_n, 32);
@@ -418,11 +437,12 @@ inline int pack_winograd(stts_ctx* c, const HostTensor& w, const HostTensor* bia
   std::vector<int> row_of((size_t)n * npad, -1);
   for (int j = 0; j < n; ++j)
     for (int co = 0; co < cout_used; ++co) row_of[(size_t)j * npad + co] = j * cout_used + co;
-  const int saved_prec = c->prec;
-  c->prec = PREC_F32;  // the transformed weights span ~3 decades (G up to 729): fp32 operands only
-  const int rc = pack_rows(c, wp, nullptr, row_of, cin_lo, cin_n, kc, cout_used, &out->planes);
-  c->prec = saved_prec;
-  STTS_TRY(rc);
+  {
+    PackMode f32 = c->pack;
+    f32.prec = PREC_F32;  // the transformed weights span ~3 decades (G up to 729): fp32 operands only
+    PackScope scope(c, f32);
+    STTS_TRY(pack_rows(c, wp, nullptr, row_of, cin_lo, cin_n, kc, cout_used, &out->planes));
+  }
   out->planes.npad = npad;
   out->planes.cin_real = cin_n;
   out->planes.rows_real = cout_used;
@@ -472,10 +492,10 @@ inline int pack_convnext_block(stts_ctx* c, const std::string& q, int h, int k, 
 inline int pack_adain_block(stts_ctx* c, const std::string& p, int cin, int cout, StyleTable* table, AdainBlockW* o) {
   o->cin = cin;
   o->cout = cout;
-  o->kcin = round_up(cin, c->kc_align);
+  o->kcin = round_up(cin, c->pack.kc_align);
   STTS_TRY(pack_plain(c, p + ".conv1", true, 0, cin, &o->conv1));
   o->w1 = WinoConv();
-  if (c->prec == PREC_F32) {
+  if (c->pack.prec == PREC_F32) {
     HostTensor w1;
     STTS_TRY(get_weight(c, p + ".conv1", &w1));
     if (w1.shape[2] == 3) STTS_TRY(pack_winograd(c, w1, find(c, p + ".conv1.bias"), 0, cin, cout, &o->w1));
@@ -483,7 +503,7 @@ inline int pack_adain_block(stts_ctx* c, const std::string& p, int cin, int cout
   STTS_TRY(pack_plain(c, p + ".conv2", true, 0, cout, &o->conv2));
   o->w2 = WinoConv();
   if (find(c, p + ".conv1x1.parametrizations.weight.original0") || find(c, p + ".conv1x1.weight")) STTS_TRY(pack_plain(c, p + ".conv1x1", false, 0, cin, &o->sc));
-  if (c->prec == PREC_F32) {  // conv2 is a plain conv + residual (the block's input, or its learned 1x1 shortcut computed first): it has a Winograd form too
+  if (c->pack.prec == PREC_F32) {  // conv2 is a plain conv + residual (the block's input, or its learned 1x1 shortcut computed first): it has a Winograd form too
     HostTensor w2;
     STTS_TRY(get_weight(c, p + ".conv2", &w2));
     if (w2.shape[2] == 3) STTS_TRY(pack_winograd(c, w2, find(c, p + ".conv2.bias"), 0, cout, cout, &o->w2));
@@ -510,19 +530,19 @@ inline int pack_wn_fused(stts_ctx* c, const std::string& q, const HostTensor& pm
     STTS_TRY(get_weight(c, q + "enc.in_layers." + std::to_string(i), &w));
     STTS_GET(b, q + "enc.in_layers." + std::to_string(i) + ".bias");
     STTS_CHECK(w.shape[0] == 2 * C && w.shape[1] == C && w.shape[2] == 5 && (int)b->data.size() == 2 * C, "wn_fused: in_layers.%d has an unexpected shape", i);
-    if (c->prec != PREC_F32) {
+    if (c->pack.prec != PREC_F32) {
       // direct form, K-major rows [tap][cin] so that k-step s = tap * 4 + (cin / 32) covers K offsets [32 s, 32 s + 32)
       std::vector<std::vector<float>> kr((size_t)2 * C, std::vector<float>(5 * C));
       for (int n = 0; n < 2 * C; ++n)
         for (int ci = 0; ci < C; ++ci)
           for (int k = 0; k < 5; ++k) kr[n][(size_t)k * C + ci] = w.data[((size_t)n * C + ci) * 5 + k];
       // wave w, tile (half h, c): output rows h * 128 + 32 w + 16 c + col
-      const std::vector<unsigned short> f16v = pack_fragments16(c->prec, kWnWaves, 5 * C / 32, 4, [&](int wv, int t, int col) {
+      const std::vector<unsigned short> f16v = pack_fragments16(c->pack.prec, kWnWaves, 5 * C / 32, 4, [&](int wv, int t, int col) {
         return kr[(size_t)(t >> 1) * C + 32 * wv + 16 * (t & 1) + col].data();
       }, f32_to_bf16, f32_to_f16);
       STTS_TRY(dev_upload(c, f16v, &o->H1[i]));
     }
-    const bool x3pack = c->prec == PREC_F32 && c->allow_x3 && c->pack_x3 && x3_enabled();
+    const bool x3pack = c->pack.prec == PREC_F32 && packs_x3(c);
     if (x3pack) {
       std::vector<std::vector<float>> kr((size_t)2 * C, std::vector<float>(5 * C));
       for (int n = 0; n < 2 * C; ++n)
@@ -534,7 +554,7 @@ inline int pack_wn_fused(stts_ctx* c, const std::string& q, const HostTensor& pm
       STTS_TRY(dev_upload(c, fx, &o->X1[i]));
       o->xp1 = (long)(fx.size() / 3 / 8);
     }
-    for (int v = 0; v < 3 && c->prec == PREC_F32; ++v) {
+    for (int v = 0; v < 3 && c->pack.prec == PREC_F32; ++v) {
       WnFusedMats mt;
       const int vm = v == 0 ? 2 : (v == 1 ? 4 : 1);
       STTS_CHECK(wn_fused_matrices(vm, &mt), "wn_fused: F(%d,5) matrices failed their self-check", vm);
@@ -560,7 +580,7 @@ inline int pack_wn_fused(stts_ctx* c, const std::string& q, const HostTensor& pm
     STTS_CHECK((n_rs == 2 * C || n_rs == C) && wr.shape[1] == C && (n_rs == C) == (i == 3), "wn_fused: res_skip_layers.%d has an unexpected shape", i);
     const auto rr = rows_of(wr);
     const int nct = n_rs / 16 / kWnWaves;  // column tiles per wave
-    if (c->prec == PREC_F32) {
+    if (c->pack.prec == PREC_F32) {
       const std::vector<float> f2 = pack_fragments(kWnWaves, C / 16, nct, [&](int wv, int t, int col) { return rr[(size_t)16 * nct * wv + 16 * t + col].data(); });
       STTS_TRY(dev_upload(c, f2, &o->W2[i]));
       if (x3pack) {
@@ -578,13 +598,13 @@ inline int pack_wn_fused(stts_ctx* c, const std::string& q, const HostTensor& pm
         STTS_TRY(dev_upload(c, fxb, &o->X2b[i]));  // (same size as X2[i]: xp2[i] is its plane stride too)
       }
     } else {
-      const std::vector<unsigned short> f2 = pack_fragments16(c->prec, kWnWaves, C / 32, nct, [&](int wv, int t, int col) {
+      const std::vector<unsigned short> f2 = pack_fragments16(c->pack.prec, kWnWaves, C / 32, nct, [&](int wv, int t, int col) {
         return wr.data.data() + ((size_t)16 * nct * wv + 16 * t + col) * C;
       }, f32_to_bf16, f32_to_f16);
       STTS_TRY(dev_upload(c, f2, &o->H2[i]));
       // wn_block16_kernel: wave w owns the res rows AND the skip rows [32 w, 32 w + 32) (tiles: res, res + 16, skip, skip + 16; layer 3: skip, skip + 16)
       const int nctb = n_rs == 2 * C ? 4 : 2;
-      const std::vector<unsigned short> f2b = pack_fragments16(c->prec, kWnWaves, C / 32, nctb, [&](int wv, int t, int col) {
+      const std::vector<unsigned short> f2b = pack_fragments16(c->pack.prec, kWnWaves, C / 32, nctb, [&](int wv, int t, int col) {
         const int row = n_rs == 2 * C ? (t < 2 ? 32 * wv + 16 * t + col : C + 32 * wv + 16 * (t - 2) + col) : 32 * wv + 16 * t + col;
         return wr.data.data() + (size_t)row * C;
       }, f32_to_bf16, f32_to_f16);
@@ -594,10 +614,10 @@ inline int pack_wn_fused(stts_ctx* c, const std::string& q, const HostTensor& pm
   }
   STTS_CHECK(pm.shape[0] == C / 2 && pm.shape[1] == C && pl.shape[0] == C / 2, "wn_fused: proj has an unexpected shape");
   const auto rm = rows_of(pm), rl = rows_of(pl);
-  if (c->prec == PREC_F32) {
+  if (c->pack.prec == PREC_F32) {
     const std::vector<float> f3 = pack_fragments(kWnWaves, C / 16, 2, [&](int wv, int t, int col) { return (t == 0 ? rm : rl)[(size_t)16 * wv + col].data(); });
     STTS_TRY(dev_upload(c, f3, &o->W3));
-    if (c->allow_x3 && c->pack_x3 && x3_enabled()) {
+    if (packs_x3(c)) {
       const std::vector<unsigned short> fx = pack_fragments_x3(kWnWaves, C / 32, 2, [&](int wv, int t, int col) {
         return (t == 0 ? pm : pl).data.data() + ((size_t)16 * wv + col) * C;
       }, split3_host);
@@ -605,7 +625,7 @@ inline int pack_wn_fused(stts_ctx* c, const std::string& q, const HostTensor& pm
       o->xp3 = (long)(fx.size() / 3 / 8);
     }
   } else {
-    const std::vector<unsigned short> f3 = pack_fragments16(c->prec, kWnWaves, C / 32, 2, [&](int wv, int t, int col) {
+    const std::vector<unsigned short> f3 = pack_fragments16(c->pack.prec, kWnWaves, C / 32, 2, [&](int wv, int t, int col) {
       return (t == 0 ? pm : pl).data.data() + ((size_t)16 * wv + col) * C;
     }, f32_to_bf16, f32_to_f16);
     STTS_TRY(dev_upload(c, f3, &o->H3));
@@ -617,10 +637,10 @@ inline int pack_wn_fused(stts_ctx* c, const std::string& q, const HostTensor& pm
   STTS_GET(bp, q + "pre.bias");
   STTS_CHECK(wp.shape[0] == C && wp.shape[1] == C / 2, "wn_fused: pre has an unexpected shape");
   const auto rp = rows_of(wp);
-  if (c->prec == PREC_F32) {
+  if (c->pack.prec == PREC_F32) {
     const std::vector<float> f4 = pack_fragments(kWnWaves, C / 32, 2, [&](int wv, int t, int col) { return rp[(size_t)32 * wv + 16 * t + col].data(); });
     STTS_TRY(dev_upload(c, f4, &o->W4));
-    if (c->allow_x3 && c->pack_x3 && x3_enabled()) {
+    if (packs_x3(c)) {
       const std::vector<unsigned short> fx = pack_fragments_x3(kWnWaves, C / 64, 2, [&](int wv, int t, int col) {
         return wp.data.data() + ((size_t)32 * wv + 16 * t + col) * (C / 2);
       }, split3_host);
@@ -628,15 +648,15 @@ inline int pack_wn_fused(stts_ctx* c, const std::string& q, const HostTensor& pm
       o->xp4 = (long)(fx.size() / 3 / 8);
     }
   } else {
-    const std::vector<unsigned short> f4 = pack_fragments16(c->prec, kWnWaves, C / 64, 2, [&](int wv, int t, int col) {
+    const std::vector<unsigned short> f4 = pack_fragments16(c->pack.prec, kWnWaves, C / 64, 2, [&](int wv, int t, int col) {
       return wp.data.data() + ((size_t)32 * wv + 16 * t + col) * (C / 2);
     }, f32_to_bf16, f32_to_f16);
     STTS_TRY(dev_upload(c, f4, &o->H4));
   }
   STTS_TRY(dev_upload(c, bp->data, &o->b4));
-  o->ready = c->prec == PREC_F32;
-  o->ready16 = c->prec != PREC_F32;
-  o->ready_x3 = c->prec == PREC_F32 && c->allow_x3 && c->pack_x3 && x3_enabled();
+  o->ready = c->pack.prec == PREC_F32;
+  o->ready16 = c->pack.prec != PREC_F32;
+  o->ready_x3 = c->pack.prec == PREC_F32 && packs_x3(c);
   return 0;
 }
 
@@ -657,14 +677,7 @@ inline int finalize_frame(stts_ctx* c, int which) {
   STTS_CHECK(d.gen_hidden > 0 && d.gen_hidden % 32 == 0 && d.gen_inter > 0 && d.gen_inter % 32 == 0,
              "generator.hidden_dim / conv_intermediate_dim must be multiples of 32");
   const std::string sp = "speech_predictor.";
-  // 16-bit operand modes: input channels padded to 64 (the K tile of conv_gemm16_kernel); the stages size their rows from the packed kc
-  struct AlignReset {
-    stts_ctx* c;
-    ~AlignReset() { c->kc_align = 32; }
-  } align_reset{c};
-  c->kc_align = c->prec != PREC_F32 ? 64 : 32;
-  // tables
-  c->cur_tag = 0;
+  // tables (context lifetime: the scope opens with tag 0)
   if (!c->hann) {
     std::vector<float> h;
     std::vector<double2> tw64;
@@ -677,7 +690,7 @@ inline int finalize_frame(stts_ctx* c, int which) {
   }
   // decoder (models/decoder.py:6-45)
   if (which & STTS_W_DECODER) {
-    c->cur_tag = STTS_W_DECODER;
+    c->pack.tag = STTS_W_DECODER;
     c->dec_style = StyleTable();
     c->dec_style.K = d.style_dim;
     HostTensor wf, wn;
@@ -700,7 +713,7 @@ inline int finalize_frame(stts_ctx* c, int which) {
   }
   // prior + flow + post_flow (models/flow.py, models/speech_predictor.py:36-62)
   if (which & STTS_W_FLOW) {
-    c->cur_tag = STTS_W_FLOW;
+    c->pack.tag = STTS_W_FLOW;
     c->flow_style = StyleTable();
     c->flow_style.K = d.style_dim;
     const int fh = d.dec_hidden / 4, half = fh / 2;
@@ -747,7 +760,7 @@ inline int finalize_frame(stts_ctx* c, int which) {
   }
   // generator (models/generator.py:340-438)
   if (which & STTS_W_GENERATOR) {
-    c->cur_tag = STTS_W_GENERATOR;
+    c->pack.tag = STTS_W_GENERATOR;
     c->gen_style = StyleTable();
     c->gen_style.K = d.style_dim;
     const std::string g = sp + "generator.";
@@ -755,7 +768,7 @@ inline int finalize_frame(stts_ctx* c, int which) {
     STTS_TRY(pack_plain(c, g + "amp_prior_conv", true, 0, geo.bins, &c->amp_prior));
     STTS_TRY(pack_plain(c, g + "phase_prior_conv", true, 0, geo.bins, &c->phase_prior));
     for (int q = 0; q < 2; ++q) c->wino_prior[q] = c->wino_out[q] = WinoConv();
-    if (c->prec == PREC_F32) {
+    if (c->pack.prec == PREC_F32) {
       for (int q = 0; q < 2; ++q) {
         const std::string nm = g + (q == 0 ? "amp_prior_conv" : "phase_prior_conv");
         HostTensor wq;
@@ -776,7 +789,7 @@ inline int finalize_frame(stts_ctx* c, int which) {
       const int nmain = geo.bins - 1, ci = (int)w.shape[1], kk = (int)w.shape[2];
       STTS_CHECK((int)w.shape[0] == geo.bins && ci == h + hp, "%s: unexpected shape", nm.c_str());
       STTS_TRY(pack_rows(c, w, b, plain_rows(nmain), 0, ci, round_up(ci, 32), nmain, which == 0 ? &c->amp_out : &c->phase_out));
-      if (c->prec == PREC_F32 && kk == 7) STTS_TRY(pack_winograd(c, w, b, 0, ci, nmain, &c->wino_out[which]));
+      if (c->pack.prec == PREC_F32 && kk == 7) STTS_TRY(pack_winograd(c, w, b, 0, ci, nmain, &c->wino_out[which]));
       std::vector<float> last((size_t)kk * ci);
       for (int t = 0; t < kk; ++t)
         for (int q = 0; q < ci; ++q) last[(size_t)t * ci + q] = w.data[((size_t)nmain * ci + q) * kk + t];
@@ -789,7 +802,6 @@ inline int finalize_frame(stts_ctx* c, int which) {
     STTS_TRY(add_style(c, &c->gen_style, g + "phase_final_layer_norm", h, &c->head_phase));
     STTS_TRY(upload_table(c, &c->gen_style));
   }
-  c->cur_tag = 0;
   c->ready |= which & (STTS_W_DECODER | STTS_W_FLOW | STTS_W_GENERATOR);
   return 0;
 }

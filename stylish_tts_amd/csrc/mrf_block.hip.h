@@ -16,6 +16,7 @@ int stts_op_mrf_block(stts_ctx* c, void* stream, const char* prefix, int n_utt, 
     auto m = std::make_unique<MrfW>();
     m->channels = channels;
     m->kernel = kernel;
+    PackScope scope(c, engine_mode(c));
     for (int i = 0; i < 3; ++i) {
       const std::string si = std::to_string(i);
       STTS_TRY(pack_plain(c, key + "convs1." + si, true, 0, channels, &m->c1[i]));

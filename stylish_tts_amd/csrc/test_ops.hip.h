@@ -17,6 +17,7 @@ int stts_op_conv1d(void* stream, int n_utt, const int32_t* seg_off_host, const i
   stts_ctx tmp;  // only for allocation bookkeeping
   tmp.prec = precision == 3 ? 0 : precision;
   tmp.allow_x3 = precision != 3;
+  PackScope scope(&tmp, engine_mode(&tmp));
   struct FreeAll {  // every exit path (including the early STTS_TRY / STTS_CHECK returns) waits for the stream and frees the temporaries
     stts_ctx& t;
     hipStream_t st;
@@ -83,6 +84,7 @@ int stts_op_conv1d_x3(void* stream, int n_utt, const int32_t* seg_off_host, cons
   stts_ctx tmp;
   tmp.prec = 0;
   tmp.allow_x3 = precision != 3;
+  PackScope scope(&tmp, engine_mode(&tmp));
   struct FreeAll {
     stts_ctx& t;
     hipStream_t st;
@@ -154,6 +156,7 @@ int stts_op_adain_block(stts_ctx* c, void* stream, const char* prefix, int n_utt
   if (!c->op_blocks.count(key)) {
     auto blk = std::make_unique<AdainBlockW>();
     auto tab = std::make_unique<StyleTable>();
+    PackScope scope(c, engine_mode(c));
     STTS_TRY(pack_adain_block(c, key, cin, cout, tab.get(), blk.get()));
     STTS_TRY(upload_table(c, tab.get()));
     c->op_blocks[key] = std::move(blk);
@@ -196,6 +199,7 @@ struct GeomOpTables {
     std::vector<float> hw;
     std::vector<double2> tw;
     signal_tables(n_fft, win, &hw, &tw);
+    PackScope scope(&tmp, engine_mode(&tmp));
     STTS_TRY(dev_upload(&tmp, hw, &hann));
     STTS_TRY(dev_upload(&tmp, tw, &tw64));
     return 0;
@@ -339,6 +343,7 @@ extern "C" int stts_bench_gemm(void* stream, int n_utt, int rows_per_utt, int ci
     uint32_t s3 = 4242;
     for (auto& v : hw.data) { s3 = s3 * 1664525u + 1013904223u; v = (((s3 >> 8) & 0xFFFF) / 32768.0f - 1.0f) * 0.05f; }
     WinoConv wc;
+    PackScope scope(&tmp, engine_mode(&tmp));
     STTS_TRY(pack_winograd(&tmp, hw, nullptr, 0, cin, cout, &wc));
     float* scratch = nullptr;
     STTS_HIP(hipMalloc(&scratch, wino_scratch_floats(s, wc) * sizeof(float)));

@@ -97,9 +97,13 @@ class HipModel:
         _lib.check(self.lib.stts_set_precision(self.ctx, self.PRECISIONS[precision]))
         # row stride of the harmonic spectra = the prior convs' packed input width, asked from the library (1025 bins padded to 32 in fp32, 64 in the 16-bit modes)
         self.har_ld = int(self.lib.stts_har_ld(self.ctx))
-        # grow-only workspaces, one per launch stream (stages issued on different streams may run concurrently)
+        # grow-only workspaces (_grow), one per launch stream (stages issued on different streams may run concurrently): the frame path's, the
+        # phoneme-rate stages' (shared with the HuBERT stages: same stream discipline), MelStyleEncoder's, CfmPitchPredictor's, AdaptiveHubert's
         self._ws: Dict[int, torch.Tensor] = {}
         self._pws: Dict[int, torch.Tensor] = {}
+        self._mws: Dict[int, torch.Tensor] = {}
+        self._cpws: Dict[int, torch.Tensor] = {}
+        self._sslws: Dict[int, torch.Tensor] = {}
         self._ws_lock = threading.Lock()
 
     def close(self):
@@ -148,14 +152,17 @@ class HipModel:
         return st, st.scaled(4, dev=off4), need
 
     # ------------------------------------------------------------------ workspace
-    def workspace(self, seg: Segments) -> torch.Tensor:
-        need = int(self.lib.stts_frame_workspace_bytes(self.ctx, seg.rows, seg.n, seg.max_len))
+    def _grow(self, pool: Dict[int, torch.Tensor], need: int) -> torch.Tensor:
+        """The current stream's workspace of `pool`, reallocated when it is smaller than `need` bytes."""
         key = torch.cuda.current_stream(self.device).cuda_stream
         with self._ws_lock:
-            ws = self._ws.get(key)
+            ws = pool.get(key)
             if ws is None or ws.numel() < need:
-                ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+                ws = pool[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
         return ws
+
+    def workspace(self, seg: Segments) -> torch.Tensor:
+        return self._grow(self._ws, int(self.lib.stts_frame_workspace_bytes(self.ctx, seg.rows, seg.n, seg.max_len)))
 
     def _f32(self, *shape):
         return torch.empty(*shape, dtype=torch.float32, device=self.device)
@@ -302,14 +309,7 @@ class HipModel:
 
     # ------------------------------------------------------------------ phoneme-rate stages (packed tokens)
     def _ph_ws(self, n_tok: int, n_frames: int, n_utt: int) -> torch.Tensor:
-        """Grow-only phoneme-stage workspace, one per launch stream (stages on different streams may run concurrently)."""
-        need = int(self.lib.stts_phoneme_workspace_bytes(self.ctx, n_tok, n_frames, n_utt))
-        key = torch.cuda.current_stream(self.device).cuda_stream
-        with self._ws_lock:
-            ws = self._pws.get(key)
-            if ws is None or ws.numel() < need:
-                ws = self._pws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return ws
+        return self._grow(self._pws, int(self.lib.stts_phoneme_workspace_bytes(self.ctx, n_tok, n_frames, n_utt)))
 
     def text_encoder(self, which: int, seg: Segments, tokens: torch.Tensor, return_hidden=False):
         """tokens int64 [n_tok] (packed) -> mu [n_tok, inter] (+ last hidden [n_tok, 128])."""
@@ -369,14 +369,7 @@ class HipModel:
 
     # ------------------------------------------------------------------ HuBERT voice conversion (packed feature frames)
     def _hb_ws(self, rows_T: int, n_utt: int, max_len: int) -> torch.Tensor:
-        """Grow-only workspace of the HuBERT stages, shared with the phoneme stages' (same stream discipline)."""
-        need = int(self.lib.stts_hubert_workspace_bytes(self.ctx, rows_T, n_utt, max_len))
-        key = torch.cuda.current_stream(self.device).cuda_stream
-        with self._ws_lock:
-            ws = self._pws.get(key)
-            if ws is None or ws.numel() < need:
-                ws = self._pws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return ws
+        return self._grow(self._pws, int(self.lib.stts_hubert_workspace_bytes(self.ctx, rows_T, n_utt, max_len)))
 
     def speaker_style(self, spk_emb: torch.Tensor, style: bool = True, pe_style: bool = True):
         """spk_emb [n_utt, ld >= speaker_embedder.hidden_dim] -> (style, pe_style) [n_utt, style_dim] each (None where not asked)."""
@@ -411,12 +404,7 @@ class HipModel:
         need = int(self.lib.stts_mel_style_workspace_bytes(self.ctx, which, seg.rows, seg.n))
         if need == 0:
             _lib.check(1)  # the weights of `which` are not finalized: the library's message
-        key = torch.cuda.current_stream(self.device).cuda_stream
-        with self._ws_lock:
-            wsd = self.__dict__.setdefault("_mws", {})
-            ws = wsd.get(key)
-            if ws is None or ws.numel() < need:
-                ws = wsd[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._grow(self._mws, need)
         out = self._f32(seg.n, style_dim)
         args = (self.ctx, _stream(), which, seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(mel), mel.shape[1], _ptr(out))
         if tap_floats:
@@ -436,12 +424,7 @@ class HipModel:
         need = int(self.lib.stts_cfm_pitch_workspace_bytes(self.ctx, seg.rows, seg.n))
         if need == 0:
             _lib.check(1)  # the weights are not finalized: the library's message
-        key = torch.cuda.current_stream(self.device).cuda_stream
-        with self._ws_lock:
-            wsd = self.__dict__.setdefault("_cpws", {})
-            ws = wsd.get(key)
-            if ws is None or ws.numel() < need:
-                ws = wsd[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._grow(self._cpws, need)
         normed = self._f32(seg.rows)
         hz = self._f32(seg.rows) if f0_log2_stats is not None else None
         mean, std = (float(f0_log2_stats[0]), float(f0_log2_stats[1])) if f0_log2_stats is not None else (0.0, 1.0)
@@ -486,12 +469,7 @@ class HipModel:
         if need == 0:
             # too short an utterance (or bad offsets): let the entry point name it, it fails before any launch
             need = 256
-        key = torch.cuda.current_stream(self.device).cuda_stream
-        with self._ws_lock:
-            wsd = self.__dict__.setdefault("_sslws", {})
-            ws = wsd.get(key)
-            if ws is None or ws.numel() < need:
-                ws = wsd[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._grow(self._sslws, need)
         wave = wave.to(self.device, torch.float32).contiguous()
         if wave.dim() != 1 or wave.numel() != seg_s.rows:
             raise ValueError(f"packed waveform of {wave.numel()} samples, the offsets describe {seg_s.rows}")

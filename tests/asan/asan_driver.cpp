@@ -2,6 +2,10 @@
 // BASELINE's configs with the HIP runtime stubbed out (hip_stub.cpp).  Exercised under -fsanitize=address,undefined:
 // weight-norm folding, row / Winograd / fragment packing, style tables, the workspace closed forms against what the stages
 // really carve (a stage returns "workspace too small" if the bound is wrong), and the launch planning of every contraction.
+// It also says what the packers wrote: after every finalize a line `digest <precision> <what> <hex>` with the stub's digest of the device
+// allocations made since the context was created.  Per precision a second context finalizes the same components in another order, with one
+// finalize in the middle that must fail, and has to end at the first context's digest: packing must not depend on what was packed before.
+#include <cinttypes>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +16,7 @@
 #include "../../include/stylish_hip.h"
 
 extern "C" long stts_stub_launch_count();
+extern "C" uint64_t stts_stub_digest();
 
 #define CK(expr)                                                                  \
   do {                                                                            \
@@ -96,6 +101,23 @@ static int phoneme_case(stts_ctx* c, const std::vector<int>& toks, const std::ve
   return 0;
 }
 
+struct Tensor {
+  std::string name;
+  int ndim;
+  int64_t shape[4];
+  std::vector<float> v;
+};
+
+// STTS_W_* masks of stts_finalize_weights: text-to-speech (frame path + phoneme-rate), the HuBERT pair, the mel-style pair, CfmPitchPredictor's network
+static const int kTts = 255, kHubert = 512 | 1024, kMelStyle = 2048 | 4096, kPitchNet = 8192;
+
+static int new_ctx(const stts_model_dims& d, int prec, const std::vector<Tensor>& w, stts_ctx** out) {
+  CK(stts_ctx_create(&d, 0, out));
+  CK(stts_set_precision(*out, prec));
+  for (const Tensor& t : w) CK(stts_load_weight(*out, t.name.c_str(), t.v.data(), t.shape, t.ndim));
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) {
     fprintf(stderr, "usage: asan_driver <weights.bin>\n");
@@ -107,48 +129,93 @@ int main(int argc, char** argv) {
     return 2;
   }
   stts_model_dims d;
-  if (fread(&d, sizeof(d), 1, f) != 1) return 2;
-  for (int prec = 0; prec < 3; prec += 2) {  // fp32 and fp16 operand modes (16-bit weight copies are packed too)
-    stts_ctx* c = nullptr;
-    CK(stts_ctx_create(&d, 0, &c));
-    CK(stts_set_precision(c, prec));
-    fseek(f, sizeof(d), SEEK_SET);
-    int n_tensors = 0;
-    for (;;) {
-      int32_t name_len = 0, ndim = 0;
-      if (fread(&name_len, 4, 1, f) != 1) break;
-      std::string name(name_len, '\0');
-      if (fread(&name[0], 1, name_len, f) != (size_t)name_len || fread(&ndim, 4, 1, f) != 1) return 2;
-      int64_t shape[4] = {1, 1, 1, 1}, count = 1;
-      for (int i = 0; i < ndim; ++i) {
-        if (fread(&shape[i], 8, 1, f) != 1) return 2;
-        count *= shape[i];
-      }
-      std::vector<float> v(count);
-      if (fread(v.data(), 4, count, f) != (size_t)count) return 2;
-      CK(stts_load_weight(c, name.c_str(), v.data(), shape, ndim));
-      ++n_tensors;
+  stts_cfm_dims cd;
+  stts_ssl_dims sd;
+  if (fread(&d, sizeof(d), 1, f) != 1 || fread(&cd, sizeof(cd), 1, f) != 1 || fread(&sd, sizeof(sd), 1, f) != 1) return 2;
+  std::vector<Tensor> w;
+  for (;;) {
+    int32_t name_len = 0;
+    Tensor t;
+    if (fread(&name_len, 4, 1, f) != 1) break;
+    t.name.assign(name_len, '\0');
+    if (fread(&t.name[0], 1, name_len, f) != (size_t)name_len || fread(&t.ndim, 4, 1, f) != 1) return 2;
+    int64_t count = 1;
+    for (int i = 0; i < 4; ++i) t.shape[i] = 1;
+    for (int i = 0; i < t.ndim; ++i) {
+      if (fread(&t.shape[i], 8, 1, f) != 1) return 2;
+      count *= t.shape[i];
     }
-    CK(stts_finalize_weights(c, 255));
-    printf("precision %d: %d tensors loaded and packed\n", prec, n_tensors);
-    if (frame_case(c, std::vector<int>(8, 960), "cfg2: 8 x 3 s")) return 1;
-    if (frame_case(c, {960}, "B = 1 x 3 s")) return 1;
-    if (frame_case(c, {40, 131, 76, 14, 15, 16, 17, 33}, "short ragged utterances")) return 1;
-    if (prec == 0) {  // (ASan shadow-poisons the 28 GB workspace reservation: once is enough)
-      std::vector<int> lens;  // cfg4: 256 utterances of 0.25 - 10 s (same generator as tests/test_hip_full_size.py would give a similar spread)
-      unsigned s = 4;
-      for (int i = 0; i < 256; ++i) {
-        s = s * 1664525u + 1013904223u;
-        lens.push_back(4 * (20 + (int)((s >> 8) % 781)));
-      }
-      if (frame_case(c, lens, "cfg4: 256 utterances of 0.25-10 s")) return 1;
-    }
-    if (frame_case(c, std::vector<int>(64, 3200), "cfg5 per GPU: 64 x 10 s")) return 1;
-    if (phoneme_case(c, std::vector<int>(64, 50), std::vector<int>(64, 240), "cfg3: 64 x 50 tokens")) return 1;
-    if (phoneme_case(c, {510, 2, 160}, {1020, 4, 800}, "token-count extremes")) return 1;
-    stts_ctx_destroy(c);
+    t.v.resize(count);
+    if (fread(t.v.data(), 4, count, f) != (size_t)count) return 2;
+    w.push_back(std::move(t));
   }
   fclose(f);
+  for (int prec = 0; prec <= 3; ++prec) {  // fp32, fp16 operands (16-bit weight copies are packed too), fp32 on the f32 matrix cores
+    if (prec == 1) continue;
+    uint64_t base = stts_stub_digest();  // (what outlives a context: the library's lazily created process-wide buffers)
+    uint64_t first = 0;
+    stts_ctx* c = nullptr;
+    if (new_ctx(d, prec, w, &c)) return 1;
+    auto digest = [&](const char* what) {
+      first = stts_stub_digest() - base;
+      printf("digest %d %s %016" PRIx64 "\n", prec, what, first);
+    };
+    CK(stts_finalize_weights(c, kTts));
+    digest("tts");
+    CK(stts_finalize_weights(c, kHubert));
+    digest("hubert");
+    CK(stts_finalize_weights(c, kMelStyle));
+    digest("mel_style");
+    CK(stts_finalize_weights(c, kPitchNet));
+    digest("cfm_pitch_net");
+    CK(stts_ssl_finalize(c, &sd));
+    digest("ssl");
+    CK(stts_cfm_finalize(c, &cd));
+    digest("cfm");
+    printf("precision %d: %zu tensors loaded and packed\n", prec, w.size());
+    if (prec != 3) {  // the stage walks: once per operand width
+      if (frame_case(c, std::vector<int>(8, 960), "cfg2: 8 x 3 s")) return 1;
+      if (frame_case(c, {960}, "B = 1 x 3 s")) return 1;
+      if (frame_case(c, {40, 131, 76, 14, 15, 16, 17, 33}, "short ragged utterances")) return 1;
+      if (prec == 0) {  // (ASan shadow-poisons the 28 GB workspace reservation: once is enough)
+        std::vector<int> lens;  // cfg4: 256 utterances of 0.25 - 10 s (same generator as tests/test_hip_full_size.py would give a similar spread)
+        unsigned s = 4;
+        for (int i = 0; i < 256; ++i) {
+          s = s * 1664525u + 1013904223u;
+          lens.push_back(4 * (20 + (int)((s >> 8) % 781)));
+        }
+        if (frame_case(c, lens, "cfg4: 256 utterances of 0.25-10 s")) return 1;
+      }
+      if (frame_case(c, std::vector<int>(64, 3200), "cfg5 per GPU: 64 x 10 s")) return 1;
+      if (phoneme_case(c, std::vector<int>(64, 50), std::vector<int>(64, 240), "cfg3: 64 x 50 tokens")) return 1;
+      if (phoneme_case(c, {510, 2, 160}, {1020, 4, 800}, "token-count extremes")) return 1;
+    }
+    stts_ctx_destroy(c);
+    // another order, a finalize that fails in the middle (a depth no weights were loaded for), then that component and the frame path again
+    base = stts_stub_digest();
+    if (new_ctx(d, prec, w, &c)) return 1;
+    CK(stts_ssl_finalize(c, &sd));
+    CK(stts_cfm_finalize(c, &cd));
+    CK(stts_finalize_weights(c, kTts));
+    CK(stts_finalize_weights(c, kPitchNet));
+    stts_cfm_dims bad = cd;
+    ++bad.depth;
+    if (stts_cfm_finalize(c, &bad) == 0) {
+      fprintf(stderr, "FAILED: stts_cfm_finalize accepted depth %d without its weights\n", bad.depth);
+      return 1;
+    }
+    CK(stts_finalize_weights(c, kMelStyle));
+    CK(stts_finalize_weights(c, kHubert));
+    CK(stts_cfm_finalize(c, &cd));
+    CK(stts_finalize_weights(c, kTts));
+    const uint64_t second = stts_stub_digest() - base;
+    stts_ctx_destroy(c);
+    if (second != first) {
+      fprintf(stderr, "FAILED: precision %d packed %016" PRIx64 " in the second order, %016" PRIx64 " in the first\n", prec, second, first);
+      return 1;
+    }
+    printf("order %d: the second order and the failed finalize end at the same digest %016" PRIx64 "\n", prec, second);
+  }
   printf("asan driver: all cases ran, %ld stubbed launches\n", stts_stub_launch_count());
   return 0;
 }

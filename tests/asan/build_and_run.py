@@ -5,8 +5,11 @@
 
 Steps: (1) hipcc --cuda-host-only -fsanitize=address,undefined -c for every translation unit of the library (no device code is generated or loaded),
 (2) link it with hip_stub.cpp into libstylish_hip_asan.so (the fat-binary symbol the host code references is defined as an
-empty blob), (3) dump the synthetic weights of every inference module to a binary file, (4) run asan_driver on it.
-Exit code 0 = no sanitizer report and every stage accepted its workspace for every shape."""
+empty blob), (3) dump the synthetic weights of every inference module, of the voice-conversion models, of the CFM estimator and of a narrow
+AdaptiveHubert to a binary file, (4) run asan_driver on it.
+Exit code 0 = no sanitizer report, every stage accepted its workspace for every shape, and the packed bytes did not depend on the order of the
+finalizes.  The driver's `digest <precision> <what> <hex>` lines say what was packed: two builds of the library pack the same bytes exactly when
+these lines are the same."""
 import os
 import struct
 import subprocess
@@ -41,24 +44,28 @@ def main(build_dir):
     exe = os.path.join(build_dir, "asan_driver")
     subprocess.check_call([cxx, *san, os.path.join(HERE, "asan_driver.cpp"), lib, f"-Wl,-rpath,{build_dir}", "-o", exe])
 
-    # weights: every inference module's synthetic state dict, in the library's naming (module + "." + key)
-    from stylish_tts_amd import _lib, params
+    # weights: every module's synthetic state dict under the name modules.py loads it by (module + "." + key); the header is the three dims structs
+    from stylish_tts_amd import _lib, hubert_ssl, params
     from stylish_tts_amd.config import load_model_config
 
     cfg = load_model_config()
+    # the narrow AdaptiveHubert of tests/golden/gen_golden_ssl.py (NARROW)
+    ssl_arch = hubert_ssl.arch(dict(hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256, conv_dim=(64,) * 7,
+                                    num_conv_pos_embeddings=32, num_conv_pos_embedding_groups=4))
+    specs = [(m, params.module_spec(m, cfg)) for t in (params.MODULE_SPECS, params.HUBERT_MODULE_SPECS, params.MEL_STYLE_MODULE_SPECS) for m in t]
+    specs += [("cfm_mel_decoder", params.cfm_mel_decoder_spec()), ("hubert", params.hubert_ssl_spec(ssl_arch))]
     wpath = os.path.join(build_dir, "weights.bin")
     with open(wpath, "wb") as f:
-        f.write(bytes(_lib.dims_from_config(cfg)))
-        for m in params.MODULE_SPECS:
-            sd = params.synth_state_dict(params.module_spec(m, cfg), 0, prefix=m + ".")
-            for k, v in sd.items():
+        f.write(bytes(_lib.dims_from_config(cfg)) + bytes(_lib.CfmDims(**params.CFM_DEFAULT_DIMS)) + bytes(hubert_ssl.dims_struct(ssl_arch)))
+        for m, spec in specs:
+            for k, v in params.synth_state_dict(spec, 0, prefix=m + ".").items():
                 name = (m + "." + k).encode()
                 shape = v.shape if v.ndim else (1,)
                 f.write(struct.pack("<i", len(name)) + name + struct.pack("<i", len(shape)) + struct.pack(f"<{len(shape)}q", *shape))
                 f.write(v.astype("<f4").tobytes())
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([exe, wpath], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    print(r.stdout[-6000:])
+    print(r.stdout)
     return r.returncode
 
 

@@ -3,23 +3,47 @@
 // (64 bytes of red zone checked by AddressSanitizer like any other heap block), copies are memcpy, kernel launches
 // are counted and otherwise ignored: what runs under the sanitizers is the library's own host code - weight folding and
 // packing, Winograd / fragment packing, workspace carving, launch planning - over the shapes of BASELINE's configs.
+// Device allocations are zero-filled and recorded, so that stts_stub_digest() can say what the packers wrote.
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 
 static long g_launches = 0;
 extern "C" long stts_stub_launch_count() { return g_launches; }
+
+static std::map<void*, size_t>& live_allocs() {
+  static std::map<void*, size_t> m;
+  return m;
+}
+// Sum mod 2^64, over the live hipMalloc allocations, of FNV-1a 64 of (size as 8 little-endian bytes, then the bytes): a sum, so the order
+// the allocations were made in does not matter and the digest of an earlier state can be subtracted.
+extern "C" uint64_t stts_stub_digest() {
+  uint64_t sum = 0;
+  for (const auto& kv : live_allocs()) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (int i = 0; i < 8; ++i) h = (h ^ ((kv.second >> (8 * i)) & 0xff)) * 0x100000001b3ull;
+    const unsigned char* b = (const unsigned char*)kv.first;
+    for (size_t i = 0; i < kv.second; ++i) h = (h ^ b[i]) * 0x100000001b3ull;
+    sum += h;
+  }
+  return sum;
+}
 
 extern "C" {
 char stts_stub_fatbin[16] = {0};
 
 hipError_t hipMalloc(void** p, size_t n) {
-  *p = malloc(n ? n : 1);
-  return *p ? hipSuccess : hipErrorOutOfMemory;
+  *p = calloc(n ? n : 1, 1);
+  if (!*p) return hipErrorOutOfMemory;
+  live_allocs()[*p] = n;
+  return hipSuccess;
 }
 hipError_t hipFree(void* p) {
+  live_allocs().erase(p);
   free(p);
   return hipSuccess;
 }
