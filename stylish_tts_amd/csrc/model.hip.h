@@ -1388,451 +1388,12 @@ inline int decoder_forward(stts_ctx* c, hipStream_t st, const Seg& s, const floa
   return pending_finish(st, &pend);  // the last block's output has no AdaIN behind it
 }
 
-#ifdef STTS_WN_TRACE
-// diagnostics build only: per-wave phase stamps of the 32 fused WaveNet launches of one flow pass, averaged to stderr
-struct WnTrace {
-  long long* dev = nullptr;
-  long blocks[32] = {};
-  static constexpr long kMax = 1024;
-};
-inline WnTrace& wn_trace() {
-  static WnTrace t;
-  return t;
-}
-inline long long* wn_trace_buffer(int launch, long blocks) {
-  WnTrace& t = wn_trace();
-  if (!t.dev) (void)hipMalloc(&t.dev, 32 * WnTrace::kMax * 64 * sizeof(long long));
-  if (blocks > WnTrace::kMax) return nullptr;
-  t.blocks[launch] = blocks;
-  (void)hipMemsetAsync(t.dev + launch * WnTrace::kMax * 64, 0, blocks * 64 * sizeof(long long), 0);
-  return t.dev + launch * WnTrace::kMax * 64;
-}
-inline void wn_trace_report(hipStream_t st) {
-  WnTrace& t = wn_trace();
-  (void)hipStreamSynchronize(st);
-  static int calls = 0;
-  if (++calls % 8 != 0) return;
-  std::vector<long long> h(WnTrace::kMax * 64);
-  for (int kind = 0; kind < 2; ++kind) {  // plain layers, last layers
-    double ph[8][6] = {}, wall = 0, clk = 0;
-    long n = 0;
-    for (int l = 0; l < 32; ++l) {
-      if ((l % 4 == 3) != (kind == 1) || !t.blocks[l]) continue;
-      (void)hipMemcpy(h.data(), t.dev + l * WnTrace::kMax * 64, t.blocks[l] * 64 * sizeof(long long), hipMemcpyDeviceToHost);
-      for (long b = 0; b < t.blocks[l]; ++b) {
-        const long long* r0 = &h[64 * b];
-        if (!r0[5]) continue;
-        for (int wv = 0; wv < kWnWaves; ++wv) {
-          const long long* r = r0 + 8 * wv;
-          for (int i = 0; i < 6; ++i) ph[wv][i] += (double)(r[i] - r0[0]);  // cycles since wave 0 started
-        }
-        wall += (double)(r0[7] - r0[6]) * 10.0;  // ns
-        clk += (double)(r0[5] - r0[0]);
-        ++n;
-      }
-    }
-    if (!n) continue;
-    const double ghz = clk / wall;
-    fprintf(stderr, "[wn trace] %s layers: %ld blocks, wave 0: %.2f us per block at %.2f GHz; per wave, us since the block started: start | prologue end | phase-1 end | gate barrier | phase-2 end | end\n",
-            kind ? "last" : "plain", n, wall / n * 1e-3, ghz);
-    for (int wv = 0; wv < kWnWaves; ++wv) {
-      fprintf(stderr, "    wave %d:", wv);
-      for (int i = 0; i < 6; ++i) fprintf(stderr, " %6.2f", ph[wv][i] / n / ghz * 1e-3);
-      fprintf(stderr, "\n");
-    }
-  }
-}
-#endif
+}  // namespace stts
 
-// ------------------------------------------------------------------------------------------------
-// stage: PriorEncoder + reverse flow + post_flow (models/flow.py:311-315, :132-151, :196-218, :63-88)
-// ------------------------------------------------------------------------------------------------
-inline int prior_flow_forward(stts_ctx* c, hipStream_t st, const Seg& s, const float* x, int ld_x, const float* style, const float* noise,
-                              float* mel, int ld_mel, float* z_prior_out, float* z_flow_out, Arena& ws, unsigned short* mel16 = nullptr,
-                              int ld_mel16 = 0) {
-  // mel16: also write mel rounded to the operand precision (the vocoder's projector reads it; 16-bit modes, large batches)
-  const stts_model_dims& d = c->d;
-  const long R = s.rows();
-  const int fh = d.dec_hidden / 4, half = fh / 2, ml = s.max_len();
-  // (kWnRowPad rows of slack: wn_fused_kernel reads whole 16-row tiles, also past the last utterance; never stored)
-  float* z = ws.get<float>((R + kWnRowPad) * fh);
-  float* hf = ws.get<float>((R + kWnRowPad) * fh);
-  float* hf2 = ws.get<float>((R + kWnRowPad) * fh);
-  float* outf = ws.get<float>((R + kWnRowPad) * fh);
-  // the fused WaveNet kernels are built for 128 flow channels (decoder.hidden_dim 512); other widths run every layer as
-  // two contractions (gate epilogue, then res/skip split-accumulate) and need the gated activations in memory
-  const bool generic = fh != kWnC;
-  float* actsg = generic ? ws.get<float>(R * fh) : nullptr;
-  float* cond = ws.get<float>((size_t)s.n_utt * c->flow_style.ld());
-  STTS_CHECK(ws.ok, "prior_flow_forward: workspace too small");
-  STTS_DRY_RETURN(ws);
-  STTS_TRY(run_style(st, c->flow_style, style, s.n_utt, cond));
-  {
-    GemmArgs a = gemm_args(s);
-    set_seg(a, 0, x, ld_x, 0, c->prior);
-    a.N = fh; a.bias = c->prior.bias; a.Z = z; a.ldz = fh; a.noise = noise; a.ldnoise = fh;
-    STTS_TRY(launch_conv_gemm(st, a, EPI_PRIOR, c->prior.npad, s.n_utt, ml));
-  }
-  if (z_prior_out) STTS_HIP(hipMemcpyAsync(z_prior_out, z, R * fh * sizeof(float), hipMemcpyDeviceToDevice, st));
-  // reversed(flows) = Flip, layer 7, Flip, layer 6, ..., Flip, layer 0: after k flips the roles of the halves swap,
-  // so layer f reads half p = (f odd) and updates the other half in place; after layer 0 the order is natural.
-  // 32-row or 16-row blocks for the fused WaveNet layer (fp32): one block per CU is resident, so a launch takes
-  // ceil(blocks / 256) rounds of ~38 us (32 rows) or ~21 us (16 rows: half the MFMA chain, but the weight staging per
-  // block is the same).  B = 8: 240 x 38 us beats 480 blocks = 2 x 21; B = 12: 720 blocks = 3 x 21 beats 360 = 2 x 38.
-  bool rows16 = false;
-  int fused_m = 0;  // fp32: wn_fused_kernel with F(2,5) (32-row blocks) or F(4,5) (64-row blocks); 0 = the staged kernels
-  if (c->prec == PREC_F32) {
-    long b64 = 0, b32 = 0, b16 = 0;
-    for (int u = 0; u < s.n_utt; ++u) {
-      const int len = s.host[u + 1] - s.host[u];
-      b64 += ceil_div(len, 64);
-      b32 += ceil_div(len, 32);
-      b16 += ceil_div(len, 16);
-    }
-    rows16 = ceil_div((int)b16, 256) * 21 < ceil_div((int)b32, 256) * 38;
-    if (c->flow[0].fused.ready) {
-      // wn_fused_kernel: one block per CU is resident, so a launch takes ceil(blocks / 256) rounds of ~kT2 us (F(2,5), 32-row
-      // blocks) or ~kT4 us (F(4,5), 64-row blocks); the staged 16-row kernel (one round = ~kT16 us) only wins while its
-      // blocks fit one round (B <= 4 at 3 s).  Measured (MI355X, tools/flow_bench.py): B = 8 28 us, B = 16 41 us (F(4,5)) vs
-      // 55 (F(2,5)), B = 64 150 us vs 209 per WaveNet layer; staged kernels 40 / - / 287.
-      const int force = getenv("STTS_WN_M") ? atoi(getenv("STTS_WN_M")) : 0;  // tests / tools: force a block shape
-      constexpr int kT16 = 22, kT2 = 28, kT4 = 41;
-      const int t16 = ceil_div((int)b16, 256) * kT16, t2 = ceil_div((int)b32, 256) * kT2, t4 = ceil_div((int)b64, 256) * kT4;
-      // the same kernel in its direct form on 16-row blocks (M = 1) takes the place of the staged 16-row kernel for the smallest
-      // batches (B = 1: 19.9 vs 21.1 us per layer, B = 4: 22.0 vs 23.2; F(2,5) there: 25.3 / 27.4)
-      constexpr int kT1 = 21;
-      const int t1 = ceil_div((int)b16, 256) * kT1;
-      (void)t16;
-      fused_m = t4 < t2 ? 4 : 2;
-      if (t1 <= std::min(t2, t4)) fused_m = 1;
-      rows16 = false;
-      if (force == 1 || force == 2 || force == 4) fused_m = force;
-      if (force == 16) {  // the staged 16-row kernel (kept for comparison)
-        fused_m = 0;
-        rows16 = true;
-      }
-    }
-  }
-  // 16-bit operand modes: wn_fused16_kernel on 64- or 128-row blocks (the taller block halves the weight stream per row; it
-  // needs ~1.5 chip rounds of blocks to pay)
-  int fused16_rt = 0;
-  if (c->prec != PREC_F32 && !generic && c->flow[0].fused.ready16) {
-    long b128 = 0;
-    for (int u = 0; u < s.n_utt; ++u) b128 += ceil_div(s.host[u + 1] - s.host[u], 128);
-    fused16_rt = b128 >= 384 ? 8 : 4;
-    // at least ~0.75 chip rounds of 128-row blocks: one launch per coupling layer with h and `out` on chip (wn_block16.hip.h)
-    if (b128 >= 192) fused16_rt = 16;
-    const int force = getenv("STTS_WN_RT") ? atoi(getenv("STTS_WN_RT")) : 0;  // tests / tools
-    if (force == 4 || force == 8 || force == 16) fused16_rt = force;
-    if (force == -1) fused16_rt = 0;  // the staged kernel
-  }
-  // split fp32 (fp32 mode): wn_fused_x3_kernel on 32-row blocks, 64-row blocks once those fill the chip more than once (the taller block halves the
-  // weight stream per row); small batches (16-row blocks win there) stay on the f32 kernel's direct form
-  int fusedx3_rt = 0;
-  if (c->prec == PREC_F32 && fused_m != 0 && fused_m != 1 && c->flow[0].fused.ready_x3) {
-    long b64 = 0, b32 = 0;
-    for (int u = 0; u < s.n_utt; ++u) {
-      b64 += ceil_div(s.host[u + 1] - s.host[u], 64);
-      b32 += ceil_div(s.host[u + 1] - s.host[u], 32);
-    }
-    // one block per CU is resident: a launch takes ceil(blocks / 256) rounds.  Fitted to 3-s batches of 8 .. 32 (us per launch): 32-row blocks 4.5 + 17.5 per
-    // round, 64-row blocks (twice the matrix work per block for one weight stream) 1.5 + 29.5 per round.  B = 8: 22 vs 31; B = 10 .. 16: 40 vs 31;
-    // B = 20 / 24: 57 vs 60; B = 32: 74 vs 60 - the measured optimum at every one of them
-    fusedx3_rt = 1.5 + 29.5 * ceil_div((int)b64, 256) < 4.5 + 17.5 * ceil_div((int)b32, 256) ? 4 : 2;
-    const int force = getenv("STTS_WN_X3") ? atoi(getenv("STTS_WN_X3")) : 0;  // tests / tools: 2 / 4 = block shape, -1 = the f32 kernel
-    if (force == 1 || force == 2 || force == 4) fusedx3_rt = force;
-    if (force == -1) fusedx3_rt = 0;
-  }
-  // small batches (the f32 kernel would run its direct form on 16-row blocks, M = 1): the split kernel on 16-row blocks too
-  if (c->prec == PREC_F32 && fused_m == 1 && c->flow[0].fused.ready_x3) {
-    fusedx3_rt = 1;
-    const int force = getenv("STTS_WN_X3") ? atoi(getenv("STTS_WN_X3")) : 0;
-    if (force == 1 || force == 2 || force == 4) fusedx3_rt = force;
-    if (force == -1) fusedx3_rt = 0;
-  }
-  // ... and one launch per COUPLING layer (wn_block_x3_kernel: four WaveNet layers + post + coupling + next pre, h and `out` on chip) with 32 output
-  // rows per block (48 computed), 48 (64 computed: what fits the LDS next to the fp32 residual stream) once the 32-row blocks exceed one chip round
-  int blockx3_rt = 0;
-  if (fusedx3_rt) {
-    long b32 = 0;
-    for (int u = 0; u < s.n_utt; ++u) b32 += ceil_div(s.host[u + 1] - s.host[u], 32);
-    (void)b32;
-    // (built, parity-tested, NOT selected: 8 launches of 98 us against 32 of 22.6 at B = 8 - 0.79 vs 0.72 ms per step - and 1.80 vs 1.30 ms at B = 16: the
-    //  2 x 8 halo rows are 1.5 x the matrix work of a 32-row block and the four layers of a block run back to back on one wave per SIMD, which costs
-    //  more than the 24 launch ramps + prologues it saves.  STTS_WN_X3B=3 | 4 selects it for experiments.)
-    const int force = getenv("STTS_WN_X3B") ? atoi(getenv("STTS_WN_X3B")) : 0;  // tests / tools: 3 / 4 = tile shape
-    if (force == 3 || force == 4) blockx3_rt = force;
-    if (force == -1) blockx3_rt = 0;
-  }
-  auto wptr = [&](const PackedConv& pc) -> const void* { return c->prec != PREC_F32 ? (const void*)pc.W16 : (const void*)pc.W; };
-  // experiments / tests: wn_fused_x3_kernel with 4 waves per block (default: eight, wn_fused_x3.hip.h); read on every call like STTS_WN_X3
-  const int x3_waves = getenv("STTS_WN_X3_WAVES") ? atoi(getenv("STTS_WN_X3_WAVES")) : 8;
-  // diagnostics (tests/test_hip_flow_layers.py; read on every call, needs z_flow_out): STTS_WN_DEBUG = +-k stops after WaveNet layer k = 4 (7 - f) + i + 1
-  // and hands back h after that layer (+k) or `out` (-k); k = 0: the first coupling layer's h_0 = pre(z).  After a coupling layer's last WaveNet layer
-  // (i = 3; the fused kernels keep the finished `out` on chip) +k hands back the next coupling layer's h_0 = pre(z) (the last coupling layer, f = 0: z) and
-  // -k the whole z, its coupled half updated.  wn_block_x3_kernel (one launch per coupling layer) answers k = 0 and the i = 3 numbers only.
-  const bool dbg_on = getenv("STTS_WN_DEBUG") && z_flow_out;
-  const int dbg_n = dbg_on ? atoi(getenv("STTS_WN_DEBUG")) : -1000;
-  auto dbg_hand_back = [&](const float* src) -> int {
-    STTS_HIP(hipGetLastError());  // (a launch error of the last kernel is reported, not hidden by the early return)
-    STTS_HIP(hipMemcpyAsync(z_flow_out, src, R * fh * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return 0;
-  };
-  float* blk_in = hf;  // wn_block16_kernel: the coupling layer's h_0 (ping-pongs between hf and hf2)
-  for (int f = 7; f >= 0; --f) {
-    const FlowLayerW& L = c->flow[f];
-    const int p = f & 1;
-    if (generic) {
-      // ResidualCouplingLayer.forward(reverse) as plain contractions (flow.py:196-218, WN :63-88): pre -> 4 x {conv k5 with
-      // the gate in its epilogue, res/skip with the h / out split in its epilogue} -> post with the coupling in its epilogue
-      GemmArgs a = gemm_args(s);
-      set_seg(a, 0, z, fh, p * half, L.pre);
-      a.N = fh; a.bias = L.pre.bias; a.Y = hf; a.ldy = fh;
-      STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, L.pre.npad, s.n_utt, ml));
-      if (dbg_n == 4 * (7 - f)) return dbg_hand_back(hf);  // k = 0, or the previous coupling layer's +k at i = 3
-      for (int i = 0; i < 4; ++i) {
-        GemmArgs g = gemm_args(s);
-        set_seg(g, 0, hf, fh, 0, L.in[i]);
-        g.N = fh; g.bias = L.in[i].bias; g.Y = actsg; g.ldy = fh;
-        g.gate = cond; g.ld_gate = c->flow_style.ld(); g.gcol0 = L.cond_col0 + i * 2 * fh; g.gC = fh;
-        STTS_TRY(launch_conv_gemm(st, g, EPI_GATE, L.in[i].npad, s.n_utt, ml));
-        GemmArgs r = gemm_args(s);
-        set_seg(r, 0, actsg, fh, 0, L.rs[i]);
-        r.N = L.rs[i].N; r.bias = L.rs[i].bias;
-        r.D0 = hf; r.ldd0 = fh; r.acc0 = 1;                 // h += rs[:fh]   (every row tile reads only its own rows of `acts`)
-        r.D1 = outf; r.ldd1 = fh; r.acc1 = i > 0;           // out (+)= rs[fh:] ; last layer: all of rs
-        r.nsplit = L.rs[i].N == 2 * fh ? fh : 0;
-        STTS_TRY(launch_conv_gemm(st, r, EPI_SPLIT_ACC, L.rs[i].npad, s.n_utt, ml));
-        if (i < 3 && (dbg_n == 4 * (7 - f) + i + 1 || dbg_n == -(4 * (7 - f) + i + 1))) return dbg_hand_back(dbg_n > 0 ? hf : outf);
-      }
-      GemmArgs q = gemm_args(s);
-      set_seg(q, 0, outf, fh, 0, L.proj);
-      q.N = half; q.bias = L.proj.bias; q.Z = z; q.ldz = fh; q.zcol0 = (1 - p) * half;
-      STTS_TRY(launch_conv_gemm(st, q, EPI_COUPLE, L.proj.npad, s.n_utt, ml));
-      if (dbg_n == -(4 * (7 - f) + 4) || (f == 0 && dbg_n == 4 * 7 + 4)) return dbg_hand_back(z);
-      continue;
-    }
-    if (f == 7) {  // later blocks get their `pre` from the tail of the previous block's last WaveNet launch
-      GemmArgs a = gemm_args(s);
-      set_seg(a, 0, z, fh, p * half, L.pre);
-      a.N = fh; a.bias = L.pre.bias; a.Y = hf; a.ldy = fh;
-      STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, L.pre.npad, s.n_utt, ml));
-      if (dbg_n == 0) return dbg_hand_back(hf);
-    }
-    if (blockx3_rt) {
-      // ---- split fp32: one launch for the whole coupling layer; reads h_0 = pre(z0) from `blk_in`, writes the next coupling layer's h_0 to the other buffer
-      WnBlockX3Args ba;
-      memset(&ba, 0, sizeof(ba));
-      ba.Hin = blk_in; ba.seg_off = s.dev; ba.gate = cond; ba.ld_gate = c->flow_style.ld();
-      double flops = 0;
-      for (int i = 0; i < 4; ++i) {
-        ba.W1[i] = L.fused.X1[i]; ba.b1[i] = L.fused.b1[i]; ba.W2[i] = L.fused.X2b[i]; ba.b2[i] = L.fused.b2[i]; ba.p2[i] = L.fused.xp2[i];
-        ba.gcol0[i] = L.cond_col0 + i * 2 * fh;
-        flops += 2.0 * (double)R * 2 * fh * 5 * fh + 2.0 * (double)R * (double)L.rs[i].N * fh;
-      }
-      ba.p1 = L.fused.xp1; ba.p3 = L.fused.xp3;
-      ba.tail = f > 0 ? 2 : 1;
-      ba.W3 = L.fused.X3; ba.b3m = L.fused.b3m; ba.b3s = L.fused.b3s; ba.Z = z; ba.ldz = fh; ba.zcol0 = (1 - p) * half;
-      flops += 2.0 * (double)R * fh * fh;
-      float* blk_out = blk_in == hf ? hf2 : hf;
-      if (f > 0) {
-        ba.W4 = c->flow[f - 1].fused.X4; ba.p4 = c->flow[f - 1].fused.xp4; ba.b4 = c->flow[f - 1].fused.b4; ba.Hpre = blk_out;
-        flops += 2.0 * (double)R * fh * half;
-      }
-      GemmProfiler& prof = gemm_profiler();
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (prof.on) {
-        e0 = prof.next();
-        e1 = prof.next();
-        // executed = the algorithmic flops x the halo recompute (16 RT computed rows per 16 RT - 16 output rows)
-        prof.add("wn_block_kernel_x3", 0, flops, flops * (16.0 * blockx3_rt) / (16.0 * blockx3_rt - 16.0), 0.0);
-      }
-      const int out_rows = 16 * blockx3_rt - 2 * kWnBlockX3Halo;
-      const dim3 bgrid(ceil_div(ml, out_rows), s.n_utt);
-      if (blockx3_rt == 3) STTS_LAUNCH_TIMED((wn_block_x3_kernel<3>), bgrid, dim3(64 * kWnWaves), st, e0, e1, ba);
-      else STTS_LAUNCH_TIMED((wn_block_x3_kernel<4>), bgrid, dim3(64 * kWnWaves), st, e0, e1, ba);
-      if (dbg_n == 4 * (7 - f) + 4 || dbg_n == -(4 * (7 - f) + 4)) return dbg_hand_back(dbg_n > 0 && f > 0 ? blk_out : z);
-      blk_in = blk_out;
-      STTS_HIP(hipGetLastError());
-      continue;
-    }
-    if (fused16_rt == 16) {
-      // ---- one launch for the whole coupling layer (16-bit modes, large batches): reads h_0 = pre(z0) from `blk_in`, writes the next
-      // coupling layer's h_0 to the other buffer (neighbouring blocks still read their halo rows of `blk_in`)
-      WnBlock16Args ba;
-      memset(&ba, 0, sizeof(ba));
-      ba.Hin = blk_in; ba.seg_off = s.dev; ba.gate = cond; ba.ld_gate = c->flow_style.ld();
-      double flops = 0;
-      for (int i = 0; i < 4; ++i) {
-        ba.W1[i] = L.fused.H1[i]; ba.b1[i] = L.fused.b1[i]; ba.W2[i] = L.fused.H2b[i]; ba.b2[i] = L.fused.b2[i];
-        ba.gcol0[i] = L.cond_col0 + i * 2 * fh;
-        flops += 2.0 * (double)R * 2 * fh * 5 * fh + 2.0 * (double)R * (double)L.rs[i].N * fh;
-      }
-      ba.tail = f > 0 ? 2 : 1;
-      ba.W3 = L.fused.H3; ba.b3m = L.fused.b3m; ba.b3s = L.fused.b3s; ba.Z = z; ba.ldz = fh; ba.zcol0 = (1 - p) * half;
-      flops += 2.0 * (double)R * fh * fh;
-      float* blk_out = blk_in == hf ? hf2 : hf;
-      if (f > 0) {
-        ba.W4 = c->flow[f - 1].fused.H4; ba.b4 = c->flow[f - 1].fused.b4; ba.Hpre = blk_out;
-        flops += 2.0 * (double)R * fh * half;
-      }
-      GemmProfiler& prof = gemm_profiler();
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (prof.on) {
-        e0 = prof.next();
-        e1 = prof.next();
-        prof.add("wn_block16_kernel", 0, flops, flops, 0.0);
-      }
-      const dim3 bgrid(ceil_div(ml, kWnBlockRows), s.n_utt);
-      if (c->prec == PREC_BF16) STTS_LAUNCH_TIMED((wn_block16_kernel<PREC_BF16>), bgrid, dim3(64 * kWnWaves), st, e0, e1, ba);
-      else STTS_LAUNCH_TIMED((wn_block16_kernel<PREC_F16>), bgrid, dim3(64 * kWnWaves), st, e0, e1, ba);
-      blk_in = blk_out;
-      STTS_HIP(hipGetLastError());
-      continue;
-    }
-    float* hcur = hf;
-    float* hnext = hf2;
-    for (int i = 0; i < 4; ++i) {
-      // one launch per WaveNet layer: conv k5 + gate + res/skip + h/out update (wn_layer.hip.h); the last one also
-      // applies the block's post projection + reverse coupling and the next block's pre projection to its rows
-      WnArgs w;
-      w.Hin = hcur; w.Hout = i < 3 ? hnext : nullptr; w.Out = outf; w.seg_off = s.dev;
-      w.Win = wptr(L.in[i]); w.bin = L.in[i].bias; w.Wrs = wptr(L.rs[i]); w.brs = L.rs[i].bias;
-      w.gate = cond; w.ld_gate = c->flow_style.ld(); w.gcol0 = L.cond_col0 + i * 2 * fh;
-      w.n_rs = L.rs[i].N; w.out_acc = i > 0;
-      w.tail = 0; w.Wproj = w.Wpre = nullptr; w.bproj = w.bpre = nullptr; w.Z = w.Hpre = nullptr; w.ldz = w.zcol0 = 0;
-      double extra = 0;
-      if (i == 3) {
-        w.tail = f > 0 ? 2 : 1;
-        w.Wproj = wptr(L.proj); w.bproj = L.proj.bias; w.Z = z; w.ldz = fh; w.zcol0 = (1 - p) * half;
-        extra = 2.0 * (double)R * fh * fh;
-        if (f > 0) {
-          const FlowLayerW& nx = c->flow[f - 1];
-          w.Wpre = wptr(nx.pre); w.bpre = nx.pre.bias; w.Hpre = hf;  // layer 3 reads hf2; hf is free and is the next block's h
-          extra += 2.0 * (double)R * fh * half;
-        }
-      }
-      GemmProfiler& prof = gemm_profiler();
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (prof.on) {
-        e0 = prof.next();
-        e1 = prof.next();
-        const double rest = 2.0 * (double)R * (double)L.rs[i].N * fh + extra, conv = 2.0 * (double)R * 2 * fh * 5 * fh;
-        // the fused kernel executes F(M,5): M + 4 instead of 5 M products per channel and group of M rows
-        prof.add(fusedx3_rt ? "wn_fused_kernel_x3" : fused_m ? "wn_fused_kernel" : (fused16_rt ? "wn_fused16_kernel" : "wn_layer_kernel"), 0, conv + rest,
-                 ((fused_m && !fusedx3_rt) ? conv * (fused_m + 4) / (5.0 * fused_m) : conv) + rest, 0.0);
-      }
-      const dim3 wgrid(ceil_div(ml, 32), s.n_utt);
-      if (fusedx3_rt) {
-        WnFusedX3Args xa;
-        memset(&xa, 0, sizeof(xa));
-        WnFused16Args& fa = xa.b;
-        fa.Hin = hcur; fa.Hout = w.Hout; fa.Out = outf; fa.seg_off = s.dev;
-        fa.W1 = L.fused.X1[i]; fa.b1 = L.fused.b1[i]; fa.W2 = L.fused.X2[i]; fa.b2 = L.fused.b2[i];
-        xa.p1 = L.fused.xp1; xa.p2 = L.fused.xp2[i]; xa.p3 = L.fused.xp3;
-        fa.gate = cond; fa.ld_gate = w.ld_gate; fa.gcol0 = w.gcol0; fa.out_acc = w.out_acc; fa.tail = w.tail;
-        fa.W3 = L.fused.X3; fa.b3m = L.fused.b3m; fa.b3s = L.fused.b3s; fa.Z = w.Z; fa.ldz = w.ldz; fa.zcol0 = w.zcol0;
-        if (w.tail > 1) { fa.W4 = c->flow[f - 1].fused.X4; xa.p4 = c->flow[f - 1].fused.xp4; fa.b4 = c->flow[f - 1].fused.b4; fa.Hpre = w.Hpre; }
-        if (s.n_utt <= kWnSegInline && !s.cap) {
-          fa.n_inline = s.n_utt;
-          memcpy(fa.seg_inline, s.host, (s.n_utt + 1) * sizeof(int));
-        }
-        const dim3 fgrid(ceil_div(ml, 16 * fusedx3_rt), s.n_utt);
-#ifdef STTS_WN_TRACE
-        xa.dbg = wn_trace_buffer((f * 4 + i), (long)fgrid.x * fgrid.y);
-#endif
-        const bool eight = x3_waves != 4;
-#define STTS_WNX3(RT_)                                                                                                                  \
-  do {                                                                                                                                   \
-    if (eight) {                                                                                                                         \
-      if (i == 3) STTS_LAUNCH_TIMED((wn_fused_x3_kernel<RT_, true, 2 * kWnWaves>), fgrid, dim3(128 * kWnWaves), st, e0, e1, xa);        \
-      else STTS_LAUNCH_TIMED((wn_fused_x3_kernel<RT_, false, 2 * kWnWaves>), fgrid, dim3(128 * kWnWaves), st, e0, e1, xa);             \
-    } else {                                                                                                                             \
-      if (i == 3) STTS_LAUNCH_TIMED((wn_fused_x3_kernel<RT_, true>), fgrid, dim3(64 * kWnWaves), st, e0, e1, xa);                       \
-      else STTS_LAUNCH_TIMED((wn_fused_x3_kernel<RT_, false>), fgrid, dim3(64 * kWnWaves), st, e0, e1, xa);                            \
-    }                                                                                                                                    \
-  } while (0)
-        if (fusedx3_rt == 4) STTS_WNX3(4);
-        else if (fusedx3_rt == 1) STTS_WNX3(1);
-        else STTS_WNX3(2);
-#undef STTS_WNX3
-      }
-      else if (fused_m) {
-        auto launch = [&](auto mtag) {
-          constexpr int M = decltype(mtag)::value;
-          WnFusedArgs<M> fa;
-          memset(&fa, 0, sizeof(fa));
-          fa.Hin = hcur; fa.Hout = w.Hout; fa.Out = outf; fa.seg_off = s.dev;
-          fa.W1 = L.fused.W1[M == 2 ? 0 : (M == 4 ? 1 : 2)][i]; fa.b1 = L.fused.b1[i]; fa.W2 = L.fused.W2[i]; fa.b2 = L.fused.b2[i];
-          fa.gate = cond; fa.ld_gate = w.ld_gate; fa.gcol0 = w.gcol0; fa.out_acc = w.out_acc; fa.tail = w.tail;
-          fa.W3 = L.fused.W3; fa.b3m = L.fused.b3m; fa.b3s = L.fused.b3s; fa.Z = w.Z; fa.ldz = w.ldz; fa.zcol0 = w.zcol0;
-          if (w.tail > 1) { fa.W4 = c->flow[f - 1].fused.W4; fa.b4 = c->flow[f - 1].fused.b4; fa.Hpre = w.Hpre; }
-          if (s.n_utt <= kWnSegInline && !s.cap) {  // (the inlined offsets are the host's: not with capacity segments)
-            fa.n_inline = s.n_utt;
-            memcpy(fa.seg_inline, s.host, (s.n_utt + 1) * sizeof(int));
-          }
-          const dim3 fgrid(ceil_div(ml, 16 * M), s.n_utt);
-#ifdef STTS_WN_TRACE
-          fa.dbg = wn_trace_buffer((f * 4 + i), (long)fgrid.x * fgrid.y);
-#endif
-          if (i == 3) STTS_LAUNCH_TIMED((wn_fused_kernel<M, true>), fgrid, dim3(64 * kWnWaves), st, e0, e1, fa);
-          else STTS_LAUNCH_TIMED((wn_fused_kernel<M, false>), fgrid, dim3(64 * kWnWaves), st, e0, e1, fa);
-        };
-        if (fused_m == 1) launch(std::integral_constant<int, 1>{});
-        else if (fused_m == 4) launch(std::integral_constant<int, 4>{});
-        else launch(std::integral_constant<int, 2>{});
-      }
-      else if (fused16_rt) {
-        WnFused16Args fa;
-        memset(&fa, 0, sizeof(fa));
-        fa.Hin = hcur; fa.Hout = w.Hout; fa.Out = outf; fa.seg_off = s.dev;
-        fa.W1 = L.fused.H1[i]; fa.b1 = L.fused.b1[i]; fa.W2 = L.fused.H2[i]; fa.b2 = L.fused.b2[i];
-        fa.gate = cond; fa.ld_gate = w.ld_gate; fa.gcol0 = w.gcol0; fa.out_acc = w.out_acc; fa.tail = w.tail;
-        fa.W3 = L.fused.H3; fa.b3m = L.fused.b3m; fa.b3s = L.fused.b3s; fa.Z = w.Z; fa.ldz = w.ldz; fa.zcol0 = w.zcol0;
-        if (w.tail > 1) { fa.W4 = c->flow[f - 1].fused.H4; fa.b4 = c->flow[f - 1].fused.b4; fa.Hpre = w.Hpre; }
-        if (s.n_utt <= kWnSegInline && !s.cap) {
-          fa.n_inline = s.n_utt;
-          memcpy(fa.seg_inline, s.host, (s.n_utt + 1) * sizeof(int));
-        }
-        auto launch16 = [&](auto ptag, auto rtag) {
-          constexpr int P = decltype(ptag)::value, RTv = decltype(rtag)::value;
-          const dim3 fgrid(ceil_div(ml, 16 * RTv), s.n_utt);
-          if (i == 3) STTS_LAUNCH_TIMED((wn_fused16_kernel<P, RTv, true>), fgrid, dim3(64 * kWnWaves), st, e0, e1, fa);
-          else STTS_LAUNCH_TIMED((wn_fused16_kernel<P, RTv, false>), fgrid, dim3(64 * kWnWaves), st, e0, e1, fa);
-        };
-        using I1 = std::integral_constant<int, PREC_BF16>;
-        using I2 = std::integral_constant<int, PREC_F16>;
-        using R4 = std::integral_constant<int, 4>;
-        using R8 = std::integral_constant<int, 8>;
-        if (c->prec == PREC_BF16) { if (fused16_rt == 8) launch16(I1{}, R8{}); else launch16(I1{}, R4{}); }
-        else { if (fused16_rt == 8) launch16(I2{}, R8{}); else launch16(I2{}, R4{}); }
-      }
-      // small batches (fp32): 16-row blocks, twice the workgroups at half the chain length (wn_layer_small.hip.h)
-      else if (rows16) STTS_LAUNCH_TIMED(wn_layer_rows16_kernel, dim3(ceil_div(ml, 16), s.n_utt), dim3(1024), st, e0, e1, w);
-      else if (c->prec == PREC_BF16) STTS_LAUNCH_TIMED(wn_layer_kernel<PREC_BF16>, wgrid, dim3(1024), st, e0, e1, w);
-      else if (c->prec == PREC_F16) STTS_LAUNCH_TIMED(wn_layer_kernel<PREC_F16>, wgrid, dim3(1024), st, e0, e1, w);
-      else STTS_LAUNCH_TIMED(wn_layer_kernel<PREC_F32>, wgrid, dim3(1024), st, e0, e1, w);
-      if (dbg_n == 4 * (7 - f) + i + 1 || dbg_n == -(4 * (7 - f) + i + 1))  // diagnostics (above); layer 3 wrote the next h_0 to hf (w.Hpre)
-        return dbg_hand_back(i < 3 ? (dbg_n > 0 ? hnext : outf) : (dbg_n > 0 && f > 0 ? hf : z));
-      std::swap(hcur, hnext);
-    }
-    STTS_HIP(hipGetLastError());
-  }
-#ifdef STTS_WN_TRACE
-  if (fused_m || fusedx3_rt) wn_trace_report(st);
-#endif
-  if (z_flow_out) STTS_HIP(hipMemcpyAsync(z_flow_out, z, R * fh * sizeof(float), hipMemcpyDeviceToDevice, st));
-  GemmArgs a = gemm_args(s);
-  set_seg(a, 0, z, fh, 0, c->post_flow);
-  a.N = d.dec_hidden; a.bias = c->post_flow.bias; a.Y = mel; a.ldy = ld_mel;
-  if (mel16 && c->post_flow.prec != PREC_F32) {
-    a.Y16 = mel16;
-    a.ldy16 = ld_mel16;
-  }
-  STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, c->post_flow.npad, s.n_utt, ml));
-  if (mel16 && c->post_flow.prec == PREC_F32) launch_cast_rows(st, c->prec, mel, ld_mel, d.dec_hidden, mel16, ld_mel16, R);
-  return 0;
-}
+#include "flow.hip.h"
+
+namespace stts {
+
 
 // ------------------------------------------------------------------------------------------------
 // stage: harmonic source + STFT (models/generator.py:247-315, :32-44, :406-410)

@@ -5,6 +5,10 @@
 // It also says what the packers wrote: after every finalize a line `digest <precision> <what> <hex>` with the stub's digest of the device
 // allocations made since the context was created.  Per precision a second context finalizes the same components in another order, with one
 // finalize in the middle that must fail, and has to end at the first context's digest: packing must not depend on what was packed before.
+// And it says which kernels the reverse flow launches: a line `flowtrace <precision> <case> <switches> : <trace>` per batch shape and setting of the
+// STTS_WN_* switches (flow_section below; the trace is the stub's run-length-encoded list of kernel, grid and block in issue order), in all four
+// precisions.  tests/test_asan_host.py compares the default choices with the forced ones; two builds plan the same launches exactly when these lines agree.
+#include <algorithm>
 #include <cinttypes>
 #include <cstdint>
 #include <cstdio>
@@ -17,6 +21,8 @@
 
 extern "C" long stts_stub_launch_count();
 extern "C" uint64_t stts_stub_digest();
+extern "C" void stts_stub_trace_begin();
+extern "C" const char* stts_stub_trace_end();
 
 #define CK(expr)                                                                  \
   do {                                                                            \
@@ -64,6 +70,89 @@ static int frame_case(stts_ctx* c, const std::vector<int>& lens, const char* wha
   CK(stts_vocoder_forward(c, nullptr, n, off.data(), off.data(), mel.data(), 512, style.data(), hs.data(), hp.data(), 1088, audio.data(), nullptr, nullptr, 0,
                           ws.data(), wsb));
   printf("  %-44s rows %8ld  workspace %8.1f MB  %ld launches per frame-path call\n", what, R, wsb / 1048576.0, fused);
+  return 0;
+}
+
+// One stts_prior_flow_forward call under `switches` ("NAME=value,NAME=value" or "-"; every other STTS_WN_* switch unset), traced.  want_z: pass a
+// z_flow_out (STTS_WN_DEBUG needs one).
+static int flow_case(stts_ctx* c, int prec, const std::vector<int>& lens, const char* what, const std::string& switches, bool want_z = false) {
+  for (const char* k : {"STTS_WN_M", "STTS_WN_RT", "STTS_WN_X3", "STTS_WN_X3B", "STTS_WN_X3_WAVES", "STTS_WN_DEBUG"}) unsetenv(k);
+  for (size_t i = 0; switches != "-" && i < switches.size();) {
+    const size_t eq = switches.find('=', i), end = std::min(switches.find(',', i), switches.size());
+    setenv(switches.substr(i, eq - i).c_str(), switches.substr(eq + 1, end - eq - 1).c_str(), 1);
+    i = end + 1;
+  }
+  const int n = (int)lens.size();
+  std::vector<int32_t> off(n + 1, 0);
+  int ml = 0;
+  for (int i = 0; i < n; ++i) {
+    off[i + 1] = off[i] + lens[i];
+    ml = lens[i] > ml ? lens[i] : ml;
+  }
+  const long R = off[n];
+  const size_t wsb = stts_frame_workspace_bytes(c, R, n, ml);
+  char* ws = (char*)malloc(wsb);  // untouched but for what the stub's copies move (the STTS_WN_DEBUG hand-back, z_flow_out)
+  if (!ws) {
+    fprintf(stderr, "cannot reserve %zu bytes of address space\n", wsb);
+    return 1;
+  }
+  auto x = buf(R * 512), style = buf((size_t)n * 64), pn = buf(R * 128), mel = buf(R * 512), zf = buf(want_z ? R * 128 : 0);
+  stts_stub_trace_begin();
+  const int rc = stts_prior_flow_forward(c, nullptr, n, off.data(), off.data(), x.data(), 512, style.data(), pn.data(), mel.data(), 512, nullptr,
+                                         want_z ? zf.data() : nullptr, ws, wsb);
+  const char* trace = stts_stub_trace_end();
+  free(ws);
+  CK(rc);
+  printf("flowtrace %d %s %s : %s\n", prec, what, switches.c_str(), trace);
+  return 0;
+}
+
+// The flow cases of one precision: the batch shapes around the thresholds of the kernel choice with no switch set, the forced choices they must
+// equal (tests/test_asan_host.py PINS), and the ragged batch of tests/test_hip_flow_layers.py under every switch that test file and the precision tests use.
+static int flow_section(stts_ctx* c, int prec) {
+  const std::vector<int> ragged = {1, 2, 15, 16, 17, 31, 33, 47, 49, 63, 65, 97, 130};
+  auto x960 = [](int b) { return std::vector<int>(b, 960); };
+#define FLOW(...)                                  \
+  do {                                             \
+    if (flow_case(c, prec, __VA_ARGS__)) return 1; \
+  } while (0)
+  if (prec == 0 || prec == 3) {
+    FLOW(x960(1), "1x960", "-");
+    FLOW(x960(8), "8x960", "-");
+    FLOW(x960(16), "16x960", "-");
+    const char* forced[3] = {prec == 0 ? "STTS_WN_M=1,STTS_WN_X3=1" : "STTS_WN_M=1", prec == 0 ? "STTS_WN_M=2,STTS_WN_X3=2" : "STTS_WN_M=2",
+                             prec == 0 ? "STTS_WN_M=4,STTS_WN_X3=4" : "STTS_WN_M=4"};
+    FLOW(x960(1), "1x960", forced[0]);
+    FLOW(x960(8), "8x960", forced[1]);
+    FLOW(x960(16), "16x960", forced[2]);
+  }
+  if (prec == 3)
+    for (const char* sw : {"STTS_WN_M=1", "STTS_WN_M=2", "STTS_WN_M=4", "STTS_WN_M=16"}) FLOW(ragged, "ragged", sw);
+  if (prec == 0) {
+    std::vector<int> many;
+    for (int i = 0; i < 7; ++i)
+      for (int l : {1, 2, 15, 16, 17, 31, 33, 63, 65, 130}) many.push_back(l);
+    FLOW(std::vector<int>(64, 3200), "64x3200", "-");
+    FLOW(ragged, "ragged", "-");
+    FLOW(many, "many", "-");
+    for (const char* rt : {"1", "2", "4"})  // VARIANTS of tests/test_hip_flow_layers.py
+      for (const char* nw : {"8", "4"}) FLOW(ragged, "ragged", std::string("STTS_WN_M=2,STTS_WN_X3=") + rt + ",STTS_WN_X3_WAVES=" + nw);
+    for (const char* sw : {"STTS_WN_M=2,STTS_WN_X3=2,STTS_WN_X3B=3", "STTS_WN_M=2,STTS_WN_X3=2,STTS_WN_X3B=4", "STTS_WN_M=1,STTS_WN_X3=-1", "STTS_WN_M=2,STTS_WN_X3=-1",
+                           "STTS_WN_M=4,STTS_WN_X3=-1", "STTS_WN_M=16,STTS_WN_X3=-1"})
+      FLOW(ragged, "ragged", sw);
+    for (const char* k : {"0", "3", "-3", "4", "-4", "32", "-32"}) FLOW(ragged, "ragged", std::string("STTS_WN_DEBUG=") + k, true);
+  }
+  if (prec == 1 || prec == 2) {
+    FLOW(x960(8), "8x960", "-");
+    FLOW(x960(23), "23x960", "-");
+    FLOW(x960(24), "24x960", "-");
+    FLOW(std::vector<int>(64, 3200), "64x3200", "-");
+    FLOW(x960(23), "23x960", "STTS_WN_RT=4");
+    FLOW(x960(24), "24x960", "STTS_WN_RT=16");
+    for (const char* sw : {"STTS_WN_RT=-1", "STTS_WN_RT=4", "STTS_WN_RT=8", "STTS_WN_RT=16"}) FLOW(ragged, "ragged", sw);
+  }
+#undef FLOW
+  for (const char* k : {"STTS_WN_M", "STTS_WN_RT", "STTS_WN_X3", "STTS_WN_X3B", "STTS_WN_X3_WAVES", "STTS_WN_DEBUG"}) unsetenv(k);
   return 0;
 }
 
@@ -151,7 +240,14 @@ int main(int argc, char** argv) {
   }
   fclose(f);
   for (int prec = 0; prec <= 3; ++prec) {  // fp32, fp16 operands (16-bit weight copies are packed too), fp32 on the f32 matrix cores
-    if (prec == 1) continue;
+    if (prec == 1) {  // bf16: the reverse flow alone (its kernel choice has branches of its own; the packing is fp16's with another rounding)
+      stts_ctx* cf = nullptr;
+      if (new_ctx(d, prec, w, &cf)) return 1;
+      CK(stts_finalize_weights(cf, STTS_W_FLOW));
+      if (flow_section(cf, prec)) return 1;
+      stts_ctx_destroy(cf);
+      continue;
+    }
     uint64_t base = stts_stub_digest();  // (what outlives a context: the library's lazily created process-wide buffers)
     uint64_t first = 0;
     stts_ctx* c = nullptr;
@@ -173,6 +269,7 @@ int main(int argc, char** argv) {
     CK(stts_cfm_finalize(c, &cd));
     digest("cfm");
     printf("precision %d: %zu tensors loaded and packed\n", prec, w.size());
+    if (flow_section(c, prec)) return 1;
     if (prec != 3) {  // the stage walks: once per operand width
       if (frame_case(c, std::vector<int>(8, 960), "cfg2: 8 x 3 s")) return 1;
       if (frame_case(c, {960}, "B = 1 x 3 s")) return 1;

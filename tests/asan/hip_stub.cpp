@@ -4,13 +4,18 @@
 // are counted and otherwise ignored: what runs under the sanitizers is the library's own host code - weight folding and
 // packing, Winograd / fragment packing, workspace carving, launch planning - over the shapes of BASELINE's configs.
 // Device allocations are zero-filled and recorded, so that stts_stub_digest() can say what the packers wrote.
+// Between stts_stub_trace_begin() and stts_stub_trace_end() every launch is also written down by name (the device name
+// __hipRegisterFunction was given for the host handle, demangled), grid and block: which kernels the launch planning chose, as text.
 #include <hip/hip_runtime.h>
+
+#include <cxxabi.h>
 
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <string>
 
 static long g_launches = 0;
 extern "C" long stts_stub_launch_count() { return g_launches; }
@@ -31,6 +36,51 @@ extern "C" uint64_t stts_stub_digest() {
     sum += h;
   }
   return sum;
+}
+
+// host handle of a kernel -> its name: demangled, without the "void stts::" in front and the parameter list behind
+static std::map<const void*, std::string>& kernel_names() {
+  static std::map<const void*, std::string> m;
+  return m;
+}
+static std::string short_name(const char* mangled) {
+  int status = 0;
+  char* dm = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
+  std::string n = status == 0 && dm ? dm : mangled;
+  free(dm);
+  if (!n.empty() && n.back() == ')') {  // the parameter list: from the parenthesis that matches the last one
+    int depth = 0;
+    for (size_t i = n.size(); i-- > 0;) {
+      depth += n[i] == ')' ? 1 : n[i] == '(' ? -1 : 0;
+      if (depth == 0) {
+        n.erase(i);
+        break;
+      }
+    }
+  }
+  for (const char* lead : {"void ", "stts::"})
+    if (n.compare(0, strlen(lead), lead) == 0) n.erase(0, strlen(lead));
+  return n;
+}
+// The trace: launches in issue order, runs of the same (kernel, grid, block) written once as `<count>x <kernel> (grid)(block)`, joined by " | "
+static struct {
+  bool on = false;
+  std::string text, last;
+  long run = 0;
+  void flush() {
+    if (run) text += (text.empty() ? "" : " | ") + std::to_string(run) + "x " + last;
+    run = 0;
+  }
+} g_trace;
+extern "C" void stts_stub_trace_begin() {
+  g_trace.on = true;
+  g_trace.text.clear();
+  g_trace.run = 0;
+}
+extern "C" const char* stts_stub_trace_end() {
+  g_trace.flush();
+  g_trace.on = false;
+  return g_trace.text.c_str();
 }
 
 extern "C" {
@@ -114,13 +164,22 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) {
   *ms = 0.001f;
   return hipSuccess;
 }
-hipError_t hipLaunchKernel(const void*, dim3 grid, dim3 block, void**, size_t, hipStream_t) {
+hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void**, size_t, hipStream_t) {
   // what a real launch would reject
   if (grid.x == 0 || grid.y == 0 || grid.z == 0 || block.x * block.y * block.z == 0 || block.x * block.y * block.z > 1024 || grid.y > 65535 || grid.z > 65535) {
     fprintf(stderr, "hip_stub: invalid launch configuration grid (%u,%u,%u) block (%u,%u,%u)\n", grid.x, grid.y, grid.z, block.x, block.y, block.z);
     abort();
   }
   ++g_launches;
+  if (g_trace.on) {
+    const auto it = kernel_names().find(f);
+    char dims[96];
+    snprintf(dims, sizeof(dims), " (%u,%u,%u)(%u,%u,%u)", grid.x, grid.y, grid.z, block.x, block.y, block.z);
+    const std::string entry = (it == kernel_names().end() ? std::string("?") : it->second) + dims;
+    if (entry != g_trace.last) g_trace.flush();
+    g_trace.last = entry;
+    ++g_trace.run;
+  }
   return hipSuccess;
 }
 hipError_t hipExtLaunchKernel(const void* f, dim3 grid, dim3 block, void** a, size_t s, hipStream_t st, hipEvent_t, hipEvent_t, int) {
@@ -131,7 +190,9 @@ void** __hipRegisterFatBinary(const void*) {
   return &h;
 }
 void __hipUnregisterFatBinary(void**) {}
-void __hipRegisterFunction(void**, const void*, char*, const char*, unsigned, void*, void*, void*, void*, int*) {}
+void __hipRegisterFunction(void**, const void* host_fn, char*, const char* device_name, unsigned, void*, void*, void*, void*, int*) {
+  kernel_names()[host_fn] = short_name(device_name);
+}
 void __hipRegisterVar(void**, void*, char*, const char*, int, size_t, int, int) {}
 static thread_local struct {
   dim3 g, b;

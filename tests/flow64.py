@@ -2,7 +2,7 @@
 WN :63-88), usable one WaveNet layer at a time.  Test infrastructure: fp32 inputs in, every operation in float64.
 
 Layout is the engine's: time-major rows [rows, C] packed utterance after utterance (`lengths` rows each), z [rows, 2 half].  The order of
-csrc/model.hip.h prior_flow_forward: coupling layers f = 7 .. 0, each preceded by a Flip, so layer f reads half p = f & 1 of z (through `pre`)
+csrc/flow.hip.h prior_flow_forward: coupling layers f = 7 .. 0, each preceded by a Flip, so layer f reads half p = f & 1 of z (through `pre`)
 and updates the other half in place; after layer 0 the halves are in their natural order.  oracle/stylish_oracle.py flow_reverse is the
 same computation in fp32 on [B, C, T] arrays.
 """

@@ -1,6 +1,6 @@
 """The reverse flow's WaveNet kernels against float64, one layer at a time (tests/flow64.py), per kernel variant.
 
-Teacher forcing: STTS_WN_DEBUG = +-k (csrc/model.hip.h prior_flow_forward) stops the flow after WaveNet layer k = 4 (7 - f) + i + 1 and hands
+Teacher forcing: STTS_WN_DEBUG = +-k (csrc/flow.hip.h WnDebugStop) stops the flow after WaveNet layer k = 4 (7 - f) + i + 1 and hands
 back h (+k) or `out` (-k); after a coupling layer's last WaveNet layer (i = 3) +k is the next coupling layer's h_0 = pre(z) and -k the whole z.
 Every layer k is recomputed in float64 from the GPU's OWN h and `out` after layer k - 1, so each comparison sees one layer's error only:
   - layers i = 0 .. 2: h' and out';
@@ -32,6 +32,8 @@ torch = pytest.importorskip("torch")
 # ragged lengths that straddle the 16-, 32- and 64-row blocks and the conv's +-2-row reach; the second batch has more than kWnSegInline = 64
 # utterances (wn_fused.hip.h), so the per-launch kernels read seg_off instead of their inlined offsets
 # (47 / 49 / 97: around wn_block_x3_kernel<4>'s 48-row output blocks)
+# (BATCHES and VARIANTS are written out a second time where Python cannot be imported - tests/asan/asan_driver.cpp flow_section, whose launch traces
+#  tests/test_asan_host.py FLOW_CASES / _VARIANTS lists: a new batch or variant goes there too)
 BATCHES = {"ragged": [1, 2, 15, 16, 17, 31, 33, 47, 49, 63, 65, 97, 130], "many": [1, 2, 15, 16, 17, 31, 33, 63, 65, 130] * 7}
 
 _ENV = ("STTS_WN_M", "STTS_WN_X3", "STTS_WN_X3B", "STTS_WN_X3_WAVES", "STTS_WN_DEBUG")

@@ -1,5 +1,8 @@
 """Time the prior + reverse-flow stage (stts_prior_flow_forward: 32 fused WaveNet-layer launches + 3 small contractions)
-for a list of batch sizes; STTS_WN_M=2|4 forces the F(2,5) / F(4,5) block shape, STTS_NO_WN_FUSED=1 the staged kernel.
+for a list of batch sizes.  Which WaveNet kernel runs: csrc/flow.hip.h plan_flow (DESIGN.md section 4 states the precedence); to force one,
+STTS_WN_M=1|2|4 (wn_fused_kernel's block shape: direct / F(2,5) / F(4,5); 16: the staged 16-row kernel), STTS_WN_X3=1|2|4|-1 (the split-fp32
+kernel's block shape; -1: the f32 kernel), STTS_WN_X3B=3|4 (one launch per coupling layer), STTS_WN_X3_WAVES=4, in the 16-bit modes
+STTS_WN_RT=4|8|16|-1; STTS_NO_WN_FUSED=1 (at finalize) leaves the staged kernels only.
 usage: python tools/flow_bench.py [batch ...]"""
 import os
 import sys
