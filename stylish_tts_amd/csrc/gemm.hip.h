@@ -1262,9 +1262,6 @@ inline double gemm_algorithmic_flops(const GemmArgs& a) {
   } while (0)
 
 // conv_gemm16_kernel (gemm16.hip.h): the 16-bit-row store contractions of large batches
-inline bool gemm16_eligible(const GemmArgs& a, int epi, int npad);
-inline long gemm16_tiles(const GemmArgs& a, int npad, int n_utt);
-inline bool gemm16_will_run(const GemmArgs& a, int epi, int npad, int n_utt);  // would launch_conv_gemm pick conv_gemm16_kernel for this call?
 template <int ABL>
 inline int launch_conv_gemm16(hipStream_t st, const GemmArgs& a, int npad, int n_utt);
 
@@ -1275,6 +1272,12 @@ void gemm_dispatch_bf16(hipStream_t st, const GemmArgs& as, int tile, int epi, i
 void gemm_dispatch_f16(hipStream_t st, const GemmArgs& as, int tile, int epi, int npad, int n_utt, int max_rows, hipEvent_t e0, hipEvent_t e1);
 void gemm_dispatch_x3(hipStream_t st, const GemmArgs& as, int tile, int epi, int npad, int n_utt, int max_rows, hipEvent_t e0, hipEvent_t e1);
 int launch_conv_gemm16_main(hipStream_t st, const GemmArgs& a, int npad, int n_utt);  // = launch_conv_gemm16<0> (gemm_tu_g16.hip)
+
+}  // namespace stts
+
+#include "gemm_plan.hip.h"  // the tile table, the switches, plan_conv_gemm, gemm16_will_run
+
+namespace stts {
 
 #ifndef STTS_GEMM_NO_LAUNCHER  // (probes that only need the types and conv_gemm16_kernel skip the ~50 instantiations below)
 template <int BM, int BN, int WM, int WN, int KS = 1, bool GL = false, int PR = PREC_F32>
@@ -1341,66 +1344,42 @@ inline void launch_cfg_x3(hipStream_t st, const GemmArgs& a, int epi, int npad, 
     STTS_LAUNCH_TIMED((conv_gemm_f32<BM, BN, WM, WN, EPI_STORE, KS, false, PREC_X3>), grid, block, st, e0, e1, a);
   }
 }
-// tile -> instantiation, per operand form.  Defined (= every kernel instantiated) only in the translation unit of that form.
+// tile -> instantiation, per operand form, template arguments from the tile table (gemm_plan.hip.h).  Defined (= every kernel instantiated) only in the
+// translation unit of that form.  The order of the cases is the order of the kernels in the code object: keep it.
+template <int T, int PR>
+inline void launch_tile(hipStream_t st, const GemmArgs& as, int epi, int npad, int n_utt, int max_rows, hipEvent_t e0, hipEvent_t e1) {
+  constexpr TileRow r = tile_row(T);
+  if constexpr ((r.forms & (PR == PREC_F32 ? FORM_F32 : FORM_16)) != 0) launch_cfg<r.BM, r.BN, r.WM, r.WN, r.KS, r.glds, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1);
+}
+template <int T>
+inline void launch_tile_x3(hipStream_t st, const GemmArgs& as, int epi, int npad, int n_utt, int max_rows, hipEvent_t e0, hipEvent_t e1) {
+  constexpr TileRow r = tile_row(T);
+  static_assert((r.forms & FORM_X3) != 0, "not a split-fp32 tile");
+  launch_cfg_x3<r.BM, r.BN, r.WM, r.WN, r.KS, r.x16 != X16_MUST ? 0 : r.glds ? 2 : 1>(st, as, epi, npad, n_utt, max_rows, e0, e1);
+}
+#define STTS_TILE_CASE(T) case T: launch_tile<T, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;
 template <int PR>
 inline void gemm_dispatch_tile(hipStream_t st, const GemmArgs& as, int tile, int epi, int npad, int n_utt, int max_rows, hipEvent_t e0, hipEvent_t e1) {
   switch (tile) {
-    case 2: launch_cfg<128, 64, 2, 2, 1, false, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;
-    case 4: launch_cfg<128, 32, 4, 1, 1, false, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;   // 32-row tile, 4 waves of one 32x32 tile each
-    case 5: launch_cfg<128, 128, 4, 2, 1, false, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;  // 8 waves per block
-    case 6: launch_cfg<128, 64, 4, 2, 1, false, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;   // 8 waves, 64-row tiles
-    case 8: launch_cfg<128, 128, 4, 2, 2, false, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;  // 16 waves: 8 positions x 2 K-groups
-    case 14:  // 256 cout x 256 rows, 8 waves of 64 x 128 (8 accumulator tiles): 16-bit operands at large batches, where the
-              // 128x128 loop is bound by L2 -> LDS staging (47 B/clk/CU needed); this tile needs 31
-      if constexpr (PR != PREC_F32) launch_cfg<256, 256, 4, 2, 1, false, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1);
-      break;
-    case 15:
-      if constexpr (PR != PREC_F32) launch_cfg<128, 256, 4, 2, 1, false, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1);
-      break;
-    case 16:  // tiles 14 / 15 with LDS-DMA staging (global_load_lds_dwordx4, three stages): 16-bit activation rows only
-      if constexpr (PR != PREC_F32) launch_cfg<256, 256, 4, 2, 1, true, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1);
-      break;
-    case 17:
-      if constexpr (PR != PREC_F32) launch_cfg<128, 256, 4, 2, 1, true, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1);
-      break;
-    case 18:  // 128 x 128, 8 waves, LDS-DMA with eight stages: one-round launches of small batches in the 16-bit modes
-      if constexpr (PR != PREC_F32) launch_cfg<128, 128, 4, 2, 1, true, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1);
-      break;
-    case 11:
-      if constexpr (PR == PREC_F32) launch_cfg<128, 128, 4, 2, 1, true>(st, as, epi, npad, n_utt, max_rows, e0, e1);  // LDS-DMA staging, 8 waves
-      break;
-    case 13:
-      if constexpr (PR == PREC_F32) launch_cfg<128, 64, 4, 2, 1, true>(st, as, epi, npad, n_utt, max_rows, e0, e1);  // LDS-DMA staging, 64-row tile
-      break;
-    default: launch_cfg<128, 32, 2, 1, 1, false, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;
+    STTS_TILE_CASE(2) STTS_TILE_CASE(4) STTS_TILE_CASE(5) STTS_TILE_CASE(6) STTS_TILE_CASE(8)
+    STTS_TILE_CASE(14) STTS_TILE_CASE(15) STTS_TILE_CASE(16) STTS_TILE_CASE(17) STTS_TILE_CASE(18)
+    STTS_TILE_CASE(11) STTS_TILE_CASE(13)
+    default: launch_tile<3, PR>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;  // (the plan admits no id without a row)
   }
 }
+#undef STTS_TILE_CASE
+#define STTS_TILE_CASE(T) case T: launch_tile_x3<T>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;
 inline void gemm_dispatch_tile_x3(hipStream_t st, const GemmArgs& as, int tile, int epi, int npad, int n_utt, int max_rows, hipEvent_t e0, hipEvent_t e1) {
   switch (tile) {
-    case 2: launch_cfg_x3<128, 64, 2, 2>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;
-    case 4: launch_cfg_x3<128, 32, 4, 1>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;
-    case 5: launch_cfg_x3<128, 128, 4, 2>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;
-    case 6: launch_cfg_x3<128, 64, 4, 2>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;
-    case 8: launch_cfg_x3<128, 128, 4, 2, 2>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;
-    case 20: launch_cfg_x3<128, 128, 2, 2>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;     // 4 waves of 64 x 64
-    case 21: launch_cfg_x3<128, 128, 2, 2, 2>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;  // 8 waves: 64 x 64 x two K-groups
-    case 22: launch_cfg_x3<128, 256, 2, 4>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;     // 8 waves of 64 x 64, 256 rows
-    // pre-split activation planes (three bf16 planes written by the producer: no split, no conversion in the loop)
-    case 25: launch_cfg_x3<128, 128, 4, 2, 1, 1>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;  // tile 5, register staging
-    case 26: launch_cfg_x3<128, 64, 4, 2, 1, 1>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;   // tile 6
-    case 27: launch_cfg_x3<128, 128, 4, 2, 1, 2>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;  // tile 5, LDS-DMA (three stages)
-    case 28: launch_cfg_x3<128, 64, 4, 2, 1, 2>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;   // tile 6, LDS-DMA
-    default: launch_cfg_x3<128, 32, 2, 1>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;
+    STTS_TILE_CASE(2) STTS_TILE_CASE(4) STTS_TILE_CASE(5) STTS_TILE_CASE(6) STTS_TILE_CASE(8)
+    STTS_TILE_CASE(20) STTS_TILE_CASE(21) STTS_TILE_CASE(22)
+    STTS_TILE_CASE(25) STTS_TILE_CASE(26) STTS_TILE_CASE(27) STTS_TILE_CASE(28)
+    default: launch_tile_x3<3>(st, as, epi, npad, n_utt, max_rows, e0, e1); break;
   }
 }
-// Process-wide switch of the split-fp32 contractions (STTS_NO_X3=1: every fp32 contraction on v_mfma_f32_32x32x2_f32, the path of rounds 1-3)
-inline bool x3_enabled() {
-  static const bool on = !(getenv("STTS_NO_X3") && atoi(getenv("STTS_NO_X3")) != 0);
-  return on;
-}
+#undef STTS_TILE_CASE
 
-// npad: padded cout of the packed weight (multiple of 128).  max_rows: longest utterance (rows).
-// Tile choice: 128x128 when that already fills the chip, else smaller row tiles for more workgroups.
+// Operand checks, the plan (gemm_plan.hip.h: plan_conv_gemm has the rules), scratch, launches.
 inline int launch_conv_gemm(hipStream_t st, const GemmArgs& a, int epi, int npad, int n_utt, int max_rows, int force_tile = 0) {
   STTS_CHECK(npad % 128 == 0, "conv_gemm: padded cout %d not a multiple of 128", npad);
   for (int i = 0; i < a.nseg; ++i) {
@@ -1412,181 +1391,24 @@ inline int launch_conv_gemm(hipStream_t st, const GemmArgs& a, int epi, int npad
   if (a.x16 && a.prec != PREC_F32)
     for (int i = 0; i < a.nseg; ++i)
       STTS_CHECK(a.seg[i].ldx % 8 == 0 && a.seg[i].xcol0 % 8 == 0, "conv_gemm: 16-bit activation rows need ldx / xcol0 multiples of 8 (segment %d)", i);
-  // 16-bit activation rows, store epilogue, at least ~one 256 x 256 tile per CU: the persistent LDS-DMA kernel (gemm16.hip.h).
-  // force_tile 19 selects it whatever the size (tests), any other forced tile keeps the launch on conv_gemm_f32.
-  if (force_tile == 19 || (force_tile == 0 && gemm16_will_run(a, epi, npad, n_utt))) {
-    if (gemm16_eligible(a, epi, npad)) return launch_conv_gemm16_main(st, a, npad, n_utt);
-  }
-  STTS_CHECK(!a.stat_part, "conv_gemm: output statistics (stat_part) exist only in conv_gemm16_kernel's epilogue: ask gemm16_will_run first");
-  STTS_CHECK(force_tile != 19, "conv_gemm: tile 19 (conv_gemm16_kernel) needs 16-bit activation rows, a store epilogue, channels in multiples of 64 and cout padded to 256");
-  constexpr int kCUs = 256;
-  const int mt = npad / 128;
-  auto row_tiles = [&](int bn) -> long {  // exact when the host offsets are known (mixed lengths)
-    if (!a.seg_host) return (long)n_utt * ceil_div(max_rows, bn);
-    long t = 0;
-    for (int u = 0; u < n_utt; ++u) t += ceil_div(a.seg_host[u + 1] - a.seg_host[u], bn);
-    return t;
-  };
-  int iters = 0;
-  for (int i = 0; i < a.nseg; ++i) iters += a.seg[i].ntaps * (a.seg[i].kc / 32);
-  // (the split-K reduce pass writes fp32 Y only: launches that want the 16-bit copy, or no fp32 output at all, stay whole)
-  const bool splittable = force_tile == 0 && epi == EPI_STORE && !a.sumsq_part && a.Y && !a.Y16;
-  // A launch takes about ceil(blocks / 256 CUs) block-times however many blocks are co-resident: a CU's matrix pipes are
-  // the shared resource (block-timeline trace, profiles/).  When the last round would be mostly empty (288 tiles = 1.125
-  // rounds for a 3.5 s batch of 8), the whole rounds run as they are and the REMAINDER row tiles run as a second launch
-  // with K cut over up to 8 blocks (+ reduce pass over those rows only): 1 + ~1/8 rounds instead of 2.
-  bool x3 = false;  // split fp32 (decided below, before any plan is made)
-  struct Plan {
-    long full_rt = 0, rem_rt = 0;  // row tiles in the plain launch / in the split-K remainder launch
-    int rem_ksp = 1;
-    double cost = 0;               // in 128-row block-times
-  };
-  auto plan_for = [&](int bn, double penalty) {
-    Plan p;
-    const long rt = row_tiles(bn), blocks = rt * mt;
-    const long whole = blocks / kCUs;
-    p.full_rt = rt;
-    p.cost = std::ceil((double)blocks / kCUs);
-    // (split fp32: whole launches.  Its blocks are 1.5 x shorter, and a remainder launch + its reduce pass then cost more than the partly empty last round:
-    //  cfg2 3.58 -> 3.475 ms per step without the 12 remainder launches and 11 reduce passes of the Winograd plane contractions; STTS_X3_REM=1 brings them back)
-    static const bool x3_rem = getenv("STTS_X3_REM") && atoi(getenv("STTS_X3_REM")) != 0;
-    if ((!x3 || x3_rem) && splittable && a.seg_host && !a.capacity && whole >= 1 && blocks % kCUs != 0) {  // (the remainder launch needs exact host offsets)
-      const long full_rt = whole * kCUs / mt, rem_blocks = (rt - full_rt) * mt;
-      const int ksp = (int)std::min<long>(8, std::min<long>(iters / 4, kCUs / std::max<long>(rem_blocks, 1)));
-      if (ksp >= 2 && full_rt > 0) {
-        const double hybrid = (double)(full_rt * mt) / kCUs + std::max((double)rem_blocks / kCUs, 1.0 / ksp) * 1.15 + 0.1;
-        if (hybrid < p.cost) {
-          p.full_rt = full_rt;
-          p.rem_rt = rt - full_rt;
-          p.rem_ksp = ksp;
-          p.cost = hybrid;
-        }
-      }
-    }
-    p.cost *= bn * penalty;
-    return p;
-  };
-  const long blocks128 = mt * row_tiles(128);
-  // split fp32: fp32 call, every segment carries the three bf16 planes of its weight, epilogue with a split instantiation
-  x3 = a.prec == PREC_F32 && x3_enabled() && (epi == EPI_STORE || epi == EPI_PRIOR);
-  for (int i = 0; i < a.nseg; ++i) x3 = x3 && a.seg[i].W16 != nullptr && a.seg[i].w16_plane > 0 && 6 * a.seg[i].w16_plane + 2L * 128 * a.seg[i].ntaps * a.seg[i].kc < (1L << 32);
-  // pre-split activation planes (x16 on an fp32 call): store epilogue, no input affine, no block split-K (the callers know: run_winograd)
-  if (a.x16 && a.prec == PREC_F32) {
-    STTS_CHECK(x3 && epi == EPI_STORE && !a.xaff && !a.sumsq_part, "conv_gemm: pre-split activation planes need the split-fp32 store contraction");
-    for (int i = 0; i < a.nseg; ++i) STTS_CHECK(a.seg[i].x_plane > 0 && a.seg[i].ldx % 8 == 0 && a.seg[i].xcol0 % 8 == 0, "conv_gemm: pre-split activation planes: segment %d misaligned", i);
-  }
-  if (force_tile >= 100) {  // tests / tools: 100 + t = tile t on the f32 matrix cores whatever the switch says
-    x3 = false;
-    force_tile -= 100;
-  }
-  if (force_tile != 0 && !((force_tile >= 2 && force_tile <= 6) || force_tile == 8 || (force_tile >= 20 && force_tile <= 22) || (a.x16 && force_tile >= 25 && force_tile <= 28))) x3 = false;  // a forced tile without a split form (LDS-DMA tiles)
-  int tile = force_tile;
-  const bool paired = epi != EPI_STORE && epi != EPI_SPLIT_ACC;  // paired epilogues need 64-column wave tiles
-  Plan plan;
-  if (tile == 0) {
-    // small launches: 32-row tiles; unpaired epilogues spread the 128 output channels over four waves (a wave's MFMA
-    // chain per iteration is then 16 instead of 32 instructions: these launches are latency-bound on that chain)
-    if (blocks128 < 24) tile = paired ? 3 : 4;
-    else if (paired) tile = 2;
-    else {
-      // 128x128 vs 128x64 tiles by that cost (576 blocks of 128x64 cost three half-sized rounds)
-      const Plan p5 = plan_for(128, 1.0), p6 = plan_for(64, 1.03);
-      tile = p5.cost <= p6.cost ? 5 : 6;
-      // split fp32, short K (at most 24 iterations: the 1 x 1 convs over 512-768 channels): the prologue and epilogue of a block are a fifth of its life, and
-      // two co-resident 128 x 64 blocks hide them behind each other's K loop (B = 8, per launch inside the step: pwconv1 94.2 -> 87.3 us, the small
-      // 1 x 1 convs 19.0 -> 16.9 / 18.7 -> 15.7; deep K keeps the 128 x 128 tile: pwconv2 85.7 vs 87.4)
-      if (x3 && iters <= 24 && !a.xaff) tile = 6;
-      plan = tile == 5 ? p5 : p6;
-      // one 128x128 tile per CU (B = 8: every 512-channel layer): two K-groups of 8 waves share each staged tile, which
-      // keeps the matrix pipes busier than 8 waves do (118 vs 125.5 us) and beats cutting K over two blocks plus the
-      // reduce pass (131 us)
-      // (fp32 only: with 16-bit operands the loop is staging-bound and 8 waves are faster, 34 vs 40 us)
-      // (split fp32: the 8-wave tile is the faster one there too, and the 16-wave tile's 128-register budget spills with the input affine)
-      if (tile == 5 && blocks128 <= kCUs && a.prec == PREC_F32 && !x3) tile = 8;
-    }
-  }
-  if (force_tile == 0 && a.prec != PREC_F32 && a.x16 && epi == EPI_STORE) {
-    // 16-bit activation rows: 256-row tiles once they fill the chip at least ~1.5 times.  128 x 256 (two blocks per CU, so
-    // one block's prologue / epilogue hides behind the other's K loop) unless K is deep (the k = 7 convs: >= 128 iterations),
-    // where the 256 x 256 tile's lower staging rate wins (B = 64: out conv 875 vs 896 us, prior conv 287 vs 302; but
-    // pwconv1 403 vs 213, decoder convs 200 vs 137: tools/gemm_bench.py TUNE=1152)
-    const long rt256 = row_tiles(256);
-    if (npad % 256 == 0 && iters >= 128 && rt256 * (npad / 256) >= 3 * kCUs / 2) tile = 14;
-    else if (rt256 * (npad / 128) >= 3 * kCUs / 2) tile = 15;
-    if (tile == 14 || tile == 15) plan = Plan();
-    if (const char* e = getenv("STTS_TILE16")) {  // experiment switch: tile for every 16-bit-row store launch
-      tile = atoi(e);
-      plan = Plan();
-    }
-  }
-  STTS_CHECK(!(a.x16 && (tile == 8 || tile == 11 || tile == 13 || a.xaff)), "conv_gemm: 16-bit activation rows need a plain register-staged tile");
-  STTS_CHECK(!(a.xaff && (tile == 11 || tile == 13)), "conv_gemm: the input affine lives on the register staging path (not tiles 11 / 13)");
-  STTS_CHECK(!((tile == 14 || tile == 15) && (a.prec == PREC_F32 || epi != EPI_STORE)), "conv_gemm: tiles 14 / 15 are for 16-bit operand store launches");
-  STTS_CHECK(!((tile >= 16 && tile <= 18) && (a.prec == PREC_F32 || epi != EPI_STORE || !a.x16)), "conv_gemm: tiles 16 - 18 are for 16-bit activation rows, store epilogue");
-  STTS_CHECK((tile != 14 && tile != 16) || npad % 256 == 0, "conv_gemm: tiles 14 / 16 need cout padded to 256");
-  if (x3 && !a.x16 && force_tile == 0 && (tile == 5 || tile == 6)) {
-    static const int x3_tile = getenv("STTS_X3_TILE") ? atoi(getenv("STTS_X3_TILE")) : 0;  // experiments: 5 / 6 / 22 for every large split-fp32 launch
-    if (x3_tile == 5 || x3_tile == 6 || x3_tile == 22) {
-      tile = x3_tile;
-      plan = Plan();
-    }
-  }
-  // (... or a launch of at least 440 such blocks that fills its last chip round to 80 %: the output convs' Winograd planes at B = 8 are 480 blocks = 1.9
-  //  rounds, 212.6 -> 193.0 and 206.5 -> 184.9 us per conv; 360 blocks = 1.4 rounds lose, pwconv1 94 -> 99)
-  const long blocks22 = row_tiles(256) * mt;
-  const bool fills22 = blocks22 >= 640 || (blocks22 >= 440 && (blocks22 % kCUs == 0 || blocks22 % kCUs >= kCUs * 4 / 5));
-  if (x3 && !a.x16 && force_tile == 0 && (tile == 5 || tile == 6) && fills22 && !getenv("STTS_X3_TILE")) {
-    // split fp32, launches of at least 2.5 chip rounds of 256-row tiles: 8 waves of 64 x 64 (half the weight staging per row, 12 instead of 18 fragment
-    // reads per 24 MFMAs).  B = 64 x 3 s: every layer 8-12 % faster than the 128 x 128 tile (decoder conv2 648 -> 595 us, output conv 3 637 -> 3 342);
-    // B = 24: the 1536- and 1024-wide layers (1 080 / 720 blocks) gain, the 512-wide ones (360 blocks = 1.4 rounds) would lose and keep the 128-row tile
-    tile = 22;
-    plan = Plan();
-  }
-  STTS_CHECK(!(tile >= 20 && tile <= 28) || x3, "conv_gemm: tiles 20 - 28 exist for the split-fp32 contractions only");
-  if (x3 && a.x16) {  // pre-split activation planes: the 128 x 128 or the 128 x 64 tile, whole launches (no block split-K, no remainder launch)
-    static const int gl_env = getenv("STTS_X3P_GLDS") ? atoi(getenv("STTS_X3P_GLDS")) : 1;  // experiments: 0 = register staging, 1 = LDS-DMA
-    if (tile < 25) tile = (tile == 5 || tile == 8 || tile == 20 || tile == 21 || tile == 22) ? (gl_env ? 27 : 25) : (gl_env ? 28 : 26);
-    plan = Plan();
-  }
-  STTS_CHECK(!(tile >= 25 && tile <= 28) || (x3 && a.x16), "conv_gemm: tiles 25 - 28 read pre-split activation planes");
-  const int bn = ((tile >= 14 && tile <= 17) || tile == 22) ? 256 : (tile == 5 || tile == 8 || tile == 11 || tile == 18 || tile == 20 || tile == 21 || tile == 25 || tile == 27) ? 128 : ((tile == 3 || tile == 4) ? 32 : 64);
-  if (plan.full_rt == 0 && plan.rem_rt == 0) plan.full_rt = row_tiles(bn);
-  if (tile == 8 || tile == 21) {
-    plan.full_rt = row_tiles(bn);
-    plan.rem_rt = 0;
-  }
-  // (intra-block K-split, tiles 8-10, and 2-wave tiles measured no better than these at any layer shape: every
-  //  configuration plateaus at ~80 % matrix-pipe occupancy)
+  GemmPlan plan = plan_conv_gemm(a, epi, npad, n_utt, max_rows, force_tile, gemm_switches());
+  STTS_CHECK(plan.ok(), "%s", plan.err);
+  if (plan.route == ROUTE_GEMM16) return launch_conv_gemm16_main(st, a, npad, n_utt);
+  if (a.prec != PREC_F32)
+    for (int i = 0; i < a.nseg; ++i) STTS_CHECK(a.seg[i].W16 != nullptr, "conv_gemm: 16-bit operand mode without 16-bit weights (segment %d)", i);
+  const int tile = plan.tile, bn = plan.bn();
   GemmArgs as = a;
   as.n_utt = n_utt;
   if (!as.zeros) as.zeros = zero_page();
   as.compact = a.seg_host != nullptr;  // grid.y = the row tiles that exist; needed for tile ranges and for balanced XCDs
-  // Block-level split-K for launches that cannot fill the chip (phoneme-rate layers, B = 1): one wave's MFMA chain over
-  // the whole K (~1 us per 32 channels x taps) is then the critical path, so K is cut over up to 8 blocks per tile.
-  int main_ksp = 1;
-  if (splittable && tile != 8 && tile != 21 && tile < 25 && plan.rem_rt == 0) {
-    const long blocks = plan.full_rt * mt;
-    // (16-bit operands: a contraction that already has one tile per CU is shorter than the reduce pass it would add)
-    // K iterations a slice must keep: 4; 8 once the launch has half a chip of blocks anyway (a 16-iteration contraction over 128-256 blocks cut in
-    // two gained less than its reduce pass costs: CFM estimator 8 x 800 frames 7.00 -> 6.82 ms; launches with fewer blocks still gain from the cut)
-    static const int min_it_env = getenv("STTS_SPLITK_MIN_ITERS") ? std::max(1, atoi(getenv("STTS_SPLITK_MIN_ITERS"))) : 0;  // experiments
-    const int min_it = min_it_env ? min_it_env : (blocks >= 128 ? 8 : 4);
-    // (fp32 on the f32 matrix cores: launches of 128-256 blocks take the 16-wave tile above, so 512 never cuts them; split fp32: like the 16-bit forms)
-    main_ksp = (int)std::min<long>(8, std::min<long>(iters / min_it, ((a.prec == PREC_F32 && !x3) ? 512 : 255) / std::max<long>(blocks, 1)));
-    if (main_ksp < 2) main_ksp = 1;
-  }
   float* part = nullptr;
-  if (main_ksp > 1 || plan.rem_rt > 0) {
-    part = splitk_scratch(st, (size_t)std::max(main_ksp, plan.rem_ksp) * a.rows_total * npad * sizeof(float));
+  if (plan.main_ksp > 1 || plan.rem_rt > 0) {
+    part = splitk_scratch(st, (size_t)std::max(plan.main_ksp, plan.rem_ksp) * a.rows_total * npad * sizeof(float));
     if (!part) {  // no scratch: one plain launch
-      main_ksp = 1;
+      plan.main_ksp = 1;
       plan.full_rt += plan.rem_rt;
       plan.rem_rt = 0;
     }
-  }
-  if (a.prec != PREC_F32) {
-    for (int i = 0; i < a.nseg; ++i) STTS_CHECK(a.seg[i].W16 != nullptr, "conv_gemm: 16-bit operand mode without 16-bit weights (segment %d)", i);
-    STTS_CHECK(tile != 11 && tile != 13, "conv_gemm: LDS-DMA tiles are fp32 only");
   }
   GemmProfiler& prof = gemm_profiler();
   const double flops = gemm_algorithmic_flops(a);
@@ -1602,12 +1424,12 @@ inline int launch_conv_gemm(hipStream_t st, const GemmArgs& a, int epi, int npad
       e0 = prof.next();
       e1 = prof.next();
       // (bench.py's roofline: "_x3" = the split-fp32 form, six bf16 MFMAs per 16 channels on the bf16 matrix cores; no suffix = the f32 matrix cores)
-      prof.add(x3 ? "conv_gemm_f32_x3" : "conv_gemm_f32", 0, flops * (double)ntiles / (double)all_rt, flops * (double)ntiles / (double)all_rt, 0.0);
+      prof.add(plan.route == ROUTE_X3 ? "conv_gemm_f32_x3" : "conv_gemm_f32", 0, flops * (double)ntiles / (double)all_rt, flops * (double)ntiles / (double)all_rt, 0.0);
     }
     // the kernels live in one translation unit per operand form (csrc/gemm_tu_*.hip, compiled in parallel)
-    if (x3) gemm_dispatch_x3(st, as, tile, epi, npad, n_utt, max_rows, e0, e1);
-    else if (a.prec == PREC_BF16) gemm_dispatch_bf16(st, as, tile, epi, npad, n_utt, max_rows, e0, e1);
-    else if (a.prec == PREC_F16) gemm_dispatch_f16(st, as, tile, epi, npad, n_utt, max_rows, e0, e1);
+    if (plan.route == ROUTE_X3) gemm_dispatch_x3(st, as, tile, epi, npad, n_utt, max_rows, e0, e1);
+    else if (plan.route == ROUTE_BF16) gemm_dispatch_bf16(st, as, tile, epi, npad, n_utt, max_rows, e0, e1);
+    else if (plan.route == ROUTE_F16) gemm_dispatch_f16(st, as, tile, epi, npad, n_utt, max_rows, e0, e1);
     else gemm_dispatch_f32(st, as, tile, epi, npad, n_utt, max_rows, e0, e1);
     if (ksp > 1 && a.defer && tile0 == 0 && ntiles == all_rt) {
       *a.defer = SplitInfo{part, ksp, a.rows_total, npad};
@@ -1631,7 +1453,7 @@ inline int launch_conv_gemm(hipStream_t st, const GemmArgs& a, int epi, int npad
     }
   };
   if (a.defer) *a.defer = SplitInfo{nullptr, 1, 0, 0};
-  if (plan.full_rt > 0) launch_range(0, plan.full_rt, main_ksp);
+  if (plan.full_rt > 0) launch_range(0, plan.full_rt, plan.main_ksp);
   if (plan.rem_rt > 0) launch_range(plan.full_rt, plan.rem_rt, plan.rem_ksp);
   STTS_HIP(hipGetLastError());
   return 0;

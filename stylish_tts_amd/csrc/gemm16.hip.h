@@ -29,8 +29,7 @@
 
 namespace stts {
 
-constexpr int kG16Tile = 256;  // rows and output channels per block
-constexpr int kG16K = 64;      // channels per K tile
+// (kG16Tile = 256 rows and output channels per block, kG16K = 64 channels per K tile, gemm16_eligible and gemm16_tiles: gemm_plan.hip.h)
 
 template <int PREC>
 __device__ __forceinline__ f32x4 g16_mfma(const f32x4 a, const f32x4 b, const f32x4 c) {
@@ -490,28 +489,6 @@ __global__ void __launch_bounds__(512, 2) conv_gemm16_kernel(const GemmArgs a) {
     for (int i = 0; i < 6; ++i) a.dbg[8 * (long)blockIdx.x + i] = tr_acc[i];
 #endif
 #endif  // __HIP_DEVICE_COMPILE__
-}
-
-// Can this contraction run on conv_gemm16_kernel?  16-bit activation rows, store epilogue, every segment's channels a multiple of 64,
-// cout padded to 256, N a multiple of 4, host offsets known (compact grid).
-inline bool gemm16_eligible(const GemmArgs& a, int epi, int npad) {
-  if (epi != EPI_STORE || a.prec == PREC_F32 || !a.x16 || !a.seg_host || a.xaff || npad % kG16Tile != 0 || a.N % 4 != 0) return false;
-  if (a.ldy % 4 || a.ycol0 % 4 || a.ldr % 4 || a.rcol0 % 4 || a.ldy16 % 4 || a.ycol16 % 4 || a.ld_ss % 4 || a.ld_stat % 4) return false;
-  for (int i = 0; i < a.nseg; ++i)
-    if (a.seg[i].kc % kG16K != 0 || a.seg[i].ldx % 8 != 0 || a.seg[i].xcol0 % 8 != 0 || !a.seg[i].W16 || a.seg[i].ldx - a.seg[i].xcol0 < a.seg[i].kc) return false;
-  return true;
-}
-
-inline bool gemm16_will_run(const GemmArgs& a, int epi, int npad, int n_utt) {
-  static const long min_tiles = getenv("STTS_GEMM16_MIN_TILES") ? atol(getenv("STTS_GEMM16_MIN_TILES")) : 192;
-  return gemm16_eligible(a, epi, npad) && gemm16_tiles(a, npad, n_utt) >= min_tiles;
-}
-
-// 256 x 256 tiles of the launch: exact from the host offsets (an upper bound when they are capacities)
-inline long gemm16_tiles(const GemmArgs& a, int npad, int n_utt) {
-  long rt = 0;
-  for (int u = 0; u < n_utt; ++u) rt += ceil_div(a.seg_host[u + 1] - a.seg_host[u], kG16Tile);
-  return rt * (npad / kG16Tile);
 }
 
 template <int ABL>

@@ -8,6 +8,13 @@
 // And it says which kernels the reverse flow launches: a line `flowtrace <precision> <case> <switches> : <trace>` per batch shape and setting of the
 // STTS_WN_* switches (flow_section below; the trace is the stub's run-length-encoded list of kernel, grid and block in issue order), in all four
 // precisions.  tests/test_asan_host.py compares the default choices with the forced ones; two builds plan the same launches exactly when these lines agree.
+// The same for the contractions: `gemmtrace <precision> <case> <force_tile> : <trace>` per case of gemm_section below (stts_op_conv1d / stts_op_conv1d_x3, so the
+// library is built with -DSTTS_TEST_OPS; a call that fails prints `error` in front of whatever it launched before failing), and
+// `launchtrace <precision> <case> : <trace>` around every stage walk.  In the compact grid of conv_gemm_f32, grid.y is the row-tile count and grid.z the split-K factor.
+// A second weight dump (a model with 96 flow channels) adds `flowtrace <precision> generic96* -` lines: the flow as plain contractions with the gate,
+// split-accumulate and couple epilogues.
+// `asan_driver <weights> gemm` prints the gemmtrace lines only (no finalize): the STTS_* switches of the contractions are read once per process, so
+// tests/asan/build_and_run.py starts one process per setting.
 #include <algorithm>
 #include <cinttypes>
 #include <cstdint>
@@ -34,6 +41,13 @@ extern "C" const char* stts_stub_trace_end();
 
 static std::vector<float> buf(size_t n) { return std::vector<float>(n ? n : 1, 0.5f); }
 
+static int g_prec = 0;  // precision of the context being walked (for the launchtrace lines)
+static void launchtrace(const char* what, const char* trace) {
+  std::string tag = what;
+  std::replace(tag.begin(), tag.end(), ' ', '_');
+  printf("launchtrace %d %s : %s\n", g_prec, tag.c_str(), trace);
+}
+
 static int frame_case(stts_ctx* c, const std::vector<int>& lens, const char* what) {
   const int n = (int)lens.size();
   std::vector<int32_t> off(n + 1, 0);
@@ -56,6 +70,7 @@ static int frame_case(stts_ctx* c, const std::vector<int>& lens, const char* wha
   }
   auto asr = buf(R * 128), pitch = buf(R), energy = buf(R), style = buf((size_t)n * 64), pn = buf(R * 128), sn = buf(R * 75), ph = buf(1), audio = buf(R * 75);
   auto x = buf(R * 512), mel = buf(R * 512), hs = buf(R * 1088), hp = buf(R * 1088);  // 1088: the spectrum row stride every operand mode accepts (fp32 needs >= 1056, the 16-bit modes 1088)
+  stts_stub_trace_begin();
   const long before = stts_stub_launch_count();
   CK(stts_frame_path(c, nullptr, n, off.data(), off.data(), asr.data(), 128, pitch.data(), energy.data(), style.data(), pn.data(), sn.data(), ph.data(), 0,
                      audio.data(), ws.data(), wsb, 0));
@@ -69,6 +84,7 @@ static int frame_case(stts_ctx* c, const std::vector<int>& lens, const char* wha
   CK(stts_harmonic_stft(c, nullptr, n, off.data(), off.data(), pitch.data(), sn.data(), ph.data(), 1, nullptr, hs.data(), hp.data(), 1088, ws.data(), wsb));
   CK(stts_vocoder_forward(c, nullptr, n, off.data(), off.data(), mel.data(), 512, style.data(), hs.data(), hp.data(), 1088, audio.data(), nullptr, nullptr, 0,
                           ws.data(), wsb));
+  launchtrace(what, stts_stub_trace_end());
   printf("  %-44s rows %8ld  workspace %8.1f MB  %ld launches per frame-path call\n", what, R, wsb / 1048576.0, fused);
   return 0;
 }
@@ -171,6 +187,7 @@ static int phoneme_case(stts_ctx* c, const std::vector<int>& toks, const std::ve
   std::vector<int32_t> dur(P, 1);
   auto mu = buf(P * 256), xh = buf(P * 128), sty = buf((size_t)n * 64), logits = buf(P * 16), f0 = buf(T), en = buf(T), enc4 = buf(4 * T * 256), up = buf(4 * T);
   std::vector<int32_t> dur_out(P), idx(4 * T + 1);
+  stts_stub_trace_begin();
   for (int which = 0; which < 3; ++which) {
     CK(stts_text_encoder_forward(c, nullptr, which, n, to.data(), to.data(), tokens.data(), mu.data(), 256, xh.data(), ws.data(), wsb));
     CK(stts_text_style_forward(c, nullptr, which, n, to.data(), to.data(), mu.data(), 256, sty.data(), ws.data(), wsb));
@@ -186,8 +203,80 @@ static int phoneme_case(stts_ctx* c, const std::vector<int>& toks, const std::ve
   }
   CK(stts_length_regulate(c, nullptr, n, dur.data(), to.data(), fo4.data(), 4 * T, 4, mu.data(), 256, 128, enc4.data(), 128, idx.data()));
   CK(stts_upsample4(c, nullptr, n, fo.data(), fo.data(), fo4.data(), f0.data(), up.data()));
+  launchtrace(what, stts_stub_trace_end());
   printf("  %-44s tokens %6ld frames %7ld  workspace %8.1f MB\n", what, P, T, wsb / 1048576.0);
   return 0;
+}
+
+// One contraction through the test operators, traced: prec 0 = fp32 (split fp32), 1 = bf16, 2 = fp16, 3 = fp32 on the f32 matrix cores.  force as the operators take it
+// (100 + t: 16-bit activation rows in the 16-bit modes); presplit: stts_op_conv1d_x3 with pre-split activation planes.  A failing call is a result, not a driver failure.
+static void gemm_case(int prec, const char* what, const std::vector<int>& lens, int cin, int cout, int k, int dil, int force, bool presplit = false) {
+  const int n = (int)lens.size();
+  std::vector<int32_t> off(n + 1, 0);
+  for (int i = 0; i < n; ++i) off[i + 1] = off[i] + lens[i];
+  const long R = off[n];
+  const int ldx = (cin + 31) / 32 * 32, ldy = (cout + 31) / 32 * 32;
+  auto x = buf(R * ldx), w = buf((size_t)cout * cin * k), b = buf(cout), y = buf(R * ldy);
+  stts_stub_trace_begin();
+  const int rc = (presplit || ((prec == 0 || prec == 3) && force == 0))
+                     ? stts_op_conv1d_x3(nullptr, n, off.data(), off.data(), x.data(), ldx, cin, nullptr, 0, 0, w.data(), b.data(), cout, k, dil, nullptr, 0, 1.0f, presplit,
+                                         y.data(), ldy, force, prec)
+                     : stts_op_conv1d(nullptr, n, off.data(), off.data(), x.data(), ldx, cin, w.data(), b.data(), cout, k, dil, 0, y.data(), ldy, force, prec);
+  const char* trace = stts_stub_trace_end();
+  printf("gemmtrace %d %s %d : %s%s\n", prec, what, force, rc ? "error " : "", trace);
+}
+
+// The contraction cases (tests/test_asan_host.py GEMM_CASES has the same list).  The batch sizes around a threshold follow from launch_conv_gemm's rules
+// (csrc/gemm_plan.hip.h), 256 CUs: see the comment of each group.
+static void gemm_section() {
+  const std::vector<int> ragged = {1, 63, 64, 65, 129};
+  auto uni = [](int b, int len) { return std::vector<int>(b, len); };
+  // every tile, forced, in each operand form it exists in (7: no such tile), 64 -> 130 channels, k = 3
+  for (int t : {2, 3, 4, 5, 6, 8, 20, 21, 22, 7}) gemm_case(0, "forced", ragged, 64, 130, 3, 1, t);
+  for (int t : {25, 26, 27, 28}) gemm_case(0, "forced", ragged, 64, 130, 3, 1, t, true);
+  for (int t : {2, 3, 4, 5, 6, 8, 11, 13}) gemm_case(3, "forced", ragged, 64, 130, 3, 1, t);
+  for (int prec : {1, 2}) {
+    for (int t : {2, 3, 4, 5, 6, 8, 14, 15}) gemm_case(prec, "forced", ragged, 64, 130, 3, 1, t);
+    for (int t : {2, 3, 4, 5, 6, 14, 15, 16, 17, 18, 19}) gemm_case(prec, "forced", ragged, 64, 130, 3, 1, 100 + t);
+  }
+  for (int prec : {0, 3}) {
+    // the AUTO geometries and the two dispatch-path shapes of tests/test_hip_split_fp32_edges.py, tile left to the plan
+    gemm_case(prec, "auto32x1025", ragged, 32, 1025, 1, 1, 0);
+    gemm_case(prec, "auto33x130", ragged, 33, 130, 3, 3, 0);
+    gemm_case(prec, "auto578x512", ragged, 578, 512, 3, 1, 0);
+    gemm_case(prec, "auto1536x64", ragged, 1536, 64, 7, 3, 0);
+    gemm_case(prec, "splitK", {1, 63}, 1536, 64, 7, 1, 0);
+    gemm_case(prec, "tile22", uni(16, 257), 32, 2048, 1, 1, 0);
+    // ... and the tiles the first two are meant to take, forced, on the same shapes
+    gemm_case(prec, "auto32x1025", ragged, 32, 1025, 1, 1, 6);
+    gemm_case(prec, "auto33x130", ragged, 33, 130, 3, 3, 4);
+    // remainder launch: 300 x 20 rows, 128 -> 64 channels, k = 3: 12 K iterations, 300 blocks of 64 rows = 256 whole + 44 with K cut in 3 (f32 matrix cores);
+    // split fp32 keeps launches whole
+    gemm_case(prec, "300x20", uni(300, 20), 128, 64, 3, 1, 0);
+  }
+  gemm_case(0, "tile22", uni(16, 257), 32, 2048, 1, 1, 22);
+  // tile 8 (f32 matrix cores): 128 x 128 blocks <= 256.  cout 128: one block per 128-row utterance
+  for (int b : {256, 257}) gemm_case(3, b == 256 ? "tile8_256" : "tile8_257", uni(b, 128), 64, 128, 3, 1, 0);
+  gemm_case(3, "tile8_256", uni(256, 128), 64, 128, 3, 1, 8);
+  // tile 22 (split fp32): blocks of 256 rows >= 640, or >= 440 with the last chip round whole or filled to 80 % (204 of 256).  cout 128: one block per 256-row
+  // utterance; 440 itself leaves 184 in its last round, so the first launch of the second kind is 460
+  for (int b : {439, 440, 459, 460, 639, 640}) {
+    const std::string what = "tile22_" + std::to_string(b);
+    gemm_case(0, what.c_str(), uni(b, 256), 32, 128, 1, 1, 0);
+    gemm_case(0, what.c_str(), uni(b, 256), 32, 128, 1, 1, 22);
+  }
+  for (int prec : {1, 2}) {
+    // 16-bit activation rows.  Tile 15: row tiles of 256 x (npad / 128) >= 384; cout 384 (npad 384: neither tile 14 nor conv_gemm16_kernel) -> 128 utterances of 256 rows
+    for (int b : {127, 128})
+      for (int f : {100, 115}) gemm_case(prec, b == 127 ? "tile15_127" : "tile15_128", uni(b, 256), 64, 384, 1, 1, f);
+    // tile 14: npad % 256 == 0, K iterations >= 128, row tiles of 256 x (npad / 256) >= 384; cout 1022 (npad 1024; N % 4 != 0 keeps it off conv_gemm16_kernel) -> 96
+    // utterances of 256 rows, 128 channels x 33 taps = 132 iterations (95 utterances: tile 15)
+    for (int b : {95, 96})
+      for (int f : {100, 114, 115}) gemm_case(prec, b == 95 ? "tile14_95" : "tile14_96", uni(b, 256), 128, 1022, 33, 1, f);
+    // conv_gemm16_kernel: 256 x 256 tiles >= 192; cout 256 -> 192 utterances of 256 rows
+    for (int b : {191, 192})
+      for (int f : {100, 119}) gemm_case(prec, b == 191 ? "gemm16_191" : "gemm16_192", uni(b, 256), 64, 256, 1, 1, f);
+  }
 }
 
 struct Tensor {
@@ -207,21 +296,14 @@ static int new_ctx(const stts_model_dims& d, int prec, const std::vector<Tensor>
   return 0;
 }
 
-int main(int argc, char** argv) {
-  if (argc < 2) {
-    fprintf(stderr, "usage: asan_driver <weights.bin>\n");
-    return 2;
-  }
-  FILE* f = fopen(argv[1], "rb");
+// a weight dump: the three dims structs, then (name, shape, fp32 data) per tensor
+static int read_weights(const char* path, stts_model_dims& d, stts_cfm_dims& cd, stts_ssl_dims& sd, std::vector<Tensor>& w) {
+  FILE* f = fopen(path, "rb");
   if (!f) {
-    perror(argv[1]);
+    perror(path);
     return 2;
   }
-  stts_model_dims d;
-  stts_cfm_dims cd;
-  stts_ssl_dims sd;
   if (fread(&d, sizeof(d), 1, f) != 1 || fread(&cd, sizeof(cd), 1, f) != 1 || fread(&sd, sizeof(sd), 1, f) != 1) return 2;
-  std::vector<Tensor> w;
   for (;;) {
     int32_t name_len = 0;
     Tensor t;
@@ -239,6 +321,21 @@ int main(int argc, char** argv) {
     w.push_back(std::move(t));
   }
   fclose(f);
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc < 2) {
+    fprintf(stderr, "usage: asan_driver <weights.bin> [gemm | <narrow weights.bin>]\n");
+    return 2;
+  }
+  gemm_section();
+  if (argc > 2 && strcmp(argv[2], "gemm") == 0) return 0;
+  stts_model_dims d;
+  stts_cfm_dims cd;
+  stts_ssl_dims sd;
+  std::vector<Tensor> w;
+  if (read_weights(argv[1], d, cd, sd, w)) return 2;
   for (int prec = 0; prec <= 3; ++prec) {  // fp32, fp16 operands (16-bit weight copies are packed too), fp32 on the f32 matrix cores
     if (prec == 1) {  // bf16: the reverse flow alone (its kernel choice has branches of its own; the packing is fp16's with another rounding)
       stts_ctx* cf = nullptr;
@@ -252,6 +349,7 @@ int main(int argc, char** argv) {
     uint64_t first = 0;
     stts_ctx* c = nullptr;
     if (new_ctx(d, prec, w, &c)) return 1;
+    g_prec = prec;
     auto digest = [&](const char* what) {
       first = stts_stub_digest() - base;
       printf("digest %d %s %016" PRIx64 "\n", prec, what, first);
@@ -312,6 +410,18 @@ int main(int argc, char** argv) {
       return 1;
     }
     printf("order %d: the second order and the failed finalize end at the same digest %016" PRIx64 "\n", prec, second);
+  }
+  if (argc > 2) {  // a model whose flow is not 128 channels wide: every coupling layer as plain contractions with the gate / split-accumulate / couple epilogues
+    stts_model_dims nd;
+    std::vector<Tensor> nw;
+    if (read_weights(argv[2], nd, cd, sd, nw)) return 2;
+    for (int prec : {0, 2, 3}) {
+      stts_ctx* cf = nullptr;
+      if (new_ctx(nd, prec, nw, &cf)) return 1;
+      CK(stts_finalize_weights(cf, STTS_W_FLOW));
+      if (flow_case(cf, prec, {1, 63, 64, 65, 129}, "generic96", "-") || flow_case(cf, prec, std::vector<int>(8, 960), "generic96_8x960", "-")) return 1;
+      stts_ctx_destroy(cf);
+    }
   }
   printf("asan driver: all cases ran, %ld stubbed launches\n", stts_stub_launch_count());
   return 0;

@@ -7,6 +7,7 @@ Steps: (1) hipcc --cuda-host-only -fsanitize=address,undefined -c for every tran
 (2) link it with hip_stub.cpp into libstylish_hip_asan.so (the fat-binary symbol the host code references is defined as an
 empty blob), (3) dump the synthetic weights of every inference module, of the voice-conversion models, of the CFM estimator and of a narrow
 AdaptiveHubert to a binary file, (4) run asan_driver on it.
+(5) run `asan_driver <weights> gemm` (the contraction cases only) once per setting of GEMM_SETTINGS, each line prefixed with `[setting]`.
 Exit code 0 = no sanitizer report, every stage accepted its workspace for every shape, and the packed bytes did not depend on the order of the
 finalizes.  The driver's `digest <precision> <what> <hex>` lines say what was packed: two builds of the library pack the same bytes exactly when
 these lines are the same."""
@@ -20,6 +21,21 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 
 
+# the process-wide switches of the contractions (csrc/gemm_plan.hip.h gemm_switches)
+GEMM_SETTINGS = ["STTS_NO_X3=1", "STTS_X3_REM=1", "STTS_X3_TILE=5", "STTS_X3_TILE=6", "STTS_X3_TILE=22", "STTS_X3P_GLDS=0", "STTS_TILE16=14", "STTS_TILE16=16", "STTS_TILE16=18",
+                 "STTS_SPLITK_MIN_ITERS=2", "STTS_GEMM16_MIN_TILES=1"]
+
+
+def write_tensors(f, m, spec):
+    from stylish_tts_amd import params
+
+    for k, v in params.synth_state_dict(spec, 0, prefix=m + ".").items():
+        name = (m + "." + k).encode()
+        shape = v.shape if v.ndim else (1,)
+        f.write(struct.pack("<i", len(name)) + name + struct.pack("<i", len(shape)) + struct.pack(f"<{len(shape)}q", *shape))
+        f.write(v.astype("<f4").tobytes())
+
+
 def main(build_dir):
     os.makedirs(build_dir, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -31,7 +47,7 @@ def main(build_dir):
     for u in entry.UNITS:
         o = os.path.join(build_dir, u.replace(".hip", "_host.o"))
         objs.append(o)
-        procs.append(subprocess.Popen([hipcc, "--offload-arch=gfx950", "--cuda-host-only", *san, "-c", os.path.join(ROOT, "stylish_tts_amd", "csrc", u), "-o", o]))
+        procs.append(subprocess.Popen([hipcc, "--offload-arch=gfx950", "--cuda-host-only", "-DSTTS_TEST_OPS", *san, "-c", os.path.join(ROOT, "stylish_tts_amd", "csrc", u), "-o", o]))
     if any(p.wait() != 0 for p in procs):
         raise subprocess.CalledProcessError(1, "hipcc --cuda-host-only")
     fatbin = sorted({s for o in objs for s in subprocess.check_output(["nm", "-u", o], text=True).split() if s.startswith("__hip_fatbin")})
@@ -42,7 +58,7 @@ def main(build_dir):
     defsym = [f"-Wl,--defsym={s}=stts_stub_fatbin" for s in fatbin]
     subprocess.check_call([cxx, "-shared", *san, *objs, stub, *defsym, "-o", lib])
     exe = os.path.join(build_dir, "asan_driver")
-    subprocess.check_call([cxx, *san, os.path.join(HERE, "asan_driver.cpp"), lib, f"-Wl,-rpath,{build_dir}", "-o", exe])
+    subprocess.check_call([cxx, *san, "-DSTTS_TEST_OPS", os.path.join(HERE, "asan_driver.cpp"), lib, f"-Wl,-rpath,{build_dir}", "-o", exe])
 
     # weights: every module's synthetic state dict under the name modules.py loads it by (module + "." + key); the header is the three dims structs
     from stylish_tts_amd import _lib, hubert_ssl, params
@@ -58,15 +74,29 @@ def main(build_dir):
     with open(wpath, "wb") as f:
         f.write(bytes(_lib.dims_from_config(cfg)) + bytes(_lib.CfmDims(**params.CFM_DEFAULT_DIMS)) + bytes(hubert_ssl.dims_struct(ssl_arch)))
         for m, spec in specs:
-            for k, v in params.synth_state_dict(spec, 0, prefix=m + ".").items():
-                name = (m + "." + k).encode()
-                shape = v.shape if v.ndim else (1,)
-                f.write(struct.pack("<i", len(name)) + name + struct.pack("<i", len(shape)) + struct.pack(f"<{len(shape)}q", *shape))
-                f.write(v.astype("<f4").tobytes())
+            write_tensors(f, m, spec)
+    # ... and the text-to-speech weights of the narrow model of tests/golden/gen_golden.py (NARROW: decoder / generator width 384): its flow has 96 channels and runs
+    # as plain contractions (gate / split-accumulate / couple epilogues)
+    narrow = load_model_config(dict(dict(cfg), decoder=dict(cfg["decoder"], hidden_dim=384, residual_dim=32),
+                                    generator=dict(cfg["generator"], input_dim=384, hidden_dim=384, conv_intermediate_dim=1152)))
+    npath = os.path.join(build_dir, "weights_narrow.bin")
+    with open(npath, "wb") as f:
+        f.write(bytes(_lib.dims_from_config(narrow)) + bytes(_lib.CfmDims(**params.CFM_DEFAULT_DIMS)) + bytes(hubert_ssl.dims_struct(ssl_arch)))
+        write_tensors(f, "speech_predictor", params.module_spec("speech_predictor", narrow))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-    r = subprocess.run([exe, wpath], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    r = subprocess.run([exe, wpath, npath], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    # the contraction cases once more under each experiment switch, one fresh process per setting (gemm_switches() reads them once per process); printed first,
+    # so that the output still ends with the whole run's last lines
+    rc = r.returncode
+    for setting in GEMM_SETTINGS:
+        if rc != 0:
+            break
+        k, v = setting.split("=")
+        g = subprocess.run([exe, wpath, "gemm"], env=dict(env, **{k: v}), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        print("".join(f"[{setting}] {line}\n" for line in g.stdout.splitlines()))
+        rc = g.returncode
     print(r.stdout)
-    return r.returncode
+    return rc
 
 
 if __name__ == "__main__":

@@ -16,7 +16,13 @@ The driver also traces which kernels the reverse flow launches (`flowtrace <prec
 run-length encoded>`), in all four precisions, over the batch shapes around the thresholds of the kernel choice (csrc/flow.hip.h plan_flow) and
 under the STTS_WN_* switches.  Every case must be there, and the choice with no switch set is pinned without a constant: its trace must equal
 the trace under the switches that force the intended kernel (PINS).  No trace is an expected value here either: two builds plan the same
-launches exactly when their flowtrace lines agree."""
+launches exactly when their flowtrace lines agree.
+
+The same for the dense contractions (csrc/gemm_plan.hip.h plan_conv_gemm): `gemmtrace <precision> <case> <force_tile> : <trace>` for every tile of the tile
+table forced in each operand form it exists in, the shapes around every threshold of the plan with the tile left to it, and the remainder launch; and
+`launchtrace <precision> <case> : <trace>` around every stage walk, and `flowtrace <precision> generic96* -` for a second model whose flow is 96 channels wide
+(every coupling layer as plain contractions with the gate / split-accumulate / couple epilogues).  The tile the plan is meant to take is pinned the same way: against the forced trace on the
+same shape.  build_and_run.py repeats the gemmtrace cases under each experiment switch (lines prefixed `[NAME=value]`, compared between builds only)."""
 import os
 import re
 import shutil
@@ -39,6 +45,24 @@ FLOW_CASES = ([(0, b, "-") for b in ("1x960", "8x960", "16x960", "64x3200", "rag
 PINS = {(0, "1x960"): "STTS_WN_M=1,STTS_WN_X3=1", (0, "8x960"): "STTS_WN_M=2,STTS_WN_X3=2", (0, "16x960"): "STTS_WN_M=4,STTS_WN_X3=4",
         (3, "1x960"): "STTS_WN_M=1", (3, "8x960"): "STTS_WN_M=2", (3, "16x960"): "STTS_WN_M=4",
         (1, "23x960"): "STTS_WN_RT=4", (1, "24x960"): "STTS_WN_RT=16", (2, "23x960"): "STTS_WN_RT=4", (2, "24x960"): "STTS_WN_RT=16"}
+
+# gemmtrace cases: (precision, case, force_tile); tests/asan/asan_driver.cpp gemm_section has the shapes
+_SPLIT, _PRESPLIT, _NATIVE = (2, 3, 4, 5, 6, 8, 20, 21, 22), (25, 26, 27, 28), (2, 3, 4, 5, 6, 8, 11, 13)
+_HALF_TILES = (2, 3, 4, 5, 6, 8, 14, 15) + tuple(100 + t for t in (2, 3, 4, 5, 6, 14, 15, 16, 17, 18))
+FORCED = {0: _SPLIT + _PRESPLIT, 3: _NATIVE, 1: _HALF_TILES, 2: _HALF_TILES}  # per form: traces pairwise distinct
+_AUTO = ("auto32x1025", "auto33x130", "auto578x512", "auto1536x64", "splitK", "tile22", "300x20")
+GEMM_CASES = ([(p, "forced", t) for p, ts in FORCED.items() for t in ts] + [(0, "forced", 7), (1, "forced", 119), (2, "forced", 119)]
+              + [(p, c, 0) for p in (0, 3) for c in _AUTO] + [(3, "tile8_257", 0)] + [(0, f"tile22_{b}", f) for b in (439, 440, 459, 460, 639, 640) for f in (0, 22)]
+              + [(p, c, 100) for p in (1, 2) for c in ("tile15_127", "tile15_128", "tile14_95", "tile14_96", "gemm16_191", "gemm16_192")])
+# the tile that is meant to run with no tile forced (no split-K, no remainder launch in these): (precision, case, unforced) -> the force that selects it
+GEMM_PINS = {(0, "auto33x130", 0): 4, (3, "auto33x130", 0): 4, (0, "auto32x1025", 0): 6, (3, "auto32x1025", 0): 6, (0, "tile22", 0): 22, (3, "tile8_256", 0): 8,
+             (0, "tile22_460", 0): 22, (0, "tile22_640", 0): 22}
+GEMM_PINS.update({(p, c, 100): f for p in (1, 2) for c, f in (("tile15_128", 115), ("tile14_95", 115), ("tile14_96", 114), ("gemm16_192", 119))})
+# ... and just below each threshold the forced tile must NOT be what runs
+GEMM_OFF = ([(0, f"tile22_{b}", 0, 22) for b in (439, 440, 459, 639)]
+            + [(p, c, 100, f) for p in (1, 2) for c, f in (("tile15_127", 115), ("tile14_95", 114), ("gemm16_191", 119))])
+LAUNCH_CASES = [(p, c) for p in (0, 2) for c in ("cfg2:_8_x_3_s", "B_=_1_x_3_s", "short_ragged_utterances", "cfg5_per_GPU:_64_x_10_s", "cfg3:_64_x_50_tokens",
+                                                 "token-count_extremes")] + [(0, "cfg4:_256_utterances_of_0.25-10_s")]
 
 
 @pytest.mark.timeout(900)
@@ -63,3 +87,43 @@ def test_host_side_under_asan_ubsan(tmp_path):
     # (the pins say something only while the forced traces differ from one another)
     assert len({traces[(0, "ragged", v)] for v in _VARIANTS}) == len(_VARIANTS)
     assert all(len({traces[(p, "ragged", f"STTS_WN_RT={rt}")] for rt in (-1, 4, 8, 16)}) == 4 for p in (1, 2))
+
+    # ---- the dense contractions
+    gemm = {(int(p), c, int(f)): t for p, c, f, t in re.findall(r"^gemmtrace (\d) (\S+) (-?\d+) : (.*)$", r.stdout, re.M)}
+    missing = [k for k in GEMM_CASES + [(p, c, f) for (p, c, _), f in GEMM_PINS.items()] + [(p, c, f) for p, c, _, f in GEMM_OFF] if k not in gemm]
+    assert not missing, missing
+    launch = {(int(p), c): t for p, c, t in re.findall(r"^launchtrace (\d) (\S+) : (.+)$", r.stdout, re.M)}
+    assert not [k for k in LAUNCH_CASES if k not in launch], sorted(launch)
+    for (prec, case, unforced), forced in GEMM_PINS.items():
+        assert not gemm[(prec, case, forced)].startswith("error") and gemm[(prec, case, unforced)] == gemm[(prec, case, forced)], (prec, case, forced, gemm[(prec, case, unforced)])
+    for prec, case, unforced, forced in GEMM_OFF:
+        assert gemm[(prec, case, unforced)] != gemm[(prec, case, forced)], (prec, case, forced)
+    assert "(1024,1,1)" in gemm[(3, "tile8_256", 0)] and "(1024,1,1)" not in gemm[(3, "tile8_257", 0)]  # (tile 8 alone has blocks of 16 waves)
+    for prec, tiles in FORCED.items():  # (the pins say something only while the forced traces differ from one another)
+        forced = [gemm[(prec, "forced", t)] for t in tiles]
+        assert len(set(forced)) == len(tiles) and not any(t.startswith("error") for t in forced), (prec, forced)
+    # whole rounds + split-K remainder: two contraction launches (the second with K cut: grid.z > 1) and one reduce pass on the f32 matrix cores, one launch in split fp32
+    rem = gemm[(3, "300x20", 0)].split(" | ")
+    assert len(rem) == 3 and all(t.startswith("1x conv_gemm_f32<") for t in rem[:2]) and rem[2].startswith("1x splitk_reduce_kernel "), rem
+    assert re.search(r"\(1,256,1\)\(", rem[0]) and re.search(r"\(1,44,3\)\(", rem[1]), rem
+    whole = gemm[(0, "300x20", 0)]
+    assert whole.startswith("1x conv_gemm_f32<") and " | " not in whole and "splitk_reduce_kernel" not in whole, whole
+    # a tile id without a row is an error and launches nothing; tile 19 on a contraction conv_gemm16_kernel cannot take (130 channels out) fails after the row cast
+    assert gemm[(0, "forced", 7)] == "error ", gemm[(0, "forced", 7)]
+    assert all(gemm[(p, "forced", 119)].startswith("error ") and "conv_gemm" not in gemm[(p, "forced", 119)] for p in (1, 2))
+    # the paired and the split-accumulate epilogues (conv_gemm_f32's fifth template argument): the prior conv (EPI_PRIOR = 4) is in every frame-path walk; gate (1),
+    # split-accumulate (2) and couple (3) are the coupling layers of a flow that is not 128 channels wide (the driver's second model: 96), on tile 3 below 24 blocks
+    # of 128 x 128 and on tile 2 above (split-accumulate is unpaired: tile 4, then 5 / 6 / 8)
+    for prec in (0, 2):
+        assert re.search(r"conv_gemm_f32<128, (64, 2, 2|32, 2, 1), 4,", launch[(prec, "cfg2:_8_x_3_s")]), prec
+    for prec in (0, 2, 3):
+        small, large = traces[(prec, "generic96", "-")], traces[(prec, "generic96_8x960", "-")]
+        for epi in (1, 3):
+            assert re.search(rf"conv_gemm_f32<128, 32, 2, 1, {epi},", small) and re.search(rf"conv_gemm_f32<128, 64, 2, 2, {epi},", large), (prec, epi)
+        assert re.search(r"conv_gemm_f32<128, 32, 4, 1, 2,", small) and re.search(r"conv_gemm_f32<128, (128|64), 4, 2, 2,", large), prec
+        assert "wn_" not in small and "wn_" not in large, prec
+    # every switch setting ran every case
+    per_setting = {}
+    for sw in re.findall(r"^\[(STTS_\w+=\d+)\] gemmtrace ", r.stdout, re.M):
+        per_setting[sw] = per_setting.get(sw, 0) + 1
+    assert len(per_setting) == 11 and set(per_setting.values()) == {len(gemm)}, per_setting

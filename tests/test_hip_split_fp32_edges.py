@@ -135,12 +135,14 @@ def test_auto_tile_exposed_products(hip, geom, path, precision):
 
 
 @pytest.mark.parametrize("precision", ["f32", "f32_native"])
-@pytest.mark.parametrize("shape", EXPOSED_SHAPES[16:18], ids=["splitK", "tile22"])
+@pytest.mark.parametrize("shape", EXPOSED_SHAPES[16:18] + EXPOSED_SHAPES[19:20], ids=["splitK", "tile22", "remainder"])
 def test_auto_tile_dispatch_paths_exposed_products(hip, shape, precision):
     """1536 -> 64, k 7, lengths [1, 63]: 2 blocks of 128 x 128 < 24 -> tile 4; 3 blocks of 32 rows, 336 K iterations -> block split-K over
     8 slices + splitk_reduce_kernel (both forms).
     32 -> 2048, 16 x 257 rows: mt 16, 768 blocks of 128 rows (3 rounds) against 1 280 of 64 rows (5 rounds x 64 x 1.03) -> tile 6; split fp32:
-    1 K iteration keeps tile 6, then 32 row tiles of 256 x 16 = 512 blocks (fills22: >= 440, whole rounds) -> tile 22.  f32 matrix cores: tile 6."""
+    1 K iteration keeps tile 6, then 32 row tiles of 256 x 16 = 512 blocks (fills22: >= 440, whole rounds) -> tile 22.  f32 matrix cores: tile 6.
+    128 -> 64, k 3, 300 x 20 rows: mt 1, 300 blocks of 128 rows (2 rounds) against 300 of 64 rows -> tile 6; 12 K iterations.  f32 matrix cores: 256 row tiles
+    as they are + the other 44 as a second launch with K cut in 3 (min(8, 12 / 4, 256 / 44)) + splitk_reduce_kernel over those rows; split fp32: one whole launch."""
     y, prod, b = run_exposed(hip, shape, precision=precision)
     check_exposed(y, prod, b, f"auto {precision} {shape[:4]}")
 

@@ -293,6 +293,7 @@ EXPOSED_SHAPES = [(cin, cout, k, dil, ragged(bn), 1000 * i + bn) for i, (cin, co
     (1536, 64, 7, 1, [1, 63], 7001),      # tile 0: 32-row tiles, block split-K over 8 slices + the reduce pass
     (32, 2048, 1, 1, [257] * 16, 7002),   # tile 0: 512 blocks of 256 rows fill the chip twice -> tile 22
     (578, 512, 3, 1, [129, 1, 300], 7003),  # the input-affine / two-segment / Winograd cases
+    (128, 64, 3, 1, [20] * 300, 7006),    # tile 0, f32 matrix cores: 300 blocks of 64 rows = 256 whole + a remainder launch of 44 with K cut in 3 + the reduce pass
 ]
 
 
