@@ -69,7 +69,8 @@ enum {
   STTS_W_PE_MEL_STYLE = 2048, /* pe_mel_style_encoder.* (not part of STTS_W_ALL)            models/models.py:57-62 */
   STTS_W_CFM_PITCH = 4096,   /* cfm_pitch_predictor.spk_emb.* (not part of STTS_W_ALL)     models/cfm/cfm_pitch_predictor.py:25-27 */
   STTS_W_CFM_PITCH_NET = 8192, /* cfm_pitch_predictor.{asr_emb, blocks, out_proj} (in_proj.* is accepted and ignored; not part of STTS_W_ALL) */
-  STTS_W_SSL = 16384         /* hubert.model.* = AdaptiveHubert (finalized by stts_ssl_finalize, not part of STTS_W_ALL)      train/models/ssl.py:16-31 */
+  STTS_W_SSL = 16384,        /* hubert.model.* = AdaptiveHubert (finalized by stts_ssl_finalize, not part of STTS_W_ALL)      train/models/ssl.py:16-31 */
+  STTS_W_RMVPE = 32768       /* rmvpe.* = the RMVPE pitch extractor E2E0 (finalized by stts_rmvpe_finalize, not part of STTS_W_ALL) train/dataprep/rmvpe/model.py:49-86 */
 };
 int stts_finalize_weights(stts_ctx* ctx, int which);
 /* Operand precision of the FRAME-RATE Conv1d / Linear contractions (call before the first stts_finalize_weights).
@@ -274,6 +275,42 @@ int stts_ssl_forward_taps(stts_ctx* ctx, void* stream, int n_utt, const int32_t*
                           float* conv_last, float* proj, float* pos, float* layers, float* hidden, void* ws, size_t ws_bytes);
 /* rows of the conv0 tap buffer of a call (its utterances start at multiples of the later strides' product) */
 int64_t stts_ssl_tap_rows(const stts_ssl_dims* dims, int n_utt, const int32_t* sample_off_host);
+
+/* ---- RMVPE pitch extractor (train/dataprep/rmvpe/: E2E0 of model.py / deepunet.py / seq.py in eval mode, mel2hidden of inference.py:28-35, the decode
+ * of utils.py:114-131, the log-mel of spec.py:39-71, the resampling of dataprep/pitch_extractor.py:136-141).  Weights are loaded under "rmvpe." with the
+ * reference's E2E0 state_dict keys; every BatchNorm (eps 1e-5, running statistics) is folded in double.  n_blocks, inter_layers and en_out_channels shape
+ * the network; en_de_layers = 5, kernel_size = (2, 2), n_gru = 1 and n_mels = 128 are the only values accepted.  Always fp32 on the f32 matrix cores,
+ * whatever stts_set_precision chose.  mel: packed time-major rows [rows_T, ld_mel >= 128] of log-mel frames at 100 frames / s, utterance u = rows
+ * [off[u], off[u + 1]), at least 17 frames each (the reflect padding to a multiple of 32 frames needs pad < frames).  Every utterance is padded on
+ * its own, the network - both GRU directions included - runs over the padded length, and the outputs are cropped: hidden [rows_T, 360] (the
+ * salience, may be null) and f0 [rows_T] in Hz (0 where the frame's largest salience is below thred; may be null).  An utterance's outputs are the
+ * same bit for bit alone and in any batch. */
+typedef struct stts_rmvpe_dims {
+  int32_t n_blocks, inter_layers, en_out_channels; /* 4, 4, 16 */
+  int32_t en_de_layers, kernel_h, kernel_w, n_gru, n_mels; /* fixed: 5, 2, 2, 1, 128 */
+} stts_rmvpe_dims;
+int stts_rmvpe_finalize(stts_ctx* ctx, const stts_rmvpe_dims* dims);
+size_t stts_rmvpe_workspace_bytes(const stts_ctx* ctx, int n_utt, const int32_t* off_host);
+int stts_rmvpe_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* mel_rows, int ld_mel, float thred,
+                       float* hidden_out, float* f0_out, void* ws, size_t ws_bytes);
+/* The same, plus intermediate activations for the tests, one after the other in `taps` (stts_rmvpe_tap_floats floats), each over the PADDED frames
+ * (utterance u's time rows start at its padded offset >> level) as channels-last rows [time row * F + f][round_up(C, 16)]: the five encoder levels'
+ * pooled outputs (level l: F = 64 >> l, C = en_out_channels << l), the intermediate's output (F = 4, C = 32 en_out_channels), the five decoder
+ * levels' outputs (level i: F = 8 << i, C = en_out_channels << (4 - i)), cnn [padded frames * 128][4] (3 channels), gru [padded frames][512]. */
+int stts_rmvpe_forward_taps(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* mel_rows, int ld_mel,
+                            float thred, float* hidden_out, float* f0_out, float* taps, void* ws, size_t ws_bytes);
+int64_t stts_rmvpe_tap_floats(const stts_rmvpe_dims* dims, int n_utt, const int32_t* off_host);
+/* Log-mel front end: wave = packed mono samples at 16 kHz, utterance u = [sample_off[u], sample_off[u + 1]), more than 512 samples each (reflect
+ * padding); STFT n_fft = win = 1024, hop 160, periodic Hann, center = True, samples / 160 + 1 frames (mel_off: their row offsets), magnitude,
+ * mel_basis [128, 513] (device) @ magnitude summed over band [128][2] (device int32: first and one-past-last nonzero bin of every filter),
+ * log(max(., 1e-5)) -> mel_out [rows, ld_mel >= 128]; mel_lin (optional) [rows, 128]: the mel before the clamp and the log.  Needs STTS_W_RMVPE. */
+int stts_rmvpe_mel(stts_ctx* ctx, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const int32_t* mel_off_host,
+                   const int32_t* mel_off_dev, const float* wave, const float* mel_basis, const int32_t* band, float* mel_out, int ld_mel, float* mel_lin);
+/* to_local_average_f0 of a salience [n_rows, ld >= 360] -> f0 [n_rows] (no weights needed) */
+int stts_rmvpe_decode(stts_ctx* ctx, void* stream, int64_t n_rows, const float* salience, int ld, float thred, float* f0_out);
+/* F.interpolate(mode="linear", align_corners=True) of every utterance's curve from its frames (off_in) to the frames of off_out, on the device */
+int stts_rmvpe_resample(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_in_dev, const int32_t* off_out_host, const int32_t* off_out_dev,
+                        const float* f0_in, float* f0_out);
 
 /* ---- HuBERT voice conversion (the reference's hubert_acoustic models, train/stage_type.py:907-1015).  Inputs are HuBERT features at the
  * mel-frame rate as packed time-major rows feats [rows_T, ld_feats] (ld_feats a multiple of 4 covering hubert.hidden_dim padded to 32, pad

@@ -95,6 +95,14 @@ SIGNATURES = {
     "stts_ssl_forward": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _SZ]),
     "stts_ssl_forward_taps": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _SZ]),
     "stts_ssl_tap_rows": (_I64, [_P, _I, _P]),
+    "stts_rmvpe_finalize": (_I, [_P, _P]),
+    "stts_rmvpe_workspace_bytes": (_SZ, [_P, _I, _P]),
+    "stts_rmvpe_forward": (_I, [_P, _P, _I, _P, _P, _P, _I, C.c_float, _P, _P, _P, _SZ]),
+    "stts_rmvpe_forward_taps": (_I, [_P, _P, _I, _P, _P, _P, _I, C.c_float, _P, _P, _P, _P, _SZ]),
+    "stts_rmvpe_tap_floats": (_I64, [_P, _I, _P]),
+    "stts_rmvpe_mel": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "stts_rmvpe_decode": (_I, [_P, _P, _I64, _P, _I, C.c_float, _P]),
+    "stts_rmvpe_resample": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     "stts_cfm_finalize": (_I, [_P, _P]),
     "stts_cfm_workspace_bytes": (_SZ, [_P, _I64, _I]),
     "stts_cfm_estimator": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _SZ]),

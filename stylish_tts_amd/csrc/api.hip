@@ -6,6 +6,7 @@
 #include "mel_style.hip.h"
 #include "cfm_pitch.hip.h"
 #include "ssl.hip.h"
+#include "rmvpe.hip.h"
 
 using namespace stts;
 
@@ -656,6 +657,138 @@ int stts_ssl_forward_taps(stts_ctx* c, void* stream, int n_utt, const int32_t* s
   return ssl_entry(c, stream, n_utt, sample_off_host, sample_off_dev, wave, off_T_host, off_T_dev, feats, ld_feats, &t, ws, ws_bytes);
   API_END
 }
+
+// ------------------------------------------------------------------------------------------------ RMVPE pitch extractor (rmvpe.hip.h)
+extern "C" {
+
+static int rmvpe_dims_from(const stts_rmvpe_dims* dims, RvDims* d) {
+  STTS_CHECK(dims, "rmvpe: null dims");
+  STTS_CHECK(dims->en_de_layers == kRvLevels && dims->kernel_h == 2 && dims->kernel_w == 2 && dims->n_gru == 1 && dims->n_mels == kRvMels,
+             "rmvpe: en_de_layers = %d, kernel_size = (%d, %d), n_gru = %d, n_mels = %d: only 5, (2, 2), 1 and 128 are built", dims->en_de_layers, dims->kernel_h,
+             dims->kernel_w, dims->n_gru, dims->n_mels);
+  d->n_blocks = dims->n_blocks;
+  d->inter_layers = dims->inter_layers;
+  d->c0 = dims->en_out_channels;
+  return 0;
+}
+
+int stts_rmvpe_finalize(stts_ctx* c, const stts_rmvpe_dims* dims) {
+  API_BEGIN
+  STTS_CHECK(c && dims, "null argument");
+  STTS_HIP(hipSetDevice(c->device));
+  c->ready &= ~STTS_W_RMVPE;
+  free_component_allocs(c, STTS_W_RMVPE);
+  RvDims d;
+  STTS_TRY(rmvpe_dims_from(dims, &d));
+  auto m = std::make_shared<RvW>();
+  PackScope scope(c, {PREC_F32, false, 32, STTS_W_RMVPE});  // fp32 on the f32 matrix cores whatever the precision (its packer reads only the tag)
+  STTS_TRY(finalize_rmvpe(c, d, m.get()));
+  c->rmvpe = m;
+  c->ready |= STTS_W_RMVPE;
+  STTS_HIP(hipDeviceSynchronize());
+  return 0;
+  API_END
+}
+
+static int rmvpe_check_offsets(int n_utt, const int32_t* off_host) {
+  STTS_CHECK(n_utt > 0 && off_host && off_host[0] == 0, "rmvpe: bad frame offsets");
+  for (int u = 0; u < n_utt; ++u) {
+    const long n = (long)off_host[u + 1] - off_host[u];
+    STTS_CHECK(n >= 17, "rmvpe: utterance %d has %ld mel frames; the reflect padding to a multiple of 32 frames needs at least 17", u, n);
+  }
+  return 0;
+}
+
+size_t stts_rmvpe_workspace_bytes(const stts_ctx* c, int n_utt, const int32_t* off_host) {
+  if (!c || !c->rmvpe || !(c->ready & STTS_W_RMVPE)) return 0;
+  if (rmvpe_check_offsets(n_utt, off_host) != 0) return 0;
+  return rmvpe_workspace_bytes(*static_cast<const RvW*>(c->rmvpe.get()), n_utt, off_host);
+}
+
+int64_t stts_rmvpe_tap_floats(const stts_rmvpe_dims* dims, int n_utt, const int32_t* off_host) {
+  RvDims d;
+  if (rmvpe_dims_from(dims, &d) != 0 || rmvpe_check_offsets(n_utt, off_host) != 0) return 0;
+  return (int64_t)rmvpe_tap_floats(d, rv_padded(n_utt, off_host));
+}
+
+static int rmvpe_entry(stts_ctx* c, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* mel, int ld, float thred, float* hidden_out,
+                       float* f0_out, float* taps, void* ws, size_t ws_bytes) {
+  STTS_CHECK(c && c->rmvpe && (c->ready & STTS_W_RMVPE), "the RMVPE weights are not finalized (stts_rmvpe_finalize)");
+  const RvW& M = *static_cast<const RvW*>(c->rmvpe.get());
+  STTS_CHECK(off_dev && mel && ws && (hidden_out || f0_out), "rmvpe: null argument");
+  STTS_TRY(rmvpe_check_offsets(n_utt, off_host));
+  STTS_CHECK(ld >= kRvMels, "mel rows: ld %d < 128 mel bins", ld);
+  STTS_CHECK(std::isfinite(thred), "rmvpe: thred must be finite");
+  STTS_HIP(hipSetDevice(c->device));
+  Arena a(ws, ws_bytes);
+  return rmvpe_forward(M, (hipStream_t)stream, n_utt, off_host, off_dev, mel, ld, thred, hidden_out, f0_out, taps, a);
+}
+
+int stts_rmvpe_forward(stts_ctx* c, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* mel_rows, int ld_mel, float thred,
+                       float* hidden_out, float* f0_out, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  return rmvpe_entry(c, stream, n_utt, off_host, off_dev, mel_rows, ld_mel, thred, hidden_out, f0_out, nullptr, ws, ws_bytes);
+  API_END
+}
+
+int stts_rmvpe_forward_taps(stts_ctx* c, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* mel_rows, int ld_mel, float thred,
+                            float* hidden_out, float* f0_out, float* taps, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  STTS_CHECK(taps, "rmvpe: null taps");
+  return rmvpe_entry(c, stream, n_utt, off_host, off_dev, mel_rows, ld_mel, thred, hidden_out, f0_out, taps, ws, ws_bytes);
+  API_END
+}
+
+int stts_rmvpe_mel(stts_ctx* c, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const int32_t* mel_off_host,
+                   const int32_t* mel_off_dev, const float* wave, const float* mel_basis, const int32_t* band, float* mel_out, int ld_mel, float* mel_lin) {
+  API_BEGIN
+  STTS_CHECK(c && c->rmvpe && (c->ready & STTS_W_RMVPE), "the RMVPE weights are not finalized (stts_rmvpe_finalize)");
+  const RvW& M = *static_cast<const RvW*>(c->rmvpe.get());
+  STTS_CHECK(n_utt > 0 && sample_off_host && sample_off_dev && mel_off_host && mel_off_dev && wave && mel_basis && band && mel_out, "rmvpe_mel: null argument");
+  STTS_CHECK(sample_off_host[0] == 0 && mel_off_host[0] == 0 && ld_mel >= kRvMels, "rmvpe_mel: bad offsets or ld_mel %d < 128", ld_mel);
+  int max_fr = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    const long n = (long)sample_off_host[u + 1] - sample_off_host[u];
+    STTS_CHECK(n > kRvNfft / 2, "rmvpe_mel: utterance %d has %ld samples; the reflect padding needs more than %d", u, n, kRvNfft / 2);
+    const int fr = mel_off_host[u + 1] - mel_off_host[u];
+    STTS_CHECK(fr == n / kRvHop + 1, "rmvpe_mel: utterance %d: %d mel rows for %ld samples (samples / 160 + 1 = %ld)", u, fr, n, n / kRvHop + 1);
+    max_fr = std::max(max_fr, fr);
+  }
+  STTS_HIP(hipSetDevice(c->device));
+  hipLaunchKernelGGL(rv_mel_kernel, dim3(ceil_div(max_fr, GeomFft<9>::kWaves), n_utt), dim3(64 * GeomFft<9>::kWaves), 0, (hipStream_t)stream, wave, sample_off_dev,
+                     mel_off_dev, M.hann, M.tw, mel_basis, band, mel_out, ld_mel, mel_lin);
+  STTS_HIP(hipGetLastError());
+  return 0;
+  API_END
+}
+
+int stts_rmvpe_decode(stts_ctx* c, void* stream, int64_t n_rows, const float* salience, int ld, float thred, float* f0_out) {
+  API_BEGIN
+  STTS_CHECK(c && n_rows > 0 && salience && f0_out && ld >= kRvClasses && std::isfinite(thred), "rmvpe_decode: bad argument");
+  STTS_HIP(hipSetDevice(c->device));
+  hipLaunchKernelGGL(rv_decode_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, salience, ld, (long)n_rows, thred, f0_out);
+  STTS_HIP(hipGetLastError());
+  return 0;
+  API_END
+}
+
+int stts_rmvpe_resample(stts_ctx* c, void* stream, int n_utt, const int32_t* off_in_dev, const int32_t* off_out_host, const int32_t* off_out_dev, const float* f0_in,
+                        float* f0_out) {
+  API_BEGIN
+  STTS_CHECK(c && n_utt > 0 && off_in_dev && off_out_host && off_out_dev && f0_in && f0_out, "rmvpe_resample: null argument");
+  int mx = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    STTS_CHECK(off_out_host[u + 1] > off_out_host[u], "rmvpe_resample: utterance %d has no output frames", u);
+    mx = std::max(mx, off_out_host[u + 1] - off_out_host[u]);
+  }
+  STTS_HIP(hipSetDevice(c->device));
+  hipLaunchKernelGGL(rv_resample_kernel, dim3(ceil_div(mx, 256), n_utt), dim3(256), 0, (hipStream_t)stream, f0_in, off_in_dev, off_out_dev, f0_out);
+  STTS_HIP(hipGetLastError());
+  return 0;
+  API_END
+}
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ HuBERT voice conversion (hubert.hip.h)
 extern "C" {

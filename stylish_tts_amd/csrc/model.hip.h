@@ -203,6 +203,7 @@ struct stts_ctx {
   std::shared_ptr<void> mel_style;  // stts::MelStyleModel (mel_style.hip.h)
   std::shared_ptr<void> cfm_pitch;  // stts::CfmPitchNetW (cfm_pitch.hip.h)
   std::shared_ptr<void> ssl;        // stts::SslW (ssl.hip.h)
+  std::shared_ptr<void> rmvpe;      // stts::RvW (rmvpe.hip.h)
 };
 
 namespace stts {

@@ -15,6 +15,8 @@ Reference classes mirrored (paths relative to /root/reference/src/stylish_tts/tr
   HubertPitchEnergyPredictor  models/pitch_energy_predictor.py:124-191
   MelStyleEncoder             models/mel_style_encoder.py:120-151
   CfmPitchPredictor           models/cfm/cfm_pitch_predictor.py:12-51 (+ norm_f0_zscore / denorm_f0_zscore, train/stage_type.py:783-829)
+  AdaptiveHubert              models/ssl.py:16-31
+  RmvpePitchExtractor         dataprep/rmvpe/inference.py:12-65 (E2E0 of model.py:49-86; MelSpectrogram of spec.py:7-71)
 
 Differences, all additive: forward() of the stochastic modules takes an optional ``noise`` dict with the three draws
 the reference takes from the global torch generator (``prior_noise`` [B,128,4T], ``src_noise`` [B,1,300T],
@@ -39,6 +41,7 @@ W_HUBERT, W_HUBERT_PE = 512, 1024  # hubert_speech_predictor.{phone_encoder, sty
 W_PE_MEL_STYLE, W_CFM_PITCH = 2048, 4096  # pe_mel_style_encoder.*; cfm_pitch_predictor.spk_emb.*
 W_CFM_PITCH_NET = 8192  # cfm_pitch_predictor.{asr_emb, blocks, out_proj}
 W_SSL = 16384  # hubert.model.* (AdaptiveHubert; finalized by stts_ssl_finalize)
+W_RMVPE = 32768  # rmvpe.* (RmvpePitchExtractor; finalized by stts_rmvpe_finalize)
 
 _ENGINES: Dict[int, HipModel] = {}
 
@@ -809,6 +812,197 @@ class AdaptiveHubert(HipModule):
         B, T = wave.shape[0], int(time_dim)
         rows = self.packed(wave, [T] * B, lengths)
         return rows[:, : self.hidden].reshape(B, T, self.hidden).permute(0, 2, 1).contiguous()
+
+
+class RmvpePitchExtractor(HipModule):
+    """The reference's RMVPE pitch extractor (train/dataprep/rmvpe/inference.py:12-65) on the engine: ``E2E0`` in eval mode, ``mel2hidden``'s
+    per-utterance reflect padding to a multiple of 32 frames, ``to_local_average_f0`` and the log-mel front end.  ``config``: E2E0's constructor
+    arguments (rmvpe.dims: n_blocks, inter_layers, en_out_channels; anything else the reference's extractor fixes raises ValueError).
+    load_state_dict takes E2E0's keys (``num_batches_tracked`` accepted and ignored).  ``mel_basis`` [128, 513] is a buffer the caller may set
+    (the reference takes it from its audio library); the default is rmvpe.default_mel_basis().  ``lengths`` / ``sample_lengths`` run ragged
+    batches in which every utterance gets what it gets alone.  Outputs past an utterance's length are 0."""
+
+    module_name = "rmvpe"
+    components = W_RMVPE
+    sr = 16000
+
+    def __init__(self, config=None, engine=None, cfg=None):
+        from . import rmvpe
+
+        self.dims = rmvpe.dims(config)
+        super().__init__(params.rmvpe_spec(self.dims), cfg or load_model_config(), engine)
+        self._basis_dev = None
+        self.mel_basis = torch.from_numpy(rmvpe.default_mel_basis())
+        self.thred = 0.03  # the voicing threshold of calls that do not name one (VoiceConverter.convert_audio)
+
+    @property
+    def mel_basis(self) -> torch.Tensor:
+        return self._mel_basis
+
+    @mel_basis.setter
+    def mel_basis(self, value):
+        from . import rmvpe
+
+        b = torch.as_tensor(value).detach().to("cpu", torch.float32).contiguous()
+        self._band = torch.from_numpy(rmvpe.basis_band(b.numpy()))  # ValueError for another shape
+        self._mel_basis = b
+        self._basis_dev = None
+
+    @classmethod
+    def from_safetensors(cls, path, config=None, engine=None):
+        """The reference's checkpoint format: one .safetensors file of E2E0's state_dict."""
+        from safetensors import safe_open
+
+        sd = {}
+        with safe_open(path, framework="pt", device="cpu") as f:
+            for k in f.keys():
+                sd[k] = f.get_tensor(k)
+        m = cls(config, engine)
+        m.load_state_dict(sd)
+        return m
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        sd = dict(state_dict)
+        for k in self._store:  # a BatchNorm's step counter plays no part in eval mode: absent or present, any value
+            if k.endswith(".num_batches_tracked"):
+                sd[k] = torch.zeros(())
+        return super().load_state_dict(sd, strict=strict, assign=assign)
+
+    def _load_into(self, eng: HipModel):
+        eng.load_state_dict(self.module_name, {k: v for k, v in self._store.items() if not k.endswith(".num_batches_tracked")})
+
+    def _bind(self):
+        eng = self._engine
+        owners = eng.__dict__.setdefault("_owners", {})
+        if self._dirty or owners.get(W_RMVPE) is not self:
+            self._load_into(eng)
+            eng.rmvpe_finalize(self.dims)
+            owners[W_RMVPE] = self
+            self._dirty = False
+
+    # ---- shapes
+    def _mel_lengths(self, mel, lengths):
+        from . import rmvpe
+
+        if mel.dim() != 3 or mel.shape[1] != rmvpe.N_MELS:
+            raise ValueError(f"RMVPE input must be a log-mel [B, {rmvpe.N_MELS}, T], got shape {tuple(mel.shape)}")
+        B, T = mel.shape[0], mel.shape[2]
+        L = [T] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).tolist()]
+        if len(L) != B or any(n > T for n in L):
+            raise ValueError(f"lengths {L} do not fit a batch of {B} x {T} frames")
+        for n in L:
+            rmvpe.padded_frames(n)  # ValueError below 17 frames, where the reference's reflect padding raises
+        return L
+
+    def _frames(self, frames, B):
+        if frames is None:
+            return None
+        Fr = [int(frames)] * B if isinstance(frames, int) else [int(v) for v in torch.as_tensor(frames).tolist()]
+        if len(Fr) != B or min(Fr) < 1:
+            raise ValueError(f"frames {Fr} must be one positive frame count per utterance")
+        return Fr
+
+    @staticmethod
+    def _unpack(rows, seg: Segments):
+        """packed [rows, ...] -> [B, max length, ...], zeros past every utterance's length"""
+        out = rows.new_zeros((seg.n, seg.max_len) + tuple(rows.shape[1:]))
+        for b in range(seg.n):
+            out[b, : seg.lengths[b]] = rows[seg.host[b] : seg.host[b + 1]]
+        return out
+
+    def _pack_mel(self, mel, L):
+        md = _f(mel, self.engine.device)
+        return torch.cat([md[b, :, : L[b]].t() for b in range(len(L))]).contiguous()
+
+    # ---- the reference's methods
+    def mel2hidden(self, mel, lengths=None):
+        """mel [B, 128, T] -> salience [B, T, 360]."""
+        L = self._mel_lengths(mel, lengths)
+        eng = self.engine
+        seg = Segments(L, eng.device)
+        h, _ = eng.rmvpe(seg, self._pack_mel(mel, L), f0=False)
+        return self._unpack(h, seg)
+
+    def decode(self, hidden, thred: float = 0.03, use_viterbi: bool = False):
+        """salience [B, T, 360] (or [T, 360]) -> f0 [B, T] in Hz, 0 on unvoiced frames."""
+        if use_viterbi:
+            raise NotImplementedError("RMVPE's Viterbi decoding is not built (its reference needs a sequence decoder whose parity is unpinned); use_viterbi=False is")
+        eng = self.engine
+        h = _f(hidden, eng.device)
+        if h.dim() not in (2, 3) or h.shape[-1] != 360:
+            raise ValueError(f"salience must be [B, T, 360], got shape {tuple(h.shape)}")
+        return eng.rmvpe_decode(h.reshape(-1, 360), thred).reshape(h.shape[:-1])
+
+    def packed(self, mel, lengths=None, frames=None, thred: float = 0.03, return_segments: bool = False):
+        """Packed f0 rows [sum frames] on the device (100 frames / s, or resampled to ``frames`` per utterance), as the engine's stages take curves."""
+        L = self._mel_lengths(mel, lengths)
+        Fr = self._frames(frames, len(L))
+        eng = self.engine
+        seg = Segments(L, eng.device)
+        _, f0 = eng.rmvpe(seg, self._pack_mel(mel, L), thred, hidden=False)
+        if Fr is not None:
+            seg_o = Segments(Fr, eng.device)
+            f0, seg = eng.rmvpe_resample(seg, f0, seg_o), seg_o
+        return (f0, seg) if return_segments else f0
+
+    def forward(self, mel, lengths=None, frames=None, thred: float = 0.03):
+        """mel [B, 128, T] -> f0 [B, T] (or [B, max frames] after the linear resampling to ``frames``)."""
+        f0, seg = self.packed(mel, lengths, frames, thred, return_segments=True)
+        return self._unpack(f0, seg)
+
+    def _wave_lengths(self, wave, sample_lengths, sample_rate):
+        from . import rmvpe
+
+        if int(sample_rate) != self.sr:
+            raise ValueError(f"RMVPE takes audio at {self.sr} Hz, got {sample_rate} (resample outside: the engine has no resampler)")
+        if wave.dim() != 2:
+            raise ValueError(f"RMVPE audio must be [B, samples], got shape {tuple(wave.shape)}")
+        B, S = wave.shape
+        L = [S] * B if sample_lengths is None else [int(v) for v in torch.as_tensor(sample_lengths).tolist()]
+        if len(L) != B or any(n > S for n in L):
+            raise ValueError(f"sample_lengths {L} do not fit a batch of {B} x {S} samples")
+        for n in L:
+            rmvpe.mel_frames(n)  # ValueError at 512 samples or fewer
+        return L
+
+    def mel_packed(self, wave, sample_lengths=None, sample_rate: int = 16000, linear: bool = False):
+        """wave [B, samples] at 16 kHz -> packed log-mel rows [sum frames, 128] and their Segments (frames = samples // 160 + 1)."""
+        L = self._wave_lengths(wave, sample_lengths, sample_rate)
+        eng = self.engine
+        if self._basis_dev is None or self._basis_dev[0].device != eng.device:
+            self._basis_dev = (self._mel_basis.to(eng.device), self._band.to(eng.device))
+        wd = _f(wave, eng.device)
+        flat = torch.cat([wd[b, : L[b]] for b in range(len(L))]).contiguous()
+        return eng.rmvpe_mel(Segments(L, eng.device), flat, self._basis_dev[0], self._basis_dev[1], linear=linear)
+
+    def mel(self, wave, sample_lengths=None, sample_rate: int = 16000):
+        """wave [B, samples] -> log-mel [B, 128, max frames] (MelSpectrogram.forward, keyshift 0, speed 1, center=True)."""
+        rows, seg = self.mel_packed(wave, sample_lengths, sample_rate)
+        return self._unpack(rows, seg).transpose(1, 2).contiguous()
+
+    def packed_from_audio(self, wave, sample_lengths=None, frames=None, thred: Optional[float] = None, sample_rate: int = 16000, return_segments: bool = False):
+        """Packed f0 rows [sum frames] on the device from audio [B, samples] at 16 kHz; thred None: ``self.thred``."""
+        from . import rmvpe
+
+        thred = self.thred if thred is None else thred
+
+        for n in self._wave_lengths(wave, sample_lengths, sample_rate):
+            rmvpe.padded_frames(rmvpe.mel_frames(n))  # ValueError below 17 frames
+        rows, seg = self.mel_packed(wave, sample_lengths, sample_rate)
+        Fr = self._frames(frames, seg.n)
+        eng = self.engine
+        _, f0 = eng.rmvpe(seg, rows, thred, hidden=False)
+        if Fr is not None:
+            seg_o = Segments(Fr, eng.device)
+            f0, seg = eng.rmvpe_resample(seg, f0, seg_o), seg_o
+        return (f0, seg) if return_segments else f0
+
+    def infer_from_audio(self, wave16k, sample_lengths=None, frames=None, thred: float = 0.03, sample_rate: int = 16000, use_viterbi: bool = False):
+        """wave [B, samples] at 16 kHz -> f0 [B, T] (T = samples // 160 + 1, or ``frames`` after the linear resampling)."""
+        if use_viterbi:
+            raise NotImplementedError("RMVPE's Viterbi decoding is not built; use_viterbi=False is")
+        f0, seg = self.packed_from_audio(wave16k, sample_lengths, frames, thred, sample_rate, return_segments=True)
+        return self._unpack(f0, seg)
 
 
 def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int] = None, hubert: bool = False, mel_style: bool = False,

@@ -478,6 +478,56 @@ def hubert_ssl_spec(arch=None, weight_norm: str = "parametrizations", p: str = "
     return s
 
 
+def _bn2d(p: str, c: int) -> Spec:
+    """BatchNorm2d's five state_dict entries; num_batches_tracked (a 0-dim counter) is accepted and ignored by the engine."""
+    return [(p + ".weight", (c,), "ln_g"), (p + ".bias", (c,), "ln_b"), (p + ".running_mean", (c,), "ln_b"), (p + ".running_var", (c,), "bn_var"),
+            (p + ".num_batches_tracked", (), "count")]
+
+
+def _conv_block_res(p: str, cin: int, cout: int) -> Spec:
+    """ConvBlockRes (rmvpe/deepunet.py:6-41).  Kinds: the first conv keeps the scale of its input, the second adds a small branch to the shortcut, and
+    a learned shortcut shrinks a little, so the residual stack stays O(1) over its 40-odd blocks (BatchNorm in eval mode does not renormalise)."""
+    s: Spec = [(p + ".conv.0.weight", (cout, cin, 3, 3), "w")] + _bn2d(p + ".conv.1", cout)
+    s += [(p + ".conv.3.weight", (cout, cout, 3, 3), "w_small")] + _bn2d(p + ".conv.4", cout)
+    if cin != cout:
+        s += [(p + ".shortcut.weight", (cout, cin, 1, 1), "w_sc"), (p + ".shortcut.bias", (cout,), "b")]
+    return s
+
+
+def rmvpe_spec(dims=None) -> Spec:
+    """E2E0.state_dict() (train/dataprep/rmvpe/model.py:49-86, deepunet.py:220-248, seq.py:4-16) in registration order.  ``dims``: rmvpe.dims()
+    fields (E2E0(4, 1, (2, 2)) when None)."""
+    from .rmvpe import GRU_HIDDEN, N_CLASS, N_MELS
+    from .rmvpe import dims as _dims
+
+    d = _dims(dims)
+    nb, c0 = d["n_blocks"], d["en_out_channels"]
+    s: Spec = _bn2d("unet.encoder.bn", 1)
+    cin, cout = 1, c0
+    for i in range(d["en_de_layers"]):
+        for b in range(nb):
+            s += _conv_block_res(f"unet.encoder.layers.{i}.conv.{b}", cin if b == 0 else cout, cout)
+        cin, cout = cout, cout * 2
+    for i in range(d["inter_layers"]):
+        for b in range(nb):
+            s += _conv_block_res(f"unet.intermediate.layers.{i}.conv.{b}", cin if (i == 0 and b == 0) else cout, cout)
+    dc = cout
+    for i in range(d["en_de_layers"]):
+        oc = dc // 2
+        q = f"unet.decoder.layers.{i}"
+        s += [(q + ".conv1.0.weight", (dc, oc, 3, 3), "w_up")] + _bn2d(q + ".conv1.1", oc)
+        for b in range(nb):
+            s += _conv_block_res(f"{q}.conv2.{b}", 2 * oc if b == 0 else oc, oc)
+        dc = oc
+    s += [("cnn.weight", (3, c0, 3, 3), "w_tiny"), ("cnn.bias", (3,), "b")]
+    g, inp = 3 * GRU_HIDDEN, 3 * N_MELS
+    for sfx in ("", "_reverse"):
+        s += [(f"fc.0.gru.weight_ih_l0{sfx}", (g, inp), "w"), (f"fc.0.gru.weight_hh_l0{sfx}", (g, GRU_HIDDEN), "w"), (f"fc.0.gru.bias_ih_l0{sfx}", (g,), "b"),
+              (f"fc.0.gru.bias_hh_l0{sfx}", (g,), "b")]
+    s += [("fc.1.weight", (N_CLASS, 2 * GRU_HIDDEN), "w_qk"), ("fc.1.bias", (N_CLASS,), "b")]
+    return s
+
+
 MEL_STYLE_MODULE_SPECS = {"pe_mel_style_encoder": pe_mel_style_encoder_spec, "cfm_pitch_predictor": cfm_pitch_predictor_module_spec}
 
 
@@ -580,6 +630,14 @@ def synth_tensor(name: str, shape: Tuple[int, ...], kind: str, seed: int = 0) ->
         v = 1.0 + 0.3 * u
     elif kind == "emb":
         v = u * np.sqrt(3.0) * (shape[1] ** -0.5)
+    elif kind == "w_sc":  # a learned 1 x 1 shortcut of a residual block
+        v = u * 0.8 * np.sqrt(3.0 / fan_in)
+    elif kind == "w_up":  # ConvTranspose2d [cin, cout, 3, 3] at stride 2: an output sees 9 / 4 taps of cin channels on average
+        v = u * np.sqrt(3.0 / (shape[0] * 2.25))
+    elif kind == "bn_var":  # a BatchNorm's running variance in [0.5, 1.5]
+        v = 1.0 + 0.5 * u
+    elif kind == "count":  # num_batches_tracked
+        v = np.zeros(n)
     elif kind == "rope_f":  # log-frequencies in [log pi, log 5 pi] (xut/axial_rope.py:110-116 initialises a linspace over that range)
         v = np.log(np.pi) + 0.5 * (u + 1.0) * np.log(5.0)
     elif kind == "time_freqs":  # the TimestepEmbedding buffer (xut/time_emb.py:14-22), formed in fp32 like torch does

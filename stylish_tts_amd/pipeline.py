@@ -225,7 +225,8 @@ class VoiceConverter:
 
     @torch.no_grad()
     def convert(self, features, lengths, spk_emb, pitch=None, energy=None, noise: Optional[Dict[str, torch.Tensor]] = None,
-                return_details: bool = False, ref_mel=None, ref_mel_lengths=None, f0_log2_stats=None, uv=None, _packed_feats=None):
+                return_details: bool = False, ref_mel=None, ref_mel_lengths=None, f0_log2_stats=None, uv=None, _packed_feats=None, _packed_pitch=None,
+                _packed_uv=None):
         """features [B, hubert_dim, T] (mel-frame rate, zero padded past lengths[b]), spk_emb [B, spk_dim]; optional pitch / energy
         [B, T] replace the predicted curves; noise: the packed draws of ``Synthesizer`` (prior_noise [4 sum T, 128], src_noise
         [4 sum T * hop / 4], init_phase [1]).  -> list of B float waveforms (hop_length samples per frame).
@@ -260,7 +261,7 @@ class VoiceConverter:
             Lm = [ref_mel.shape[2]] * len(L) if ref_mel_lengths is None else [int(v) for v in torch.as_tensor(ref_mel_lengths).tolist()]
             if len(Lm) != len(L) or min(Lm) < 1 or max(Lm) > ref_mel.shape[2]:
                 raise ValueError(f"ref_mel_lengths {Lm} do not fit ref_mel of shape {tuple(ref_mel.shape)}")
-        elif (pitch is None) != (energy is None):
+        elif _packed_pitch is None and (pitch is None) != (energy is None):
             raise ValueError("give both pitch and energy, or neither")
         st = Segments(L, dev)
         st4 = st.scaled(4)
@@ -272,8 +273,11 @@ class VoiceConverter:
             md = _f(ref_mel, dev)
             mel_rows = torch.cat([md[b, :, : Lm[b]].t() for b in range(len(L))]).contiguous()
             spk = eng.mel_style(W_CFM_PITCH, Segments(Lm, dev), mel_rows, 256)
-            uv_rows = _pack_curve(uv, L, dev) if uv is not None else None
+            uv_rows = _pack_curve(uv, L, dev) if uv is not None else _packed_uv
             _, f0 = eng.cfm_pitch(st, feats, spk, f0_log2_stats=f0_log2_stats, uv=uv_rows)
+            en = eng.hubert_pitch_energy(st, feats, pe_style)[1] if energy is None else _pack_curve(energy, L, dev)
+        elif _packed_pitch is not None:  # convert_audio's extracted curve (packed rows); energy predicted unless given
+            f0 = _packed_pitch
             en = eng.hubert_pitch_energy(st, feats, pe_style)[1] if energy is None else _pack_curve(energy, L, dev)
         elif pitch is None:
             f0, en = eng.hubert_pitch_energy(st, feats, pe_style)
@@ -293,11 +297,14 @@ class VoiceConverter:
         return waves
 
     @torch.no_grad()
-    def convert_audio(self, wave, sample_lengths, frames, spk_emb, ssl=None, **kw):
+    def convert_audio(self, wave, sample_lengths, frames, spk_emb, ssl=None, pitch_extractor=None, **kw):
         """Voice conversion from audio: wave [B, samples] at hubert.sr (zero padded past sample_lengths[b]), frames [B] = the mel-frame count
         of every utterance (the reference's time_dim; an argument, so the host reads nothing back) -> HuBERT features on the engine
         (``ssl``: the modules.AdaptiveHubert bound to this engine, or the one among this converter's modules) written as the packed rows
-        convert() consumes, then convert() with the same keywords (pitch, energy, noise, ref_mel, ...)."""
+        convert() consumes, then convert() with the same keywords (pitch, energy, noise, ref_mel, ...).
+        pitch_extractor (a modules.RmvpePitchExtractor; the audio must be at its 16 kHz): the source's own F0 is extracted on the engine and
+        resampled to ``frames``.  Without ref_mel it becomes the pitch (energy from HubertPitchEnergyPredictor unless given); with ref_mel it
+        gives the voicing flags uv = (f0 == 0), formed on the device, unless uv is given.  The host reads nothing back."""
         from .modules import AdaptiveHubert
 
         if ssl is None:
@@ -309,6 +316,18 @@ class VoiceConverter:
         T = [int(v) for v in torch.as_tensor(frames).tolist()]
         ssl._engine = ssl._engine or self.eng
         feats = ssl.packed(wave, T, sample_lengths)
+        if pitch_extractor is not None:
+            if kw.get("pitch") is not None:
+                raise ValueError("give pitch_extractor (F0 from the source audio) or pitch, not both")
+            if pitch_extractor.sr != ssl.sr:
+                raise ValueError(f"the pitch extractor takes audio at {pitch_extractor.sr} Hz, the content encoder at {ssl.sr} Hz")
+            pitch_extractor._engine = pitch_extractor._engine or self.eng
+            f0 = pitch_extractor.packed_from_audio(wave, sample_lengths, T)
+            if kw.get("ref_mel") is not None:
+                if kw.get("uv") is None:
+                    kw["_packed_uv"] = (f0 == 0).to(torch.float32)
+            else:
+                kw["_packed_pitch"] = f0
         return self.convert(None, T, spk_emb, _packed_feats=feats, **kw)
 
     def convert_int16(self, features, lengths, spk_emb, pitch=None, energy=None, noise=None, out_prefix: Optional[str] = None):

@@ -104,6 +104,7 @@ class HipModel:
         self._mws: Dict[int, torch.Tensor] = {}
         self._cpws: Dict[int, torch.Tensor] = {}
         self._sslws: Dict[int, torch.Tensor] = {}
+        self._rvws: Dict[int, torch.Tensor] = {}
         self._ws_lock = threading.Lock()
 
     def close(self):
@@ -487,3 +488,65 @@ class HipModel:
                                                   _ptr(t["layers"]), _ptr(t["hidden"]), _ptr(ws), ws.numel()))
         t["frames"] = fr
         return feats, t
+
+    # ------------------------------------------------------------------ RMVPE pitch extractor (packed log-mel frames at 100 frames / s)
+    def rmvpe_finalize(self, dims) -> None:
+        """Pack the weights loaded under "rmvpe." for E2E0's constructor arguments ``dims`` (rmvpe.dims); include/stylish_hip.h, stts_rmvpe_finalize."""
+        from . import rmvpe
+
+        self._rv_dims_d = dict(dims)
+        self._rv_dims = rmvpe.dims_struct(dims)
+        _lib.check(self.lib.stts_rmvpe_finalize(self.ctx, C.byref(self._rv_dims)))
+
+    def rmvpe(self, seg: Segments, mel_rows: torch.Tensor, thred: float = 0.03, hidden: bool = True, f0: bool = True, taps: bool = False):
+        """mel_rows [rows_T, ld >= 128] packed time-major log-mel frames (utterance offsets seg, at least 17 frames each) -> (hidden [rows_T, 360]
+        or None, f0 [rows_T] in Hz or None); taps=True appends the flat tap buffer (include/stylish_hip.h, stts_rmvpe_forward_taps).  Nothing is
+        read back by the host."""
+        if getattr(self, "_rv_dims", None) is None:
+            _lib.check(self.lib.stts_rmvpe_forward(self.ctx, _stream(), 0, None, None, None, 0, 0.0, None, None, None, 0))  # not finalized: the library's message
+        if mel_rows.dim() != 2 or mel_rows.shape[0] != seg.rows:
+            raise ValueError(f"packed mel of shape {tuple(mel_rows.shape)}, the offsets describe {seg.rows} frames")
+        need = int(self.lib.stts_rmvpe_workspace_bytes(self.ctx, seg.n, seg.host_ptr)) or 256  # 0: too short an utterance - the entry point names it
+        ws = self._grow(self._rvws, need)
+        mel_rows = mel_rows.to(self.device, torch.float32).contiguous()
+        h = self._f32(seg.rows, 360) if hidden else None
+        f = self._f32(seg.rows) if f0 else None
+        args = (self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(mel_rows), mel_rows.shape[1], float(thred), _ptr(h), _ptr(f))
+        if not taps:
+            _lib.check(self.lib.stts_rmvpe_forward(*args, _ptr(ws), ws.numel()))
+            return h, f
+        t = self._f32(max(1, int(self.lib.stts_rmvpe_tap_floats(C.byref(self._rv_dims), seg.n, seg.host_ptr))))
+        _lib.check(self.lib.stts_rmvpe_forward_taps(*args, _ptr(t), _ptr(ws), ws.numel()))
+        return h, f, t
+
+    def rmvpe_mel(self, seg_s: Segments, wave: torch.Tensor, basis: torch.Tensor, band: torch.Tensor, linear: bool = False):
+        """wave [sum samples] packed mono audio at 16 kHz -> (log-mel rows [sum frames, 128], their Segments); linear=True also returns the mel
+        before the clamp and the log.  basis [128, 513] float32 and band [128, 2] int32 on the device (include/stylish_hip.h, stts_rmvpe_mel)."""
+        from . import rmvpe
+
+        seg_m = Segments([rmvpe.mel_frames(n) for n in seg_s.lengths], self.device)
+        wave = wave.to(self.device, torch.float32).contiguous()
+        if wave.dim() != 1 or wave.numel() != seg_s.rows:
+            raise ValueError(f"packed waveform of {wave.numel()} samples, the offsets describe {seg_s.rows}")
+        out = self._f32(seg_m.rows, 128)
+        lin = self._f32(seg_m.rows, 128) if linear else None
+        _lib.check(self.lib.stts_rmvpe_mel(self.ctx, _stream(), seg_s.n, seg_s.host_ptr, _ptr(seg_s.dev), seg_m.host_ptr, _ptr(seg_m.dev), _ptr(wave), _ptr(basis),
+                                           _ptr(band), _ptr(out), 128, _ptr(lin)))
+        return (out, seg_m, lin) if linear else (out, seg_m)
+
+    def rmvpe_decode(self, salience: torch.Tensor, thred: float = 0.03) -> torch.Tensor:
+        """salience [rows, 360] -> f0 [rows] in Hz (to_local_average_f0; include/stylish_hip.h, stts_rmvpe_decode)."""
+        s = salience.to(self.device, torch.float32).contiguous()
+        if s.dim() != 2 or s.shape[1] != 360 or s.shape[0] < 1:
+            raise ValueError(f"salience must be [rows, 360], got shape {tuple(s.shape)}")
+        out = self._f32(s.shape[0])
+        _lib.check(self.lib.stts_rmvpe_decode(self.ctx, _stream(), s.shape[0], _ptr(s), 360, float(thred), _ptr(out)))
+        return out
+
+    def rmvpe_resample(self, seg_in: Segments, f0: torch.Tensor, seg_out: Segments) -> torch.Tensor:
+        """Packed curves at seg_in's frames -> packed curves at seg_out's frames, linear with align_corners=True, on the device."""
+        if seg_in.n != seg_out.n or f0.numel() != seg_in.rows:
+            raise ValueError(f"{f0.numel()} values for {seg_in.rows} frames in {seg_in.n} utterances, {seg_out.n} output utterances")
+        out = self._f32(seg_out.rows)
+        _lib.check(self.lib.stts_rmvpe_resample(self.ctx, _stream(), seg_in.n, _ptr(seg_in.dev), seg_out.host_ptr, _ptr(seg_out.dev), _ptr(f0.contiguous()), _ptr(out)))
+        return out
