@@ -70,7 +70,8 @@ enum {
   STTS_W_CFM_PITCH = 4096,   /* cfm_pitch_predictor.spk_emb.* (not part of STTS_W_ALL)     models/cfm/cfm_pitch_predictor.py:25-27 */
   STTS_W_CFM_PITCH_NET = 8192, /* cfm_pitch_predictor.{asr_emb, blocks, out_proj} (in_proj.* is accepted and ignored; not part of STTS_W_ALL) */
   STTS_W_SSL = 16384,        /* hubert.model.* = AdaptiveHubert (finalized by stts_ssl_finalize, not part of STTS_W_ALL)      train/models/ssl.py:16-31 */
-  STTS_W_RMVPE = 32768       /* rmvpe.* = the RMVPE pitch extractor E2E0 (finalized by stts_rmvpe_finalize, not part of STTS_W_ALL) train/dataprep/rmvpe/model.py:49-86 */
+  STTS_W_RMVPE = 32768,      /* rmvpe.* = the RMVPE pitch extractor E2E0 (finalized by stts_rmvpe_finalize, not part of STTS_W_ALL) train/dataprep/rmvpe/model.py:49-86 */
+  STTS_W_ALIGNER = 65536     /* text_aligner.* = the TDNN CTC aligner (finalized by stts_aligner_finalize, not part of STTS_W_ALL)           train/models/text_aligner.py */
 };
 int stts_finalize_weights(stts_ctx* ctx, int which);
 /* Operand precision of the FRAME-RATE Conv1d / Linear contractions (call before the first stts_finalize_weights).
@@ -311,6 +312,42 @@ int stts_rmvpe_decode(stts_ctx* ctx, void* stream, int64_t n_rows, const float* 
 /* F.interpolate(mode="linear", align_corners=True) of every utterance's curve from its frames (off_in) to the frames of off_out, on the device */
 int stts_rmvpe_resample(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_in_dev, const int32_t* off_out_host, const int32_t* off_out_dev,
                         const float* f0_in, float* f0_out);
+
+/* ---- Text aligner and CTC forced alignment (train/models/text_aligner.py: tdnn_blstm_ctc_model, CTCModel.forward in eval mode;
+ * train/dataprep/align_text.py:159-210: torch_align), component STTS_W_ALIGNER with the keys "text_aligner.*".  Always fp32, whatever
+ * stts_set_precision chose.  The layer spec: n_tdnn x ("tdnn", tdnn_kernel[i], stride 1, dilation 1) - Conv1d with "same" zero padding, ReLU, then
+ * BatchNorm1d(affine=False) in eval mode - followed by one ("ffn", ffn_layers) with its skip add, and encoder_output_layer hidden -> classes
+ * (classes = tokens + 1).  A "blstm" entry cannot be built in the reference and has no form here. */
+typedef struct stts_aligner_dims {
+  int32_t n_mels, hidden, classes; /* 80, 640, 179 for tdnn_blstm_ctc_model_base(80, 178) */
+  int32_t n_tdnn, ffn_layers;      /* 3, 5 */
+  int32_t tdnn_kernel[4];          /* 5, 3, 3 (odd, at most 7) */
+} stts_aligner_dims;
+int stts_aligner_finalize(stts_ctx* ctx, const stts_aligner_dims* dims);
+size_t stts_aligner_workspace_bytes(const stts_ctx* ctx, int n_utt, const int32_t* off_host);
+/* mel_rows [rows, ld_mel >= n_mels]: the normalised log-mel as packed time-major rows with off[n_utt + 1] row offsets (host and device copies of
+ * the SAME offsets) -> log_probs [rows, ld_out >= classes] = log_softmax of the output layer.  A segment's convolutions see zeros beyond its own
+ * rows (the reference's length mask before every TDNN layer), and an utterance's rows are the same bit for bit alone and in any batch. */
+int stts_aligner_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* mel_rows, int ld_mel,
+                         float* log_probs, int ld_out, void* ws, size_t ws_bytes);
+/* The same, also writing taps (stts_aligner_tap_floats floats): the output of every TDNN layer after its BatchNorm [rows, hidden] each, the Ffn
+ * output [rows, hidden], the logits [rows, classes], one after the other. */
+int stts_aligner_forward_taps(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* mel_rows, int ld_mel,
+                              float* log_probs, int ld_out, float* taps, void* ws, size_t ws_bytes);
+int64_t stts_aligner_tap_floats(const stts_aligner_dims* dims, int n_utt, const int32_t* off_host);
+/* CTC forced alignment (what the reference takes from its audio library, one utterance at a time on the CPU) and torch_align's post-processing,
+ * one workgroup per utterance, no weights.  log_probs [sum T, ld >= classes] with frame offsets t_off, targets [sum P] int32 with token offsets
+ * p_off (1 <= P <= 510 per utterance), blank the blank id.  Viterbi over the 2 P + 1 states (blank, token, blank, ..): stay, +1, and +2 only into a
+ * token state whose token differs from the token two states back; start in state 0 or 1, end in state 2 P or 2 P - 1.  Ties: the smaller jump
+ * wins; at the end the final blank wins.  Outputs: path [sum T] the label of every frame, scores [sum T] = log_probs[t][path[t]], durations
+ * [sum P] = frames of token p plus the blank frames that follow it (blank frames in front of the first token count to token 0: the reference's loop
+ * trips its own assert on such a path), left / right [sum P]: torch_align's boundary probabilities, 0 in the last entry.  path_given != 0: path is
+ * an INPUT and only the post-processing runs (no workspace needed).  A (T, targets) pair with fewer frames than tokens plus adjacent equal pairs
+ * has no valid path: the outputs are then meaningless, every access still in bounds (the Python shim refuses such input). */
+size_t stts_ctc_align_workspace_bytes(int n_utt, const int32_t* t_off_host, const int32_t* p_off_host);
+int stts_ctc_align(void* stream, int n_utt, const int32_t* t_off_host, const int32_t* t_off_dev, const int32_t* p_off_host, const int32_t* p_off_dev,
+                   const float* log_probs, int ld, int classes, int blank, const int32_t* targets, int path_given, int32_t* path, float* scores,
+                   int32_t* durations, float* left, float* right, void* ws, size_t ws_bytes);
 
 /* ---- HuBERT voice conversion (the reference's hubert_acoustic models, train/stage_type.py:907-1015).  Inputs are HuBERT features at the
  * mel-frame rate as packed time-major rows feats [rows_T, ld_feats] (ld_feats a multiple of 4 covering hubert.hidden_dim padded to 32, pad

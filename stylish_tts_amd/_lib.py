@@ -103,6 +103,13 @@ SIGNATURES = {
     "stts_rmvpe_mel": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "stts_rmvpe_decode": (_I, [_P, _P, _I64, _P, _I, C.c_float, _P]),
     "stts_rmvpe_resample": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
+    "stts_aligner_finalize": (_I, [_P, _P]),
+    "stts_aligner_workspace_bytes": (_SZ, [_P, _I, _P]),
+    "stts_aligner_forward": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _SZ]),
+    "stts_aligner_forward_taps": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _SZ]),
+    "stts_aligner_tap_floats": (_I64, [_P, _I, _P]),
+    "stts_ctc_align_workspace_bytes": (_SZ, [_I, _P, _P]),
+    "stts_ctc_align": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
     "stts_cfm_finalize": (_I, [_P, _P]),
     "stts_cfm_workspace_bytes": (_SZ, [_P, _I64, _I]),
     "stts_cfm_estimator": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _SZ]),

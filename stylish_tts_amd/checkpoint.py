@@ -24,6 +24,8 @@ MODEL_ORDER = (
     "hubert_speech_predictor", "hubert_pitch_energy_predictor",
 )
 INFERENCE_MODULES = ("speech_predictor", "duration_predictor", "pitch_energy_predictor", "pe_text_encoder", "pe_text_style_encoder")
+# the alignment model (modules.TextAligner, build_inference_modules(aligner=True)): model index 0; pass INFERENCE_MODULES + ALIGNER_MODULES to the readers
+ALIGNER_MODULES = ("text_aligner",)
 
 
 def _indexed(stem: str, ext: str, i: int) -> str:

@@ -7,6 +7,7 @@
 #include "cfm_pitch.hip.h"
 #include "ssl.hip.h"
 #include "rmvpe.hip.h"
+#include "aligner.hip.h"
 
 using namespace stts;
 
@@ -657,6 +658,117 @@ int stts_ssl_forward_taps(stts_ctx* c, void* stream, int n_utt, const int32_t* s
   return ssl_entry(c, stream, n_utt, sample_off_host, sample_off_dev, wave, off_T_host, off_T_dev, feats, ld_feats, &t, ws, ws_bytes);
   API_END
 }
+
+// ------------------------------------------------------------------------------------------------ text aligner + CTC forced alignment (aligner.hip.h)
+extern "C" {
+
+static int aligner_dims_from(const stts_aligner_dims* dims, AlDims* d) {
+  STTS_CHECK(dims, "aligner: null dims");
+  STTS_CHECK(dims->n_tdnn >= 1 && dims->n_tdnn <= kAlMaxTdnn, "aligner: %d tdnn layers outside [1, %d]", dims->n_tdnn, kAlMaxTdnn);
+  d->n_mels = dims->n_mels;
+  d->hidden = dims->hidden;
+  d->classes = dims->classes;
+  d->n_tdnn = dims->n_tdnn;
+  d->ffn_layers = dims->ffn_layers;
+  for (int i = 0; i < dims->n_tdnn; ++i) d->tdnn_k[i] = dims->tdnn_kernel[i];
+  return 0;
+}
+
+int stts_aligner_finalize(stts_ctx* c, const stts_aligner_dims* dims) {
+  API_BEGIN
+  STTS_CHECK(c && dims, "null argument");
+  STTS_HIP(hipSetDevice(c->device));
+  c->ready &= ~STTS_W_ALIGNER;
+  free_component_allocs(c, STTS_W_ALIGNER);
+  AlDims d;
+  STTS_TRY(aligner_dims_from(dims, &d));
+  auto m = std::make_shared<AlW>();
+  // fp32 whatever the precision; the contractions in the split-fp32 form unless the engine is STTS_PREC_F32_NATIVE (aligner.hip.h)
+  PackScope scope(c, {PREC_F32, true, 32, STTS_W_ALIGNER});
+  STTS_TRY(finalize_aligner(c, d, m.get()));
+  c->aligner = m;
+  c->ready |= STTS_W_ALIGNER;
+  STTS_HIP(hipDeviceSynchronize());
+  return 0;
+  API_END
+}
+
+static int aligner_check_offsets(int n_utt, const int32_t* off_host) {
+  STTS_CHECK(n_utt > 0 && off_host && off_host[0] == 0, "aligner: bad frame offsets");
+  for (int u = 0; u < n_utt; ++u) STTS_CHECK(off_host[u + 1] > off_host[u], "aligner: utterance %d has no mel frames", u);
+  STTS_CHECK(off_host[n_utt] <= kAlMaxRows, "aligner: %d rows in one call, at most %ld", off_host[n_utt], kAlMaxRows);
+  return 0;
+}
+
+size_t stts_aligner_workspace_bytes(const stts_ctx* c, int n_utt, const int32_t* off_host) {
+  if (!c || !c->aligner || !(c->ready & STTS_W_ALIGNER)) return 0;
+  if (aligner_check_offsets(n_utt, off_host) != 0) return 0;
+  return aligner_workspace_bytes(static_cast<const AlW*>(c->aligner.get())->d, n_utt, off_host[n_utt]);
+}
+
+int64_t stts_aligner_tap_floats(const stts_aligner_dims* dims, int n_utt, const int32_t* off_host) {
+  AlDims d;
+  if (aligner_dims_from(dims, &d) != 0 || aligner_check_offsets(n_utt, off_host) != 0) return 0;
+  return (int64_t)aligner_tap_floats(d, off_host[n_utt]);
+}
+
+static int aligner_entry(stts_ctx* c, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* mel, int ld_mel, float* log_probs,
+                         int ld_out, float* taps, void* ws, size_t ws_bytes) {
+  STTS_CHECK(c && c->aligner && (c->ready & STTS_W_ALIGNER), "the text aligner's weights are not finalized (stts_aligner_finalize)");
+  const AlW& M = *static_cast<const AlW*>(c->aligner.get());
+  STTS_CHECK(off_dev && mel && log_probs && ws, "aligner: null argument");
+  STTS_TRY(aligner_check_offsets(n_utt, off_host));
+  STTS_CHECK(ld_mel >= M.d.n_mels && ld_out >= M.d.classes, "aligner: ld_mel %d < %d mel bins or ld_out %d < %d classes", ld_mel, M.d.n_mels, ld_out, M.d.classes);
+  STTS_HIP(hipSetDevice(c->device));
+  Seg s{n_utt, off_host, off_dev};
+  Arena a(ws, ws_bytes);
+  return aligner_forward(M, (hipStream_t)stream, s, mel, ld_mel, log_probs, ld_out, taps, a);
+}
+
+int stts_aligner_forward(stts_ctx* c, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* mel_rows, int ld_mel, float* log_probs,
+                         int ld_out, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  return aligner_entry(c, stream, n_utt, off_host, off_dev, mel_rows, ld_mel, log_probs, ld_out, nullptr, ws, ws_bytes);
+  API_END
+}
+
+int stts_aligner_forward_taps(stts_ctx* c, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* mel_rows, int ld_mel,
+                              float* log_probs, int ld_out, float* taps, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  STTS_CHECK(taps, "aligner: null taps");
+  return aligner_entry(c, stream, n_utt, off_host, off_dev, mel_rows, ld_mel, log_probs, ld_out, taps, ws, ws_bytes);
+  API_END
+}
+
+static int ctc_check_offsets(int n_utt, const int32_t* t_off_host, const int32_t* p_off_host) {
+  STTS_CHECK(n_utt > 0 && t_off_host && p_off_host && t_off_host[0] == 0 && p_off_host[0] == 0, "ctc_align: bad offsets");
+  for (int u = 0; u < n_utt; ++u) {
+    const long T = (long)t_off_host[u + 1] - t_off_host[u], P = (long)p_off_host[u + 1] - p_off_host[u];
+    STTS_CHECK(T >= 1, "ctc_align: utterance %d has no frames", u);
+    STTS_CHECK(P >= 1 && P <= kCtcMaxTokens, "ctc_align: utterance %d has %ld tokens, outside [1, %d]", u, P, kCtcMaxTokens);
+  }
+  return 0;
+}
+
+size_t stts_ctc_align_workspace_bytes(int n_utt, const int32_t* t_off_host, const int32_t* p_off_host) {
+  if (ctc_check_offsets(n_utt, t_off_host, p_off_host) != 0) return 0;
+  return ctc_workspace_bytes(n_utt, t_off_host, p_off_host);
+}
+
+int stts_ctc_align(void* stream, int n_utt, const int32_t* t_off_host, const int32_t* t_off_dev, const int32_t* p_off_host, const int32_t* p_off_dev,
+                   const float* log_probs, int ld, int classes, int blank, const int32_t* targets, int path_given, int32_t* path, float* scores, int32_t* durations,
+                   float* left, float* right, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  STTS_CHECK(t_off_dev && p_off_dev && log_probs && targets && path && scores && durations && left && right, "ctc_align: null argument");
+  STTS_TRY(ctc_check_offsets(n_utt, t_off_host, p_off_host));
+  STTS_CHECK(classes >= 2 && ld >= classes && blank >= 0 && blank < classes, "ctc_align: %d classes in rows of %d, blank %d", classes, ld, blank);
+  STTS_CHECK(path_given || (ws && ws_bytes >= ctc_workspace_bytes(n_utt, t_off_host, p_off_host)), "ctc_align: workspace too small (stts_ctc_align_workspace_bytes)");
+  return ctc_align((hipStream_t)stream, n_utt, t_off_dev, p_off_dev, log_probs, ld, classes, blank, targets, path_given, path, scores, durations, left, right,
+                   (unsigned char*)ws);
+  API_END
+}
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ RMVPE pitch extractor (rmvpe.hip.h)
 extern "C" {

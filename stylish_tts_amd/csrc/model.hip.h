@@ -204,6 +204,7 @@ struct stts_ctx {
   std::shared_ptr<void> cfm_pitch;  // stts::CfmPitchNetW (cfm_pitch.hip.h)
   std::shared_ptr<void> ssl;        // stts::SslW (ssl.hip.h)
   std::shared_ptr<void> rmvpe;      // stts::RvW (rmvpe.hip.h)
+  std::shared_ptr<void> aligner;    // stts::AlW (aligner.hip.h)
 };
 
 namespace stts {

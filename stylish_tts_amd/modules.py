@@ -17,6 +17,7 @@ Reference classes mirrored (paths relative to /root/reference/src/stylish_tts/tr
   CfmPitchPredictor           models/cfm/cfm_pitch_predictor.py:12-51 (+ norm_f0_zscore / denorm_f0_zscore, train/stage_type.py:783-829)
   AdaptiveHubert              models/ssl.py:16-31
   RmvpePitchExtractor         dataprep/rmvpe/inference.py:12-65 (E2E0 of model.py:49-86; MelSpectrogram of spec.py:7-71)
+  TextAligner                 models/text_aligner.py:16-127 (tdnn_blstm_ctc_model / CTCModel) + dataprep/align_text.py:159-210 (torch_align)
 
 Differences, all additive: forward() of the stochastic modules takes an optional ``noise`` dict with the three draws
 the reference takes from the global torch generator (``prior_noise`` [B,128,4T], ``src_noise`` [B,1,300T],
@@ -42,6 +43,7 @@ W_PE_MEL_STYLE, W_CFM_PITCH = 2048, 4096  # pe_mel_style_encoder.*; cfm_pitch_pr
 W_CFM_PITCH_NET = 8192  # cfm_pitch_predictor.{asr_emb, blocks, out_proj}
 W_SSL = 16384  # hubert.model.* (AdaptiveHubert; finalized by stts_ssl_finalize)
 W_RMVPE = 32768  # rmvpe.* (RmvpePitchExtractor; finalized by stts_rmvpe_finalize)
+W_ALIGNER = 65536  # text_aligner.* (TextAligner; finalized by stts_aligner_finalize)
 
 _ENGINES: Dict[int, HipModel] = {}
 
@@ -1005,12 +1007,117 @@ class RmvpePitchExtractor(HipModule):
         return self._unpack(f0, seg)
 
 
+class TextAligner(HipModule):
+    """The reference's text aligner (train/models/text_aligner.py: ``tdnn_blstm_ctc_model``, ``CTCModel.forward`` in eval mode) and the forced
+    alignment of train/dataprep/align_text.py (``torch_align``) on the engine.  Constructor: ``tdnn_blstm_ctc_model``'s arguments, with
+    ``tdnn_blstm_ctc_model_base``'s spec as the default (``drop_out`` is the identity in eval mode); a spec the engine has no form for - a
+    'blstm' entry, which the reference cannot build either - raises ValueError.  load_state_dict takes CTCModel's keys (``num_batches_tracked``
+    accepted and ignored).  Always fp32.  Ragged batches: every utterance gets what it gets alone, bit for bit."""
+
+    module_name = "text_aligner"
+    components = W_ALIGNER
+
+    def __init__(self, n_mels: int = 80, num_symbols: int = 178, hidden_dim: int = 640, drop_out: float = 0.1, tdnn_blstm_spec=None, engine=None, cfg=None):
+        from . import aligner
+
+        self.dims = aligner.dims(n_mels, num_symbols, hidden_dim, aligner.BASE_SPEC if tdnn_blstm_spec is None else tdnn_blstm_spec)
+        self.n_mels, self.num_symbols, self.blank = self.dims["n_mels"], self.dims["num_symbols"], self.dims["num_symbols"]
+        super().__init__(params.text_aligner_spec(self.dims), cfg or load_model_config(), engine)
+
+    @classmethod
+    def from_safetensors(cls, path, n_mels: int = 80, num_symbols: int = 178, engine=None):
+        """The reference's alignment model file (dataset.alignment_model_path): one .safetensors file of CTCModel's state_dict."""
+        from safetensors import safe_open
+
+        sd = {}
+        with safe_open(path, framework="pt", device="cpu") as f:
+            for k in f.keys():
+                sd[k] = f.get_tensor(k)
+        m = cls(n_mels, num_symbols, engine=engine)
+        m.load_state_dict(sd)
+        return m
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        sd = dict(state_dict)
+        for k in self._store:  # a BatchNorm's step counter plays no part in eval mode: absent or present, any value
+            if k.endswith(".num_batches_tracked"):
+                sd[k] = torch.zeros(())
+        return super().load_state_dict(sd, strict=strict, assign=assign)
+
+    def _load_into(self, eng: HipModel):
+        eng.load_state_dict(self.module_name, {k: v for k, v in self._store.items() if not k.endswith(".num_batches_tracked")})
+
+    def _bind(self):
+        eng = self._engine
+        owners = eng.__dict__.setdefault("_owners", {})
+        if self._dirty or owners.get(W_ALIGNER) is not self:
+            self._load_into(eng)
+            eng.aligner_finalize(self.dims)
+            owners[W_ALIGNER] = self
+            self._dirty = False
+
+    def _lengths(self, sources, source_lengths):
+        if sources.dim() != 3 or sources.shape[2] != self.n_mels:
+            raise ValueError(f"aligner input must be [B, T, {self.n_mels}], got shape {tuple(sources.shape)}")
+        B, T = sources.shape[0], sources.shape[1]
+        L = [T] * B if source_lengths is None else [int(v) for v in torch.as_tensor(source_lengths).tolist()]
+        if len(L) != B or any(n > T or n < 1 for n in L):
+            raise ValueError(f"source_lengths {L} do not fit a batch of {B} x {T} frames")
+        return L
+
+    def packed(self, sources, source_lengths=None, taps: bool = False):
+        """sources [B, T, n_mels] -> (packed log-prob rows [sum T, classes] on the device, their Segments[, taps])."""
+        L = self._lengths(sources, source_lengths)
+        eng = self.engine
+        seg = Segments(L, eng.device)
+        xd = _f(sources, eng.device)
+        rows = torch.cat([xd[b, : L[b]] for b in range(len(L))]).contiguous()
+        out = eng.text_aligner(seg, rows, taps=taps)
+        return (out[0], seg, out[1]) if taps else (out, seg)
+
+    def forward(self, sources, source_lengths):
+        """CTCModel.forward: (ctc_log_prob [T, B, V + 1], None).  Rows past an utterance's length are 0 (the reference computes values from masked
+        frames there that nothing reads)."""
+        lp, seg = self.packed(sources, source_lengths)
+        T = sources.shape[1]
+        out = lp.new_zeros((T, seg.n, lp.shape[1]))
+        for b in range(seg.n):
+            out[: seg.lengths[b], b] = lp[seg.host[b] : seg.host[b + 1]]
+        return out, None
+
+    def align(self, mels, mel_lengths, texts, text_lengths):
+        """calculate_alignments' core for a ragged batch (align_text.py:138-152): mels [B, T, n_mels] normalised log-mel, texts [B, P] token ids ->
+        (list of [3, P] float tensors (pred_dur, left, right), list of per-frame path log-probs ``scores`` [T]), all on the device.  One
+        deviation from torch_align: blank frames in front of the first token count to token 0 (the reference's loop trips its assert there).
+        ValueError where no alignment exists: fewer frames than tokens plus adjacent equal pairs."""
+        from . import aligner
+
+        L = self._lengths(mels, mel_lengths)
+        texts = torch.as_tensor(texts)
+        PL = [int(v) for v in torch.as_tensor(text_lengths).tolist()]
+        if texts.dim() != 2 or len(PL) != len(L) or any(n > texts.shape[1] for n in PL):
+            raise ValueError(f"texts of shape {tuple(texts.shape)} with text_lengths {PL} do not fit {len(L)} utterances")
+        toks = [[int(v) for v in texts[b, : PL[b]].tolist()] for b in range(len(L))]
+        for b, tk in enumerate(toks):
+            aligner.check_alignable(L[b], tk, f"utterance {b}")
+            if any(not 0 <= v < self.num_symbols for v in tk):
+                raise ValueError(f"utterance {b}: token ids must lie in [0, {self.num_symbols})")
+        lp, seg = self.packed(mels, L)
+        eng = self.engine
+        seg_p = Segments(PL, eng.device)
+        tg = torch.tensor([v for tk in toks for v in tk], dtype=torch.int32, device=eng.device)
+        r = eng.ctc_align(seg, lp, seg_p, tg, self.blank)
+        stack = torch.stack([r["durations"].to(torch.float32), r["left"], r["right"]])
+        return ([stack[:, seg_p.host[b] : seg_p.host[b + 1]] for b in range(seg.n)], [r["scores"][seg.host[b] : seg.host[b + 1]] for b in range(seg.n)])
+
+
 def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int] = None, hubert: bool = False, mel_style: bool = False,
-                            cfm_pitch: bool = False, ssl: bool = False):
+                            cfm_pitch: bool = False, ssl: bool = False, aligner: bool = False):
     """The five modules of the inference composition (models/models.py:32-63, :79-101), optionally with synthetic weights.
     hubert=True adds the voice-conversion pair hubert_speech_predictor / hubert_pitch_energy_predictor (models/models.py:92-101);
     mel_style=True adds pe_mel_style_encoder (models/models.py:57-62); cfm_pitch=True adds cfm_pitch_predictor (models/models.py:72-75);
-    ssl=True adds hubert, the AdaptiveHubert content encoder shaped by hubert.arch / hubert.sr (train/models/ssl.py:16-31)."""
+    ssl=True adds hubert, the AdaptiveHubert content encoder shaped by hubert.arch / hubert.sr (train/models/ssl.py:16-31);
+    aligner=True adds text_aligner, tdnn_blstm_ctc_model_base(n_mels, text_encoder.tokens) (models/models.py:28-30)."""
     cfg = cfg or load_model_config()
     m = dict(
         speech_predictor=SpeechPredictor(cfg, engine=engine),
@@ -1036,6 +1143,8 @@ def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int]
 
         sr, a = hubert_ssl_config(cfg)
         m["hubert"] = AdaptiveHubert(None, cfg.sample_rate, sr, config=a, cfg=cfg, engine=engine)
+    if aligner:
+        m["text_aligner"] = TextAligner(cfg.n_mels, cfg.text_encoder.tokens, engine=engine, cfg=cfg)
     if synthetic_seed is not None:
         for mod in m.values():
             mod.load_synthetic(synthetic_seed)

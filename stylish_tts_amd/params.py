@@ -528,6 +528,26 @@ def rmvpe_spec(dims=None) -> Spec:
     return s
 
 
+def text_aligner_spec(dims=None) -> Spec:
+    """tdnn_blstm_ctc_model(...).state_dict() (train/models/text_aligner.py:16-30, :130-207, :245-264) in registration order.  ``dims``:
+    aligner.dims() (tdnn_blstm_ctc_model_base(80, 178) when None).  A TDNN layer is Sequential(Conv1d, ReLU, BatchNorm1d(affine=False), Dropout):
+    the BatchNorm's running statistics sit at index 2; the Ffn is Sequential(Linear, ReLU, Dropout, ...): Linear j at index 3 j."""
+    from .aligner import dims as _dims
+
+    d = dims if dims is not None else _dims()
+    H = d["hidden"]
+    s: Spec = []
+    for i, k in enumerate(d["tdnn_kernel"]):
+        q = f"encoder.layers.{i}"
+        s += _conv(q + ".0", H, d["n_mels"] if i == 0 else H, k)
+        s += [(q + ".2.running_mean", (H,), "ln_b"), (q + ".2.running_var", (H,), "bn_var"), (q + ".2.num_batches_tracked", (), "count")]
+    n = len(d["tdnn_kernel"])
+    for j in range(d["ffn_layers"]):
+        s += _linear(f"encoder.layers.{n}.ffn.{3 * j}", H, H)
+    s += [("encoder_output_layer.weight", (d["classes"], H), "w_qk"), ("encoder_output_layer.bias", (d["classes"],), "b")]
+    return s
+
+
 MEL_STYLE_MODULE_SPECS = {"pe_mel_style_encoder": pe_mel_style_encoder_spec, "cfm_pitch_predictor": cfm_pitch_predictor_module_spec}
 
 

@@ -105,6 +105,8 @@ class HipModel:
         self._cpws: Dict[int, torch.Tensor] = {}
         self._sslws: Dict[int, torch.Tensor] = {}
         self._rvws: Dict[int, torch.Tensor] = {}
+        self._alws: Dict[int, torch.Tensor] = {}
+        self._ctcws: Dict[int, torch.Tensor] = {}
         self._ws_lock = threading.Lock()
 
     def close(self):
@@ -549,4 +551,67 @@ class HipModel:
             raise ValueError(f"{f0.numel()} values for {seg_in.rows} frames in {seg_in.n} utterances, {seg_out.n} output utterances")
         out = self._f32(seg_out.rows)
         _lib.check(self.lib.stts_rmvpe_resample(self.ctx, _stream(), seg_in.n, _ptr(seg_in.dev), seg_out.host_ptr, _ptr(seg_out.dev), _ptr(f0.contiguous()), _ptr(out)))
+        return out
+
+    # ------------------------------------------------------------------ text aligner + CTC forced alignment (packed normalised log-mel rows)
+    def aligner_finalize(self, dims) -> None:
+        """Pack the weights loaded under "text_aligner." for the dims of aligner.dims(); include/stylish_hip.h, stts_aligner_finalize."""
+        from . import aligner
+
+        self._al_dims_d = dict(dims)
+        self._al_dims = aligner.dims_struct(dims)
+        _lib.check(self.lib.stts_aligner_finalize(self.ctx, C.byref(self._al_dims)))
+
+    def text_aligner(self, seg: Segments, mel_rows: torch.Tensor, taps: bool = False):
+        """mel_rows [rows_T, ld >= n_mels] packed time-major normalised log-mel (utterance offsets seg) -> log_probs [rows_T, classes]; taps=True
+        also returns a dict of the intermediate rows (include/stylish_hip.h, stts_aligner_forward_taps).  Nothing is read back by the host."""
+        if getattr(self, "_al_dims", None) is None:
+            _lib.check(self.lib.stts_aligner_forward(self.ctx, _stream(), 0, None, None, None, 0, None, 0, None, 0))  # not finalized: the library's message
+        if mel_rows.dim() != 2 or mel_rows.shape[0] != seg.rows:
+            raise ValueError(f"packed mel of shape {tuple(mel_rows.shape)}, the offsets describe {seg.rows} frames")
+        d = self._al_dims_d
+        need = int(self.lib.stts_aligner_workspace_bytes(self.ctx, seg.n, seg.host_ptr)) or 256  # 0: bad offsets - the entry point names them
+        ws = self._grow(self._alws, need)
+        mel_rows = mel_rows.to(self.device, torch.float32).contiguous()
+        V, H = d["classes"], d["hidden"]
+        lp = self._f32(seg.rows, V)
+        args = (self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(mel_rows), mel_rows.shape[1], _ptr(lp), V)
+        if not taps:
+            _lib.check(self.lib.stts_aligner_forward(*args, _ptr(ws), ws.numel()))
+            return lp
+        t = self._f32(max(1, int(self.lib.stts_aligner_tap_floats(C.byref(self._al_dims), seg.n, seg.host_ptr))))
+        _lib.check(self.lib.stts_aligner_forward_taps(*args, _ptr(t), _ptr(ws), ws.numel()))
+        R, n = seg.rows, len(d["tdnn_kernel"])
+        out = {f"tdnn{i}": t[i * R * H : (i + 1) * R * H].view(R, H) for i in range(n)}
+        out["ffn"] = t[n * R * H : (n + 1) * R * H].view(R, H)
+        out["logits"] = t[(n + 1) * R * H : (n + 1) * R * H + R * V].view(R, V)
+        return lp, out
+
+    def ctc_align(self, seg_t: Segments, log_probs: torch.Tensor, seg_p: Segments, targets: torch.Tensor, blank: int, path: Optional[torch.Tensor] = None):
+        """CTC forced alignment and torch_align's post-processing on the device (include/stylish_hip.h, stts_ctc_align): log_probs [sum T, ld] with
+        frame offsets seg_t, targets [sum P] with token offsets seg_p -> dict(path [sum T] int32, scores [sum T], durations [sum P] int32,
+        left [sum P], right [sum P]).  ``path`` given: only the post-processing runs on it.  Nothing is read back by the host."""
+        if seg_t.n != seg_p.n:
+            raise ValueError(f"{seg_t.n} utterances of frames but {seg_p.n} of tokens")
+        lp = log_probs.to(self.device, torch.float32).contiguous()
+        if lp.dim() != 2 or lp.shape[0] != seg_t.rows:
+            raise ValueError(f"log-probs of shape {tuple(lp.shape)}, the offsets describe {seg_t.rows} frames")
+        tg = targets.to(self.device, torch.int32).contiguous()
+        if tg.dim() != 1 or tg.numel() != seg_p.rows:
+            raise ValueError(f"{tg.numel()} targets, the offsets describe {seg_p.rows}")
+        given = path is not None
+        if given:
+            p = path.to(self.device, torch.int32).contiguous().clone()
+            if p.dim() != 1 or p.numel() != seg_t.rows:
+                raise ValueError(f"a path of {p.numel()} labels for {seg_t.rows} frames")
+            ws = None
+        else:
+            p = torch.empty(seg_t.rows, dtype=torch.int32, device=self.device)
+            need = int(self.lib.stts_ctc_align_workspace_bytes(seg_t.n, seg_t.host_ptr, seg_p.host_ptr)) or 256  # 0: bad offsets - the entry point names them
+            ws = self._grow(self._ctcws, need)
+        out = dict(path=p, scores=self._f32(seg_t.rows), durations=torch.empty(seg_p.rows, dtype=torch.int32, device=self.device), left=self._f32(seg_p.rows),
+                   right=self._f32(seg_p.rows))
+        _lib.check(self.lib.stts_ctc_align(_stream(), seg_t.n, seg_t.host_ptr, _ptr(seg_t.dev), seg_p.host_ptr, _ptr(seg_p.dev), _ptr(lp), lp.shape[1], lp.shape[1],
+                                           int(blank), _ptr(tg), 1 if given else 0, _ptr(p), _ptr(out["scores"]), _ptr(out["durations"]), _ptr(out["left"]),
+                                           _ptr(out["right"]), _ptr(ws), 0 if ws is None else ws.numel()))
         return out
