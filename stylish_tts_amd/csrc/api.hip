@@ -3,6 +3,7 @@
 #include "model.hip.h"
 #include "cfm.hip.h"
 #include "hubert.hip.h"
+#include "conv2d.hip.h"
 #include "mel_style.hip.h"
 #include "cfm_pitch.hip.h"
 #include "ssl.hip.h"

@@ -8,9 +8,7 @@
 
 namespace stts {
 
-// no packed-fp32 instructions in these fp32 kernels (they run beside the split-fp32 contractions on other streams)
-#define STTS_CP_NO_PK __attribute__((target("no-packed-fp32-ops")))
-
+// The kernels here carry STTS_NO_PK: they run beside the split-fp32 contractions on other streams.
 constexpr int kCpHidden = 256;  // hidden_dim, hard-coded in the reference
 constexpr int kCpInter = 1024;  // hidden_dim * 4
 constexpr int kCpBlocks = 4;
@@ -29,7 +27,7 @@ struct CfmPitchNetW {  // STTS_W_CFM_PITCH_NET: cfm_pitch_predictor.{asr_emb, bl
 // ------------------------------------------------------------------------------------------------ kernels
 // in place: X[r][0, C) = mish(X[r][0, C)) over the utterances' rows (bounds from the device offsets); C % 4 == 0.
 // grid (ceil(max_len * C / 4 / 256) capped, n_utt)
-__global__ void STTS_CP_NO_PK __launch_bounds__(256) cp_mish_rows_kernel(float* __restrict__ X, int ldx, int C, const int* __restrict__ seg_off) {
+__global__ void STTS_NO_PK __launch_bounds__(256) cp_mish_rows_kernel(float* __restrict__ X, int ldx, int C, const int* __restrict__ seg_off) {
   const int u = blockIdx.y;
   const int lo = seg_off[u], len = seg_off[u + 1] - lo;
   const int c4 = C / 4;
@@ -43,7 +41,7 @@ __global__ void STTS_CP_NO_PK __launch_bounds__(256) cp_mish_rows_kernel(float* 
 
 // style projections with a wide style (K = 256: style_fc_kernel covers K <= 128): out[u][j] = b[j] + sum_k W[j][k] s[u][k], one wave per
 // row j, lane-strided partial sums then the butterfly - the same operations for an utterance whatever n_utt is.  grid ceil(J / 4), block 256.
-__global__ void STTS_CP_NO_PK __launch_bounds__(256) cp_style_kernel(const float* __restrict__ W, const float* __restrict__ b, const float* __restrict__ s,
+__global__ void STTS_NO_PK __launch_bounds__(256) cp_style_kernel(const float* __restrict__ W, const float* __restrict__ b, const float* __restrict__ s,
                                                                     float* __restrict__ out, int J, int K, int n_utt, int lds_s, int ld_out) {
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -63,7 +61,7 @@ __global__ void STTS_CP_NO_PK __launch_bounds__(256) cp_style_kernel(const float
 // The product x * std and the sum are rounded separately (no FMA), as torch evaluates the reference's expression; 2^a is formed in double
 // and rounded to fp32 once (correctly rounded but for ties; torch's own fp32 2**a is within 1 ulp of that).
 // grid (ceil(max_len / 4), n_utt), block 256 = 4 rows.
-__global__ void STTS_CP_NO_PK __launch_bounds__(256) cp_out_kernel(const float* __restrict__ X, int ldx, int C, const int* __restrict__ seg_off,
+__global__ void STTS_NO_PK __launch_bounds__(256) cp_out_kernel(const float* __restrict__ X, int ldx, int C, const int* __restrict__ seg_off,
                                                                   const float* __restrict__ w, float bias, float* __restrict__ normed,
                                                                   float* __restrict__ hz, float mean, float stdv, const float* __restrict__ uv) {
   const int u = blockIdx.y, lane = threadIdx.x & 63;

@@ -45,6 +45,9 @@ inline int fail(const char* fmt, ...) {
     if (_r != 0) return _r; \
   } while (0)
 
+// the fp32 kernels that carry this are built without packed-fp32 instructions
+#define STTS_NO_PK __attribute__((target("no-packed-fp32-ops")))
+
 inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 

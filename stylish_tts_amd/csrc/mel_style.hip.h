@@ -7,41 +7,24 @@
 //
 // Layout: channels-last packed rows.  The input of the encoder is the mel [B, 1, F = n_mels, T]; at every
 // level the activation of utterance u is the rows (off[u] + t) * F + f, t < T_u, f < F, each row ld(C) = round_up(C, 16) floats with
-// the channels contiguous (the pad channels hold zeros).  A 2-D convolution is an implicit GEMM over those rows: M = output positions,
-// N = cout, K = k * k * ld(cin) in tap-major order; the operand load gathers the tap's input row and zero-fills the frequency edges and
-// the utterance boundaries, so no im2col buffer exists.
+// the channels contiguous (the pad channels hold zeros).  Every 3 x 3 pad-1, 1 x 1 and 5 x 5 valid conv is conv2d_kernel (conv2d.hip.h)
+// with K = k * k * ld(cin), taps in the order dt * k + df, npad = round_up(cout, 64) (the 64 x 64 tile) and one fmaf chain per slice.
 #pragma once
 
 namespace stts {
 
-constexpr int kMsBM = 64, kMsBN = 64, kMsBK = 16;  // contraction tile: 4 waves of 32 x 32, K chunk of 16 (one tap, 16 channels)
 constexpr int kMsMaxBlocks = 4;
-constexpr int kMsMinOut = 5;
+constexpr int kMsMinOut = 5;  // the 5 x 5 valid conv needs 5 x 5 positions after the last downsampling
 // split-K: a contraction with K >= 2 kMsSplitK runs as ceil(K / kMsSplitK) slices whose partial sums are added in slice order by
-// ms_splitk_reduce_kernel.  The slice count depends on K only (the weights), never on the batch: the bits stay batch-independent.
-constexpr int kMsSplitK = 1024;  // the 5 x 5 valid conv needs 5 x 5 positions after the last downsampling
+// conv2d_reduce_kernel.  The slice count depends on K only (the weights), never on the batch: the bits stay batch-independent.
+constexpr int kMsSplitK = 1024;
 
 inline int ms_ld(int c) { return round_up(c, 16); }
-
-// no packed-fp32 instructions in these fp32 kernels (-DSTTS_MS_ALLOW_PACKED builds them with, to measure the rule)
-#ifdef STTS_MS_ALLOW_PACKED
-#define STTS_MS_NO_PK
-#else
-#define STTS_MS_NO_PK __attribute__((target("no-packed-fp32-ops")))
-#endif
-
-typedef float ms_f32x4 __attribute__((ext_vector_type(4)));  // one 16 x 16 accumulator tile per lane: 4 floats
-
-struct MsConv {  // spectral-norm-folded conv, packed [k * k * ldk][npad] (K row = (dt * k + df) * ldk + ci), bias [cout] or null
-  int cout = 0, cin = 0, k = 0, ldk = 0, npad = 0;
-  float* w = nullptr;
-  float* b = nullptr;
-};
 
 struct MsBlockW {
   int cin = 0, cout = 0;
   bool down = false, learned_sc = false;
-  MsConv conv1, conv2, sc;                  // sc: conv1x1 (no bias) when cin != cout
+  Conv2dW conv1, conv2, sc;                  // sc: conv1x1 (no bias) when cin != cout
   float* dw_w = nullptr;                    // downsample_res: depthwise 3 x 3 stride 2, [c][kF][kT]
   float* dw_b = nullptr;
 };
@@ -52,7 +35,7 @@ struct MelStyleW {
   float* w0 = nullptr;  // shared.0: 1 -> c0, [c0][kF][kT]
   float* b0 = nullptr;
   MsBlockW blk[kMsMaxBlocks];
-  MsConv conv5;         // shared.6: 5 x 5 valid
+  Conv2dW conv5;        // shared.6: 5 x 5 valid
   float* wl = nullptr;  // unshared [style_dim][c_last]
   float* bl = nullptr;
   int min_frames() const {  // the shortest T whose last level still has kMsMinOut columns
@@ -69,19 +52,6 @@ struct MelStyleModel {
 };
 
 // ------------------------------------------------------------------------------------------------ kernels
-__device__ __forceinline__ float ms_lrelu(float v) { return v > 0.f ? v : 0.2f * v; }
-
-// the utterance of packed time row tr: the largest u with off[u] <= tr
-__device__ __forceinline__ int ms_utt(const int* __restrict__ off, int n_utt, int tr) {
-  int lo = 0, hi = n_utt - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= tr) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // Time offsets of every level from the mel offsets, on the device (no host copy): out[l][u], l = 0 .. n_down the levels
 // (T_{l+1} = ceil(T_l / 2)), l = n_down + 1 the 5 x 5 conv's output (T_last - 4).  One thread: n_utt is small.
 __global__ void ms_offsets_kernel(const int* __restrict__ off, int n_utt, int n_down, int* __restrict__ out) {
@@ -99,7 +69,7 @@ __global__ void ms_offsets_kernel(const int* __restrict__ off, int n_utt, int n_
 }
 
 // shared.0: Conv2d(1 -> C, 3 x 3, pad 1) straight from the mel rows mel[(off[u] + t) * ldm + f].  One thread per (row, channel).
-__global__ void __launch_bounds__(256) STTS_MS_NO_PK
+__global__ void __launch_bounds__(256) STTS_NO_PK
 ms_conv0_kernel(const float* __restrict__ mel, int ldm, const int* __restrict__ off, int n_utt, int F, long rows, const float* __restrict__ w,
                 const float* __restrict__ b, int C, int ldc, float* __restrict__ Y) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -111,7 +81,7 @@ ms_conv0_kernel(const float* __restrict__ mel, int ldm, const int* __restrict__ 
     return;
   }
   const int tr = (int)(m / F), f = (int)(m - (long)tr * F);
-  const int u = ms_utt(off, n_utt, tr);
+  const int u = utt_of_row(off, n_utt, 0, tr);
   const int t = tr - off[u], T = off[u + 1] - off[u];
   float s = 0.f;
   for (int df = 0; df < 3; ++df) {
@@ -127,7 +97,7 @@ ms_conv0_kernel(const float* __restrict__ mel, int ldm, const int* __restrict__ 
 }
 
 // downsample_res ("half"): depthwise Conv2d(C, 3 x 3, stride 2, pad 1) + bias, level l -> l + 1 (F / 2 x ceil(T / 2)).
-__global__ void __launch_bounds__(256) STTS_MS_NO_PK
+__global__ void __launch_bounds__(256) STTS_NO_PK
 ms_dw_down_kernel(const float* __restrict__ X, const int* __restrict__ offIn, const int* __restrict__ offOut, int n_utt, int F, long rows_out,
                   const float* __restrict__ w, const float* __restrict__ b, int C, int ldc, float* __restrict__ Y) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -140,7 +110,7 @@ ms_dw_down_kernel(const float* __restrict__ X, const int* __restrict__ offIn, co
   }
   const int Fo = F / 2;
   const int tr = (int)(m / Fo), fo = (int)(m - (long)tr * Fo);
-  const int u = ms_utt(offOut, n_utt, tr);
+  const int u = utt_of_row(offOut, n_utt, 0, tr);
   const int to = tr - offOut[u], T = offIn[u + 1] - offIn[u];
   const long base = offIn[u];
   float s = 0.f;
@@ -157,7 +127,7 @@ ms_dw_down_kernel(const float* __restrict__ X, const int* __restrict__ offIn, co
 }
 
 // DownSample("half"): the last time column replicated when T is odd, then avg_pool2d(2).  Level l -> l + 1.
-__global__ void __launch_bounds__(256) STTS_MS_NO_PK
+__global__ void __launch_bounds__(256) STTS_NO_PK
 ms_pool_half_kernel(const float* __restrict__ X, const int* __restrict__ offIn, const int* __restrict__ offOut, int n_utt, int F, long rows_out, int C,
                     int ldc, float* __restrict__ Y) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -170,7 +140,7 @@ ms_pool_half_kernel(const float* __restrict__ X, const int* __restrict__ offIn, 
   }
   const int Fo = F / 2;
   const int tr = (int)(m / Fo), fo = (int)(m - (long)tr * Fo);
-  const int u = ms_utt(offOut, n_utt, tr);
+  const int u = utt_of_row(offOut, n_utt, 0, tr);
   const int to = tr - offOut[u], T = offIn[u + 1] - offIn[u];
   const long base = offIn[u];
   const int t0 = 2 * to, t1 = min(2 * to + 1, T - 1), f0 = 2 * fo;
@@ -179,141 +149,9 @@ ms_pool_half_kernel(const float* __restrict__ X, const int* __restrict__ offIn, 
   Y[i] = s / 4.f;
 }
 
-struct MsGemm {
-  const float* X;          // input rows [(offIn[u] + t) * F + f][ldk]
-  const int* offIn;        // time offsets of the input level
-  const int* offOut;       // time offsets of the output level
-  int n_utt, F, Fo, pad, k;
-  long rows_out;           // output rows = offOut[n_utt] * Fo
-  const float* W;          // [k * k * ldk][npad]
-  int ldk, npad, N;
-  const float* bias;       // [N] or null
-  const float* R;          // residual [rows_out][ldy] or null (conv2: the shortcut)
-  float div;               // the result is divided by div (conv2 of a ResBlk: sqrt(2); else 1)
-  float* Y;                // [rows_out][ldy], ldy = ms_ld(N); channels N .. ldy - 1 are written as 0
-  int ldy;
-  int k_slice;             // K per slice (blockIdx.z); the whole K when not split
-  float* P;                // split-K: raw partial sums [slices][rows_out][ldy] instead of Y (the epilogue runs in the reduce)
-};
-
-// Implicit-GEMM 2-D convolution on the f32 matrix cores.  Output (u, t, f) reads input (t + dt - pad, f + df - pad) for the k x k taps;
-// positions outside [0, T_u) x [0, F) are zeros (the operand load skips them).  LRELU: LeakyReLU(0.2) on the operand as it is loaded.
-// Each output element is one K loop in a fixed order (per slice), independent of the other rows: the same bits alone and in any batch.
-// grid (ceil(rows_out / 64), npad / 64, slices), block 256: wave w computes rows 32 (w / 2) .., columns 32 (w % 2) .. with 2 x 2 16 x 16 MFMA tiles.
-template <bool LRELU>
-__global__ void __launch_bounds__(256) STTS_MS_NO_PK ms_conv_kernel(MsGemm g) {
-  __shared__ float As[kMsBK][kMsBM + 4];
-  __shared__ float Bs[kMsBK][kMsBN + 4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long m0 = (long)blockIdx.x * kMsBM;
-  const int n0 = blockIdx.y * kMsBN;
-  // the A row this thread loads (4 consecutive channels of it per K chunk)
-  const int ar = tid >> 2, akq = (tid & 3) * 4;
-  const long m = m0 + ar;
-  const bool mval = m < g.rows_out;
-  int t = 0, f = 0, T = 0;
-  long base = 0;
-  if (mval) {
-    const int tr = (int)(m / g.Fo);
-    f = (int)(m - (long)tr * g.Fo);
-    const int u = ms_utt(g.offOut, g.n_utt, tr);
-    t = tr - g.offOut[u];
-    T = g.offIn[u + 1] - g.offIn[u];
-    base = g.offIn[u];
-  }
-  const int bk = tid >> 4, bn = (tid & 15) * 4;
-  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-  ms_f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = ms_f32x4{0.f, 0.f, 0.f, 0.f};
-  const int K = g.k * g.k * g.ldk;
-  const int kb = blockIdx.z * g.k_slice, ke = min(K, kb + g.k_slice);
-  for (int k0 = kb; k0 < ke; k0 += kMsBK) {
-    const int tap = k0 / g.ldk, ci = k0 - tap * g.ldk + akq;
-    const int ti = t + tap / g.k - g.pad, fi = f + tap % g.k - g.pad;
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (mval && ti >= 0 && ti < T && fi >= 0 && fi < g.F) {
-      a = *reinterpret_cast<const float4*>(g.X + ((base + ti) * g.F + fi) * (long)g.ldk + ci);
-      if (LRELU) {
-        a.x = ms_lrelu(a.x);
-        a.y = ms_lrelu(a.y);
-        a.z = ms_lrelu(a.z);
-        a.w = ms_lrelu(a.w);
-      }
-    }
-    const float4 b = *reinterpret_cast<const float4*>(g.W + (long)(k0 + bk) * g.npad + n0 + bn);
-    __syncthreads();  // the previous chunk's reads are done
-    As[akq + 0][ar] = a.x;
-    As[akq + 1][ar] = a.y;
-    As[akq + 2][ar] = a.z;
-    As[akq + 3][ar] = a.w;
-    *reinterpret_cast<float4*>(&Bs[bk][bn]) = b;
-    __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < kMsBK; kk += 4) {
-      const int kl = kk + (lane >> 4);
-      float av[2], bv[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) av[i] = As[kl][wm + i * 16 + (lane & 15)];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) bv[j] = Bs[kl][wn + j * 16 + (lane & 15)];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-    }
-  }
-  // D of a 16 x 16 tile: lane l holds rows 4 (l / 16) + r, r < 4, of column l % 16
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + wn + j * 16 + (lane & 15);
-      if (n >= g.ldy) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long mo = m0 + wm + i * 16 + 4 * (lane >> 4) + r;
-        if (mo >= g.rows_out) continue;
-        if (g.P) {
-          g.P[((long)blockIdx.z * g.rows_out + mo) * g.ldy + n] = acc[i][j][r];
-          continue;
-        }
-        float v = 0.f;
-        if (n < g.N) {
-          v = acc[i][j][r];
-          if (g.bias) v += g.bias[n];
-          if (g.R) v = g.R[mo * g.ldy + n] + v;
-          v = v / g.div;
-        }
-        g.Y[mo * g.ldy + n] = v;
-      }
-    }
-}
-
-// Split-K epilogue: the slices' partial sums in slice order, then bias, residual and the division as ms_conv_kernel's epilogue.
-__global__ void __launch_bounds__(256) STTS_MS_NO_PK
-ms_splitk_reduce_kernel(const float* __restrict__ P, int slices, long rows_out, int ldy, int N, const float* __restrict__ bias, const float* __restrict__ R,
-                        float div, float* __restrict__ Y) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const long total = rows_out * ldy;
-  if (i >= total) return;
-  const int n = (int)(i % ldy);
-  float v = 0.f;
-  if (n < N) {
-    v = P[i];
-    for (int z = 1; z < slices; ++z) v += P[(long)z * total + i];
-    if (bias) v += bias[n];
-    if (R) v = R[i] + v;
-    v = v / div;
-  }
-  Y[i] = v;
-}
-
 // Tail, one block per utterance: mean of the 5 x 5 conv's output over its (F - 4) x (T - 4) positions (rows in order, fixed), LeakyReLU,
 // then unshared (Linear).  No atomics: an utterance's style is the same bits alone and in a batch.
-__global__ void __launch_bounds__(256) STTS_MS_NO_PK
+__global__ void __launch_bounds__(256) STTS_NO_PK
 ms_tail_kernel(const float* __restrict__ H, int ldh, const int* __restrict__ off5, int Fo, int C, const float* __restrict__ Wl, const float* __restrict__ bl,
                int S, float* __restrict__ out, int ld_out) {
   extern __shared__ float hm[];  // [C]
@@ -323,7 +161,7 @@ ms_tail_kernel(const float* __restrict__ H, int ldh, const int* __restrict__ off
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     float s = 0.f;
     for (long r = r0; r < r1; ++r) s += H[r * ldh + c];
-    hm[c] = ms_lrelu(s / n);
+    hm[c] = lrelu02(s / n);
   }
   __syncthreads();
   for (int j = threadIdx.x; j < S; j += blockDim.x) {
@@ -356,29 +194,26 @@ inline int spectral_norm_weight(stts_ctx* c, const std::string& p, HostTensor* w
   return 0;
 }
 
-inline int ms_pack_conv(stts_ctx* c, const std::string& p, bool bias, MsConv* o) {
+// a spectral-norm-folded Conv2d [cout, cin, k, k] (cout < 0: any) for conv2d_kernel: taps in the order dt * k + df, tap (dt, df) reads (t + dt - pad, f + df - pad)
+inline int ms_pack_conv(stts_ctx* c, const std::string& p, bool bias, int cout, int cin, int k, int pad, Conv2dW* o) {
   HostTensor w;
   STTS_TRY(spectral_norm_weight(c, p, &w));
-  STTS_CHECK(w.shape.size() == 4 && w.shape[2] == w.shape[3], "%s: expected a square Conv2d weight", p.c_str());
-  o->cout = (int)w.shape[0];
-  o->cin = (int)w.shape[1];
-  o->k = (int)w.shape[2];
-  o->ldk = ms_ld(o->cin);
-  o->npad = round_up(o->cout, kMsBN);
-  const int k = o->k;
-  std::vector<float> pk((size_t)k * k * o->ldk * o->npad, 0.f);
-  for (int n = 0; n < o->cout; ++n)
-    for (int ci = 0; ci < o->cin; ++ci)
-      for (int df = 0; df < k; ++df)
-        for (int dt = 0; dt < k; ++dt)
-          pk[((size_t)(dt * k + df) * o->ldk + ci) * o->npad + n] = w.data[(((size_t)n * o->cin + ci) * k + df) * k + dt];
-  STTS_TRY(dev_upload(c, pk, &o->w));
-  if (bias) {
-    STTS_GET(b, p + ".bias");
-    STTS_CHECK((int)b->data.size() == o->cout, "%s.bias: %zu values for %d channels", p.c_str(), b->data.size(), o->cout);
-    STTS_TRY(dev_upload(c, b->data, &o->b));
+  STTS_CHECK(w.shape.size() == 4 && (cout < 0 || w.shape[0] == cout) && w.shape[1] == cin && w.shape[2] == k && w.shape[3] == k, "%s: expected a [%d, %d, %d, %d] Conv2d weight",
+             p.c_str(), cout, cin, k, k);
+  cout = (int)w.shape[0];
+  int dt[kConvMaxTaps], df[kConvMaxTaps];
+  for (int tap = 0; tap < k * k; ++tap) {
+    dt[tap] = tap / k - pad;
+    df[tap] = tap % k - pad;
   }
-  return 0;
+  std::vector<double> b;
+  if (bias) {
+    STTS_GET(bt, p + ".bias");
+    STTS_CHECK((int)bt->data.size() == cout, "%s.bias: %zu values for %d channels", p.c_str(), bt->data.size(), cout);
+    b.assign(bt->data.begin(), bt->data.end());
+  }
+  return conv2d_pack(c, cout, round_up(cout, 64), cin, 0, ms_ld(cin), 0, k * k, dt, df,
+                     [&](int n, int ci, int tap) { return (double)w.data[(((size_t)n * cin + ci) * k + tap % k) * k + tap / k]; }, bias ? &b : nullptr, o);
 }
 
 inline int ms_upload_small(stts_ctx* c, const std::string& p, int C, float** w, float** b) {  // a [C, 1, 3, 3] conv (conv0 / depthwise)
@@ -407,15 +242,11 @@ inline int finalize_mel_style_one(stts_ctx* c, MelStyleW* E, int which) {
     MsBlockW& B = E->blk[i];
     const std::string q = p + "shared." + std::to_string(i + 1) + ".";
     B.cin = cin;
-    STTS_TRY(ms_pack_conv(c, q + "conv1", true, &B.conv1));
-    STTS_TRY(ms_pack_conv(c, q + "conv2", true, &B.conv2));
-    STTS_CHECK(B.conv1.k == 3 && B.conv2.k == 3 && B.conv1.cin == cin && B.conv1.cout == cin && B.conv2.cin == cin, "%s: conv1 / conv2 shapes do not chain", q.c_str());
+    STTS_TRY(ms_pack_conv(c, q + "conv1", true, cin, cin, 3, 1, &B.conv1));
+    STTS_TRY(ms_pack_conv(c, q + "conv2", true, -1, cin, 3, 1, &B.conv2));
     B.cout = B.conv2.cout;
     B.learned_sc = B.cin != B.cout;
-    if (B.learned_sc) {
-      STTS_TRY(ms_pack_conv(c, q + "conv1x1", false, &B.sc));
-      STTS_CHECK(B.sc.k == 1 && B.sc.cin == cin && B.sc.cout == B.cout, "%sconv1x1: expected [%d, %d, 1, 1]", q.c_str(), B.cout, cin);
-    }
+    if (B.learned_sc) STTS_TRY(ms_pack_conv(c, q + "conv1x1", false, B.cout, cin, 1, 0, &B.sc));
     B.down = find(c, q + "downsample_res.conv.weight_orig") != nullptr;
     if (B.down) {
       STTS_TRY(ms_upload_small(c, q + "downsample_res.conv", cin, &B.dw_w, &B.dw_b));
@@ -430,8 +261,7 @@ inline int finalize_mel_style_one(stts_ctx* c, MelStyleW* E, int which) {
   const int fdiv = 1 << E->n_down;
   STTS_CHECK(E->n_mels % fdiv == 0 && E->n_mels / fdiv >= kMsMinOut, "n_mels = %d: the encoder needs a multiple of %d of at least %d", E->n_mels, fdiv,
              fdiv * kMsMinOut);
-  STTS_TRY(ms_pack_conv(c, p + "shared.6", true, &E->conv5));
-  STTS_CHECK(E->conv5.k == 5 && E->conv5.cin == cin && E->conv5.cout == cin, "%sshared.6: expected [%d, %d, 5, 5]", p.c_str(), cin, cin);
+  STTS_TRY(ms_pack_conv(c, p + "shared.6", true, cin, cin, kMsMinOut, 0, &E->conv5));
   STTS_GET(wl, p + "unshared.weight");
   STTS_GET(bl, p + "unshared.bias");
   STTS_CHECK(wl->shape.size() == 2 && wl->shape[1] == cin && (int64_t)bl->data.size() == wl->shape[0], "%sunshared: expected [style_dim, %d]", p.c_str(), cin);
@@ -476,16 +306,13 @@ inline int ms_plan(const MelStyleW& E, int n_utt, const int* off, MsPlan* P) {
   return 0;
 }
 
-inline int ms_slices(const MsConv& w) {
-  const int K = w.k * w.k * w.ldk;
-  return K >= 2 * kMsSplitK ? ceil_div(K, kMsSplitK) : 1;
-}
+inline int ms_slices(const Conv2dW& w) { return w.K >= 2 * kMsSplitK ? ceil_div(w.K, kMsSplitK) : 1; }
 
 // floats of split-K scratch (one buffer, reused by the convs one after the other): rows(l) = output rows at level l, l = n_down + 1 the 5 x 5 output
 template <typename Rows>
 inline size_t ms_split_floats(const MelStyleW& E, Rows rows) {
   size_t mx = 0;
-  auto need = [&](const MsConv& w, size_t r) {
+  auto need = [&](const Conv2dW& w, size_t r) {
     if (ms_slices(w) > 1) mx = std::max(mx, (size_t)ms_slices(w) * r * ms_ld(w.cout));
   };
   int l = 0;
@@ -530,19 +357,25 @@ inline size_t mel_style_workspace_bytes(const MelStyleW& E, int64_t rows_T, int 
 
 // ------------------------------------------------------------------------------------------------ MelStyleEncoder.forward
 // P: split-K partials, ms_slices(w) * rows_out * ms_ld(cout) floats (unused when the conv is not split)
-inline int ms_conv(hipStream_t st, const MsConv& w, bool lrelu, const float* X, const int* offIn, const int* offOut, int n_utt, int F, int Fo, int pad, long rows_out,
-                   const float* R, float div, float* Y, float* P) {
-  if (rows_out == 0) return 0;
-  const int slices = ms_slices(w), ldy = ms_ld(w.cout);
-  STTS_CHECK(slices == 1 || P, "mel_style: no split-K scratch");
-  MsGemm g{X, offIn, offOut, n_utt, F, Fo, pad, w.k, rows_out, w.w, w.ldk, w.npad, w.cout, w.b, R, div, Y, ldy,
-           slices == 1 ? w.k * w.k * w.ldk : kMsSplitK, slices == 1 ? nullptr : P};
-  const dim3 grid((unsigned)((rows_out + kMsBM - 1) / kMsBM), w.npad / kMsBN, slices);
-  if (lrelu) hipLaunchKernelGGL(ms_conv_kernel<true>, grid, dim3(256), 0, st, g);
-  else hipLaunchKernelGGL(ms_conv_kernel<false>, grid, dim3(256), 0, st, g);
-  if (slices > 1)
-    hipLaunchKernelGGL(ms_splitk_reduce_kernel, dim3((unsigned)((rows_out * ldy + 255) / 256)), dim3(256), 0, st, P, slices, rows_out, ldy, w.cout, w.b, R, div, Y);
-  return 0;
+// the base grid is the output level (offOut, Fo columns); the input level (offIn, F columns) differs from it only for the 5 x 5 valid conv
+inline int ms_conv(hipStream_t st, const Conv2dW& w, bool lrelu, const float* X, const int* offIn, const int* offOut, int n_utt, int F, int Fo, long rows_out, const float* R,
+                   float div, float* Y, float* P) {
+  const int slices = ms_slices(w);
+  Conv2dArgs g = conv2d_args(w);
+  g.X0 = X;
+  g.offIn = offIn;
+  g.offOut = offOut;
+  g.n_utt = n_utt;
+  g.Fin = F;
+  g.F = Fo;
+  g.rows = rows_out;
+  g.chunk = slices == 1 ? w.K : kMsSplitK;
+  g.R = R;
+  g.div = div;
+  g.Y = Y;
+  g.ldy = ms_ld(w.cout);
+  g.P = slices == 1 ? nullptr : P;
+  return conv2d_launch(st, g, lrelu, slices);
 }
 
 inline unsigned ms_grid(long n) { return (unsigned)((n + 255) / 256); }
@@ -579,14 +412,14 @@ inline int mel_style_forward(const MelStyleW& E, hipStream_t st, const Seg& s, c
     float* sc = B.learned_sc ? ws.get<float>((size_t)ro * ldo) : xp;
     STTS_CHECK(ws.ok, "mel_style_forward: workspace too small");
     // residual: conv1(lrelu(x)) [+ downsample_res]; the shortcut: avg-pool first, then the 1 x 1 conv (linear maps commute; 1/4 of its flops)
-    STTS_TRY(ms_conv(st, B.conv1, true, x, off(l), off(l), n, P.F[l], P.F[l], 1, ri, nullptr, 1.f, h1, part));
+    STTS_TRY(ms_conv(st, B.conv1, true, x, off(l), off(l), n, P.F[l], P.F[l], ri, nullptr, 1.f, h1, part));
     if (B.down) {
       hipLaunchKernelGGL(ms_dw_down_kernel, dim3(ms_grid(ro * ldi)), dim3(256), 0, st, h1, off(l), off(lo), n, P.F[l], ro, B.dw_w, B.dw_b, B.cin, ldi, hd);
       hipLaunchKernelGGL(ms_pool_half_kernel, dim3(ms_grid(ro * ldi)), dim3(256), 0, st, x, off(l), off(lo), n, P.F[l], ro, B.cin, ldi, xp);
     }
-    if (B.learned_sc) STTS_TRY(ms_conv(st, B.sc, false, xp, off(lo), off(lo), n, P.F[lo], P.F[lo], 0, ro, nullptr, 1.f, sc, part));
+    if (B.learned_sc) STTS_TRY(ms_conv(st, B.sc, false, xp, off(lo), off(lo), n, P.F[lo], P.F[lo], ro, nullptr, 1.f, sc, part));
     // out = (shortcut + conv2(lrelu(hd)) + b2) / sqrt(2)
-    STTS_TRY(ms_conv(st, B.conv2, true, hd, off(lo), off(lo), n, P.F[lo], P.F[lo], 1, ro, sc, 1.41421356237309515f, out, part));
+    STTS_TRY(ms_conv(st, B.conv2, true, hd, off(lo), off(lo), n, P.F[lo], P.F[lo], ro, sc, 1.41421356237309515f, out, part));
     if (tap) {
       STTS_HIP(hipMemcpyAsync(tap, out, (size_t)ro * ldo * sizeof(float), hipMemcpyDeviceToDevice, st));
       tap += (size_t)ro * ldo;
@@ -598,7 +431,7 @@ inline int mel_style_forward(const MelStyleW& E, hipStream_t st, const Seg& s, c
   const long r5 = P.rows(nl);
   float* h5 = ws.get<float>((size_t)r5 * ms_ld(E.c_last));
   STTS_CHECK(ws.ok, "mel_style_forward: workspace too small");
-  STTS_TRY(ms_conv(st, E.conv5, true, x, off(l), off(nl), n, P.F[l], P.F[nl], 0, r5, nullptr, 1.f, h5, part));
+  STTS_TRY(ms_conv(st, E.conv5, true, x, off(l), off(nl), n, P.F[l], P.F[nl], r5, nullptr, 1.f, h5, part));
   hipLaunchKernelGGL(ms_tail_kernel, dim3(n), dim3(256), (size_t)E.c_last * sizeof(float), st, h5, ms_ld(E.c_last), off(nl), P.F[nl], E.c_last, E.wl, E.bl,
                      E.style_dim, style_out, ld_style);
   STTS_HIP(hipGetLastError());

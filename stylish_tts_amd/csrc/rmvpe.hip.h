@@ -9,15 +9,13 @@
 // activation row of (t, f) is ((offP[u] >> l) + t) * F_l + f, rv_ld(C) = round_up(C, 16) floats with the channels contiguous and the pad channels zero.
 // Levels halve exactly, so one offset array serves every level.
 //
-// Every convolution is one kernel, rv_conv_kernel, an implicit GEMM on v_mfma_f32_16x16x4_f32: M = positions of the BASE grid, N = cout, K = taps x
-// (channels of segment 0 | channels of segment 1).  Two segments read cat(upsampled, skip) without a concat buffer.  A base position (t, f) writes the
-// output position (t * up + pt, f * up + pf): up = 1 is a plain convolution, up = 2 one of the four sub-pixel convolutions of a stride-2 transposed
-// convolution.  A contraction over frames (the GRU's input projection, the head) is the same kernel with F = 1 and one tap.
+// Every convolution is conv2d_kernel (conv2d.hip.h): the base grid and the input are the same level (offP for both row maps,
+// the level as the shift), two segments read cat(upsampled, skip), up = 2 is one of the four sub-pixel convolutions of a stride-2 transposed
+// convolution, and the GRU's input projection and the head are the same kernel with F = 1 and one tap.  rv_npad picks the tile.
 //
-// Summation: K is cut into chunks of kRvChunk = 256 in weight order; a chunk is one fp32 fmaf chain on the matrix core, and the chunk sums are added
-// in chunk order.  Shallow layers add them in the kernel (a second accumulator), layers whose base grid is level 3 or deeper run the chunks as grid
-// slices and rv_reduce_kernel adds them in the same order.  Which of the two a layer does depends on the layer only, and so does every other order of
-// operations: an utterance's result is the same bits alone and in any batch.
+// Summation: chains of kRvChunk = 256 in weight order, the chunk sums added in chunk order.  Shallow layers add them in the kernel, layers whose base
+// grid is level 3 or deeper run the chunks as grid slices and conv2d_reduce_kernel adds them in the same order.  Which of the two a layer does depends
+// on the layer only, and so does every other order of operations: an utterance's result is the same bits alone and in any batch.
 #pragma once
 
 namespace stts {
@@ -25,30 +23,18 @@ namespace stts {
 constexpr int kRvLevels = 5, kRvMels = 128, kRvClasses = 360, kRvHid = 256, kRvMaxBlocks = 8, kRvMaxInter = 8;
 constexpr int kRvChunk = 256;     // K per accumulator chain
 constexpr int kRvSplitLevel = 3;  // base grids at this level or deeper run their K chunks as grid slices
-constexpr int kRvBK = 16;
 constexpr int kRvNfft = 1024, kRvHop = 160, kRvBins = 513;
 
 inline int rv_ld(int c) { return round_up(c, 16); }
-
-#define STTS_RV_NO_PK __attribute__((target("no-packed-fp32-ops")))
-
-enum { RV_ACT_NONE = 0, RV_ACT_RELU = 1, RV_ACT_SIGMOID = 2 };
 
 struct RvDims {
   int n_blocks = 0, inter_layers = 0, c0 = 0;
 };
 
-struct RvConvW {  // packed [K][npad], K row = tap * (ld0 + ld1) + channel (segment 0 first)
-  int cout = 0, ld0 = 0, ld1 = 0, ntap = 0, npad = 0, K = 0;
-  int dt[9] = {}, df[9] = {};
-  float* w = nullptr;
-  float* b = nullptr;
-};
-
 struct RvBlockW {  // ConvBlockRes: relu(bn(conv3x3)) twice, + shortcut
   int cin = 0, cout = 0;
   bool has_sc = false;
-  RvConvW c1, c2, sc;
+  Conv2dW c1, c2, sc;
 };
 
 struct RvW {
@@ -58,27 +44,15 @@ struct RvW {
   float *w0 = nullptr, *b0 = nullptr, *wsc0 = nullptr, *bsc0 = nullptr;  // the first block's cin = 1 conv (BN folded) [c0][9] and its 1 x 1 shortcut
   RvBlockW enc[kRvLevels][kRvMaxBlocks];                                   // enc[0][0].c1 / .sc are unused (w0 / wsc0)
   RvBlockW inter[kRvMaxInter][kRvMaxBlocks];
-  RvConvW up[kRvLevels][4];                                                // decoder conv1 as four sub-pixel convolutions, parity pt * 2 + pf
+  Conv2dW up[kRvLevels][4];                                                // decoder conv1 as four sub-pixel convolutions, parity pt * 2 + pf
   RvBlockW dec[kRvLevels][kRvMaxBlocks];
-  RvConvW cnn, ih, head;
+  Conv2dW cnn, ih, head;
   float *whh = nullptr, *bhh = nullptr;  // [dir][k][768] (k-major), [dir][768]
   float* hann = nullptr;
   double2* tw = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------------ kernels
-typedef float rv_f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int rv_utt(const int* __restrict__ offP, int n_utt, int sh, int tr) {  // the utterance of time row tr of level sh
-  int lo = 0, hi = n_utt - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if ((offP[mid] >> sh) <= tr) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // offP[u] = sum over v < u of round_up(T_v, 32); one thread (n_utt is small)
 __global__ void rv_offsets_kernel(const int* __restrict__ off, int n_utt, int* __restrict__ offP) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -91,7 +65,7 @@ __global__ void rv_offsets_kernel(const int* __restrict__ off, int n_utt, int* _
 
 // The first ConvBlockRes's cin = 1 half: x = bn(mel) gathered with the reflect padding (frame p >= T reads frame 2 (T - 1) - p), zero outside the padded
 // image; H = relu(conv3x3(x) + b) (BN folded), S = wsc x + bsc (the 1 x 1 shortcut).  One thread per (row, channel).
-__global__ void __launch_bounds__(256) STTS_RV_NO_PK
+__global__ void __launch_bounds__(256) STTS_NO_PK
 rv_conv0_kernel(const float* __restrict__ mel, int ldm, const int* __restrict__ off, const int* __restrict__ offP, int n_utt, long rows, float bn_a, float bn_b,
                 const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ wsc, const float* __restrict__ bsc, int C, int ldc,
                 float* __restrict__ H, float* __restrict__ S) {
@@ -105,7 +79,7 @@ rv_conv0_kernel(const float* __restrict__ mel, int ldm, const int* __restrict__ 
     return;
   }
   const int tr = (int)(m / kRvMels), f = (int)(m - (long)tr * kRvMels);
-  const int u = rv_utt(offP, n_utt, 0, tr);
+  const int u = utt_of_row(offP, n_utt, 0, tr);
   const int t = tr - offP[u], Tp = offP[u + 1] - offP[u], T = off[u + 1] - off[u];
   const float* x = mel + (long)off[u] * ldm;
   float s = 0.f, centre = 0.f;
@@ -126,7 +100,7 @@ rv_conv0_kernel(const float* __restrict__ mel, int ldm, const int* __restrict__ 
 }
 
 // AvgPool2d(2): level l -> l + 1.  One thread per (output row, 4 channels).
-__global__ void __launch_bounds__(256) STTS_RV_NO_PK rv_pool_kernel(const float* __restrict__ X, int Fo, long rows_out, int ldc, float* __restrict__ Y) {
+__global__ void __launch_bounds__(256) STTS_NO_PK rv_pool_kernel(const float* __restrict__ X, int Fo, long rows_out, int ldc, float* __restrict__ Y) {
   const int c4n = ldc / 4;
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= rows_out * c4n) return;
@@ -145,186 +119,11 @@ __global__ void __launch_bounds__(256) STTS_RV_NO_PK rv_pool_kernel(const float*
   *reinterpret_cast<float4*>(Y + m * ldc + c) = y;
 }
 
-struct RvGemm {
-  const float* X0;  // segment 0 rows [(offP[u] >> sh) + t) * F + f][ld0]
-  const float* X1;  // segment 1 (null when ld1 == 0)
-  int ld0, ld1;
-  const int* offP;
-  int n_utt, sh, F;  // base grid: level sh, F columns
-  int ntap;
-  int dt[9], df[9];  // tap i reads base position (t + dt[i], f + df[i]); outside the utterance's grid: zero
-  int up, pt, pf;    // output position (t * up + pt, f * up + pf) of a grid up * F wide
-  long rows;         // base positions
-  const float* W;    // [K][npad]
-  int npad, N, K;
-  const float* bias;
-  int act;
-  const float* R;  // residual [output rows][ldy] or null, added after the activation
-  float* Y;
-  int ldy;
-  float* P;  // slices: partial sums [slice][base position][ldy] (the epilogue runs in rv_reduce_kernel)
-};
-
-struct RvRow {
-  int t, f, T;
-  long tr0;   // first time row of the utterance at the base level
-  long orow;  // output row
-};
-
-__device__ __forceinline__ RvRow rv_row(const RvGemm& g, long m) {
-  RvRow r;
-  const int tr = (int)(m / g.F);
-  r.f = (int)(m - (long)tr * g.F);
-  const int u = rv_utt(g.offP, g.n_utt, g.sh, tr);
-  r.tr0 = g.offP[u] >> g.sh;
-  r.t = tr - (int)r.tr0;
-  r.T = (g.offP[u + 1] >> g.sh) - (int)r.tr0;
-  r.orow = ((r.tr0 + r.t) * g.up + g.pt) * (long)(g.F * g.up) + r.f * g.up + g.pf;
-  return r;
-}
-
-__device__ __forceinline__ float rv_epilogue(const RvGemm& g, float v, int n, long orow) {
-  if (g.bias) v += g.bias[n];
-  if (g.act == RV_ACT_RELU) v = fmaxf(v, 0.f);
-  else if (g.act == RV_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
-  if (g.R) v += g.R[orow * g.ldy + n];
-  return v;
-}
-
-// grid (ceil(rows / BM), npad / BN, slices), block 256 = 4 waves as WM x WN, each MT x NT tiles of 16 x 16.  BM = 16 MT WM, BN = 16 NT WN.
-// The next K step's operands are loaded into registers while the matrix cores run the current one.
-template <int MT, int NT, int WM, int WN>
-__global__ void __launch_bounds__(256) STTS_RV_NO_PK rv_conv_kernel(RvGemm g) {
-  static_assert(WM * WN == 4, "four waves");
-  constexpr int BM = 16 * MT * WM, BN = 16 * NT * WN;
-  constexpr int RA = BM / 64;                 // A rows per thread (4 channels of each per K step)
-  constexpr int NB = (kRvBK * BN / 4 + 255) / 256;  // B float4s per thread
-  __shared__ float As[kRvBK][BM + 4];
-  __shared__ float Bs[kRvBK][BN + 4];
-  __shared__ long orow_s[BM];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long m0 = (long)blockIdx.x * BM;
-  const int n0 = blockIdx.y * BN;
-  const int akq = (tid & 3) * 4;
-  RvRow row[RA];
-  bool mval[RA];
-#pragma unroll
-  for (int j = 0; j < RA; ++j) {
-    const long m = m0 + (tid >> 2) + 64 * j;
-    mval[j] = m < g.rows;
-    row[j] = rv_row(g, mval[j] ? m : 0);
-  }
-  for (int r = tid; r < BM; r += 256) orow_s[r] = m0 + r < g.rows ? rv_row(g, m0 + r).orow : -1;
-  const int Kt = g.ld0 + g.ld1;
-  const int kb = g.P ? blockIdx.z * kRvChunk : 0, ke = g.P ? min(g.K, kb + kRvChunk) : g.K;
-  float4 ra[RA], rb[NB];
-  auto load = [&](int k0) {
-    const int tap = k0 / Kt, cc = k0 - tap * Kt;
-    const bool s1 = cc >= g.ld0;
-    const float* X = s1 ? g.X1 : g.X0;
-    const int ld = s1 ? g.ld1 : g.ld0, ci = (s1 ? cc - g.ld0 : cc) + akq;
-#pragma unroll
-    for (int j = 0; j < RA; ++j) {
-      const int ti = row[j].t + g.dt[tap], fi = row[j].f + g.df[tap];
-      ra[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (mval[j] && ti >= 0 && ti < row[j].T && fi >= 0 && fi < g.F) ra[j] = *reinterpret_cast<const float4*>(X + ((row[j].tr0 + ti) * g.F + fi) * (long)ld + ci);
-    }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int i = tid + 256 * j;
-      if (i < kRvBK * BN / 4) rb[j] = *reinterpret_cast<const float4*>(g.W + (long)(k0 + i / (BN / 4)) * g.npad + n0 + (i % (BN / 4)) * 4);
-    }
-  };
-  const int wm = (wave / WN) * MT * 16, wn = (wave % WN) * NT * 16;
-  rv_f32x4 acc[MT][NT], tot[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = tot[i][j] = rv_f32x4{0.f, 0.f, 0.f, 0.f};
-  load(kb);
-  for (int k0 = kb; k0 < ke; k0 += kRvBK) {
-    __syncthreads();  // the previous step's reads are done
-#pragma unroll
-    for (int j = 0; j < RA; ++j) {
-      const int ar = (tid >> 2) + 64 * j;
-      As[akq + 0][ar] = ra[j].x;
-      As[akq + 1][ar] = ra[j].y;
-      As[akq + 2][ar] = ra[j].z;
-      As[akq + 3][ar] = ra[j].w;
-    }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int i = tid + 256 * j;
-      if (i < kRvBK * BN / 4) *reinterpret_cast<float4*>(&Bs[i / (BN / 4)][(i % (BN / 4)) * 4]) = rb[j];
-    }
-    __syncthreads();
-    if (k0 + kRvBK < ke) load(k0 + kRvBK);
-#pragma unroll
-    for (int kk = 0; kk < kRvBK; kk += 4) {
-      const int kl = kk + (lane >> 4);
-      float av[MT], bv[NT];
-#pragma unroll
-      for (int i = 0; i < MT; ++i) av[i] = As[kl][wm + i * 16 + (lane & 15)];
-#pragma unroll
-      for (int j = 0; j < NT; ++j) bv[j] = Bs[kl][wn + j * 16 + (lane & 15)];
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-    }
-    if ((k0 + kRvBK - kb) % kRvChunk == 0 || k0 + kRvBK >= ke) {  // end of a chunk: its sum joins the total
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          tot[i][j] += acc[i][j];
-          acc[i][j] = rv_f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    }
-  }
-  // D of a 16 x 16 tile: lane l holds rows 4 (l / 16) + r, r < 4, of column l % 16
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int n = n0 + wn + j * 16 + (lane & 15);
-      if (n >= g.ldy) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int ml = wm + i * 16 + 4 * (lane >> 4) + r;
-        const long orow = orow_s[ml];
-        if (orow < 0) continue;
-        if (g.P) {
-          g.P[((long)blockIdx.z * g.rows + m0 + ml) * g.ldy + n] = tot[i][j][r];
-          continue;
-        }
-        g.Y[orow * g.ldy + n] = n < g.N ? rv_epilogue(g, tot[i][j][r], n, orow) : 0.f;
-      }
-    }
-}
-
-// the slices' sums in slice order, then the epilogue of rv_conv_kernel
-__global__ void __launch_bounds__(256) STTS_RV_NO_PK rv_reduce_kernel(RvGemm g, int slices) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const long total = g.rows * g.ldy;
-  if (i >= total) return;
-  const long m = i / g.ldy;
-  const int n = (int)(i - m * g.ldy);
-  const long orow = rv_row(g, m).orow;
-  float v = 0.f;
-  if (n < g.N) {
-    v = g.P[i];
-    for (int z = 1; z < slices; ++z) v += g.P[(long)z * total + i];
-    v = rv_epilogue(g, v, n, orow);
-  }
-  g.Y[orow * g.ldy + n] = v;
-}
-
 // GRU recurrence (torch gate order r, z, n; n = tanh(W_in x + b_in + r (W_hn h + b_hn))): one workgroup per (utterance, direction), thread j = gate row j.
 // W_hh^T is [k][768]: thread j keeps the first 128 k of its row in registers and streams the other 128 from L2 every step (786 KB of W_hh are more than a
 // CU holds); h lives in LDS.  xi = W_ih x + b_ih for every frame [frames][2 x 768].  Each dot product is one fmaf chain in k order.  No workgroup waits
 // on another.  The backward direction starts at the last PADDED frame.
-__global__ void __launch_bounds__(768) STTS_RV_NO_PK rv_gru_kernel(const float* __restrict__ xi, const int* __restrict__ offP, const float* __restrict__ WhhT,
+__global__ void __launch_bounds__(768) STTS_NO_PK rv_gru_kernel(const float* __restrict__ xi, const int* __restrict__ offP, const float* __restrict__ WhhT,
                                                                   const float* __restrict__ bhh, float* __restrict__ out) {
   constexpr int H = kRvHid, G = 3 * kRvHid, KR = 128;
   __shared__ __attribute__((aligned(16))) float h[H];
@@ -380,7 +179,7 @@ __global__ void __launch_bounds__(768) STTS_RV_NO_PK rv_gru_kernel(const float* 
 }
 
 // hidden[off[u] + t][0 .. 360) = HP[offP[u] + t][0 .. 360), t < T_u (the crop of mel2hidden); grid (ceil(max T * 360 / 256), n_utt)
-__global__ void __launch_bounds__(256) STTS_RV_NO_PK rv_crop_kernel(const float* __restrict__ HP, int ldh, const int* __restrict__ off, const int* __restrict__ offP,
+__global__ void __launch_bounds__(256) STTS_NO_PK rv_crop_kernel(const float* __restrict__ HP, int ldh, const int* __restrict__ off, const int* __restrict__ offP,
                                                        float* __restrict__ out) {
   const int u = blockIdx.y;
   const long total = (long)(off[u + 1] - off[u]) * kRvClasses;
@@ -393,7 +192,7 @@ __global__ void __launch_bounds__(256) STTS_RV_NO_PK rv_crop_kernel(const float*
 
 // to_local_average_f0: one wave per frame.  c = the first argmax bin; the salience-weighted mean of 20 i + 1997.379... cents over [c - 4, c + 5) clipped to
 // [0, 360); f0 = 10 * 2^(cents / 1200), 0 where the frame's maximum is below thred.  The nine-term sums and the power run in double (one lane).
-__global__ void __launch_bounds__(256) STTS_RV_NO_PK rv_decode_kernel(const float* __restrict__ S, int ld, long rows, float thred, float* __restrict__ f0) {
+__global__ void __launch_bounds__(256) STTS_NO_PK rv_decode_kernel(const float* __restrict__ S, int ld, long rows, float thred, float* __restrict__ f0) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
@@ -431,7 +230,7 @@ __global__ void __launch_bounds__(256) STTS_RV_NO_PK rv_decode_kernel(const floa
 }
 
 // F.interpolate(mode="linear", align_corners=True) of every utterance's curve from its L frames to its n frames; positions in double
-__global__ void __launch_bounds__(256) STTS_RV_NO_PK rv_resample_kernel(const float* __restrict__ X, const int* __restrict__ off_in, const int* __restrict__ off_out,
+__global__ void __launch_bounds__(256) STTS_NO_PK rv_resample_kernel(const float* __restrict__ X, const int* __restrict__ off_in, const int* __restrict__ off_out,
                                                            float* __restrict__ Y) {
   const int u = blockIdx.y;
   const int L = off_in[u + 1] - off_in[u], n = off_out[u + 1] - off_out[u];
@@ -449,7 +248,7 @@ __global__ void __launch_bounds__(256) STTS_RV_NO_PK rv_resample_kernel(const fl
 // Log-mel of rmvpe/spec.py (n_fft = win = 1024, hop 160, periodic Hann, center=True with reflect padding, magnitude, mel basis, log(clamp(., 1e-5))):
 // one wave per frame on the one-wave FFT of signal_geom.hip.h (H = 512, fp64), the 513 magnitudes in LDS, then mel m = the basis row's nonzero band
 // [band[2 m], band[2 m + 1]) summed in bin order.  Writes time-major rows [frame][ld_out >= 128]; lin (optional): the mel before the clamp and the log.
-__global__ void __launch_bounds__(64 * GeomFft<9>::kWaves) STTS_RV_NO_PK
+__global__ void __launch_bounds__(64 * GeomFft<9>::kWaves) STTS_NO_PK
 rv_mel_kernel(const float* __restrict__ wave, const int* __restrict__ samp_off, const int* __restrict__ mel_off, const float* __restrict__ hann,
               const double2* __restrict__ twiddle, const float* __restrict__ basis, const int* __restrict__ band, float* __restrict__ out, int ld_out,
               float* __restrict__ lin) {
@@ -527,38 +326,6 @@ inline int rv_bn(stts_ctx* c, const std::string& p, int C, std::vector<double>* 
 
 inline int rv_npad(int cout) { return cout <= 16 ? 16 : cout <= 32 ? 32 : round_up(cout, 64); }
 
-// wf(n, channel of cat(segment 0, segment 1), tap) -> the weight in double
-template <typename WF>
-inline int rv_pack(stts_ctx* c, int cout, int cin0, int cin1, int ld0, int ld1, int ntap, const int* dt, const int* df, WF wf, const std::vector<double>* bias,
-                   RvConvW* o) {
-  *o = RvConvW();
-  o->cout = cout;
-  o->ld0 = ld0;
-  o->ld1 = ld1;
-  o->ntap = ntap;
-  o->npad = rv_npad(cout);
-  o->K = ntap * (ld0 + ld1);
-  STTS_CHECK(o->K % kRvBK == 0 && ld0 % 4 == 0 && ld1 % 4 == 0 && cin0 <= ld0 && cin1 <= ld1 && ntap >= 1 && ntap <= 9, "rmvpe: a conv of %d x (%d + %d) does not pack", ntap,
-             ld0, ld1);
-  for (int i = 0; i < ntap; ++i) {
-    o->dt[i] = dt[i];
-    o->df[i] = df[i];
-  }
-  std::vector<float> pk((size_t)o->K * o->npad, 0.f);
-  for (int tap = 0; tap < ntap; ++tap)
-    for (int ci = 0; ci < cin0 + cin1; ++ci) {
-      const size_t k = (size_t)tap * (ld0 + ld1) + (ci < cin0 ? ci : ld0 + ci - cin0);
-      for (int n = 0; n < cout; ++n) pk[k * o->npad + n] = (float)wf(n, ci, tap);
-    }
-  STTS_TRY(dev_upload(c, pk, &o->w));
-  if (bias) {
-    std::vector<float> b(cout);
-    for (int n = 0; n < cout; ++n) b[n] = (float)(*bias)[n];
-    STTS_TRY(dev_upload(c, b, &o->b));
-  }
-  return 0;
-}
-
 static const int kRvDt3[9] = {-1, -1, -1, 0, 0, 0, 1, 1, 1}, kRvDf3[9] = {-1, 0, 1, -1, 0, 1, -1, 0, 1};
 static const int kRvZero[1] = {0};
 
@@ -571,13 +338,13 @@ inline int rv_get_conv(stts_ctx* c, const std::string& name, int d0, int d1, int
 }
 
 // Conv2d(cin -> cout, 3 x 3, no bias) + BatchNorm folded in double; cin = cin0 + cin1 over two segments
-inline int rv_pack_conv_bn(stts_ctx* c, const std::string& conv, const std::string& bn, int cout, int cin0, int cin1, RvConvW* o) {
+inline int rv_pack_conv_bn(stts_ctx* c, const std::string& conv, const std::string& bn, int cout, int cin0, int cin1, Conv2dW* o) {
   const HostTensor* w;
   STTS_TRY(rv_get_conv(c, conv + ".weight", cout, cin0 + cin1, 3, &w));
   std::vector<double> sc, sh;
   STTS_TRY(rv_bn(c, bn, cout, &sc, &sh));
   const int cin = cin0 + cin1;
-  return rv_pack(c, cout, cin0, cin1, rv_ld(cin0), cin1 ? rv_ld(cin1) : 0, 9, kRvDt3, kRvDf3,
+  return conv2d_pack(c, cout, rv_npad(cout), cin0, cin1, rv_ld(cin0), cin1 ? rv_ld(cin1) : 0, 9, kRvDt3, kRvDf3,
                  [&](int n, int ci, int tap) { return (double)w->data[((size_t)n * cin + ci) * 9 + tap] * sc[n]; }, &sh, o);
 }
 
@@ -595,7 +362,7 @@ inline int rv_pack_block(stts_ctx* c, const std::string& p, int cin0, int cin1, 
     STTS_GET(b, p + "shortcut.bias");
     STTS_CHECK((int)b->data.size() == cout, "%sshortcut.bias: expected %d values", p.c_str(), cout);
     std::vector<double> bb(b->data.begin(), b->data.end());
-    STTS_TRY(rv_pack(c, cout, cin0, cin1, rv_ld(cin0), cin1 ? rv_ld(cin1) : 0, 1, kRvZero, kRvZero, [&](int n, int ci, int) { return (double)w->data[(size_t)n * cin + ci]; }, &bb,
+    STTS_TRY(conv2d_pack(c, cout, rv_npad(cout), cin0, cin1, rv_ld(cin0), cin1 ? rv_ld(cin1) : 0, 1, kRvZero, kRvZero, [&](int n, int ci, int) { return (double)w->data[(size_t)n * cin + ci]; }, &bb,
                      &B->sc));
   } else {
     STTS_CHECK(!find(c, p + "shortcut.weight"), "%sshortcut is present but the block keeps its channel count", p.c_str());
@@ -691,7 +458,7 @@ inline int finalize_rmvpe(stts_ctx* c, const RvDims& d, RvW* M) {
             tdf[ntap] = dff[b];
             tk[ntap++] = kt[a] * 3 + kf[b];
           }
-        STTS_TRY(rv_pack(c, oc, dc, 0, rv_ld(dc), 0, ntap, tdt, tdf, [&](int n, int ci, int tap) { return (double)w->data[((size_t)ci * oc + n) * 9 + tk[tap]] * sc[n]; }, &sh,
+        STTS_TRY(conv2d_pack(c, oc, rv_npad(oc), dc, 0, rv_ld(dc), 0, ntap, tdt, tdf, [&](int n, int ci, int tap) { return (double)w->data[((size_t)ci * oc + n) * 9 + tk[tap]] * sc[n]; }, &sh,
                          &M->up[i][pt * 2 + pf]));
       }
     for (int b = 0; b < d.n_blocks; ++b) {
@@ -709,7 +476,7 @@ inline int finalize_rmvpe(stts_ctx* c, const RvDims& d, RvW* M) {
     STTS_GET(b, p + "cnn.bias");
     STTS_CHECK((int)b->data.size() == 3, "rmvpe.cnn.bias: expected 3 values");
     std::vector<double> bb(b->data.begin(), b->data.end());
-    STTS_TRY(rv_pack(c, 3, d.c0, 0, rv_ld(d.c0), 0, 9, kRvDt3, kRvDf3, [&](int n, int ci, int tap) { return (double)w->data[((size_t)n * d.c0 + ci) * 9 + tap]; }, &bb, &M->cnn));
+    STTS_TRY(conv2d_pack(c, 3, rv_npad(3), d.c0, 0, rv_ld(d.c0), 0, 9, kRvDt3, kRvDf3, [&](int n, int ci, int tap) { return (double)w->data[((size_t)n * d.c0 + ci) * 9 + tap]; }, &bb, &M->cnn));
   }
   // ---- BiGRU: W_ih of both directions repacked to the channels-last columns (reference feature c * 128 + f -> column f * 4 + c), W_hh transposed
   {
@@ -729,7 +496,7 @@ inline int finalize_rmvpe(stts_ctx* c, const RvDims& d, RvW* M) {
     }
     std::vector<double> bi(2 * G);
     for (int n = 0; n < 2 * G; ++n) bi[n] = bih[n / G]->data[n % G];
-    STTS_TRY(rv_pack(c, 2 * G, 4 * kRvMels, 0, 4 * kRvMels, 0, 1, kRvZero, kRvZero,
+    STTS_TRY(conv2d_pack(c, 2 * G, rv_npad(2 * G), 4 * kRvMels, 0, 4 * kRvMels, 0, 1, kRvZero, kRvZero,
                      [&](int n, int col, int) {
                        const int f = col / 4, ch = col % 4;
                        return ch < 3 ? (double)wih[n / G]->data[(size_t)(n % G) * IN + ch * kRvMels + f] : 0.0;
@@ -750,7 +517,7 @@ inline int finalize_rmvpe(stts_ctx* c, const RvDims& d, RvW* M) {
     STTS_CHECK(w->shape.size() == 2 && w->shape[0] == kRvClasses && w->shape[1] == 2 * kRvHid && (int)b->data.size() == kRvClasses, "rmvpe.fc.1: expected a Linear(%d, %d)",
                2 * kRvHid, kRvClasses);
     std::vector<double> bb(b->data.begin(), b->data.end());
-    STTS_TRY(rv_pack(c, kRvClasses, 2 * kRvHid, 0, 2 * kRvHid, 0, 1, kRvZero, kRvZero, [&](int n, int ci, int) { return (double)w->data[(size_t)n * 2 * kRvHid + ci]; }, &bb, &M->head));
+    STTS_TRY(conv2d_pack(c, kRvClasses, rv_npad(kRvClasses), 2 * kRvHid, 0, 2 * kRvHid, 0, 1, kRvZero, kRvZero, [&](int n, int ci, int) { return (double)w->data[(size_t)n * 2 * kRvHid + ci]; }, &bb, &M->head));
   }
   {  // the front end's window and twiddles
     std::vector<float> hann;
@@ -770,12 +537,12 @@ inline long rv_padded(int n_utt, const int* off) {
   return tp;
 }
 
-inline int rv_slices(const RvConvW& w, int sh) { return sh >= kRvSplitLevel && w.K > kRvChunk ? ceil_div(w.K, kRvChunk) : 1; }
+inline int rv_slices(const Conv2dW& w, int sh) { return sh >= kRvSplitLevel && w.K > kRvChunk ? ceil_div(w.K, kRvChunk) : 1; }
 
 // floats of slice scratch for Tp padded frames: the largest of every split layer (one buffer, the layers run one after the other)
 inline size_t rv_partial_floats(const RvW& M, long Tp) {
   size_t mx = 0;
-  auto need = [&](const RvConvW& w, int sh) {
+  auto need = [&](const Conv2dW& w, int sh) {
     if (rv_slices(w, sh) > 1) mx = std::max(mx, (size_t)rv_slices(w, sh) * (size_t)(Tp >> sh) * (kRvMels >> sh) * rv_ld(w.cout));
   };
   auto block = [&](const RvBlockW& B, int sh) {
@@ -815,62 +582,41 @@ struct RvRun {
 };
 
 // one convolution / contraction: base grid level sh with F columns (F = 1, sh = 0: frames)
-inline int rv_launch(const RvRun& r, const RvConvW& w, int sh, int F, int up, int pt, int pf, const float* X0, const float* X1, int act, const float* R, float* Y, int ldy) {
-  RvGemm g;
+inline int rv_launch(const RvRun& r, const Conv2dW& w, int sh, int F, int up, int pt, int pf, const float* X0, const float* X1, int act, const float* R, float* Y, int ldy) {
+  const int slices = F == 1 ? 1 : rv_slices(w, sh);
+  Conv2dArgs g = conv2d_args(w);
   g.X0 = X0;
   g.X1 = X1;
-  g.ld0 = w.ld0;
-  g.ld1 = w.ld1;
-  g.offP = r.offP;
+  g.offIn = g.offOut = r.offP;
   g.n_utt = r.n_utt;
   g.sh = sh;
-  g.F = F;
-  g.ntap = w.ntap;
-  for (int i = 0; i < 9; ++i) {
-    g.dt[i] = w.dt[i];
-    g.df[i] = w.df[i];
-  }
+  g.Fin = g.F = F;
   g.up = up;
   g.pt = pt;
   g.pf = pf;
   g.rows = (r.Tp >> sh) * F;
-  g.W = w.w;
-  g.npad = w.npad;
-  g.N = w.cout;
-  g.K = w.K;
-  g.bias = w.b;
+  g.chunk = kRvChunk;
   g.act = act;
   g.R = R;
   g.Y = Y;
   g.ldy = ldy;
-  const int slices = F == 1 ? 1 : rv_slices(w, sh);
   g.P = slices > 1 ? r.part : nullptr;
-  STTS_CHECK(slices == 1 || r.part, "rmvpe: no slice scratch");
-  STTS_CHECK(w.ld1 == 0 || X1, "rmvpe: a two-segment conv without its second input");
-  if (g.rows == 0) return 0;
-#define STTS_RV_CONV(MT, NT, WM, WN) \
-  hipLaunchKernelGGL((rv_conv_kernel<MT, NT, WM, WN>), dim3((unsigned)((g.rows + 16 * MT * WM - 1) / (16 * MT * WM)), w.npad / (16 * NT * WN), slices), dim3(256), 0, r.st, g)
-  if (w.npad == 16) STTS_RV_CONV(4, 1, 4, 1);
-  else if (w.npad == 32) STTS_RV_CONV(2, 2, 4, 1);
-  else STTS_RV_CONV(2, 2, 2, 2);
-#undef STTS_RV_CONV
-  if (slices > 1) hipLaunchKernelGGL(rv_reduce_kernel, dim3((unsigned)((g.rows * ldy + 255) / 256)), dim3(256), 0, r.st, g, slices);
-  return 0;
+  return conv2d_launch(r.st, g, false, slices);
 }
 
-inline int rv_conv3(const RvRun& r, const RvConvW& w, int l, const float* X0, const float* X1, int act, const float* R, float* Y) {
+inline int rv_conv3(const RvRun& r, const Conv2dW& w, int l, const float* X0, const float* X1, int act, const float* R, float* Y) {
   return rv_launch(r, w, l, kRvMels >> l, 1, 0, 0, X0, X1, act, R, Y, rv_ld(w.cout));
 }
 
 // ConvBlockRes at level l: x (and x1, the second segment) -> out; h and s are scratch.  out = relu(c2(relu(c1 x))) + (sc x | x)
 inline int rv_block(const RvRun& r, const RvBlockW& B, int l, const float* x, const float* x1, float* h, float* s, float* out) {
-  STTS_TRY(rv_conv3(r, B.c1, l, x, x1, RV_ACT_RELU, nullptr, h));
+  STTS_TRY(rv_conv3(r, B.c1, l, x, x1, CONV_ACT_RELU, nullptr, h));
   const float* res = x;
   if (B.has_sc) {
-    STTS_TRY(rv_conv3(r, B.sc, l, x, x1, RV_ACT_NONE, nullptr, s));
+    STTS_TRY(rv_conv3(r, B.sc, l, x, x1, CONV_ACT_NONE, nullptr, s));
     res = s;
   }
-  return rv_conv3(r, B.c2, l, h, nullptr, RV_ACT_RELU, res, out);
+  return rv_conv3(r, B.c2, l, h, nullptr, CONV_ACT_RELU, res, out);
 }
 
 // floats of the taps of Tp padded frames: enc0 .. 4 (pooled), inter, dec0 .. 4, cnn [Tp * 128][4], gru [Tp][512]
@@ -933,7 +679,7 @@ inline int rmvpe_forward(const RvW& M, hipStream_t st, int n_utt, const int* off
         const long rows = Tp * kRvMels;
         hipLaunchKernelGGL(rv_conv0_kernel, dim3((unsigned)((rows * rv_ld(C) + 255) / 256)), dim3(256), 0, st, mel, ld, off_dev, offP, n_utt, rows, M.bn_a, M.bn_b, M.w0, M.b0,
                            M.wsc0, M.bsc0, C, rv_ld(C), h, s);
-        STTS_TRY(rv_conv3(r, M.enc[0][0].c2, 0, h, nullptr, RV_ACT_RELU, s, out));
+        STTS_TRY(rv_conv3(r, M.enc[0][0].c2, 0, h, nullptr, CONV_ACT_RELU, s, out));
       } else {
         STTS_TRY(rv_block(r, M.enc[l][b], l, x, nullptr, h, s, out));
       }
@@ -958,7 +704,7 @@ inline int rmvpe_forward(const RvW& M, hipStream_t st, int n_utt, const int* off
   for (int i = 0; i < kRvLevels; ++i) {
     const int li = kRvLevels - i, lo = li - 1, C = d.c0 << lo;
     float* o = spare(2);
-    for (int q = 0; q < 4; ++q) STTS_TRY(rv_launch(r, M.up[i][q], li, kRvMels >> li, 2, q >> 1, q & 1, x, nullptr, RV_ACT_RELU, nullptr, o, rv_ld(C)));
+    for (int q = 0; q < 4; ++q) STTS_TRY(rv_launch(r, M.up[i][q], li, kRvMels >> li, 2, q >> 1, q & 1, x, nullptr, CONV_ACT_RELU, nullptr, o, rv_ld(C)));
     hold(o);
     for (int b = 0; b < d.n_blocks; ++b) {
       o = spare(2);
@@ -968,12 +714,12 @@ inline int rmvpe_forward(const RvW& M, hipStream_t st, int n_utt, const int* off
     STTS_TRY(keep(x, rv_level_floats(M, Tp, lo, C)));
   }
   // ---- cnn, BiGRU, head
-  STTS_TRY(rv_launch(r, M.cnn, 0, kRvMels, 1, 0, 0, x, nullptr, RV_ACT_NONE, nullptr, cnn, 4));
+  STTS_TRY(rv_launch(r, M.cnn, 0, kRvMels, 1, 0, 0, x, nullptr, CONV_ACT_NONE, nullptr, cnn, 4));
   STTS_TRY(keep(cnn, (size_t)Tp * kRvMels * 4));
-  STTS_TRY(rv_launch(r, M.ih, 0, 1, 1, 0, 0, cnn, nullptr, RV_ACT_NONE, nullptr, xi, 6 * kRvHid));
+  STTS_TRY(rv_launch(r, M.ih, 0, 1, 1, 0, 0, cnn, nullptr, CONV_ACT_NONE, nullptr, xi, 6 * kRvHid));
   hipLaunchKernelGGL(rv_gru_kernel, dim3(n_utt, 2), dim3(768), 0, st, xi, offP, M.whh, M.bhh, gru);
   STTS_TRY(keep(gru, (size_t)Tp * 2 * kRvHid));
-  STTS_TRY(rv_launch(r, M.head, 0, 1, 1, 0, 0, gru, nullptr, RV_ACT_SIGMOID, nullptr, hp, kRvClasses));
+  STTS_TRY(rv_launch(r, M.head, 0, 1, 1, 0, 0, gru, nullptr, CONV_ACT_SIGMOID, nullptr, hp, kRvClasses));
   int maxT = 0;
   for (int u = 0; u < n_utt; ++u) maxT = std::max(maxT, off_host[u + 1] - off_host[u]);
   float* hid = hidden_out;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-layer times of MelStyleEncoder from a rocprofv3 --kernel-trace CSV of tools/mel_style_bench.py: the engine's dispatches of one call
-come in a fixed order (csrc/mel_style.hip.h, mel_style_forward), so each call's ms_* kernels are labelled by position and averaged.
+come in a fixed order (csrc/mel_style.hip.h, mel_style_forward; the convolutions are csrc/conv2d.hip.h), so each call's ms_* and conv2d_* kernels are labelled by position and averaged.
 
     python tools/mel_style_layers.py <..._kernel_trace.csv>
 """
@@ -10,7 +10,7 @@ from collections import OrderedDict, defaultdict
 
 
 def short(name: str) -> str:
-    for k in ("ms_offsets", "ms_conv0", "ms_conv_kernel<true>", "ms_conv_kernel<false>", "ms_splitk_reduce", "ms_dw_down", "ms_pool_half", "ms_tail"):
+    for k in ("ms_offsets", "ms_conv0", "conv2d_kernel<2, 2, 2, 2, true>", "conv2d_kernel<2, 2, 2, 2, false>", "conv2d_reduce", "ms_dw_down", "ms_pool_half", "ms_tail"):
         if k in name:
             return k
     return ""
@@ -38,7 +38,7 @@ def main(path: str):
         for i, (k, gx, gy, gz) in enumerate(sig):
             us = sum(c[i][1] for c in cs) / len(cs)
             tot += us
-            print(f"  {i:2d} {k:24s} grid {gx:6d} x {gy:2d} x {gz:2d}  {us:9.1f}")
+            print(f"  {i:2d} {k:34s} grid {gx:6d} x {gy:2d} x {gz:2d}  {us:9.1f}")
         print(f"  total {tot:.1f} us")
 
 
