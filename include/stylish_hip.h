@@ -410,6 +410,34 @@ int stts_cfm_pitch_forward_taps(stts_ctx* ctx, void* stream, int n_utt, const in
                                 const float* spk_style, float* out_normed, float* out_hz, float f0_log2_mean, float f0_log2_std, const float* uv,
                                 float* taps, void* ws, size_t ws_bytes);
 
+/* ---- Log-mel front end of a recording: torchaudio.transforms.MelSpectrogram(n_mels, n_fft, win_length, hop_length, sample_rate) at its defaults
+ * (power 2, torch.stft center=True / pad_mode="reflect", periodic Hann(win_length) centred in the frame, HTK mel scale, f_min 0,
+ * f_max sample_rate / 2, norm None) followed by the reference's own arithmetic:
+ *   mel_rows = (log(1e-5 + mel) - mean) / std    calculate_mel (train/stage_type.py:1023-1032), preprocess (train/dataprep/align_text.py:112-117)
+ *   energy   = sum_m (1e-5 + mel)^0.33           log_norm of that normalised mel (train/utils.py:71-77; the mean / std cancel)
+ *   raw_rows = log(1e-5 + mel)                   what compute_log_mel_stats averages (train/utils.py:80-148)
+ * wave: packed mono audio at sample_rate, utterance u = samples [sample_off[u], sample_off[u+1]), more than n_fft / 2 of them (torch.stft refuses
+ * less); it gets row_off[u+1] - row_off[u] frames, between 1 and samples / hop_length + 1: frame f is centred on sample hop_length * f of the
+ * utterance's own reflect-padded signal.  The caller resolves the frame policy into row_off (calculate_mel: samples / hop + 1 rounded down
+ * to even; preprocess: samples / hop; all: samples / hop + 1).  mel_rows / raw_rows: time-major [rows, ld >= n_mels] (columns >= n_mels are not
+ * written) - the layout stts_mel_style_forward and stts_aligner_forward read; energy [rows].  Each of the three may be null, not all.
+ * n_fft a power of two in [256, 4096], 1 <= win_length <= n_fft, hop_length >= 1, 1 <= n_mels <= 256.  The transform, the mel sums, the log and the
+ * normalisation run in fp64 and round once to fp32.  The tables of (n_fft, win_length, n_mels, sample_rate) are built on first use and kept in
+ * the context.  Every frame's results are independent of the batch around it.  *_host / *_dev must hold the same offsets. */
+int stts_log_mel_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev,
+                         const int32_t* row_off_host, const int32_t* row_off_dev, const float* wave, int n_fft, int win_length, int hop_length, int n_mels,
+                         int sample_rate, double mean, double std, float* mel_rows, int ld, float* energy, float* raw_rows);
+/* compute_log_mel_stats (train/utils.py:80-148) over the same packed batch with ALL samples / hop_length + 1 frames of every utterance:
+ * partials [rows][2] (fp64) = each frame's sum of log(1e-5 + mel) and of its square over the mel axis; stats [3] (fp64, device) = mean, std
+ * (unbiased variance, clamped at 1e-12) and the value count rows * n_mels, reduced from the partials in a fixed order: bit-identical from run to run. */
+int stts_log_mel_stats(stts_ctx* ctx, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev,
+                       const int32_t* row_off_host, const int32_t* row_off_dev, const float* wave, int n_fft, int win_length, int hop_length, int n_mels,
+                       int sample_rate, double* partials, double* stats);
+/* The mel filters stts_log_mel_forward uses (torchaudio.functional.melscale_fbanks(n_fft / 2 + 1, 0, sample_rate // 2, n_mels, sample_rate,
+ * norm=None, mel_scale="htk"), built in float64 and rounded once to fp32), on the host: weights [n_mels][n_fft / 2 + 1], band [n_mels][2] = the
+ * nonzero bins [first, one past the last) of every filter (0, 0: an empty filter).  No context, no GPU. */
+int stts_log_mel_filters(int n_fft, int n_mels, int sample_rate, int32_t* band, float* weights);
+
 /* Layout bridge for the nn.Module shims: reference [B, C, T] (equal T) <-> time-major rows. */
 int stts_to_time_major(void* stream, const float* x_bct, int B, int C, int T, float* y, int ldy);
 int stts_to_channel_major(void* stream, const float* x, int ldx, int B, int C, int T, float* y_bct);

@@ -110,6 +110,9 @@ SIGNATURES = {
     "stts_aligner_tap_floats": (_I64, [_P, _I, _P]),
     "stts_ctc_align_workspace_bytes": (_SZ, [_I, _P, _P]),
     "stts_ctc_align": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
+    "stts_log_mel_forward": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_double, C.c_double, _P, _I, _P, _P]),
+    "stts_log_mel_stats": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "stts_log_mel_filters": (_I, [_I, _I, _I, _P, _P]),
     "stts_cfm_finalize": (_I, [_P, _P]),
     "stts_cfm_workspace_bytes": (_SZ, [_P, _I64, _I]),
     "stts_cfm_estimator": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _SZ]),

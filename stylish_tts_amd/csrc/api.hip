@@ -9,6 +9,7 @@
 #include "ssl.hip.h"
 #include "rmvpe.hip.h"
 #include "aligner.hip.h"
+#include "log_mel.hip.h"
 
 using namespace stts;
 
@@ -896,6 +897,68 @@ int stts_rmvpe_resample(stts_ctx* c, void* stream, int n_utt, const int32_t* off
   }
   STTS_HIP(hipSetDevice(c->device));
   hipLaunchKernelGGL(rv_resample_kernel, dim3(ceil_div(mx, 256), n_utt), dim3(256), 0, (hipStream_t)stream, f0_in, off_in_dev, off_out_dev, f0_out);
+  STTS_HIP(hipGetLastError());
+  return 0;
+  API_END
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ log-mel front end (log_mel.hip.h)
+extern "C" {
+
+int stts_log_mel_filters(int n_fft, int n_mels, int sample_rate, int32_t* band, float* weights) {
+  API_BEGIN
+  STTS_CHECK(band && weights, "log_mel_filters: null argument");
+  STTS_TRY(log_mel_check_geometry(n_fft, n_fft, 1, n_mels, sample_rate));
+  std::vector<int> b;
+  std::vector<float> w;
+  log_mel_filters(n_fft, n_mels, sample_rate, &b, &w);
+  std::copy(b.begin(), b.end(), band);
+  std::copy(w.begin(), w.end(), weights);
+  return 0;
+  API_END
+}
+
+static int log_mel_entry(stts_ctx* c, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const int32_t* row_off_host,
+                         const int32_t* row_off_dev, const float* wave, int n_fft, int win_length, int hop_length, int n_mels, int sample_rate, double mean, double stdv,
+                         float* mel_rows, int ld, float* energy, float* raw_rows, double* partials) {
+  STTS_CHECK(c && sample_off_dev && row_off_dev && wave, "log_mel: null argument");
+  STTS_TRY(log_mel_check_geometry(n_fft, win_length, hop_length, n_mels, sample_rate));
+  int max_fr = 0;
+  STTS_TRY(log_mel_check_offsets(n_utt, sample_off_host, row_off_host, n_fft, hop_length, &max_fr));
+  STTS_CHECK(!(mel_rows || raw_rows) || ld >= n_mels, "log_mel: ld %d < %d mel bins", ld, n_mels);
+  STTS_CHECK(std::isfinite(mean) && std::isfinite(stdv) && stdv != 0.0, "log_mel: mean %g / std %g", mean, stdv);
+  STTS_HIP(hipSetDevice(c->device));
+  const LogMelTables* t = nullptr;
+  STTS_TRY(log_mel_tables(c, n_fft, win_length, n_mels, sample_rate, &t));
+  return launch_log_mel((hipStream_t)stream, *t, n_fft, win_length, hop_length, n_mels, n_utt, max_fr, sample_off_dev, row_off_dev, wave, mean, stdv, mel_rows, ld,
+                        energy, raw_rows, partials);
+}
+
+int stts_log_mel_forward(stts_ctx* c, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const int32_t* row_off_host,
+                         const int32_t* row_off_dev, const float* wave, int n_fft, int win_length, int hop_length, int n_mels, int sample_rate, double mean, double std,
+                         float* mel_rows, int ld, float* energy, float* raw_rows) {
+  API_BEGIN
+  STTS_CHECK(mel_rows || energy || raw_rows, "log_mel: no output");
+  return log_mel_entry(c, stream, n_utt, sample_off_host, sample_off_dev, row_off_host, row_off_dev, wave, n_fft, win_length, hop_length, n_mels, sample_rate, mean, std,
+                       mel_rows, ld, energy, raw_rows, nullptr);
+  API_END
+}
+
+int stts_log_mel_stats(stts_ctx* c, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const int32_t* row_off_host,
+                       const int32_t* row_off_dev, const float* wave, int n_fft, int win_length, int hop_length, int n_mels, int sample_rate, double* partials,
+                       double* stats) {
+  API_BEGIN
+  STTS_CHECK(partials && stats, "log_mel_stats: null argument");
+  STTS_CHECK(n_utt > 0 && sample_off_host && row_off_host && hop_length >= 1, "log_mel_stats: bad offsets");
+  for (int u = 0; u < n_utt; ++u) {
+    const long n = (long)sample_off_host[u + 1] - sample_off_host[u];
+    STTS_CHECK(row_off_host[u + 1] - row_off_host[u] == n / hop_length + 1, "log_mel_stats: utterance %d must have all of its %ld frames", u, n / hop_length + 1);
+  }
+  STTS_TRY(log_mel_entry(c, stream, n_utt, sample_off_host, sample_off_dev, row_off_host, row_off_dev, wave, n_fft, win_length, hop_length, n_mels, sample_rate, 0.0, 1.0,
+                         nullptr, 0, nullptr, nullptr, partials));
+  hipLaunchKernelGGL(log_mel_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (long)row_off_host[n_utt], n_mels, stats);
   STTS_HIP(hipGetLastError());
   return 0;
   API_END

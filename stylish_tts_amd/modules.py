@@ -18,6 +18,8 @@ Reference classes mirrored (paths relative to /root/reference/src/stylish_tts/tr
   AdaptiveHubert              models/ssl.py:16-31
   RmvpePitchExtractor         dataprep/rmvpe/inference.py:12-65 (E2E0 of model.py:49-86; MelSpectrogram of spec.py:7-71)
   TextAligner                 models/text_aligner.py:16-127 (tdnn_blstm_ctc_model / CTCModel) + dataprep/align_text.py:159-210 (torch_align)
+  LogMelSpectrogram           torchaudio MelSpectrogram + calculate_mel (stage_type.py:1023-1032), preprocess (dataprep/align_text.py:112-117),
+                              log_norm / compute_log_mel_stats (utils.py:71-148)
 
 Differences, all additive: forward() of the stochastic modules takes an optional ``noise`` dict with the three draws
 the reference takes from the global torch generator (``prior_noise`` [B,128,4T], ``src_noise`` [B,1,300T],
@@ -426,6 +428,103 @@ class STFT(torch.nn.Module):
         return wave if length is None else wave[..., :length]
 
 
+class LogMelSpectrogram(torch.nn.Module):
+    """The reference's mel front end on the engine: ``torchaudio.transforms.MelSpectrogram(n_mels, n_fft, win_length, hop_length, sample_rate)`` at its
+    defaults followed by ``(log(1e-5 + mel) - mean) / std`` - calculate_mel (train/stage_type.py:1023-1032) with frames="even", preprocess
+    (train/dataprep/align_text.py:112-117) with frames="drop_last" - plus log_norm's energy curve and compute_log_mel_stats (train/utils.py:71-148).
+    Audio in at ``sample_rate`` (the engine has no resampler); ragged batches through ``lengths`` [B] samples, every utterance getting what it gets
+    alone, bit for bit.  Only torchaudio's defaults are built: HTK scale, norm None, power 2, f_min 0, f_max sample_rate / 2."""
+
+    def __init__(self, n_mels, n_fft, win_length, hop_length, sample_rate, mean=-4.0, std=4.0, frames="even", engine=None, cfg=None):
+        from . import log_mel
+
+        super().__init__()
+        log_mel.check_geometry(n_fft, win_length, hop_length, n_mels, sample_rate)
+        log_mel.frames(n_fft, hop_length, frames)  # ValueError for an unknown policy
+        self.n_mels, self.n_fft, self.win_length, self.hop_length, self.sample_rate = int(n_mels), int(n_fft), int(win_length), int(hop_length), int(sample_rate)
+        self.mean, self.std, self.frames = float(mean), float(std), frames
+        self._engine = engine
+        self._cfg = cfg
+
+    @classmethod
+    def from_config(cls, cfg, n_mels=None, **kw):
+        """The front end of a model config: its n_fft / win_length / hop_length / sample_rate, ``cfg.n_mels`` mel bins unless given (the text
+        aligner's is 80)."""
+        return cls(cfg.n_mels if n_mels is None else n_mels, cfg.n_fft, cfg.win_length, cfg.hop_length, cfg.sample_rate, cfg=cfg, **kw)
+
+    @property
+    def engine(self) -> HipModel:
+        if self._engine is None:
+            self._engine = get_engine(self._cfg, 0)
+        return self._engine
+
+    def _geom(self):
+        return self.n_fft, self.win_length, self.hop_length, self.n_mels, self.sample_rate
+
+    def _lengths(self, wave, lengths):
+        if wave.dim() != 2:
+            raise ValueError(f"audio must be [B, samples], got shape {tuple(wave.shape)}")
+        B, S = wave.shape
+        L = [S] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).tolist()]
+        if len(L) != B or any(n > S for n in L):
+            raise ValueError(f"lengths {L} do not fit a batch of {B} x {S} samples")
+        return L
+
+    def frame_counts(self, lengths, frames=None):
+        """Frames of utterances of ``lengths`` samples (host arithmetic only); ValueError for a length the transform refuses."""
+        from . import log_mel
+
+        return log_mel.frame_counts(lengths, self.n_fft, self.hop_length, self.frames if frames is None else frames)
+
+    def _run(self, wave, lengths, frames=None, mean=None, std=None, **kw):
+        L = self._lengths(wave, lengths)
+        self.frame_counts(L, frames)  # ValueError before any device work
+        eng = self.engine
+        wd = _f(wave, eng.device)
+        flat = torch.cat([wd[b, : L[b]] for b in range(len(L))]).contiguous()
+        return eng.log_mel(Segments(L, eng.device), flat, *self._geom(), mean=self.mean if mean is None else mean, std=self.std if std is None else std,
+                           frames=self.frames if frames is None else frames, **kw)
+
+    def packed(self, wave, lengths=None, **kw):
+        """wave [B, samples] -> (normalised log-mel rows [sum frames, n_mels] packed time-major on the device, their Segments): what
+        ``HipModel.mel_style`` / ``HipModel.text_aligner`` read.  Keywords: frames / mean / std override the constructor's; ld, out, energy, raw as
+        ``HipModel.log_mel``.  The host reads nothing back."""
+        return self._run(wave, lengths, **kw)
+
+    def forward(self, wave, lengths=None):
+        """wave [B, samples] -> (mel [B, n_mels, T_max], mel_length [B]), zero padded past each length (calculate_mel's return for a dense batch)."""
+        rows, seg = self._run(wave, lengths)
+        out = rows.new_zeros((seg.n, seg.max_len, self.n_mels))
+        for b in range(seg.n):
+            out[b, : seg.lengths[b]] = rows[seg.host[b] : seg.host[b + 1]]
+        return out.transpose(1, 2).contiguous(), torch.tensor(seg.lengths, dtype=torch.long, device=rows.device)
+
+    def energy(self, wave, lengths=None, packed: bool = False):
+        """log_norm(mel, mean, std) of the normalised mel (train/utils.py:71-77) = sum_m (1e-5 + mel)^0.33: energy [B, T_max] zero padded, or with
+        packed=True (rows [sum frames], Segments)."""
+        _, seg, en = self._run(wave, lengths, mel=False, energy=True)
+        if packed:
+            return en, seg
+        out = en.new_zeros((seg.n, seg.max_len))
+        for b in range(seg.n):
+            out[b, : seg.lengths[b]] = en[seg.host[b] : seg.host[b + 1]]
+        return out
+
+    def stats(self, waves, return_partials: bool = False):
+        """compute_log_mel_stats (train/utils.py:80-148) over a list of 1-D recordings at ``sample_rate`` (or a dense [B, samples] batch):
+        (mean, std, count) of log(1e-5 + mel) over every frame, reduced on the device in a fixed order."""
+        from . import log_mel
+
+        ws = [w for w in waves] if not (isinstance(waves, torch.Tensor) and waves.dim() == 1) else [waves]
+        if not ws or any(w.dim() != 1 for w in ws):
+            raise ValueError("stats takes a list of 1-D recordings or a [B, samples] batch")
+        L = [int(w.numel()) for w in ws]
+        log_mel.frame_counts(L, self.n_fft, self.hop_length, "all")
+        eng = self.engine
+        flat = torch.cat([_f(w, eng.device) for w in ws]).contiguous()
+        return eng.log_mel_stats(Segments(L, eng.device), flat, *self._geom(), return_partials=return_partials)
+
+
 class ExportModel(torch.nn.Module):
     """models/export_model.py:5-45: the inference composition (B = 1 in the reference: '1 1 l -> l')."""
 
@@ -608,6 +707,19 @@ class MelStyleEncoder(HipModule):
 
     def forward(self, x, lengths=None):
         return self.run(x, lengths)[0]
+
+    def from_audio(self, wave, lengths, mel_stats, front: Optional["LogMelSpectrogram"] = None):
+        """wave [B, samples] at the model's sample rate (lengths [B] samples, or None) -> style [B, style_dim]: the ``dim_in``-mel front end of the
+        model config (LogMelSpectrogram.from_config, frames="even"; ``front`` to give another) normalised by mel_stats = (mean, std), its packed
+        rows handed to the encoder as they are.  Equals forward() on LogMelSpectrogram.forward's output, bit for bit; no host read in between."""
+        if front is None:
+            front = LogMelSpectrogram.from_config(self.cfg, self.dim_in, mean=mel_stats[0], std=mel_stats[1])
+        if front.n_mels != self.dim_in:
+            raise ValueError(f"the front end has {front.n_mels} mel bins, the encoder takes {self.dim_in}")
+        eng = self.engine
+        front._engine = eng
+        rows, seg = front.packed(wave, lengths, mean=mel_stats[0], std=mel_stats[1])
+        return eng.mel_style(self.components, seg, rows, self.style_dim)
 
     def run(self, x, lengths=None, taps: bool = False):
         """(style, taps or None); taps = the four ResBlk outputs as lists of per-utterance [cout, F, T] tensors."""
@@ -1085,14 +1197,9 @@ class TextAligner(HipModule):
             out[: seg.lengths[b], b] = lp[seg.host[b] : seg.host[b + 1]]
         return out, None
 
-    def align(self, mels, mel_lengths, texts, text_lengths):
-        """calculate_alignments' core for a ragged batch (align_text.py:138-152): mels [B, T, n_mels] normalised log-mel, texts [B, P] token ids ->
-        (list of [3, P] float tensors (pred_dur, left, right), list of per-frame path log-probs ``scores`` [T]), all on the device.  One
-        deviation from torch_align: blank frames in front of the first token count to token 0 (the reference's loop trips its assert there).
-        ValueError where no alignment exists: fewer frames than tokens plus adjacent equal pairs."""
+    def _check_texts(self, L, texts, text_lengths):
         from . import aligner
 
-        L = self._lengths(mels, mel_lengths)
         texts = torch.as_tensor(texts)
         PL = [int(v) for v in torch.as_tensor(text_lengths).tolist()]
         if texts.dim() != 2 or len(PL) != len(L) or any(n > texts.shape[1] for n in PL):
@@ -1102,13 +1209,42 @@ class TextAligner(HipModule):
             aligner.check_alignable(L[b], tk, f"utterance {b}")
             if any(not 0 <= v < self.num_symbols for v in tk):
                 raise ValueError(f"utterance {b}: token ids must lie in [0, {self.num_symbols})")
-        lp, seg = self.packed(mels, L)
+        return toks, PL
+
+    def _align_rows(self, lp, seg, toks, PL):
         eng = self.engine
         seg_p = Segments(PL, eng.device)
         tg = torch.tensor([v for tk in toks for v in tk], dtype=torch.int32, device=eng.device)
         r = eng.ctc_align(seg, lp, seg_p, tg, self.blank)
         stack = torch.stack([r["durations"].to(torch.float32), r["left"], r["right"]])
         return ([stack[:, seg_p.host[b] : seg_p.host[b + 1]] for b in range(seg.n)], [r["scores"][seg.host[b] : seg.host[b + 1]] for b in range(seg.n)])
+
+    def align(self, mels, mel_lengths, texts, text_lengths):
+        """calculate_alignments' core for a ragged batch (align_text.py:138-152): mels [B, T, n_mels] normalised log-mel, texts [B, P] token ids ->
+        (list of [3, P] float tensors (pred_dur, left, right), list of per-frame path log-probs ``scores`` [T]), all on the device.  One
+        deviation from torch_align: blank frames in front of the first token count to token 0 (the reference's loop trips its assert there).
+        ValueError where no alignment exists: fewer frames than tokens plus adjacent equal pairs."""
+        L = self._lengths(mels, mel_lengths)
+        toks, PL = self._check_texts(L, texts, text_lengths)
+        lp, seg = self.packed(mels, L)
+        return self._align_rows(lp, seg, toks, PL)
+
+    def align_audio(self, wave, sample_lengths, texts, text_lengths, mel_stats=(-4.0, 4.0), front: Optional["LogMelSpectrogram"] = None):
+        """align() from recordings: wave [B, samples] at the model's sample rate (sample_lengths [B], or None) through preprocess's front end
+        (align_text.py:112-117: the ``n_mels``-mel transform of the model config, the last frame dropped, normalised by mel_stats = (mean, std);
+        ``front`` to give another LogMelSpectrogram), its packed rows handed to the aligner as they are.  Equals align() on that mel, bit for bit;
+        the frame counts follow from the sample counts on the host."""
+        if front is None:
+            front = LogMelSpectrogram.from_config(self.cfg, self.n_mels, mean=mel_stats[0], std=mel_stats[1], frames="drop_last")
+        if front.n_mels != self.n_mels:
+            raise ValueError(f"the front end has {front.n_mels} mel bins, the aligner takes {self.n_mels}")
+        Ls = front._lengths(wave, sample_lengths)
+        L = front.frame_counts(Ls, "drop_last")
+        toks, PL = self._check_texts(L, texts, text_lengths)
+        eng = self.engine
+        front._engine = eng
+        rows, seg = front.packed(wave, Ls, frames="drop_last", mean=mel_stats[0], std=mel_stats[1])
+        return self._align_rows(eng.text_aligner(seg, rows), seg, toks, PL)
 
 
 def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int] = None, hubert: bool = False, mel_style: bool = False,

@@ -226,16 +226,20 @@ class VoiceConverter:
     @torch.no_grad()
     def convert(self, features, lengths, spk_emb, pitch=None, energy=None, noise: Optional[Dict[str, torch.Tensor]] = None,
                 return_details: bool = False, ref_mel=None, ref_mel_lengths=None, f0_log2_stats=None, uv=None, _packed_feats=None, _packed_pitch=None,
-                _packed_uv=None):
+                _packed_uv=None, ref_wave=None, ref_wave_lengths=None, mel_stats=(-4.0, 4.0), energy_wave=None, energy_wave_lengths=None):
         """features [B, hubert_dim, T] (mel-frame rate, zero padded past lengths[b]), spk_emb [B, spk_dim]; optional pitch / energy
         [B, T] replace the predicted curves; noise: the packed draws of ``Synthesizer`` (prior_noise [4 sum T, 128], src_noise
         [4 sum T * hop / 4], init_phase [1]).  -> list of B float waveforms (hop_length samples per frame).
         ref_mel [B, n_mels, Tm] (normalised mel of the target speaker, ref_mel_lengths [B] optional): F0 comes from the CFM pitch predictor
         (cfm_pitch_predictor: STTS_W_CFM_PITCH | STTS_W_CFM_PITCH_NET on this engine) on the same features, denormed on the device with
         f0_log2_stats = (log2 mean, log2 std) of the training set, 0 where uv [B, T] > 0; energy is HubertPitchEnergyPredictor's unless
-        given."""
+        given.
+        ref_wave [B, samples] (the target speaker's recording at the model's sample rate, ref_wave_lengths [B] optional) in place of ref_mel: its
+        normalised log-mel (modules.LogMelSpectrogram.from_config, mel_stats = (mean, std) of the training set) is computed on the engine and its
+        packed rows go to the speaker encoder as they are.  energy_wave [B, samples] (the SOURCE at the model's sample rate) in place of energy:
+        the curve is LogMelSpectrogram.energy of it (log_norm, train/utils.py:71-77); its frame counts must equal ``lengths``."""
         from .config import check_width
-        from .modules import _pack_curve, _pack_rows, _f
+        from .modules import LogMelSpectrogram, _pack_curve, _pack_rows, _f
 
         eng, dev = self.eng, self.eng.device
         for m in self._modules:
@@ -250,39 +254,64 @@ class VoiceConverter:
                 raise ValueError(f"lengths {L} do not describe features of shape {tuple(features.shape)} / {spk_emb.shape[0]} speaker embeddings")
         elif spk_emb.shape[0] != len(L) or min(L) <= 0 or _packed_feats.shape[0] != sum(L):
             raise ValueError(f"lengths {L} do not describe {_packed_feats.shape[0]} packed feature rows / {spk_emb.shape[0]} speaker embeddings")
-        cfm = ref_mel is not None
+        if ref_mel is not None and ref_wave is not None:
+            raise ValueError("give ref_mel or ref_wave (its mel is computed on the engine), not both")
+        if energy is not None and energy_wave is not None:
+            raise ValueError("give energy or energy_wave (its energy curve is computed on the engine), not both")
+        front = None
+        if ref_wave is not None or energy_wave is not None:
+            front = LogMelSpectrogram.from_config(self.cfg, mean=mel_stats[0], std=mel_stats[1], engine=eng)
+        if energy_wave is not None:
+            Le = front.frame_counts(front._lengths(energy_wave, energy_wave_lengths))
+            if Le != L:
+                raise ValueError(f"energy_wave gives {Le} mel frames, lengths are {L}")
+        has_energy = energy is not None or energy_wave is not None
+        cfm = ref_mel is not None or ref_wave is not None
         if cfm:
             if pitch is not None:
                 raise ValueError("give ref_mel (F0 from the CFM pitch predictor) or pitch, not both")
             if f0_log2_stats is None:
                 raise ValueError("ref_mel needs f0_log2_stats = (log2 F0 mean, log2 F0 std) of the training set")
-            if ref_mel.dim() != 3 or ref_mel.shape[0] != len(L):
+            if ref_wave is not None:
+                if ref_wave.dim() != 2 or ref_wave.shape[0] != len(L):
+                    raise ValueError(f"ref_wave must be [{len(L)}, samples], got shape {tuple(ref_wave.shape)}")
+                front.frame_counts(front._lengths(ref_wave, ref_wave_lengths))  # ValueError for a recording the transform refuses
+            elif ref_mel.dim() != 3 or ref_mel.shape[0] != len(L):
                 raise ValueError(f"ref_mel must be [{len(L)}, n_mels, Tm], got shape {tuple(ref_mel.shape)}")
-            Lm = [ref_mel.shape[2]] * len(L) if ref_mel_lengths is None else [int(v) for v in torch.as_tensor(ref_mel_lengths).tolist()]
-            if len(Lm) != len(L) or min(Lm) < 1 or max(Lm) > ref_mel.shape[2]:
-                raise ValueError(f"ref_mel_lengths {Lm} do not fit ref_mel of shape {tuple(ref_mel.shape)}")
-        elif _packed_pitch is None and (pitch is None) != (energy is None):
+            if ref_mel is not None:
+                Lm = [ref_mel.shape[2]] * len(L) if ref_mel_lengths is None else [int(v) for v in torch.as_tensor(ref_mel_lengths).tolist()]
+                if len(Lm) != len(L) or min(Lm) < 1 or max(Lm) > ref_mel.shape[2]:
+                    raise ValueError(f"ref_mel_lengths {Lm} do not fit ref_mel of shape {tuple(ref_mel.shape)}")
+        elif _packed_pitch is None and (pitch is None) != (not has_energy):
             raise ValueError("give both pitch and energy, or neither")
         st = Segments(L, dev)
         st4 = st.scaled(4)
         feats = _pack_rows(eng, features, L) if _packed_feats is None else _packed_feats
-        style, pe_style = eng.speaker_style(_f(spk_emb, dev), pe_style=energy is None)
+        style, pe_style = eng.speaker_style(_f(spk_emb, dev), pe_style=not has_energy)
+        en_given = None
+        if energy_wave is not None:
+            en_given = front.energy(energy_wave, energy_wave_lengths, packed=True)[0]
+        elif energy is not None:
+            en_given = _pack_curve(energy, L, dev)
         if cfm:
             from .modules import W_CFM_PITCH
 
-            md = _f(ref_mel, dev)
-            mel_rows = torch.cat([md[b, :, : Lm[b]].t() for b in range(len(L))]).contiguous()
-            spk = eng.mel_style(W_CFM_PITCH, Segments(Lm, dev), mel_rows, 256)
+            if ref_wave is not None:
+                mel_rows, seg_m = front.packed(ref_wave, ref_wave_lengths)
+            else:
+                md = _f(ref_mel, dev)
+                mel_rows, seg_m = torch.cat([md[b, :, : Lm[b]].t() for b in range(len(L))]).contiguous(), Segments(Lm, dev)
+            spk = eng.mel_style(W_CFM_PITCH, seg_m, mel_rows, 256)
             uv_rows = _pack_curve(uv, L, dev) if uv is not None else _packed_uv
             _, f0 = eng.cfm_pitch(st, feats, spk, f0_log2_stats=f0_log2_stats, uv=uv_rows)
-            en = eng.hubert_pitch_energy(st, feats, pe_style)[1] if energy is None else _pack_curve(energy, L, dev)
+            en = eng.hubert_pitch_energy(st, feats, pe_style)[1] if en_given is None else en_given
         elif _packed_pitch is not None:  # convert_audio's extracted curve (packed rows); energy predicted unless given
             f0 = _packed_pitch
-            en = eng.hubert_pitch_energy(st, feats, pe_style)[1] if energy is None else _pack_curve(energy, L, dev)
+            en = eng.hubert_pitch_energy(st, feats, pe_style)[1] if en_given is None else en_given
         elif pitch is None:
             f0, en = eng.hubert_pitch_energy(st, feats, pe_style)
         else:
-            f0, en = _pack_curve(pitch, L, dev), _pack_curve(energy, L, dev)
+            f0, en = _pack_curve(pitch, L, dev), en_given
         asr = eng.hubert_encoder(st, feats)
         p4, e4 = eng.upsample4(st, st4, f0), eng.upsample4(st, st4, en)
         R = st4.rows
@@ -301,7 +330,7 @@ class VoiceConverter:
         """Voice conversion from audio: wave [B, samples] at hubert.sr (zero padded past sample_lengths[b]), frames [B] = the mel-frame count
         of every utterance (the reference's time_dim; an argument, so the host reads nothing back) -> HuBERT features on the engine
         (``ssl``: the modules.AdaptiveHubert bound to this engine, or the one among this converter's modules) written as the packed rows
-        convert() consumes, then convert() with the same keywords (pitch, energy, noise, ref_mel, ...).
+        convert() consumes, then convert() with the same keywords (pitch, energy, noise, ref_mel, ref_wave, energy_wave, ...).
         pitch_extractor (a modules.RmvpePitchExtractor; the audio must be at its 16 kHz): the source's own F0 is extracted on the engine and
         resampled to ``frames``.  Without ref_mel it becomes the pitch (energy from HubertPitchEnergyPredictor unless given); with ref_mel it
         gives the voicing flags uv = (f0 == 0), formed on the device, unless uv is given.  The host reads nothing back."""
@@ -323,7 +352,7 @@ class VoiceConverter:
                 raise ValueError(f"the pitch extractor takes audio at {pitch_extractor.sr} Hz, the content encoder at {ssl.sr} Hz")
             pitch_extractor._engine = pitch_extractor._engine or self.eng
             f0 = pitch_extractor.packed_from_audio(wave, sample_lengths, T)
-            if kw.get("ref_mel") is not None:
+            if kw.get("ref_mel") is not None or kw.get("ref_wave") is not None:
                 if kw.get("uv") is None:
                     kw["_packed_uv"] = (f0 == 0).to(torch.float32)
             else:

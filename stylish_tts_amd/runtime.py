@@ -553,6 +553,55 @@ class HipModel:
         _lib.check(self.lib.stts_rmvpe_resample(self.ctx, _stream(), seg_in.n, _ptr(seg_in.dev), seg_out.host_ptr, _ptr(seg_out.dev), _ptr(f0.contiguous()), _ptr(out)))
         return out
 
+    # ------------------------------------------------------------------ log-mel front end (packed waveforms at the model's sample rate)
+    def _log_mel_args(self, seg_s: Segments, wave: torch.Tensor, n_fft, win_length, hop_length, n_mels, sample_rate, frames):
+        from . import log_mel
+
+        log_mel.check_geometry(n_fft, win_length, hop_length, n_mels, sample_rate)
+        seg_m = Segments(log_mel.frame_counts(seg_s.lengths, int(n_fft), int(hop_length), frames), self.device)
+        wave = wave.to(self.device, torch.float32).contiguous()
+        if wave.dim() != 1 or wave.numel() != seg_s.rows:
+            raise ValueError(f"packed waveform of {wave.numel()} samples, the offsets describe {seg_s.rows}")
+        args = (self.ctx, _stream(), seg_s.n, seg_s.host_ptr, _ptr(seg_s.dev), seg_m.host_ptr, _ptr(seg_m.dev), _ptr(wave), int(n_fft), int(win_length),
+                int(hop_length), int(n_mels), int(sample_rate))
+        return seg_m, wave, args
+
+    def log_mel(self, seg_s: Segments, wave: torch.Tensor, n_fft: int, win_length: int, hop_length: int, n_mels: int, sample_rate: int, mean: float = -4.0,
+                std: float = 4.0, frames: str = "even", ld: Optional[int] = None, mel: bool = True, energy: bool = False, raw: bool = False,
+                out: Optional[torch.Tensor] = None):
+        """wave [sum samples] packed mono audio at sample_rate (utterance offsets seg_s) -> (mel rows [sum frames, ld >= n_mels] or None, their Segments
+        [, energy [sum frames]][, raw log-mel rows]): (log(1e-5 + MelSpectrogram(wave)) - mean) / std as the packed time-major rows mel_style /
+        text_aligner read, in one launch (include/stylish_hip.h, stts_log_mel_forward).  frames: "even" (calculate_mel), "drop_last" (preprocess) or "all"
+        (log_mel.frames).  out: rows to write into (columns >= n_mels keep their values).  ValueError for a geometry or a length the transform
+        refuses.  Nothing is read back by the host."""
+        seg_m, wave, args = self._log_mel_args(seg_s, wave, n_fft, win_length, hop_length, n_mels, sample_rate, frames)
+        if not (mel or energy or raw):
+            raise ValueError("log_mel: no output asked for")
+        ld = int(n_mels) if ld is None else int(ld)
+        if out is not None:
+            if out.dtype != torch.float32 or out.device != self.device or out.dim() != 2 or out.shape[0] != seg_m.rows or not out.is_contiguous():
+                raise ValueError(f"out must be contiguous float32 [{seg_m.rows}, ld] on {self.device}, got {tuple(out.shape)}")
+            ld, mel = out.shape[1], True
+        if ld < int(n_mels):
+            raise ValueError(f"ld {ld} < n_mels {n_mels}")
+        rows = out if out is not None else (self._f32(seg_m.rows, ld) if mel else None)
+        en = self._f32(seg_m.rows) if energy else None
+        rw = self._f32(seg_m.rows, ld) if raw else None
+        _lib.check(self.lib.stts_log_mel_forward(*args, float(mean), float(std), _ptr(rows), ld, _ptr(en), _ptr(rw)))
+        return (rows, seg_m) + ((en,) if energy else ()) + ((rw,) if raw else ())
+
+    def log_mel_stats(self, seg_s: Segments, wave: torch.Tensor, n_fft: int, win_length: int, hop_length: int, n_mels: int, sample_rate: int,
+                      return_partials: bool = False):
+        """compute_log_mel_stats (train/utils.py:80-148) of the packed recordings on the device, over all samples // hop + 1 frames of each:
+        (mean, std, count) as Python numbers (the one host read; include/stylish_hip.h, stts_log_mel_stats); return_partials=True appends the
+        per-frame sums [sum frames, 2] (float64, on the device) and their Segments."""
+        seg_m, wave, args = self._log_mel_args(seg_s, wave, n_fft, win_length, hop_length, n_mels, sample_rate, "all")
+        part = torch.empty(seg_m.rows, 2, dtype=torch.float64, device=self.device)
+        stats = torch.empty(3, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.stts_log_mel_stats(*args, _ptr(part), _ptr(stats)))
+        m, s, n = stats.cpu().tolist()
+        return (m, s, int(n)) + ((part, seg_m) if return_partials else ())
+
     # ------------------------------------------------------------------ text aligner + CTC forced alignment (packed normalised log-mel rows)
     def aligner_finalize(self, dims) -> None:
         """Pack the weights loaded under "text_aligner." for the dims of aligner.dims(); include/stylish_hip.h, stts_aligner_finalize."""
