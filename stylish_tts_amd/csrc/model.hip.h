@@ -914,7 +914,14 @@ inline void set_seg(GemmArgs& a, int i, const float* X, int ldx, int xcol0, cons
 struct WinoScratch {
   float* p = nullptr;
   bool setup = false;
+  int mp_kc = 0;  // > 0: every conv's M planes start behind input planes of this many columns (chained convs, winograd_bridge_kernel: conv A's M planes and conv B's input planes are live together); 0: behind the conv's own
   explicit operator bool() const { return p != nullptr; }
+};
+// which of a Winograd-form conv's three launches run: all of them, or (chained convs, winograd_bridge_kernel) the contraction with
+// its input planes already in the scratch and / or its M planes left there for the next bridge
+struct WinoForm {
+  bool planes_ready = false;  // no input transform
+  bool stop = false;          // no output transform
 };
 inline size_t wino_scratch_floats(const Seg& s, const WinoConv& wc) {
   const long pr = wino_plane_rows(s.rows(), s.n_utt);
@@ -923,7 +930,7 @@ inline size_t wino_scratch_floats(const Seg& s, const WinoConv& wc) {
 }
 template <int N>
 inline int run_winograd_n(hipStream_t st, const Seg& s, const float* X, int ldx, const WinoConv& wc, float* Y, int ldy, int act, const float* R, int ldr,
-                          float alpha, WinoScratch& scratch, const float* aff = nullptr, int ld_aff = 0, float* stat = nullptr, int ld_stat = 0) {
+                          float alpha, WinoScratch& scratch, const float* aff = nullptr, int ld_aff = 0, float* stat = nullptr, int ld_stat = 0, WinoForm form = WinoForm{}) {
   const int n = wc.mats.n, kc = wc.planes.kc, ldm = round_up(wc.planes.N, 32), ml = s.max_len();
   long pr = 0;  // rows of a component plane: the groups of 4 output rows of all utterances, packed
   for (int u = 0; u < s.n_utt; ++u) pr += ceil_div(s.host[u + 1] - s.host[u], kWinoM);
@@ -937,8 +944,9 @@ inline int run_winograd_n(hipStream_t st, const Seg& s, const float* X, int ldx,
   //  launch loses its remainder-round plan: cfg2 2 037 vs 2 145 utt/s.  STTS_X3_PRESPLIT=1 switches it on for experiments.)
   static const bool presplit_env = getenv("STTS_X3_PRESPLIT") && atoi(getenv("STTS_X3_PRESPLIT")) != 0;
   const bool presplit = presplit_env && x3_enabled() && wc.planes.w16_plane > 0 && wc.planes.prec == PREC_F32 && kc % 8 == 0;
+  STTS_CHECK(!(form.planes_ready || form.stop || scratch.mp_kc) || (!presplit && scratch.mp_kc >= kc), "winograd conv: chained form with pre-split planes or without a common plane layout");
   const long xplane = (long)n * pr_cap * kc;  // elements between two split planes
-  float* Mp = Xp + (size_t)n * pr_cap * kc * 3 / 2;
+  float* Mp = Xp + (size_t)n * pr_cap * (scratch.mp_kc ? scratch.mp_kc : kc) * 3 / 2;
   WinoIn ti;
   WinoOut to;
   memcpy(ti.Bt, wc.mats.Bt, sizeof(ti.Bt));
@@ -956,7 +964,8 @@ inline int run_winograd_n(hipStream_t st, const Seg& s, const float* X, int ldx,
     hipLaunchKernelGGL(wino_setup_kernel, dim3(1), dim3(64), 0, st, s.dev, s.n_utt, kWinoMaxN, goff, segp);
     scratch.setup = true;
   }
-  if (presplit)
+  if (form.planes_ready) {  // (a bridge wrote them)
+  } else if (presplit)
     hipLaunchKernelGGL((winograd_input_kernel<N, true>), dim3(ceil_div(groups, 4), ceil_div(kc / 4, 64), s.n_utt), dim3(64, 4), 0, st, X, ldx,
                        wc.planes.cin_real, s.dev, wc.pad, ti, Xp, kc, goff, aff, ld_aff, xplane);
   else
@@ -982,7 +991,8 @@ inline int run_winograd_n(hipStream_t st, const Seg& s, const float* X, int ldx,
     }
   }
   // stat: the output transform also leaves the AdaIN statistics of Y per chunk of kWinoStatChunk rows (wino_stat_chunks(s) chunks per utterance)
-  if (stat)
+  if (form.stop) {
+  } else if (stat)
     hipLaunchKernelGGL((winograd_output_kernel<N, true>), dim3(ceil_div(groups, 4), ceil_div(ceil_div(wc.planes.N, 4), 64), s.n_utt), dim3(64, 4), 0, st, Mp, ldm, goff,
                        s.dev, to, wc.planes.bias, act, R, ldr, alpha, Y, ldy, wc.planes.N, stat, ld_stat, ceil_div(groups, 4));
   else
@@ -999,12 +1009,56 @@ inline int run_winograd_n(hipStream_t st, const Seg& s, const float* X, int ldx,
 }
 inline int wino_stat_chunks(const Seg& s) { return ceil_div(ceil_div(s.max_len(), kWinoM), 4); }
 inline int run_winograd(hipStream_t st, const Seg& s, const float* X, int ldx, const WinoConv& wc, float* Y, int ldy, int act, const float* R, int ldr,
-                        float alpha, WinoScratch& scratch, const float* aff = nullptr, int ld_aff = 0, float* stat = nullptr, int ld_stat = 0) {
+                        float alpha, WinoScratch& scratch, const float* aff = nullptr, int ld_aff = 0, float* stat = nullptr, int ld_stat = 0, WinoForm form = WinoForm{}) {
   STTS_CHECK(wc.ready && (wc.mats.n == 8 || wc.mats.n == 12), "winograd conv not packed");
   STTS_CHECK(ldx % 4 == 0 && ldy % 4 == 0 && (!R || ldr % 4 == 0), "winograd conv: leading dimensions must be multiples of 4");
   STTS_CHECK(!stat || (ld_stat % 4 == 0 && ld_stat >= round_up(wc.planes.N, 4)), "winograd conv: statistics rows of %d floats do not cover %d channels", ld_stat, wc.planes.N);
-  return wc.mats.n == 8 ? run_winograd_n<8>(st, s, X, ldx, wc, Y, ldy, act, R, ldr, alpha, scratch, aff, ld_aff, stat, ld_stat)
-                        : run_winograd_n<12>(st, s, X, ldx, wc, Y, ldy, act, R, ldr, alpha, scratch, aff, ld_aff, stat, ld_stat);
+  return wc.mats.n == 8 ? run_winograd_n<8>(st, s, X, ldx, wc, Y, ldy, act, R, ldr, alpha, scratch, aff, ld_aff, stat, ld_stat, form)
+                        : run_winograd_n<12>(st, s, X, ldx, wc, Y, ldy, act, R, ldr, alpha, scratch, aff, ld_aff, stat, ld_stat, form);
+}
+
+// The one launch between two chained F(6,3) convs A -> AdaIN -> LeakyReLU -> B (winograd_bridge_kernel, slabs of W channels): A ran with WinoForm::stop (its M
+// planes are in the scratch), B runs with WinoForm::planes_ready.  Y = (A's output + bias [+ R]) * alpha is written only if given.  gb / gcol0 / C: the style
+// columns and channel count of the norm.  B's input columns beyond A's cout are constant columns: their chunk statistics (part, chunks of kWinoStatChunk rows,
+// wino_stat_chunks(s) per utterance) and rows (Xc) come from the caller.
+// A block holds one thread per (group, 4 channels) of its utterance: utterances of up to kWinoBridgeGroups groups (1 536 rows).
+inline bool wino_bridge_fits(const Seg& s, const WinoConv& A, const WinoConv& Bc, int W) {
+  return A.ready && Bc.ready && A.mats.n == 8 && Bc.mats.n == 8 && Bc.pad == 1 && A.planes.N % W == 0 && Bc.planes.kc % W == 0 && Bc.planes.kc >= A.planes.N &&
+         W == 16 && ceil_div(s.max_len(), kWinoM) <= kWinoBridgeGroups;
+}
+inline int run_wino_bridge(hipStream_t st, const Seg& s, const WinoConv& A, const float* R, int ldr, float alpha, float* Y, int ldy, const WinoConv& Bc,
+                           const float* gb, int ld_gb, int gcol0, int C, const float* part, int ldpart, const float* Xc, int ldxc, WinoScratch& scratch, int W) {
+  STTS_CHECK(wino_bridge_fits(s, A, Bc, W), "winograd bridge: unsupported convs or utterance length");
+  STTS_CHECK(scratch.setup && scratch.mp_kc >= Bc.planes.kc && scratch.mp_kc >= A.planes.kc, "winograd bridge: the scratch holds no planes in the common layout");
+  STTS_CHECK(Bc.planes.kc == A.planes.N || (part && Xc && ldxc % 4 == 0), "winograd bridge: constant columns without statistics or rows");
+  STTS_CHECK((!R || ldr % 4 == 0) && (!Y || ldy % 4 == 0) && C <= Bc.planes.kc && C >= A.planes.N, "winograd bridge: bad leading dimensions or channel count");
+  const long pr_cap = wino_plane_rows(s.rows(), s.n_utt);
+  WinoBridge a;
+  memset(&a, 0, sizeof(a));
+  int* segp = reinterpret_cast<int*>(scratch.p);
+  float* Xp = scratch.p + round_up(s.n_utt + 1 + 16, 32);
+  a.Mp = Xp + (size_t)A.mats.n * pr_cap * scratch.mp_kc * 3 / 2;
+  a.ldm = round_up(A.planes.N, 32);
+  a.bias = A.planes.bias; a.act = ACT_NONE; a.R = R; a.ldr = ldr; a.alpha = alpha; a.Y = Y; a.ldy = ldy; a.Nout = A.planes.N;
+  a.gb = gb; a.ld_gb = ld_gb; a.gcol0 = gcol0; a.C = C; a.eps = 1e-5f;
+  a.part = part; a.ldpart = ldpart; a.nchunk = wino_stat_chunks(s); a.Xc = Xc; a.ldxc = ldxc;
+  a.Xp = Xp; a.kc = Bc.planes.kc;
+  a.goff = segp + 16; a.seg_off = s.dev;
+  memcpy(a.to.At, A.mats.At, sizeof(a.to.At));
+  memcpy(a.ti.Bt, Bc.mats.Bt, sizeof(a.ti.Bt));
+  const dim3 grid(Bc.planes.kc / W, s.n_utt), block(std::max(256, round_up(ceil_div(s.max_len(), kWinoM) * (W / 4), 64)));
+  // measurement: the bridge is transform time of conv B - a record of B's family with no flops of its own (bench.py's roofline times a Winograd-form conv with its transforms)
+  GemmProfiler& prof = gemm_profiler();
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (prof.on) {
+    e0 = prof.next();
+    e1 = prof.next();
+    prof.add((x3_enabled() && Bc.planes.w16_plane > 0) ? "winograd_conv_x3" : "winograd_conv", 0, 0.0, 0.0, 0.0);
+  }
+  if (e0) hipExtLaunchKernelGGL((winograd_bridge_kernel<8, 16>), grid, block, 0, st, e0, e1, 0, a);
+  else hipLaunchKernelGGL((winograd_bridge_kernel<8, 16>), grid, block, 0, st, a);
+  STTS_HIP(hipGetLastError());
+  return 0;
 }
 
 inline int run_style(hipStream_t st, const StyleTable& t, const float* style, int n_utt, float* out) {
@@ -1078,6 +1132,31 @@ inline long fold_rows() {
   static const long v = getenv("STTS_FOLD_ROWS") ? atol(getenv("STTS_FOLD_ROWS")) : 2500;
   return v;
 }
+// fp32 Winograd branch of the decoder: the slab width of winograd_bridge_kernel (one launch between an AdaIN block's chained convs), or 0 for the three
+// launches (output transform with statistics, affine table, input transform).  A bridge block holds the whole time axis of its utterance, so the launch
+// pays only when (utterances x slabs) covers a good part of the chip, and stops paying once there are more blocks than the chip holds at a time (two of
+// ten waves per CU at 3-s utterances).  Rule: 96 <= utterances x (hidden_dim / 16) <= 384, i.e. 3 to 12 utterances at 512 channels, every utterance at most 1 536 rows.
+// Measured per step, three launches -> bridge, 3-s utterances, same box, same build, alternated: B = 3: 2.112 -> 2.057 ms (-2.6 %), B = 4: 2.312 -> 2.241
+// (-3.1 %), B = 6: 2.737 -> 2.665 (-2.6 %), B = 8: 3.246 -> 3.198 (-1.5 %), B = 12: 4.349 -> 4.317 (-0.7 %), B = 16: 5.538 -> 5.546 (+0.1 %: stays); cfg4
+// (256 ragged utterances, calls of more than 12): 150.0 vs 149.8 ms forced on (stays); B = 1, 2 and a single 10-s utterance never reach the Winograd
+// branch or exceed a block.  STTS_ADAIN_BRIDGE (read per call): 0 = never, 1 = wherever the kernel can run.
+constexpr int kBridgeSlab = 16;
+constexpr int kBridgeMinBlocks = 96, kBridgeMaxBlocks = 384;
+inline int adain_bridge_slab(const Seg& s, const AdainBlockW* blocks, int nblocks) {
+  const char* env = getenv("STTS_ADAIN_BRIDGE");
+  const int forced = env ? (atoi(env) != 0) : -1;
+  if (forced == 0) return 0;
+  if (getenv("STTS_X3_PRESPLIT") && atoi(getenv("STTS_X3_PRESPLIT")) != 0) return 0;  // (pre-split input planes: another layout)
+  const int slab = kBridgeSlab;
+  for (int i = 0; i < nblocks; ++i) {
+    const AdainBlockW& B = blocks[i];
+    if (!wino_bridge_fits(s, B.w1, B.w2, slab) || B.w2.planes.kc != B.cout) return 0;
+    if (i + 1 < nblocks && (!wino_bridge_fits(s, B.w2, blocks[i + 1].w1, slab) || blocks[i + 1].cin < B.cout)) return 0;
+  }
+  if (forced == 1) return slab;
+  const long nb = (long)s.n_utt * (blocks[0].cout / slab);
+  return nb >= kBridgeMinBlocks && nb <= kBridgeMaxBlocks ? slab : 0;
+}
 // A second stream for a contraction that is independent of the launches around it (run_adain_block: the learned 1x1 shortcut next to conv1), with the
 // fork / join events that order it against the caller's stream and an output buffer of its own ([rows, cout]).
 struct SideWork {
@@ -1093,6 +1172,13 @@ struct AdainStats {
   int out_ld = 0;
   bool out_ready = false;
   int chunk_rows = kStatChunk;  // kWinoStatChunk: fp32 Winograd branch, the statistics come out of the convs' output transforms (winograd_output_kernel<N, true>)
+  // fp32 Winograd branch, chained (decoder_forward, adain_bridge_slab): ONE launch between two convs (winograd_bridge_kernel) instead of output transform,
+  // affine table and input transform - the statistics never leave the block that reduces them, `mid` and `out` stay unused
+  int bridge_w = 0;                   // slab width, 0: off
+  const AdainBlockW* next = nullptr;  // the block whose conv1 consumes this block's output (null: the output transform writes y, nothing follows)
+  const float* cst = nullptr;         // chunk statistics of the next block's constant input columns (layout of `in`, cst_ld columns)
+  int cst_ld = 0;
+  bool planes_ready = false;          // the previous block's bridge has written conv1's input planes
 };
 // AdaptiveDecoderBlock (models/ada_norm.py:166-182).  x [rows, ldx] (cols >= cin may hold anything when
 // kcin == round_up(cin) because the packed weights are zero there, but AdaIN writes zeros anyway).
@@ -1155,6 +1241,7 @@ inline int run_adain_block(hipStream_t st, const Seg& s, const AdainBlockW& B, c
   // fp32 Winograd branch: every normalised tensor is the output of a Winograd conv (conv1 -> norm2, conv2 -> the next block's norm1), whose output
   // transform leaves the chunk statistics behind: the norms keep only their 64-thread affine launch (no adain_partial_kernel pass)
   const bool wstats = stats && stats->chunk_rows == kWinoStatChunk && wino1 && wino2;
+  const int bw = wstats ? stats->bridge_w : 0;
   auto affine_from = [&](const float* part, int C, int ld_aff, int gcol0, float* aff) {
     const int wch = wino_stat_chunks(s), ldp = round_up(C, 32);
     STTS_LAUNCH_PROF("adain_affine_lanes_kernel", (size_t)s.n_utt * wch * 2 * ldp * 4, adain_affine_lanes_kernel, dim3(ceil_div(ld_aff, 16), s.n_utt), dim3(256), st, part, ldp, wch, s.dev, style_out, ld_style,
@@ -1193,9 +1280,14 @@ inline int run_adain_block(hipStream_t st, const Seg& s, const AdainBlockW& B, c
   if (wino1) {
     // large batches: conv1 (k = 3) in Winograd F(6,3) form, 8 instead of 18 multiplies per 6 outputs (winograd.hip.h); AdaIN + LeakyReLU ride
     // in its input transform (an elementwise, bandwidth-bound kernel: there the affine is free, unlike in the K loop)
+    if (bw && stats->planes_ready) {  // the previous block's bridge has normalised and transformed x
+      STTS_TRY(run_winograd(st, s, nullptr, 0, B.w1, nullptr, 0, ACT_NONE, nullptr, 0, 1.0f, *wino, nullptr, 0, nullptr, 0, WinoForm{true, true}));
+    } else {
     if (wstats && stats->in_ready) affine_from(stats->in, B.cin, B.kcin, B.n1.col0, act1);
     else affine(x, ldx, B.cin, B.kcin, B.n1.col0, act1);
-    STTS_TRY(run_winograd(st, s, x, ldx, B.w1, hbuf, B.cout, ACT_NONE, nullptr, 0, 1.0f, *wino, act1, B.kcin, wstats ? stats->mid : nullptr, round_up(B.cout, 32)));
+    STTS_TRY(run_winograd(st, s, x, ldx, B.w1, hbuf, B.cout, ACT_NONE, nullptr, 0, 1.0f, *wino, act1, B.kcin, wstats && !bw ? stats->mid : nullptr, round_up(B.cout, 32),
+                          WinoForm{false, bw != 0}));
+    }
   } else {
     if (fuse_stats && gemm16_will_run(a, EPI_STORE, B.conv1.npad, s.n_utt)) {
       a.stat_part = stats->mid; a.ld_stat = round_up(B.cout, 32); a.stat_nchunk = nchunk;
@@ -1214,7 +1306,8 @@ inline int run_adain_block(hipStream_t st, const Seg& s, const AdainBlockW& B, c
     b.xaff = act2;
     b.ld_xaff = B.cout;
   } else if (wino2) {
-    if (wstats) affine_from(stats->mid, B.cout, B.cout, B.n2.col0, act2);
+    if (bw) {  // norm2 rides in the bridge below
+    } else if (wstats) affine_from(stats->mid, B.cout, B.cout, B.n2.col0, act2);
     else affine(hbuf, B.cout, B.cout, B.cout, B.n2.col0, act2);
   } else {
     STTS_TRY(run_adain(st, s, hbuf, B.cout, B.cout, act2, B.cout, style_out, ld_style, B.n2.col0, ACT_LRELU, nullptr, mid_ready ? stats->mid : ss, h16, mid_ready));
@@ -1253,6 +1346,17 @@ inline int run_adain_block(hipStream_t st, const Seg& s, const AdainBlockW& B, c
       STTS_TRY(shortcut(st, act1));
       res = act1;
       ld_res = B.cout;
+    }
+    if (bw) {
+      // conv1 -> norm2 -> conv2: contraction, bridge, contraction (conv1's output is needed by nobody else: hbuf stays unwritten); with a next block, conv2 ->
+      // its norm1 -> its conv1 the same way - that bridge writes y (+ residual, / sqrt 2), the next block's shortcut and residual input
+      STTS_TRY(run_wino_bridge(st, s, B.w1, nullptr, 0, 1.0f, nullptr, 0, B.w2, style_out, ld_style, B.n2.col0, B.cout, nullptr, 0, nullptr, 0, *wino, bw));
+      const AdainBlockW* nb = stats->next;
+      STTS_TRY(run_winograd(st, s, nullptr, 0, B.w2, y, ldy, ACT_NONE, res, ld_res, b.alpha, *wino, nullptr, 0, nullptr, 0, WinoForm{true, nb != nullptr}));
+      if (nb) STTS_TRY(run_wino_bridge(st, s, B.w2, res, ld_res, b.alpha, y, ldy, nb->w1, style_out, ld_style, nb->n1.col0, nb->cin, stats->cst, stats->cst_ld, y, ldy, *wino, bw));
+      stats->planes_ready = nb != nullptr;
+      STTS_HIP(hipGetLastError());
+      return 0;
     }
     const bool leave = wstats && stats->out;  // the statistics of y for the next block's norm1 (its hidden columns)
     STTS_TRY(run_winograd(st, s, hbuf, B.cout, B.w2, y, ldy, ACT_NONE, res, ld_res, b.alpha, *wino, act2, B.cout, leave ? stats->out : nullptr, leave ? stats->out_ld : 0));
@@ -1339,18 +1443,21 @@ inline int decoder_forward(stts_ctx* c, hipStream_t st, const Seg& s, const floa
   stats.mid = ss_mid;
   stats.out = ss_in;
   stats.out_ld = round_up(ccat, 32);
+  // one launch between the chained convs where the batch covers the chip with (utterance, slab) blocks (adain_bridge_slab); hbuf, ss_mid and the hidden columns
+  // of ss_in are then unused
+  const int bridge_w = wstat_mode ? adain_bridge_slab(s, c->dec, 5) : 0;
+  if (bridge_w) {
+    stats.bridge_w = bridge_w;
+    stats.cst = ss_in;
+    stats.cst_ld = stats.out_ld;
+    wino.mp_kc = c->dec[1].w1.planes.kc;  // (the scratch is sized by this conv)
+  }
   // small batches: a block's conv2 leaves its split-K reduce pass to the next block's first statistics launch (PendingReduce)
   PendingReduce pend;
-  STTS_TRY(run_adain_block(st, s, c->dec[0], sty, lds, enc_in, ldenc, xa, ldcat, act1, hbuf, act2, ss, 0, &wino, xs16b, false, xs16a, ldcat, use_stats ? &stats : nullptr,
-                           nullptr, &pend));
-  if (x16) {
-    cast_tail(xa, xs16a);
-    cast_tail(xb, xs16b);
-  }
-  // (once, as soon as a block has left statistics of its output: whichever block that is, the constant columns must be there before the next norm1 merges them)
   bool const_ready = false;
+  // the chunk statistics of the constant columns [asr_res | F0 | N] of every later block's input, ONCE (xa and xb hold the same constant columns)
   auto const_columns = [&]() -> int {
-    if (!stats.out_ready || const_ready) return 0;
+    if (!(stats.out_ready || bridge_w) || const_ready) return 0;
     const int nchunk = ceil_div(s.max_len(), stats.chunk_rows), cc0 = d.dec_hidden, ncst = ccat - cc0;
     STTS_CHECK(cc0 % 32 == 0, "decoder_forward: hidden_dim must be a multiple of 32");
     STTS_LAUNCH_PROF("adain_partial_kernel", (size_t)R * ncst * 4, adain_partial_kernel, dim3(ceil_div(ncst, 32), nchunk, s.n_utt), dim3(256), st, xa + cc0, ldcat, ncst, s.dev,
@@ -1358,6 +1465,18 @@ inline int decoder_forward(stts_ctx* c, hipStream_t st, const Seg& s, const floa
     const_ready = true;
     return 0;
   };
+  if (bridge_w) {  // (block 0's second bridge already merges them)
+    STTS_CHECK(c->dec[0].cout == d.dec_hidden, "decoder_forward: the blocks' width %d is not hidden_dim %d", c->dec[0].cout, d.dec_hidden);
+    STTS_TRY(const_columns());
+    stats.next = &c->dec[1];
+  }
+  STTS_TRY(run_adain_block(st, s, c->dec[0], sty, lds, enc_in, ldenc, xa, ldcat, act1, hbuf, act2, ss, 0, &wino, xs16b, false, xs16a, ldcat, use_stats ? &stats : nullptr,
+                           nullptr, &pend));
+  if (x16) {
+    cast_tail(xa, xs16a);
+    cast_tail(xb, xs16b);
+  }
+  // (once, as soon as a block has left statistics of its output: whichever block that is, the constant columns must be there before the next norm1 merges them)
   STTS_TRY(const_columns());
   float* cur = xa;
   float* nxt = xb;
@@ -1379,6 +1498,7 @@ inline int decoder_forward(stts_ctx* c, hipStream_t st, const Seg& s, const floa
       stats.in = ss_in;
       stats.in_ready = stats.out_ready;  // (the previous block's conv2 - conv_gemm16_kernel's epilogue or the fp32 Winograd output transform - left the statistics of its output)
       stats.out = i == 4 ? nullptr : ss_in;
+      stats.next = bridge_w && i < 4 ? &c->dec[i + 1] : nullptr;
       STTS_TRY(run_adain_block(st, s, c->dec[i], sty, lds, cur, ldcat, dst, ldd, act1, hbuf, act2, ss, 0, &wino, cur16, x16, i == 4 ? nullptr : nxt16, ldcat,
                                use_stats ? &stats : nullptr, &pend, &pend, side.stream ? &side : nullptr));
       std::swap(cur, nxt);

@@ -279,4 +279,226 @@ __global__ void __launch_bounds__(256) winograd_output_kernel(const float* __res
   }
 }
 
+// The three launches between two chained F(6,3) convs A -> AdaIN -> LeakyReLU -> B as ONE: winograd_output_kernel<N, true> of A, adain_affine_lanes_kernel
+// and winograd_input_kernel<N> of B.  AdaIN's statistic spans the whole utterance, so a block owns the whole time axis of W = 16 channels of one utterance
+// and nothing crosses a block: grid (kc_B / W, n_utt), block = 4 lanes of 4 channels x one thread per group of six rows (up to kWinoBridgeGroups groups =
+// 1 536 rows: longer utterances keep the three launches).  A thread forms its six rows ONCE and keeps them in registers:
+//   rows    of A from its M planes (winograd_output_kernel's expression; written to Y where the caller needs them), per-group (mean, M2), four groups
+//           merged into a 24-row chunk (winograd_output_kernel<N, true>'s formulas), the chunk table in LDS;
+//   merge   adain_affine_lanes_kernel's: chunk ch on lane ch % 16, lane sums added in lane order, mean then M2 -> scale / shift in LDS;
+//   planes  the affine and LeakyReLU of winograd_input_kernel on the rows in registers, the two halo rows of a group from its neighbours through LDS,
+//           B^T, the input planes of B.
+// Slabs at and beyond A's cout are B's constant input columns (the decoder's [asr_res | F0 | N]): their chunk statistics exist (`part`,
+// adain_partial_kernel's layout with chunks of kWinoStatChunk rows), the same merge, the rows from Xc.
+// Every value comes from the same expression in the same order as in the three kernels: the planes and Y are theirs bit for bit.
+constexpr int kWinoBridgeGroups = 256;
+struct WinoBridge {
+  const float* Mp;  // conv A: winograd_output_kernel's arguments
+  int ldm;
+  const float* bias;
+  int act;
+  const float* R;
+  int ldr;
+  float alpha;
+  float* Y;  // null: nobody else reads A's output
+  int ldy, Nout;
+  const float* gb;  // the AdaIN of B's input: adain_affine_lanes_kernel's arguments
+  int ld_gb, gcol0, C;
+  float eps;
+  const float* part;  // constant columns: their chunk statistics and rows (columns as in B's input)
+  int ldpart, nchunk;
+  const float* Xc;
+  int ldxc;
+  float* Xp;  // conv B's input planes [N][plane rows, kc]
+  int kc;
+  const int* goff;
+  const int* seg_off;
+  WinoOut to;
+  WinoIn ti;
+};
+
+template <int N>
+__device__ __forceinline__ void wino_bridge_rows(const WinoBridge& a, int lo, int len, long plane_rows, long prow, int g, int n4, bool write, f32x4 (&o)[kWinoM]) {
+  f32x4 m[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) m[j] = *reinterpret_cast<const f32x4*>(a.Mp + ((long)j * plane_rows + prow) * a.ldm + n4);
+  f32x4 b = {0.f, 0.f, 0.f, 0.f};
+  if (a.bias) b = *reinterpret_cast<const f32x4*>(a.bias + n4);
+#pragma unroll
+  for (int i = 0; i < kWinoM; ++i) {
+    const int row = g * kWinoM + i;
+    if (row < len) {
+      f32x4 v = b;
+#pragma unroll
+      for (int j = 0; j < N; ++j) v += a.to.At[i][j] * m[j];
+      f32x4 e;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) e[c] = act_apply(v[c], a.act);
+      if (a.R) e += *reinterpret_cast<const f32x4*>(a.R + (long)(lo + row) * a.ldr + n4);
+      e *= a.alpha;
+      if (write) *reinterpret_cast<f32x4*>(a.Y + (long)(lo + row) * a.ldy + n4) = e;
+      o[i] = e;
+    }
+  }
+}
+// a lane's share of adain_affine_lanes_kernel's two phases (p0: the channel's column of the chunk table, ldp floats between its mean and M2 rows)
+__device__ __forceinline__ float wino_bridge_mean_part(const float* p0, int ldp, int nch, int len, int lane) {
+  float acc = 0.f;
+#pragma unroll 4
+  for (int ch = lane; ch < nch; ch += 16) {
+    const float nc = (float)min(kWinoStatChunk, len - ch * kWinoStatChunk);
+    acc += nc * p0[(long)ch * 2 * ldp];
+  }
+  return acc;
+}
+__device__ __forceinline__ float wino_bridge_m2_part(const float* p0, int ldp, int nch, int len, int lane, float mean) {
+  float acc = 0.f;
+#pragma unroll 4
+  for (int ch = lane; ch < nch; ch += 16) {
+    const float nc = (float)min(kWinoStatChunk, len - ch * kWinoStatChunk);
+    const float* p = p0 + (long)ch * 2 * ldp;
+    const float d = p[0] - mean;
+    acc += p[ldp] + nc * d * d;
+  }
+  return acc;
+}
+
+template <int N, int W>
+__global__ void __launch_bounds__(1024) winograd_bridge_kernel(const WinoBridge a) {
+  static_assert(N == 8 && W == 16, "F(6,3), slabs of 16 channels (the merge below is adain_affine_lanes_kernel's block: 16 channels x 16 lanes)");
+  constexpr int L = W / 4;  // lanes of a group
+  __shared__ f32x4 red[2][1024];  // group (mean | M2) of every thread, later its (first | last) activated row
+  __shared__ float tab[(kWinoBridgeGroups / 4) * 2 * W];  // [chunk][mean | M2][W]
+  __shared__ float mred[16][17];
+  __shared__ float s_sc[W], s_sh[W];
+  const int u = blockIdx.y, tid = threadIdx.x;
+  const int lo = a.seg_off[u], len = a.seg_off[u + 1] - lo;
+  const int groups = (len + kWinoM - 1) / kWinoM;
+  if (groups * L > (int)blockDim.x) return;  // (uniform; the launcher sizes the block by the upper bounds of the lengths)
+  const bool cst = (int)blockIdx.x * W >= a.Nout;  // a slab of constant columns
+  const int ln = tid % L, g = tid / L;
+  const int c4 = (int)blockIdx.x * W + ln * 4;
+  const long plane_rows = a.goff[gridDim.y], prow0 = a.goff[u];
+  const bool live = g < groups;
+  f32x4 d[N];
+#pragma unroll
+  for (int q = 0; q < N; ++q) d[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (!cst) {
+    f32x4 o[kWinoM];
+#pragma unroll
+    for (int i = 0; i < kWinoM; ++i) o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (live) wino_bridge_rows<N>(a, lo, len, plane_rows, prow0 + g, g, c4, a.Y != nullptr, o);
+    const int gn = min(kWinoM, max(0, len - g * kWinoM));
+    f32x4 gmean = {0.f, 0.f, 0.f, 0.f}, gm2 = {0.f, 0.f, 0.f, 0.f};
+    if (gn > 0) {
+#pragma unroll
+      for (int i = 0; i < kWinoM; ++i) gmean += o[i];
+      gmean *= 1.0f / (float)gn;
+#pragma unroll
+      for (int i = 0; i < kWinoM; ++i) {
+        if (i < gn) {
+          const f32x4 dv = o[i] - gmean;
+          gm2 += dv * dv;
+        }
+      }
+    }
+    red[0][tid] = gmean;
+    red[1][tid] = gm2;
+    __syncthreads();
+    const int base = (g >> 2) * kWinoStatChunk;
+    if ((g & 3) == 0 && base < len) {
+      const int nrows = min(kWinoStatChunk, len - base);
+      f32x4 mean = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int w = 0; w < 4; ++w) mean += (float)min(kWinoM, max(0, len - base - w * kWinoM)) * red[0][tid + w * L];
+      mean *= 1.0f / (float)nrows;
+      f32x4 m2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const f32x4 dv = red[0][tid + w * L] - mean;
+        m2 += red[1][tid + w * L] + (float)min(kWinoM, max(0, len - base - w * kWinoM)) * dv * dv;
+      }
+      *reinterpret_cast<f32x4*>(tab + ((g >> 2) * 2) * W + ln * 4) = mean;
+      *reinterpret_cast<f32x4*>(tab + ((g >> 2) * 2 + 1) * W + ln * 4) = m2;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < kWinoM; ++i) d[i + 1] = o[i];
+  } else if (live) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      const int row = g * kWinoM - 1 + q;
+      if (row >= 0 && row < len && c4 < a.C) d[q] = *reinterpret_cast<const f32x4*>(a.Xc + (long)(lo + row) * a.ldxc + c4);
+    }
+  }
+  {  // threads 0 .. 255: adain_affine_lanes_kernel's block
+    const int cl = tid & 15, lane = (tid >> 4) & 15;
+    const bool mt = tid < 256;
+    const int nch = (len + kWinoStatChunk - 1) / kWinoStatChunk;
+    const int c = (int)blockIdx.x * W + cl;
+    const bool ok = c < a.C;
+    const float* pg = a.part + ((long)u * a.nchunk * 2) * a.ldpart + (ok ? c : 0);
+    float acc = 0.f;
+    if (mt) acc = cst ? wino_bridge_mean_part(pg, a.ldpart, nch, len, lane) : wino_bridge_mean_part(tab + cl, W, nch, len, lane);
+    if (mt) mred[lane][cl] = acc;
+    __syncthreads();
+    float mean = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mean += mred[i][cl];
+    mean /= (float)len;
+    __syncthreads();
+    if (mt) acc = cst ? wino_bridge_m2_part(pg, a.ldpart, nch, len, lane, mean) : wino_bridge_m2_part(tab + cl, W, nch, len, lane, mean);
+    if (mt) mred[lane][cl] = acc;
+    __syncthreads();
+    if (tid < 16) {
+      float sc = 0.f, sh = 0.f;
+      if (ok && len > 0) {
+        float m2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) m2 += mred[i][cl];
+        const float rstd = rsqrtf(m2 / (float)len + a.eps);
+        const float gm = a.gb[(long)u * a.ld_gb + a.gcol0 + c], be = a.gb[(long)u * a.ld_gb + a.gcol0 + a.C + c];
+        sc = rstd * (1.0f + gm);
+        sh = be - mean * sc;
+      }
+      s_sc[cl] = sc;
+      s_sh[cl] = sh;
+    }
+    __syncthreads();
+  }
+  const f32x4 sc = *reinterpret_cast<const f32x4*>(s_sc + ln * 4), sh = *reinterpret_cast<const f32x4*>(s_sh + ln * 4);
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    const int row = g * kWinoM - 1 + q;
+    const bool in = row >= 0 && row < len && c4 < a.C && (cst || (q > 0 && q < N - 1));  // (a hidden slab's halo rows come activated from the neighbours)
+    if (in) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float y = (sc[e] == 0.0f ? 0.0f : d[q][e] * sc[e]) + sh[e];
+        d[q][e] = y >= 0.0f ? y : 0.2f * y;
+      }
+    }
+    if (c4 + 3 >= a.C) {
+#pragma unroll
+      for (int e = 1; e < 4; ++e)
+        if (c4 + e >= a.C) d[q][e] = 0.0f;
+    }
+  }
+  if (!cst) {  // the row before the group is the last row of group g - 1, the row after it the first of group g + 1 (zeros outside the utterance)
+    red[0][tid] = d[1];
+    red[1][tid] = d[N - 2];
+    __syncthreads();
+    if (live && g > 0) d[0] = red[1][tid - L];
+    if (live && (g + 1) * kWinoM < len) d[N - 1] = red[0][tid + L];
+  }
+  if (!live) return;
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < N; ++q) v += a.ti.Bt[j][q] * d[q];
+    *reinterpret_cast<f32x4*>(a.Xp + ((long)j * plane_rows + prow0 + g) * a.kc + c4) = v;
+  }
+}
+
 }  // namespace stts
