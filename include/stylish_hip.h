@@ -487,6 +487,38 @@ int stts_op_conv1d(void* stream, int n_utt, const int32_t* seg_off_host, const i
 int stts_op_conv1d_x3(void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, const float* x, int ldx, int cin,
                       const float* x2, int ldx2, int cin2, const float* w_host, const float* bias_host, int cout, int k, int dil, const float* aff_host,
                       int xaff_mode, float slope, int presplit, float* y, int ldy, int force_tile, int precision);
+/* The store contraction of the 16-bit operand modes with its WHOLE epilogue (tests/test_hip_gemm16_epilogues.py):
+ *   v = (act(sum_i conv1d(x_i, w_i) + bias) + R) * alpha  ->  Y (fp32), Y16 (v rounded to the mode), GRN sums of squares, AdaIN statistics.
+ * One or two K segments, each with its own fp32 rows x_i [rows, ldx_i] (rounded to the mode by the operator; pad columns cin_i .. ldx_i
+ * may hold any finite values), host weight [cout, cin_i, k_i] (k_i odd), dilation; the packed weights have cin_i padded to 64 and cout to 256,
+ * so force_tile 19 (conv_gemm16_kernel) is eligible for any cin; other tiles: conv_gemm_f32 on 16-bit rows (5, 6, 14 - 18).
+ * Every output is optional (null) and caller-owned; *_elems is the element count of the caller's buffer: a launch that could reach
+ * beyond one of them is refused.  sumsq [utt * ss_stride + 32-row slot][ld_ss]; stat [((utt * stat_nchunk + 128-row chunk) * 2 + {mean, M2})][ld_stat]
+ * (tile 19 only).  tune: 0 or 0x4000 (conv_gemm16_kernel's generic store body).  capacity 1: seg_off_host are cumulative capacities,
+ * seg_off_dev the real offsets (STTS_SEG_CAPACITY).  precision: STTS_PREC_BF16 or _F16. */
+typedef struct stts_conv_epi_seg {
+  const float* x;
+  const float* w_host;
+  int64_t x_elems;
+  int32_t ldx, cin, k, dil;
+} stts_conv_epi_seg;
+typedef struct stts_conv_epi_args {
+  const int32_t* seg_off_host;
+  const int32_t* seg_off_dev;
+  stts_conv_epi_seg seg[2];
+  const float* bias_host;
+  const float* r;
+  float* y;
+  uint16_t* y16;
+  float* sumsq;
+  float* stat;
+  int64_t r_elems, y_elems, y16_elems, sumsq_elems, stat_elems;
+  int32_t n_utt, capacity, nseg, cout, act;
+  float alpha;
+  int32_t ldr, rcol0, ldy, ycol0, ldy16, ycol16, ld_ss, ss_stride, ld_stat, stat_nchunk;
+  int32_t force_tile, tune, precision;
+} stts_conv_epi_args;
+int stts_op_conv1d_epi(void* stream, const stts_conv_epi_args* args);
 /* AdaptiveDecoderBlock.forward (models/ada_norm.py:166-182) with weights named `prefix` + reference keys. */
 int stts_op_adain_block(stts_ctx* ctx, void* stream, const char* prefix, int n_utt, const int32_t* seg_off_host,
                         const int32_t* seg_off_dev, const float* x, int ldx, int cin, int cout, const float* style, float* y, int ldy,

@@ -51,6 +51,22 @@ _I = C.c_int
 _SZ = C.c_size_t
 _I64 = C.c_int64
 
+
+class ConvEpiSeg(C.Structure):
+    """include/stylish_hip.h: stts_conv_epi_seg (test surface)."""
+    _fields_ = [("x", _P), ("w_host", _P), ("x_elems", _I64), ("ldx", C.c_int32), ("cin", C.c_int32), ("k", C.c_int32), ("dil", C.c_int32)]
+
+
+class ConvEpiArgs(C.Structure):
+    """include/stylish_hip.h: stts_conv_epi_args (test surface)."""
+    _fields_ = ([("seg_off_host", _P), ("seg_off_dev", _P), ("seg", ConvEpiSeg * 2)]
+                + [(n, _P) for n in ("bias_host", "r", "y", "y16", "sumsq", "stat")]
+                + [(n, _I64) for n in ("r_elems", "y_elems", "y16_elems", "sumsq_elems", "stat_elems")]
+                + [(n, C.c_int32) for n in ("n_utt", "capacity", "nseg", "cout", "act")]
+                + [("alpha", C.c_float)]
+                + [(n, C.c_int32) for n in ("ldr", "rcol0", "ldy", "ycol0", "ldy16", "ycol16", "ld_ss", "ss_stride", "ld_stat", "stat_nchunk",
+                                            "force_tile", "tune", "precision")])
+
 # name -> (restype, argtypes); mirrors include/stylish_hip.h one to one
 SIGNATURES = {
     "stts_last_error": (C.c_char_p, []),
@@ -130,6 +146,7 @@ TEST_SIGNATURES = {
     "stts_bench_gemm": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_double), _I]),
     "stts_op_conv1d": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I]),
     "stts_op_conv1d_x3": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I, C.c_float, _I, _P, _I, _I, _I]),
+    "stts_op_conv1d_epi": (_I, [_P, C.POINTER(ConvEpiArgs)]),
     "stts_op_adain_block": (_I, [_P, _P, C.c_char_p, _I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _SZ]),
     "stts_op_attention": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I]),
     "stts_op_stft_geom": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I]),

@@ -135,6 +135,101 @@ int stts_op_conv1d_x3(void* stream, int n_utt, const int32_t* seg_off_host, cons
   API_END
 }
 
+// The store contraction of the 16-bit operand modes with every epilogue feature under the caller's control (include/stylish_hip.h).  Follows the 16-bit
+// branch of stts_op_conv1d; weights are packed with cin padded to 64 and cout to 256 (plain_rows pads to 128, which would make cout = 384 ineligible
+// for conv_gemm16_kernel).  Every buffer the launch may touch is checked against the caller's element counts BEFORE anything is launched.
+int stts_op_conv1d_epi(void* stream, const stts_conv_epi_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p && p->seg_off_host && p->seg_off_dev && p->n_utt > 0, "op_conv1d_epi: null / empty argument");
+  STTS_CHECK(p->precision == PREC_BF16 || p->precision == PREC_F16, "op_conv1d_epi: precision must be STTS_PREC_BF16 or _F16");
+  STTS_CHECK(p->nseg == 1 || p->nseg == 2, "op_conv1d_epi: one or two K segments");
+  STTS_CHECK(p->cout > 0 && p->act >= ACT_NONE && p->act <= ACT_LRELU, "op_conv1d_epi: cout / act out of range");
+  STTS_CHECK(p->tune == 0 || p->tune == 0x4000, "op_conv1d_epi: tune is 0 or 0x4000");
+  STTS_CHECK(find_tile(p->force_tile) || p->force_tile == 19, "op_conv1d_epi: force_tile must name a tile");
+  STTS_CHECK(p->y || p->y16, "op_conv1d_epi: no output rows requested");
+  const int n_utt = p->n_utt, N = p->cout;
+  // offsets: non-decreasing on both sides; capacity: the real offsets (read back here, the operator is no hot path) lie inside the capacities
+  std::vector<int> dev(n_utt + 1);
+  STTS_HIP(hipStreamSynchronize(st));
+  STTS_HIP(hipMemcpy(dev.data(), p->seg_off_dev, dev.size() * sizeof(int), hipMemcpyDeviceToHost));
+  STTS_CHECK(p->seg_off_host[0] == 0 && dev[0] == 0, "op_conv1d_epi: offsets start at 0");
+  for (int u = 0; u < n_utt; ++u) {
+    const int cap = p->seg_off_host[u + 1] - p->seg_off_host[u], len = dev[u + 1] - dev[u];
+    STTS_CHECK(cap >= 0 && len >= 0 && len <= cap && dev[u] <= p->seg_off_host[u], "op_conv1d_epi: utterance %d: %d rows at %d, capacity %d at %d", u, len, dev[u], cap,
+               p->seg_off_host[u]);
+    STTS_CHECK(p->capacity || (len == cap && dev[u] == p->seg_off_host[u]), "op_conv1d_epi: host and device offsets differ without the capacity flag (utterance %d)", u);
+  }
+  Seg s{n_utt, p->seg_off_host, p->seg_off_dev, p->capacity != 0};
+  const long R = s.rows();
+  const int max_len = s.max_len();
+  STTS_CHECK(R > 0, "op_conv1d_epi: no rows");
+  const int npad = round_up(N, 256);
+  // the widest row the kernels may touch: conv_gemm16_kernel prefetches the residual over the whole 256-channel tile (columns >= N are read, not used)
+  // (`touched` columns of the last row must still lie inside the buffer; the window itself inside a row)
+  auto fits = [&](long elems, int ld, int col0, int touched) { return col0 >= 0 && ld >= col0 + N && (R - 1) * ld + col0 + touched <= elems; };
+  STTS_CHECK(!p->y || fits(p->y_elems, p->ldy, p->ycol0, N), "op_conv1d_epi: Y window [%d, %d) x %ld rows outside ldy %d / %ld elements", p->ycol0, p->ycol0 + N, R, p->ldy,
+             (long)p->y_elems);
+  STTS_CHECK(!p->y16 || fits(p->y16_elems, p->ldy16, p->ycol16, N), "op_conv1d_epi: Y16 window outside its buffer");
+  STTS_CHECK(!p->r || fits(p->r_elems, p->ldr, p->rcol0, p->force_tile == 19 ? npad : N), "op_conv1d_epi: residual window (tile 19 reads whole 256-channel tiles) outside its buffer");
+  STTS_CHECK(!p->sumsq || (p->ld_ss >= N && p->ss_stride >= ceil_div(max_len, 32) && (long)n_utt * p->ss_stride * p->ld_ss <= p->sumsq_elems),
+             "op_conv1d_epi: sumsq_part needs ld_ss >= cout, ss_stride >= ceil(max_len / 32) and n_utt * ss_stride * ld_ss elements");
+  STTS_CHECK(!p->stat || p->force_tile == 19, "op_conv1d_epi: output statistics exist only on tile 19 (conv_gemm16_kernel)");
+  STTS_CHECK(!p->stat || (p->ld_stat >= N && p->stat_nchunk >= ceil_div(max_len, 128) && (long)n_utt * p->stat_nchunk * 2 * p->ld_stat <= p->stat_elems),
+             "op_conv1d_epi: stat_part needs ld_stat >= cout, stat_nchunk >= ceil(max_len / 128) and n_utt * stat_nchunk * 2 * ld_stat elements");
+  // (conv_gemm16_kernel stores and loads four channels at a time: gemm_plan.hip.h gemm16_eligible, asked here so that a refusal comes before the row cast)
+  STTS_CHECK(p->force_tile != 19 || (N % 4 == 0 && p->ldy % 4 == 0 && p->ycol0 % 4 == 0 && p->ldy16 % 4 == 0 && p->ycol16 % 4 == 0 && p->ldr % 4 == 0 && p->rcol0 % 4 == 0 &&
+                                     p->ld_ss % 4 == 0 && p->ld_stat % 4 == 0),
+             "op_conv1d_epi: tile 19 needs cout, every leading dimension and every first column in multiples of 4");
+  for (int i = 0; i < p->nseg; ++i) {
+    const stts_conv_epi_seg& g = p->seg[i];
+    STTS_CHECK(g.x && g.w_host && g.cin > 0 && g.k > 0 && g.k % 2 == 1 && g.dil > 0, "op_conv1d_epi: segment %d: null operand, or k not odd", i);
+    STTS_CHECK(g.ldx % 32 == 0 && g.ldx >= round_up(g.cin, 64) && R * g.ldx <= g.x_elems, "op_conv1d_epi: segment %d: ldx must be a multiple of 32 covering cin padded to 64, x [rows, ldx]", i);
+  }
+  stts_ctx tmp;  // only for allocation bookkeeping
+  tmp.prec = p->precision;
+  tmp.allow_x3 = false;
+  PackScope scope(&tmp, engine_mode(&tmp));
+  struct FreeAll {  // every exit path waits for the stream and frees the temporaries
+    stts_ctx& t;
+    hipStream_t st;
+    ~FreeAll() {
+      (void)hipStreamSynchronize(st);
+      for (void* q : t.allocs) (void)hipFree(q);
+    }
+  } free_all{tmp, st};
+  std::vector<int> rows256(npad, -1);
+  for (int i = 0; i < N; ++i) rows256[i] = i;
+  HostTensor b;
+  b.shape = {N};
+  if (p->bias_host) b.data.assign(p->bias_host, p->bias_host + N);
+  PackedConv pc[2];
+  GemmArgs a = gemm_args(s);
+  for (int i = 0; i < p->nseg; ++i) {
+    const stts_conv_epi_seg& g = p->seg[i];
+    HostTensor w;
+    w.shape = {N, g.cin, g.k};
+    w.data.assign(g.w_host, g.w_host + (size_t)N * g.cin * g.k);
+    STTS_TRY(pack_rows(&tmp, w, (i == 0 && p->bias_host) ? &b : nullptr, rows256, 0, g.cin, round_up(g.cin, 64), N, &pc[i]));
+    unsigned short* x16 = nullptr;
+    STTS_HIP(hipMalloc(&x16, (size_t)R * g.ldx * sizeof(unsigned short)));
+    tmp.allocs.push_back(x16);
+    launch_cast_rows(st, p->precision, g.x, g.ldx, g.ldx, x16, g.ldx, R);
+    set_seg(a, i, reinterpret_cast<const float*>(x16), g.ldx, 0, pc[i], (g.k - 1) / 2, g.dil);
+  }
+  a.x16 = 1;
+  a.N = N; a.bias = pc[0].bias; a.act = p->act; a.alpha = p->alpha; a.tune = p->tune;
+  a.Y = p->y; a.ldy = p->ldy; a.ycol0 = p->ycol0;
+  a.Y16 = p->y16; a.ldy16 = p->ldy16; a.ycol16 = p->ycol16;
+  a.R = p->r; a.ldr = p->ldr; a.rcol0 = p->rcol0;
+  a.sumsq_part = p->sumsq; a.ld_ss = p->ld_ss; a.ss_stride = p->ss_stride;
+  a.stat_part = p->stat; a.ld_stat = p->ld_stat; a.stat_nchunk = p->stat_nchunk;
+  STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, npad, n_utt, max_len, p->force_tile));
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
 static int op_scratch(Arena& a, const Seg& s, int kc, int cout, float** act1, float** h, float** act2, float** ss, float** sty, int ld_sty) {
   const long R = s.rows();
   const int n_utt = s.n_utt;

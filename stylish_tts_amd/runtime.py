@@ -258,6 +258,46 @@ class HipModel:
                                               force_tile, self.PRECISIONS[precision or self.precision]))
         return y
 
+    def op_conv1d_epi(self, seg: Segments, segments, bias: Optional[np.ndarray], precision: str, force_tile: int, act=0, alpha=1.0, r=None, rcol0=0,
+                      y=None, ycol0=0, y16=None, ycol16=0, sumsq=None, stat=None, tune=0):
+        """stts_op_conv1d_epi: the 16-bit store contraction with its whole epilogue, written INTO the caller's tensors (nothing is allocated or cleared
+        here, so a test can pre-fill them with a sentinel).  segments: one or two (x [rows, ldx] fp32, cin, w [cout, cin, k], dil); r / y fp32
+        [rows, ld], y16 int16 [rows, ld] (the mode's bit patterns), sumsq fp32 [n_utt, ss_stride, ld_ss], stat fp32 [n_utt, nchunk, 2, ld_stat].
+        A capacity `seg` (host = cumulative capacities, dev = real offsets) sets the capacity flag."""
+        a = _lib.ConvEpiArgs()
+        keep = []
+        a.seg_off_host, a.seg_off_dev = seg.host_ptr, _ptr(seg.dev)
+        a.n_utt, a.capacity, a.nseg = seg.n, int(seg.is_capacity), len(segments)
+        a.cout = int(segments[0][2].shape[0])
+        for i, (x, cin, w, dil) in enumerate(segments):
+            assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2 and w.shape[0] == a.cout and w.shape[1] == cin
+            w = np.ascontiguousarray(w, np.float32)
+            keep.append(w)
+            s = a.seg[i]
+            s.x, s.w_host, s.x_elems = _ptr(x), w.ctypes.data_as(C.c_void_p), x.numel()
+            s.ldx, s.cin, s.k, s.dil = x.shape[1], cin, w.shape[2], dil
+        if bias is not None:
+            b = np.ascontiguousarray(bias, np.float32)
+            assert b.shape == (a.cout,)
+            keep.append(b)
+            a.bias_host = b.ctypes.data_as(C.c_void_p)
+        a.act, a.alpha, a.force_tile, a.tune, a.precision = act, alpha, force_tile, tune, self.PRECISIONS[precision]
+        for t, dt in ((r, torch.float32), (y, torch.float32), (y16, torch.int16), (sumsq, torch.float32), (stat, torch.float32)):
+            assert t is None or (t.dtype == dt and t.is_contiguous() and t.is_cuda)
+        if r is not None:
+            a.r, a.r_elems, a.ldr, a.rcol0 = _ptr(r), r.numel(), r.shape[1], rcol0
+        if y is not None:
+            a.y, a.y_elems, a.ldy, a.ycol0 = _ptr(y), y.numel(), y.shape[1], ycol0
+        if y16 is not None:
+            a.y16, a.y16_elems, a.ldy16, a.ycol16 = _ptr(y16), y16.numel(), y16.shape[1], ycol16
+        if sumsq is not None:
+            assert sumsq.dim() == 3 and sumsq.shape[0] == seg.n
+            a.sumsq, a.sumsq_elems, a.ss_stride, a.ld_ss = _ptr(sumsq), sumsq.numel(), sumsq.shape[1], sumsq.shape[2]
+        if stat is not None:
+            assert stat.dim() == 4 and stat.shape[0] == seg.n and stat.shape[2] == 2
+            a.stat, a.stat_elems, a.stat_nchunk, a.ld_stat = _ptr(stat), stat.numel(), stat.shape[1], stat.shape[3]
+        _lib.check(self.lib.stts_op_conv1d_epi(_stream(), C.byref(a)))
+
     def op_adain_block(self, prefix: str, seg: Segments, x, cin, cout, style):
         y = self._f32(seg.rows, cout)
         ws = self.workspace(seg)

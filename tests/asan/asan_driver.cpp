@@ -16,6 +16,7 @@
 // `asan_driver <weights> gemm` prints the gemmtrace lines only (no finalize): the STTS_* switches of the contractions are read once per process, so
 // tests/asan/build_and_run.py starts one process per setting.
 #include <algorithm>
+#include <array>
 #include <cinttypes>
 #include <cstdint>
 #include <cstdio>
@@ -279,6 +280,79 @@ static void gemm_section() {
   }
 }
 
+// stts_op_conv1d_epi (the store contraction of the 16-bit modes with its whole epilogue, tests/test_hip_gemm16_epilogues.py): its host side - the argument
+// checks against the caller's element counts, the 256-row packing of each segment, the offsets read back in capacity mode - on three launches that must go
+// through and on the combinations it must refuse BEFORE anything is launched.  `epitrace <case> : [error ]<trace>`.
+static void epi_case(const char* what, int prec, int tile, const std::vector<int>& caps, const std::vector<int>& lens, std::vector<std::array<int, 3>> segs, int cout,
+                     int ldy, int ycol0, int ldy16, int ycol16, int ldr, int rcol0, bool ss, int ld_stat, int shrink = 0) {
+  const int n = (int)lens.size();
+  const bool capacity = caps != lens;
+  std::vector<int32_t> host(n + 1, 0), dev(n + 1, 0);
+  int max_len = 0;
+  for (int i = 0; i < n; ++i) {
+    host[i + 1] = host[i] + caps[i];
+    dev[i + 1] = dev[i] + lens[i];
+    max_len = std::max(max_len, caps[i]);
+  }
+  const long R = host[n];
+  stts_conv_epi_args a;
+  memset(&a, 0, sizeof(a));
+  std::vector<std::vector<float>> keep;
+  a.seg_off_host = host.data();
+  a.seg_off_dev = dev.data();
+  a.n_utt = n;
+  a.capacity = capacity;
+  a.nseg = (int)segs.size();
+  a.cout = cout;
+  a.alpha = 0.5f;
+  a.force_tile = tile;
+  a.precision = prec;
+  for (int i = 0; i < a.nseg; ++i) {
+    const int cin = segs[i][0], k = segs[i][1], ldx = (cin + 63) / 64 * 64;
+    keep.push_back(buf(R * ldx));
+    a.seg[i].x = keep.back().data();
+    a.seg[i].x_elems = R * ldx;
+    keep.push_back(buf((size_t)cout * cin * k));
+    a.seg[i].w_host = keep.back().data();
+    a.seg[i].ldx = ldx; a.seg[i].cin = cin; a.seg[i].k = k; a.seg[i].dil = segs[i][2];
+  }
+  auto bias = buf(cout);
+  a.bias_host = bias.data();
+  std::vector<float> y, r, sums, stat;
+  std::vector<uint16_t> y16;
+  if (ldy) { y.assign(R * ldy - shrink, 0.f); a.y = y.data(); a.y_elems = (int64_t)y.size(); a.ldy = ldy; a.ycol0 = ycol0; }
+  if (ldy16) { y16.assign(R * ldy16, 0); a.y16 = y16.data(); a.y16_elems = (int64_t)y16.size(); a.ldy16 = ldy16; a.ycol16 = ycol16; }
+  if (ldr) { r = buf(R * ldr); a.r = r.data(); a.r_elems = (int64_t)r.size(); a.ldr = ldr; a.rcol0 = rcol0; }
+  if (ss) {
+    a.ss_stride = (max_len + 31) / 32; a.ld_ss = (cout + 31) / 32 * 32;
+    sums.assign((size_t)n * a.ss_stride * a.ld_ss, 0.f); a.sumsq = sums.data(); a.sumsq_elems = (int64_t)sums.size();
+  }
+  if (ld_stat) {
+    a.stat_nchunk = (max_len + 127) / 128; a.ld_stat = ld_stat;
+    stat.assign((size_t)n * a.stat_nchunk * 2 * ld_stat, 0.f); a.stat = stat.data(); a.stat_elems = (int64_t)stat.size();
+  }
+  stts_stub_trace_begin();
+  const int rc = stts_op_conv1d_epi(nullptr, &a);
+  const char* trace = stts_stub_trace_end();
+  printf("epitrace %s : %s%s\n", what, rc ? "error " : "", trace);
+}
+
+static void epi_section() {
+  const std::vector<int> lens = {257, 128, 5}, caps = {300, 128, 261};
+  // go through: conv2 (k 3) + shortcut (k 1) with both outputs and statistics on conv_gemm16_kernel; windows, a residual and GRN sums on a 16-bit-row tile; capacity segments
+  epi_case("two_segments", 1, 19, lens, lens, {{256, 3, 1}, {130, 1, 1}}, 256, 256, 0, 256, 0, 0, 0, false, 320);
+  epi_case("windows_tile15", 2, 15, lens, lens, {{64, 3, 3}}, 132, 160, 8, 136, 4, 288, 12, true, 0);
+  epi_case("capacity", 1, 19, caps, lens, {{64, 3, 1}}, 512, 512, 0, 512, 0, 0, 0, true, 0);
+  // refused: statistics off tile 19; a Y window past its row; a Y buffer one element short; the residual of tile 19 without room for the whole channel tile;
+  // a tile id without a row; real lengths beyond their capacities
+  epi_case("refuse_stat_tile15", 1, 15, lens, lens, {{64, 1, 1}}, 256, 256, 0, 0, 0, 0, 0, false, 256);
+  epi_case("refuse_window", 1, 19, lens, lens, {{64, 1, 1}}, 256, 256, 4, 0, 0, 0, 0, false, 0);
+  epi_case("refuse_short_buffer", 1, 19, lens, lens, {{64, 1, 1}}, 256, 256, 0, 0, 0, 0, 0, false, 0, 1);
+  epi_case("refuse_residual_room", 1, 19, lens, lens, {{64, 1, 1}}, 132, 160, 0, 0, 0, 136, 4, false, 0);
+  epi_case("refuse_tile", 1, 7, lens, lens, {{64, 1, 1}}, 256, 256, 0, 0, 0, 0, 0, false, 0);
+  epi_case("refuse_overflow", 1, 19, lens, caps, {{64, 1, 1}}, 256, 256, 0, 0, 0, 0, 0, false, 0);
+}
+
 struct Tensor {
   std::string name;
   int ndim;
@@ -331,6 +405,7 @@ int main(int argc, char** argv) {
   }
   gemm_section();
   if (argc > 2 && strcmp(argv[2], "gemm") == 0) return 0;
+  epi_section();
   stts_model_dims d;
   stts_cfm_dims cd;
   stts_ssl_dims sd;

@@ -122,6 +122,12 @@ def test_host_side_under_asan_ubsan(tmp_path):
             assert re.search(rf"conv_gemm_f32<128, 32, 2, 1, {epi},", small) and re.search(rf"conv_gemm_f32<128, 64, 2, 2, {epi},", large), (prec, epi)
         assert re.search(r"conv_gemm_f32<128, 32, 4, 1, 2,", small) and re.search(r"conv_gemm_f32<128, (128|64), 4, 2, 2,", large), prec
         assert "wn_" not in small and "wn_" not in large, prec
+    # stts_op_conv1d_epi's host side (asan_driver.cpp epi_section): the three launches run the kernel they name, a refused combination launches NOTHING
+    epi = dict(re.findall(r"^epitrace (\S+) : (.*)$", r.stdout, re.M))
+    assert "conv_gemm16_kernel<" in epi["two_segments"] and "conv_gemm16_kernel<" in epi["capacity"] and "conv_gemm_f32<" in epi["windows_tile15"], epi
+    assert not any(epi[k].startswith("error") for k in ("two_segments", "capacity", "windows_tile15")), epi
+    refused = [k for k in epi if k.startswith("refuse_")]
+    assert len(refused) == 6 and all(epi[k].strip() == "error" for k in refused), epi
     # every switch setting ran every case
     per_setting = {}
     for sw in re.findall(r"^\[(STTS_\w+=\d+)\] gemmtrace ", r.stdout, re.M):
