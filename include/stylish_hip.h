@@ -438,6 +438,30 @@ int stts_log_mel_stats(stts_ctx* ctx, void* stream, int n_utt, const int32_t* sa
  * nonzero bins [first, one past the last) of every filter (0, 0: an empty filter).  No context, no GPU. */
 int stts_log_mel_filters(int n_fft, int n_mels, int sample_rate, int32_t* band, float* weights);
 
+/* ---- Windowed-sinc sample-rate conversion: torchaudio.transforms.Resample(orig_freq, new_freq, resampling_method, lowpass_filter_width, rolloff,
+ * beta) / functional.resample from their published definition, with the float64 result as the target:
+ *   o, n = orig_freq, new_freq over their gcd;  base = min(o, n) * rolloff;  width = ceil(lowpass_filter_width * o / base);  taps = 2 width + o
+ *   coefficient[p][j] = sinc(pi t) * window(t) * base / o,  t = clamp((-p / n + j / o) * base, -lpw, lpw),  p in [0, n), j in [-width, width + o)
+ *   window: method 0 = sinc_interp_hann, cos(pi t / (2 lpw))^2;  method 1 = sinc_interp_kaiser, I0(beta sqrt(1 - (t / lpw)^2)) / I0(beta)
+ *   output q n + p of an utterance = sum_j coefficient[p][j] * sample[q o + j], samples outside the utterance zero;  ceil(n samples / o) outputs
+ * The coefficients are built on the device in fp64 and kept unrounded (torchaudio rounds them, and p / n, to fp32: not mirrored); products and the sum
+ * are fp64, the taps are added in tap order and the sum is rounded once to fp32.  Every output is independent of the batch around its utterance.
+ * Limits (a nonzero status names the number): o, n <= 1024, n * taps <= 2^20, 1 <= lowpass_filter_width <= 256, 0 < rolloff <= 1, 0 <= beta <= 512,
+ * every utterance at least 1 sample.  Equal rates copy the input. */
+/* Host arithmetic only (no context, no GPU): the reduced rates, width and taps; any out pointer may be null. */
+int stts_resample_geometry(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int* o, int* n, int* width, int* taps);
+/* ceil(new_freq * samples / orig_freq) on the reduced rates; -1 for a negative count or a rate below 1.  Host only. */
+int64_t stts_resample_out_length(int64_t samples, int orig_freq, int new_freq);
+/* Consecutive outputs of an utterance that one row of blocks of the resampling kernel computes at these rates (what tests place their lengths
+ * around); -1 for rates out of range.  Host only. */
+int stts_resample_tile(int orig_freq, int new_freq);
+/* in: packed mono audio at orig_freq, utterance u = samples [off_in[u], off_in[u+1]); out: packed, utterance u = [off_out[u], off_out[u+1]), which must
+ * hold exactly stts_resample_out_length of its input count.  beta is read under method 1 only.  The table of (o, n, lowpass_filter_width, rolloff,
+ * method, beta) is built on first use (that call waits for it) and kept in the context.  *_host / *_dev must hold the same offsets. */
+int stts_resample_forward(stts_ctx* ctx, void* stream, int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int method, double beta,
+                          int n_utt, const int32_t* off_in_host, const int32_t* off_in_dev, const int32_t* off_out_host, const int32_t* off_out_dev,
+                          const float* in, float* out);
+
 /* Layout bridge for the nn.Module shims: reference [B, C, T] (equal T) <-> time-major rows. */
 int stts_to_time_major(void* stream, const float* x_bct, int B, int C, int T, float* y, int ldy);
 int stts_to_channel_major(void* stream, const float* x, int ldx, int B, int C, int T, float* y_bct);

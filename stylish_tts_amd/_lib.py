@@ -129,6 +129,10 @@ SIGNATURES = {
     "stts_log_mel_forward": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_double, C.c_double, _P, _I, _P, _P]),
     "stts_log_mel_stats": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "stts_log_mel_filters": (_I, [_I, _I, _I, _P, _P]),
+    "stts_resample_geometry": (_I, [_I, _I, _I, C.c_double, _P, _P, _P, _P]),
+    "stts_resample_out_length": (_I64, [_I64, _I, _I]),
+    "stts_resample_tile": (_I, [_I, _I]),
+    "stts_resample_forward": (_I, [_P, _P, _I, _I, _I, C.c_double, _I, C.c_double, _I, _P, _P, _P, _P, _P, _P]),
     "stts_cfm_finalize": (_I, [_P, _P]),
     "stts_cfm_workspace_bytes": (_SZ, [_P, _I64, _I]),
     "stts_cfm_estimator": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _SZ]),

@@ -10,6 +10,7 @@
 #include "rmvpe.hip.h"
 #include "aligner.hip.h"
 #include "log_mel.hip.h"
+#include "resample.hip.h"
 
 using namespace stts;
 
@@ -961,6 +962,59 @@ int stts_log_mel_stats(stts_ctx* c, void* stream, int n_utt, const int32_t* samp
   hipLaunchKernelGGL(log_mel_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (long)row_off_host[n_utt], n_mels, stats);
   STTS_HIP(hipGetLastError());
   return 0;
+  API_END
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ windowed-sinc resampler (resample.hip.h)
+extern "C" {
+
+int stts_resample_geometry(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int* o, int* n, int* width, int* taps) {
+  API_BEGIN
+  ResampleGeom g;
+  STTS_TRY(resample_geometry(orig_freq, new_freq, lowpass_filter_width, rolloff, &g));
+  if (o) *o = g.o;
+  if (n) *n = g.n;
+  if (width) *width = g.width;
+  if (taps) *taps = g.taps;
+  return 0;
+  API_END
+}
+
+int64_t stts_resample_out_length(int64_t samples, int orig_freq, int new_freq) {
+  if (samples < 0 || orig_freq < 1 || new_freq < 1) return -1;
+  const long d = resample_gcd(orig_freq, new_freq);
+  return resample_out_length(samples, (int)(orig_freq / d), (int)(new_freq / d));
+}
+
+int stts_resample_tile(int orig_freq, int new_freq) {
+  if (orig_freq < 1 || new_freq < 1) return -1;
+  const long d = resample_gcd(orig_freq, new_freq);
+  if (orig_freq / d > kResampleMaxFreq || new_freq / d > kResampleMaxFreq) return -1;
+  return resample_tile((int)(orig_freq / d), (int)(new_freq / d));
+}
+
+int stts_resample_forward(stts_ctx* c, void* stream, int orig_freq, int new_freq, int lowpass_filter_width, double rolloff, int method, double beta, int n_utt,
+                          const int32_t* off_in_host, const int32_t* off_in_dev, const int32_t* off_out_host, const int32_t* off_out_dev, const float* in,
+                          float* out) {
+  API_BEGIN
+  // the interface conditions first: they read host arrays only, so a caller without a context still gets the status that names the number
+  ResampleGeom g;
+  STTS_TRY(resample_geometry(orig_freq, new_freq, lowpass_filter_width, rolloff, &g));
+  STTS_CHECK(method == RESAMPLE_HANN || method == RESAMPLE_KAISER, "resample: method %d is neither 0 (sinc_interp_hann) nor 1 (sinc_interp_kaiser)", method);
+  STTS_CHECK(method != RESAMPLE_KAISER || (std::isfinite(beta) && beta >= 0.0 && beta <= 512.0), "resample: beta %g is outside [0, 512]", beta);
+  long max_out = 0;
+  STTS_TRY(resample_check_offsets(n_utt, off_in_host, off_out_host, g, &max_out));
+  STTS_CHECK(c && off_in_dev && off_out_dev && in && out, "resample: null argument");
+  STTS_HIP(hipSetDevice(c->device));
+  if (g.o == g.n) {  // equal rates: the input bits
+    STTS_HIP(hipMemcpyAsync(out, in, (size_t)off_in_host[n_utt] * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+  }
+  const ResampleTable* t = nullptr;
+  STTS_TRY(resample_table(c, (hipStream_t)stream, g, lowpass_filter_width, rolloff, method, beta, &t));
+  return launch_resample((hipStream_t)stream, *t, g, n_utt, max_out, off_in_dev, off_out_dev, in, out);
   API_END
 }
 

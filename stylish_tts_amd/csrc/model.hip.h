@@ -7,6 +7,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/stylish_hip.h"
@@ -210,6 +211,9 @@ struct stts_ctx {
   // log-mel front end (log_mel.hip.h): window, twiddles and mel filters per (n_fft, win_length, n_mels, sample_rate), context lifetime
   std::map<std::array<int, 4>, std::shared_ptr<void>> log_mel;  // stts::LogMelTables
   std::mutex log_mel_mu;
+  // resampler (resample.hip.h): the fp64 coefficient table per (o, n, lowpass_filter_width, rolloff, method, beta), context lifetime
+  std::map<std::tuple<int, int, int, double, int, double>, std::shared_ptr<void>> resample;  // stts::ResampleTable
+  std::mutex resample_mu;
 };
 
 namespace stts {

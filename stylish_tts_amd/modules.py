@@ -20,6 +20,7 @@ Reference classes mirrored (paths relative to /root/reference/src/stylish_tts/tr
   TextAligner                 models/text_aligner.py:16-127 (tdnn_blstm_ctc_model / CTCModel) + dataprep/align_text.py:159-210 (torch_align)
   LogMelSpectrogram           torchaudio MelSpectrogram + calculate_mel (stage_type.py:1023-1032), preprocess (dataprep/align_text.py:112-117),
                               log_norm / compute_log_mel_stats (utils.py:71-148)
+  Resample                    torchaudio.transforms.Resample as models/ssl.py:21-24 and dataprep/rmvpe/inference.py:50-59 build it
 
 Differences, all additive: forward() of the stochastic modules takes an optional ``noise`` dict with the three draws
 the reference takes from the global torch generator (``prior_noise`` [B,128,4T], ``src_noise`` [B,1,300T],
@@ -432,7 +433,7 @@ class LogMelSpectrogram(torch.nn.Module):
     """The reference's mel front end on the engine: ``torchaudio.transforms.MelSpectrogram(n_mels, n_fft, win_length, hop_length, sample_rate)`` at its
     defaults followed by ``(log(1e-5 + mel) - mean) / std`` - calculate_mel (train/stage_type.py:1023-1032) with frames="even", preprocess
     (train/dataprep/align_text.py:112-117) with frames="drop_last" - plus log_norm's energy curve and compute_log_mel_stats (train/utils.py:71-148).
-    Audio in at ``sample_rate`` (the engine has no resampler); ragged batches through ``lengths`` [B] samples, every utterance getting what it gets
+    Audio in at ``sample_rate`` (``Resample`` converts another rate); ragged batches through ``lengths`` [B] samples, every utterance getting what it gets
     alone, bit for bit.  Only torchaudio's defaults are built: HTK scale, norm None, power 2, f_min 0, f_max sample_rate / 2."""
 
     def __init__(self, n_mels, n_fft, win_length, hop_length, sample_rate, mean=-4.0, std=4.0, frames="even", engine=None, cfg=None):
@@ -523,6 +524,74 @@ class LogMelSpectrogram(torch.nn.Module):
         eng = self.engine
         flat = torch.cat([_f(w, eng.device) for w in ws]).contiguous()
         return eng.log_mel_stats(Segments(L, eng.device), flat, *self._geom(), return_partials=return_partials)
+
+
+class Resample(torch.nn.Module):
+    """``torchaudio.transforms.Resample`` on the engine, same constructor: windowed-sinc conversion from ``orig_freq`` to ``new_freq``
+    ("sinc_interp_hann" or "sinc_interp_kaiser").  The target is torchaudio's float64 result: the coefficients stay fp64 on the device, so the fp32
+    roundings torchaudio applies to them are not reproduced (resample.py, csrc/resample.hip.h).  Ragged batches through ``lengths``: every utterance
+    gets what it gets alone, bit for bit.  Equal rates return the input's values."""
+
+    def __init__(self, orig_freq: int = 16000, new_freq: int = 16000, resampling_method: str = "sinc_interp_hann", lowpass_filter_width: int = 6,
+                 rolloff: float = 0.99, beta: Optional[float] = None, engine=None, cfg=None):
+        from . import resample
+
+        super().__init__()
+        self.o, self.n, self.width, self.taps, _, _ = resample.check(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        self.resampling_method, self.lowpass_filter_width, self.rolloff, self.beta = resampling_method, int(lowpass_filter_width), float(rolloff), beta
+        self._engine = engine
+        self._cfg = cfg
+
+    @property
+    def engine(self) -> HipModel:
+        if self._engine is None:
+            self._engine = get_engine(self._cfg, 0)
+        return self._engine
+
+    def out_lengths(self, lengths):
+        """Output sample counts ceil(n * samples / o) of utterances of ``lengths`` samples (host arithmetic only)."""
+        from . import resample
+
+        return resample.out_lengths(lengths, self.orig_freq, self.new_freq)
+
+    def _lengths(self, wave, lengths):
+        if wave.dim() != 2:
+            raise ValueError(f"audio must be [B, samples], got shape {tuple(wave.shape)}")
+        B, S = wave.shape
+        L = [S] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()]
+        if len(L) != B or any(n > S for n in L):
+            raise ValueError(f"lengths {L} do not fit a batch of {B} x {S} samples")
+        self.out_lengths(L)  # ValueError for an utterance without a sample, before any device work
+        return L
+
+    def packed_rows(self, flat, seg: Segments):
+        """Packed samples [sum samples] with their Segments -> (packed samples at new_freq, their Segments), on the device."""
+        return self.engine.resample(seg, flat, self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff, self.resampling_method, self.beta)
+
+    def packed(self, waveform, lengths=None):
+        """waveform [B, samples] -> (packed samples at new_freq [sum ceil(n samples / o)] on the device, their Segments).  The host reads nothing back."""
+        L = self._lengths(waveform, lengths)
+        eng = self.engine
+        wd = _f(waveform, eng.device)
+        flat = torch.cat([wd[b, : L[b]] for b in range(len(L))]).contiguous()
+        return self.packed_rows(flat, Segments(L, eng.device))
+
+    def forward(self, waveform, lengths=None):
+        """waveform [..., time] -> [..., ceil(n time / o)], as torchaudio gives it; with ``lengths`` [...] every utterance is converted on its own
+        and the samples past its output length are zero."""
+        shape = tuple(waveform.shape)
+        if len(shape) < 1:
+            raise ValueError("audio must have a time axis")
+        rows, seg = self.packed(waveform.reshape(-1, shape[-1]), lengths)
+        if lengths is None:
+            return rows.reshape(shape[:-1] + (seg.lengths[0],))
+        from . import resample
+
+        out = rows.new_zeros((seg.n, resample.out_length(shape[-1], self.orig_freq, self.new_freq)))
+        for b in range(seg.n):
+            out[b, : seg.lengths[b]] = rows[seg.host[b] : seg.host[b + 1]]
+        return out.reshape(shape[:-1] + (out.shape[1],))
 
 
 class ExportModel(torch.nn.Module):
@@ -848,7 +917,8 @@ class AdaptiveHubert(HipModule):
     load_state_dict takes the reference's keys (``model.*``; masked_spec_embed and final_proj.* are stored and unused).
     ``lengths`` (optional, [B] samples) runs a ragged batch: each utterance gets what the reference gives it alone (the reference's own
     padded batch lets GroupNorm, the positional conv and the attention see the padding); without it the batch is dense and equals the
-    reference on it.  The reference resamples model_sr -> hubert_sr first; this shim takes audio that already is at hubert_sr."""
+    reference on it.  The reference resamples model_sr -> hubert_sr first; this shim takes audio that already is at hubert_sr unless
+    ``sample_rate`` names another rate (``sample_rate=self.model_sr``: the reference's own forward), which is converted on the engine."""
 
     module_name = "hubert"
     components = W_SSL
@@ -900,31 +970,44 @@ class AdaptiveHubert(HipModule):
 
         return hubert_ssl.frames(samples, self.arch)
 
-    def _lengths(self, wave, lengths):
+    def _lengths(self, wave, lengths, sample_rate=None):
+        """Sample counts at the rate of ``wave`` and at hubert_sr (the same list without a resampling)."""
         if wave.dim() != 2:
             raise ValueError(f"AdaptiveHubert input must be [B, samples], got shape {tuple(wave.shape)}")
         B, S = wave.shape
         L = [S] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).tolist()]
         if len(L) != B or any(n < 1 or n > S for n in L):
             raise ValueError(f"lengths {L} do not fit a batch of {B} x {S} samples")
-        for n in L:
-            self.frames(n)  # ValueError below the receptive field, where the reference raises
-        return L
+        Lr = L
+        if sample_rate is not None and int(sample_rate) != self.sr:
+            from . import resample
 
-    def packed(self, wave, time_dims, lengths=None, taps: bool = False):
-        """Packed rows [sum time_dims, ld] (the ``feats`` of the engine's HuBERT stages) for per-utterance ``time_dims``."""
-        L = self._lengths(wave, lengths)
+            resample.check(sample_rate, self.sr)
+            Lr = resample.out_lengths(L, sample_rate, self.sr)
+        for n in Lr:
+            self.frames(n)  # ValueError below the receptive field, where the reference raises
+        return L, Lr
+
+    def packed(self, wave, time_dims, lengths=None, taps: bool = False, sample_rate: Optional[int] = None):
+        """Packed rows [sum time_dims, ld] (the ``feats`` of the engine's HuBERT stages) for per-utterance ``time_dims``.  sample_rate: the rate of
+        ``wave`` where it is not hubert_sr - ``Resample(sample_rate, hubert_sr)`` at torchaudio's defaults runs first, on the device, and the
+        receptive-field check applies to the resampled length."""
+        L, Lr = self._lengths(wave, lengths, sample_rate)
         T = [int(t) for t in time_dims]
         if len(T) != len(L) or min(T) < 1:
             raise ValueError(f"time_dim {T} must be one positive frame count per utterance")
         eng = self.engine
         wd = _f(wave, eng.device)
         flat = torch.cat([wd[b, : L[b]] for b in range(len(L))]).contiguous()
-        return eng.hubert_ssl(Segments(L, eng.device), flat, Segments(T, eng.device), taps=taps)
+        seg = Segments(L, eng.device)
+        if Lr is not L:
+            flat, seg = eng.resample(seg, flat, int(sample_rate), self.sr)
+        return eng.hubert_ssl(seg, flat, Segments(T, eng.device), taps=taps)
 
-    def forward(self, wave, time_dim, lengths=None):
+    def forward(self, wave, time_dim, lengths=None, sample_rate: Optional[int] = None):
+        """sample_rate=None: ``wave`` is at hubert_sr.  sample_rate=self.model_sr is the reference's own forward (resample, then the network)."""
         B, T = wave.shape[0], int(time_dim)
-        rows = self.packed(wave, [T] * B, lengths)
+        rows = self.packed(wave, [T] * B, lengths, sample_rate=sample_rate)
         return rows[:, : self.hidden].reshape(B, T, self.hidden).permute(0, 2, 1).contiguous()
 
 
@@ -1064,45 +1147,60 @@ class RmvpePitchExtractor(HipModule):
         f0, seg = self.packed(mel, lengths, frames, thred, return_segments=True)
         return self._unpack(f0, seg)
 
-    def _wave_lengths(self, wave, sample_lengths, sample_rate):
+    RESAMPLE_WIDTH = 128  # the lowpass_filter_width of the reference's resampler (inference.py:55-57)
+
+    def _wave_lengths(self, wave, sample_lengths, sample_rate, resample: bool = False):
+        """Sample counts at the rate of ``wave`` and at 16 kHz (the same list without a resampling); the length checks apply to the latter."""
         from . import rmvpe
 
-        if int(sample_rate) != self.sr:
-            raise ValueError(f"RMVPE takes audio at {self.sr} Hz, got {sample_rate} (resample outside: the engine has no resampler)")
+        if int(sample_rate) != self.sr and not resample:
+            raise ValueError(f"RMVPE takes audio at {self.sr} Hz, got {sample_rate} (pass resample=True to convert it on the engine, as the reference does)")
         if wave.dim() != 2:
             raise ValueError(f"RMVPE audio must be [B, samples], got shape {tuple(wave.shape)}")
         B, S = wave.shape
         L = [S] * B if sample_lengths is None else [int(v) for v in torch.as_tensor(sample_lengths).tolist()]
         if len(L) != B or any(n > S for n in L):
             raise ValueError(f"sample_lengths {L} do not fit a batch of {B} x {S} samples")
-        for n in L:
-            rmvpe.mel_frames(n)  # ValueError at 512 samples or fewer
-        return L
+        Lr = L
+        if int(sample_rate) != self.sr:
+            from . import resample as rs
 
-    def mel_packed(self, wave, sample_lengths=None, sample_rate: int = 16000, linear: bool = False):
-        """wave [B, samples] at 16 kHz -> packed log-mel rows [sum frames, 128] and their Segments (frames = samples // 160 + 1)."""
-        L = self._wave_lengths(wave, sample_lengths, sample_rate)
+            rs.check(sample_rate, self.sr, self.RESAMPLE_WIDTH)
+            Lr = rs.out_lengths(L, sample_rate, self.sr)
+        for n in Lr:
+            rmvpe.mel_frames(n)  # ValueError at 512 samples or fewer
+        return L, Lr
+
+    def mel_packed(self, wave, sample_lengths=None, sample_rate: int = 16000, linear: bool = False, resample: bool = False):
+        """wave [B, samples] at 16 kHz -> packed log-mel rows [sum frames, 128] and their Segments (frames = samples // 160 + 1).  resample=True:
+        ``wave`` is at ``sample_rate`` and the reference's Resample(sample_rate, 16000, lowpass_filter_width=128) runs first, on the device."""
+        L, Lr = self._wave_lengths(wave, sample_lengths, sample_rate, resample)
         eng = self.engine
         if self._basis_dev is None or self._basis_dev[0].device != eng.device:
             self._basis_dev = (self._mel_basis.to(eng.device), self._band.to(eng.device))
         wd = _f(wave, eng.device)
         flat = torch.cat([wd[b, : L[b]] for b in range(len(L))]).contiguous()
-        return eng.rmvpe_mel(Segments(L, eng.device), flat, self._basis_dev[0], self._basis_dev[1], linear=linear)
+        seg = Segments(L, eng.device)
+        if Lr is not L:
+            flat, seg = eng.resample(seg, flat, int(sample_rate), self.sr, self.RESAMPLE_WIDTH)
+        return eng.rmvpe_mel(seg, flat, self._basis_dev[0], self._basis_dev[1], linear=linear)
 
-    def mel(self, wave, sample_lengths=None, sample_rate: int = 16000):
+    def mel(self, wave, sample_lengths=None, sample_rate: int = 16000, resample: bool = False):
         """wave [B, samples] -> log-mel [B, 128, max frames] (MelSpectrogram.forward, keyshift 0, speed 1, center=True)."""
-        rows, seg = self.mel_packed(wave, sample_lengths, sample_rate)
+        rows, seg = self.mel_packed(wave, sample_lengths, sample_rate, resample=resample)
         return self._unpack(rows, seg).transpose(1, 2).contiguous()
 
-    def packed_from_audio(self, wave, sample_lengths=None, frames=None, thred: Optional[float] = None, sample_rate: int = 16000, return_segments: bool = False):
-        """Packed f0 rows [sum frames] on the device from audio [B, samples] at 16 kHz; thred None: ``self.thred``."""
+    def packed_from_audio(self, wave, sample_lengths=None, frames=None, thred: Optional[float] = None, sample_rate: int = 16000, return_segments: bool = False,
+                          resample: bool = False):
+        """Packed f0 rows [sum frames] on the device from audio [B, samples] at 16 kHz (resample=True: at ``sample_rate``, converted on the engine
+        first); thred None: ``self.thred``."""
         from . import rmvpe
 
         thred = self.thred if thred is None else thred
 
-        for n in self._wave_lengths(wave, sample_lengths, sample_rate):
+        for n in self._wave_lengths(wave, sample_lengths, sample_rate, resample)[1]:
             rmvpe.padded_frames(rmvpe.mel_frames(n))  # ValueError below 17 frames
-        rows, seg = self.mel_packed(wave, sample_lengths, sample_rate)
+        rows, seg = self.mel_packed(wave, sample_lengths, sample_rate, resample=resample)
         Fr = self._frames(frames, seg.n)
         eng = self.engine
         _, f0 = eng.rmvpe(seg, rows, thred, hidden=False)
@@ -1111,11 +1209,13 @@ class RmvpePitchExtractor(HipModule):
             f0, seg = eng.rmvpe_resample(seg, f0, seg_o), seg_o
         return (f0, seg) if return_segments else f0
 
-    def infer_from_audio(self, wave16k, sample_lengths=None, frames=None, thred: float = 0.03, sample_rate: int = 16000, use_viterbi: bool = False):
-        """wave [B, samples] at 16 kHz -> f0 [B, T] (T = samples // 160 + 1, or ``frames`` after the linear resampling)."""
+    def infer_from_audio(self, wave16k, sample_lengths=None, frames=None, thred: float = 0.03, sample_rate: int = 16000, use_viterbi: bool = False,
+                         resample: bool = False):
+        """wave [B, samples] at 16 kHz -> f0 [B, T] (T = samples // 160 + 1, or ``frames`` after the linear resampling).  resample=True with another
+        ``sample_rate`` is the reference's infer_from_audio: its width-128 resampler to 16 kHz runs first."""
         if use_viterbi:
             raise NotImplementedError("RMVPE's Viterbi decoding is not built; use_viterbi=False is")
-        f0, seg = self.packed_from_audio(wave16k, sample_lengths, frames, thred, sample_rate, return_segments=True)
+        f0, seg = self.packed_from_audio(wave16k, sample_lengths, frames, thred, sample_rate, return_segments=True, resample=resample)
         return self._unpack(f0, seg)
 
 

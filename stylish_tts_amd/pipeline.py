@@ -326,14 +326,17 @@ class VoiceConverter:
         return waves
 
     @torch.no_grad()
-    def convert_audio(self, wave, sample_lengths, frames, spk_emb, ssl=None, pitch_extractor=None, **kw):
+    def convert_audio(self, wave, sample_lengths, frames, spk_emb, ssl=None, pitch_extractor=None, sample_rate=None, **kw):
         """Voice conversion from audio: wave [B, samples] at hubert.sr (zero padded past sample_lengths[b]), frames [B] = the mel-frame count
         of every utterance (the reference's time_dim; an argument, so the host reads nothing back) -> HuBERT features on the engine
         (``ssl``: the modules.AdaptiveHubert bound to this engine, or the one among this converter's modules) written as the packed rows
         convert() consumes, then convert() with the same keywords (pitch, energy, noise, ref_mel, ref_wave, energy_wave, ...).
         pitch_extractor (a modules.RmvpePitchExtractor; the audio must be at its 16 kHz): the source's own F0 is extracted on the engine and
         resampled to ``frames``.  Without ref_mel it becomes the pitch (energy from HubertPitchEnergyPredictor unless given); with ref_mel it
-        gives the voicing flags uv = (f0 == 0), formed on the device, unless uv is given.  The host reads nothing back."""
+        gives the voicing flags uv = (f0 == 0), formed on the device, unless uv is given.  The host reads nothing back.
+        sample_rate: the rate of ``wave`` where it is not hubert.sr.  The content encoder then gets torchaudio's default (width-6) resampling of it
+        and the pitch extractor the reference's width-128 one, each from the original recording, on the engine.  At the model's sample rate the
+        same ``wave`` may also be passed as ref_wave / energy_wave: one recording in, at one rate."""
         from .modules import AdaptiveHubert
 
         if ssl is None:
@@ -344,14 +347,20 @@ class VoiceConverter:
             raise ValueError(f"the content encoder has width {ssl.hidden}; hubert.hidden_dim is {self.hubert_dim}")
         T = [int(v) for v in torch.as_tensor(frames).tolist()]
         ssl._engine = ssl._engine or self.eng
-        feats = ssl.packed(wave, T, sample_lengths)
+        if sample_rate is not None and (int(sample_rate) != sample_rate or int(sample_rate) < 1):
+            raise ValueError(f"sample_rate {sample_rate} must be a positive integer")
         if pitch_extractor is not None:
             if kw.get("pitch") is not None:
                 raise ValueError("give pitch_extractor (F0 from the source audio) or pitch, not both")
-            if pitch_extractor.sr != ssl.sr:
+            if sample_rate is None and pitch_extractor.sr != ssl.sr:
                 raise ValueError(f"the pitch extractor takes audio at {pitch_extractor.sr} Hz, the content encoder at {ssl.sr} Hz")
+        feats = ssl.packed(wave, T, sample_lengths) if sample_rate is None else ssl.packed(wave, T, sample_lengths, sample_rate=int(sample_rate))
+        if pitch_extractor is not None:
             pitch_extractor._engine = pitch_extractor._engine or self.eng
-            f0 = pitch_extractor.packed_from_audio(wave, sample_lengths, T)
+            if sample_rate is None:
+                f0 = pitch_extractor.packed_from_audio(wave, sample_lengths, T)
+            else:
+                f0 = pitch_extractor.packed_from_audio(wave, sample_lengths, T, sample_rate=int(sample_rate), resample=True)
             if kw.get("ref_mel") is not None or kw.get("ref_wave") is not None:
                 if kw.get("uv") is None:
                     kw["_packed_uv"] = (f0 == 0).to(torch.float32)

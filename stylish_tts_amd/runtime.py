@@ -642,6 +642,25 @@ class HipModel:
         m, s, n = stats.cpu().tolist()
         return (m, s, int(n)) + ((part, seg_m) if return_partials else ())
 
+    # ------------------------------------------------------------------ windowed-sinc resampler (packed waveforms at any rate)
+    def resample(self, seg_in: Segments, wave: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,
+                 resampling_method: str = "sinc_interp_hann", beta: Optional[float] = None):
+        """wave [sum samples] packed mono audio at orig_freq (utterance offsets seg_in) -> (wave_out [sum ceil(n samples / o)] at new_freq, seg_out):
+        torchaudio.transforms.Resample(orig_freq, new_freq, resampling_method, lowpass_filter_width, rolloff, beta) of every utterance on its own, with
+        the float64 result as the target (fp64 coefficients, products and sums, one rounding; include/stylish_hip.h, stts_resample_forward).  Equal
+        rates return a copy of the input.  ValueError outside the limits of resample.check.  Nothing is read back by the host."""
+        from . import resample
+
+        _, _, _, _, method, b = resample.check(orig_freq, new_freq, lowpass_filter_width, rolloff, resampling_method, beta)
+        seg_out = Segments(resample.out_lengths(seg_in.lengths, orig_freq, new_freq), self.device)
+        wave = wave.to(self.device, torch.float32).contiguous()
+        if wave.dim() != 1 or wave.numel() != seg_in.rows:
+            raise ValueError(f"packed waveform of {wave.numel()} samples, the offsets describe {seg_in.rows}")
+        out = self._f32(seg_out.rows)
+        _lib.check(self.lib.stts_resample_forward(self.ctx, _stream(), int(orig_freq), int(new_freq), int(lowpass_filter_width), float(rolloff), method, b,
+                                                  seg_in.n, seg_in.host_ptr, _ptr(seg_in.dev), seg_out.host_ptr, _ptr(seg_out.dev), _ptr(wave), _ptr(out)))
+        return out, seg_out
+
     # ------------------------------------------------------------------ text aligner + CTC forced alignment (packed normalised log-mel rows)
     def aligner_finalize(self, dims) -> None:
         """Pack the weights loaded under "text_aligner." for the dims of aligner.dims(); include/stylish_hip.h, stts_aligner_finalize."""
