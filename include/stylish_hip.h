@@ -166,7 +166,10 @@ int stts_frame_path(stts_ctx* ctx, void* stream, int n_utt, const int32_t* seg_o
                     float* audio_out, void* ws, size_t ws_bytes, int seg_flags);
 
 /* ---- phoneme-rate predictors.  Sequences are packed: tok_off[n_utt+1] token offsets, tokens int64 [n_tok]. ---- */
-size_t stts_phoneme_workspace_bytes(const stts_ctx* ctx, int64_t n_tokens, int64_t n_frames, int n_utt);
+/* Workspace the four stages below accept for `n_tokens` tokens and `n_frames` frames in `n_utt` utterances, the longest having
+ * `max_tokens` tokens and `max_frames` frames.  Like every stts_*_workspace_bytes query but the CTC one it is a dry run of the
+ * stages' own carving, so the finalized components decide it. */
+size_t stts_phoneme_workspace_bytes(const stts_ctx* ctx, int64_t n_tokens, int64_t n_frames, int n_utt, int max_tokens, int max_frames);
 
 /* TextEncoder.forward (models/text_encoder.py:433-462).  which: 0 duration_predictor.text_encoder,
  * 1 speech_predictor.text_encoder, 2 pe_text_encoder.  -> mu [n_tok, ld_mu >= inter_dim] (proj_m), optional x [n_tok, 128]. */

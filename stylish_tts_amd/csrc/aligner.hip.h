@@ -285,11 +285,6 @@ inline int aligner_ld_mel(const AlDims& d) { return round_up(d.n_mels, 32); }
 inline int aligner_ld_logits(const AlDims& d) { return round_up(d.classes, 32); }
 inline size_t aligner_tap_floats(const AlDims& d, long rows) { return (size_t)rows * ((size_t)(d.n_tdnn + 1) * d.hidden + d.classes); }
 
-inline size_t aligner_workspace_bytes(const AlDims& d, int n_utt, long rows) {
-  const size_t fl = (size_t)rows * (aligner_ld_mel(d) + 3 * (size_t)d.hidden + aligner_ld_logits(d)) + (size_t)std::max(0, d.n_tdnn - 1) * n_utt * 2 * d.hidden;
-  return fl * sizeof(float) + 8 * 256;
-}
-
 // one dense contraction, whole, on the one tile (see the head of this file)
 inline int aligner_gemm(hipStream_t st, const Seg& s, const float* X, int ldx, const PackedConv& w, float* Y, int ldy, int act, const float* xaff, int ld_xaff,
                         const float* R = nullptr, int ldr = 0) {
@@ -311,6 +306,7 @@ inline int aligner_forward(const AlW& M, hipStream_t st, const Seg& s, const flo
   float* logits = ws.get<float>((size_t)R * ldl);
   float* tab = ws.get<float>((size_t)std::max(1, n_tab) * n_utt * 2 * H);
   STTS_CHECK(ws.ok, "aligner_forward: workspace too small");
+  STTS_DRY_RETURN(ws);
   const unsigned row_blocks = (unsigned)std::max<long>(1, std::min<long>(2048, (R * H / 4 + 255) / 256));
   hipLaunchKernelGGL(aligner_prepare_kernel, dim3((unsigned)std::max<long>(1, std::min<long>(1024, (R * ldm + 255) / 256))), dim3(256), 0, st, mel, ld_mel, d.n_mels, s.dev,
                      n_utt, m, ldm, M.bn, n_tab, H, tab);
@@ -344,6 +340,12 @@ inline int aligner_forward(const AlW& M, hipStream_t st, const Seg& s, const flo
                      taps ? taps + (size_t)(d.n_tdnn + 1) * R * H : nullptr);
   STTS_HIP(hipGetLastError());
   return 0;
+}
+
+// workspace bytes for these host offsets: a dry run of the carving above
+inline size_t aligner_workspace_bytes(const AlW& M, int n_utt, const int* off) {
+  const Seg s{n_utt, off, nullptr};
+  return dry_run_bytes([&](Arena a) { (void)aligner_forward(M, nullptr, s, nullptr, 0, nullptr, 0, nullptr, a); });
 }
 
 // ------------------------------------------------------------------------------------------------ alignment launches

@@ -354,8 +354,8 @@ int stts_to_channel_major(void* stream, const float* x, int ldx, int B, int C, i
   READY_CHECK(c->phoneme, mask);                                                     \
   PhonemeModel& M = *static_cast<PhonemeModel*>(c->phoneme.get())
 
-size_t stts_phoneme_workspace_bytes(const stts_ctx* c, int64_t n_tokens, int64_t n_frames, int n_utt) {
-  return phoneme_workspace_bytes(c, n_tokens, n_frames, n_utt);
+size_t stts_phoneme_workspace_bytes(const stts_ctx* c, int64_t n_tokens, int64_t n_frames, int n_utt, int max_tokens, int max_frames) {
+  return phoneme_workspace_bytes(c, n_tokens, n_frames, n_utt, max_tokens, max_frames);
 }
 
 int stts_text_encoder_forward(stts_ctx* c, void* stream, int which, int n_utt, const int32_t* tok_off_host, const int32_t* tok_off_dev,
@@ -706,7 +706,7 @@ static int aligner_check_offsets(int n_utt, const int32_t* off_host) {
 size_t stts_aligner_workspace_bytes(const stts_ctx* c, int n_utt, const int32_t* off_host) {
   if (!c || !c->aligner || !(c->ready & STTS_W_ALIGNER)) return 0;
   if (aligner_check_offsets(n_utt, off_host) != 0) return 0;
-  return aligner_workspace_bytes(static_cast<const AlW*>(c->aligner.get())->d, n_utt, off_host[n_utt]);
+  return aligner_workspace_bytes(*static_cast<const AlW*>(c->aligner.get()), n_utt, off_host);
 }
 
 int64_t stts_aligner_tap_floats(const stts_aligner_dims* dims, int n_utt, const int32_t* off_host) {
@@ -1027,7 +1027,7 @@ extern "C" {
   READY_CHECK(c->hubert, mask);                                                      \
   HubertModel& H = *static_cast<HubertModel*>(c->hubert.get())
 
-size_t stts_hubert_workspace_bytes(const stts_ctx* c, int64_t rows_T, int n_utt, int max_len) { return c ? hubert_workspace_bytes(c, rows_T, n_utt, max_len) : 0; }
+size_t stts_hubert_workspace_bytes(const stts_ctx* c, int64_t rows_T, int n_utt, int max_len) { return hubert_workspace_bytes(c, rows_T, n_utt, max_len); }
 
 int stts_speaker_style(stts_ctx* c, void* stream, int n_utt, const float* spk_emb, int ld, float* style_out, float* pe_style_out, void* ws, size_t ws_bytes) {
   API_BEGIN

@@ -479,19 +479,14 @@ inline int cfm_estimator(stts_ctx* c, const CfmModel& M, hipStream_t st, const S
   return 0;
 }
 
-// Workspace bytes of one estimator evaluation over `R` rows in `n_utt` utterances (a dry run of the carving above).
+// Workspace bytes of one estimator evaluation over `R` rows in `n_utt` utterances: a dry run of the carving above (which reads the rows
+// and the utterance count only; the synthetic batch has the longest utterance they allow).
 inline size_t cfm_workspace_bytes(stts_ctx* c, const CfmModel& M, int64_t R, int n_utt) {
   if (R <= 0 || n_utt <= 0) return 0;
-  std::vector<int> off(n_utt + 1, 0);
-  for (int u = 0; u < n_utt; ++u) off[u + 1] = (int)(R * (u + 1) / n_utt);
-  Seg s{n_utt, off.data(), nullptr};
-  DryRun& dr = dry_run();
-  dr.on = true;
-  dr.peak = 0;
-  Arena a(reinterpret_cast<char*>((uintptr_t)1 << 20), (size_t)1 << 46);
-  (void)cfm_estimator(c, M, nullptr, s, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, a);
-  dr.on = false;
-  return dr.peak + 4096;
+  const SynthSeg syn(R, n_utt, 0);
+  return dry_run_bytes([&](Arena a) {
+    (void)cfm_estimator(c, M, nullptr, syn.seg(), nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, a);
+  });
 }
 
 }  // namespace stts

@@ -126,15 +126,6 @@ inline int finalize_cfm_pitch_net(stts_ctx* c, CfmPitchNetW* W) {
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ workspace
-// an upper bound from the row count alone (the GRN partial sums are sized for an utterance of all rows_T)
-inline size_t cfm_pitch_workspace_bytes(const CfmPitchNetW& W, int64_t rows_T, int n_utt) {
-  const size_t R = (size_t)std::max<int64_t>(rows_T, 1), U = (size_t)std::max(n_utt, 1);
-  const size_t ss = U * (size_t)(ceil_div((int)R, 128) * 4) * kCpInter;
-  const size_t fl = R * (kCpInter + 3 * kCpHidden) + ss + U * kCpInter + U * (size_t)W.blk[0].pw2.npad * kCpInter + U * W.table.ld();
-  return fl * sizeof(float) + 16 * 256;  // (Arena rounds each of its ~10 buffers up to 256 bytes)
-}
-
 // ------------------------------------------------------------------------------------------------ CfmPitchPredictor.forward (frame-rate part)
 // asr [rows, ld_asr >= asr_dim] packed by s, spk [n_utt, 256] (the spk_emb style) -> normed [rows] (out_proj), optionally hz [rows]
 // (denorm_f0_zscore with the given log2 statistics and uv [rows] or null).  taps (or null): [5][rows][256] = asr_emb output, then each block's.
@@ -152,6 +143,7 @@ inline int cfm_pitch_forward(const CfmPitchNetW& W, hipStream_t st, const Seg& s
   float* w2u = ws.get<float>((size_t)s.n_utt * W.blk[0].pw2.npad * inter);
   float* sty = ws.get<float>((size_t)s.n_utt * W.table.ld());
   STTS_CHECK(ws.ok, "cfm_pitch_forward: workspace too small");
+  STTS_DRY_RETURN(ws);
   // asr_emb: 1x1 -> Mish (a pass of its own: the shared contraction epilogue stays as it is) -> 1x1
   STTS_TRY(gemm_store(st, s, asr, ld_asr, 0, W.emb0, U, inter, 0));
   hipLaunchKernelGGL(cp_mish_rows_kernel, dim3((unsigned)std::min(1024, std::max(1, ceil_div(ml * (inter / 4), 256))), s.n_utt), dim3(256), 0, st, U, inter, inter,
@@ -171,6 +163,13 @@ inline int cfm_pitch_forward(const CfmPitchNetW& W, hipStream_t st, const Seg& s
   hipLaunchKernelGGL(cp_out_kernel, dim3(ceil_div(ml, 4), s.n_utt), dim3(256), 0, st, cur, h, h, s.dev, W.out_w, W.out_b, normed, hz, mean, stdv, uv);
   STTS_HIP(hipGetLastError());
   return 0;
+}
+
+// Workspace bytes from the row count alone: a dry run with one utterance holding all the rows the others leave (the GRN partial sums
+// grow with the longest utterance).
+inline size_t cfm_pitch_workspace_bytes(const CfmPitchNetW& W, int64_t rows_T, int n_utt) {
+  const SynthSeg syn(rows_T, n_utt, 0);
+  return dry_run_bytes([&](Arena a) { (void)cfm_pitch_forward(W, nullptr, syn.seg(), nullptr, 0, nullptr, nullptr, nullptr, 0.f, 1.f, nullptr, nullptr, a); });
 }
 
 }  // namespace stts

@@ -197,20 +197,6 @@ inline int finalize_hubert(stts_ctx* c, HubertModel* M, int which) {
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ workspace
-inline size_t speaker_part_floats(int n_utt, int spk_dim, int n_cols) { return (size_t)n_utt * ceil_div(spk_dim, kSpkChunk) * n_cols; }
-
-inline size_t hubert_workspace_bytes(const stts_ctx* c, int64_t rows_T, int n_utt, int max_len) {
-  const stts_model_dims& d = c->d;
-  const size_t C = d.inter_dim, Cp = d.inter_dim + d.style_dim, R4 = 4 * (size_t)rows_T;
-  const size_t enc = R4 * (C * 7 + d.te_filter + 8) + (size_t)rows_T * C;  // x, t, qkv, att (+ the 4T output before repeat)
-  const size_t pe = (size_t)rows_T * (C + Cp * 16 + 8);                     // phone_quant, prosody + its scratch, branches
-  const size_t wino = ((size_t)rows_T / kWinoM + n_utt + 1) * kWinoMaxN * 3 * Cp + 1024;  // wino_scratch_floats, bounded above
-  const size_t stats = (size_t)n_utt * (ceil_div(std::max(1, max_len), kStatChunk) + 1) * 2 * round_up((int)Cp, 32);  // adain_part_floats
-  const size_t per = (size_t)n_utt * (1024 + 16) + 4 * (size_t)n_utt * (20 * 1024);  // style tables, offsets, speaker partial sums (spk_dim up to 20480)
-  return (enc + pe + wino + stats + per) * sizeof(float) + ((size_t)4 << 20);
-}
-
 // ------------------------------------------------------------------------------------------------ speaker styles
 // spk_emb [n_utt, ld >= spk_dim] -> style_out [n_utt, 64] (hubert_speech_predictor.style_encoder) and / or pe_style_out [n_utt, 64]
 // (hubert_pitch_energy_predictor.style_encoder); a null output is skipped (its component need not be finalized).
@@ -224,8 +210,9 @@ inline int speaker_style(stts_ctx* c, const HubertModel& M, hipStream_t st, int 
   STTS_CHECK(ld >= K, "speaker embedding: ld %d < spk_dim %d", ld, K);
   const int na = want_sp ? S.h1 : 0, nb = want_pe ? P.sd : 0, N = na + nb;
   const int nchunk = ceil_div(K, kSpkChunk);
-  float* part = ws.get<float>(speaker_part_floats(n_utt, K, N));
+  float* part = ws.get<float>((size_t)n_utt * nchunk * N);
   STTS_CHECK(ws.ok, "speaker_style: workspace too small");
+  STTS_DRY_RETURN(ws);
   hipLaunchKernelGGL(speaker_partial_kernel, dim3(ceil_div(N, 4 * kSpkCols), nchunk), dim3(256), 0, st, spk, ld, n_utt, K, want_sp ? S.w1 : nullptr, na,
                      want_pe ? P.ws : nullptr, nb, part);
   const size_t shm = (size_t)(na + (want_sp ? S.h2 : 0)) * sizeof(float);
@@ -254,6 +241,7 @@ inline int hubert_encoder_forward(stts_ctx* c, const HubertModel& M, hipStream_t
   float* att = ws.get<float>(R4 * C);
   float* ff = ws.get<float>(R4 * E.filter);
   STTS_CHECK(ws.ok, "hubert_encoder_forward: workspace too small");
+  STTS_DRY_RETURN(ws);
   Seg s4{sT.n_utt, host4.data(), dev4};
   hipLaunchKernelGGL(scale_offsets_kernel, dim3(1), dim3(256), 0, st, sT.dev, sT.n_utt, 4, dev4);
   STTS_TRY(gemm_store(st, sT, feats, ld_f, 0, S.emb, e, C, 0));
@@ -285,11 +273,17 @@ inline int hubert_pitch_energy_forward(stts_ctx* c, const HubertModel& M, hipStr
   WinoScratch wino;  // large batches: Winograd convs (as the text predictor's blocks)
   if (R > fold_rows() && P.f0[0].w1.ready) wino.p = ws.get<float>(wino_scratch_floats(s, P.f0[0].w1));
   STTS_CHECK(ws.ok, "hubert_pitch_energy_forward: workspace too small");
+  const int lds = P.table.ld();
+  auto prosody = [&]() { Arena a = ws.rest(); return prosody_forward(st, P.pros, s, q, d, pe_style, sty, lds, row_utt, pros, a); };
+  {
+    DryScope dry;
+    STTS_TRY(prosody());
+  }
+  STTS_DRY_RETURN(ws);
   hipLaunchKernelGGL(row_utt_kernel, dim3(ceil_div(s.max_len(), 256), s.n_utt), dim3(256), 0, st, s.dev, s.n_utt, row_utt);
   STTS_TRY(gemm_store(st, s, feats, ld_f, 0, P.quant, q, d, 0));
   STTS_TRY(run_style(st, P.table, pe_style, s.n_utt, sty));
-  const int lds = P.table.ld();
-  { Arena a(ws.base + ws.used, ws.cap - ws.used); STTS_TRY(prosody_forward(st, P.pros, s, q, d, pe_style, sty, lds, row_utt, pros, a)); }
+  STTS_TRY(prosody());
   for (int br = 0; br < 2; ++br) {
     const AdainBlockW* blocks = br == 0 ? P.f0 : P.n;
     const float* cur = pros;
@@ -304,6 +298,30 @@ inline int hubert_pitch_energy_forward(stts_ctx* c, const HubertModel& M, hipStr
   }
   STTS_HIP(hipGetLastError());
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ workspace
+// Bytes that the three entry points above accept for `rows_T` feature frames in `n_utt` utterances, the longest of `max_len` frames:
+// the largest of their dry runs (speaker_style with both style encoders, where finalized; rows_T = 0: speaker_style alone).
+inline size_t hubert_workspace_bytes(const stts_ctx* cc, int64_t rows_T, int n_utt, int max_len) {
+  stts_ctx* c = const_cast<stts_ctx*>(cc);
+  if (!c || !c->hubert || n_utt <= 0) return 0;
+  const bool frames = rows_T > 0 && max_len > 0;
+  const HubertModel& M = *static_cast<const HubertModel*>(c->hubert.get());
+  const SynthSeg syn(rows_T, n_utt, max_len);
+  const Seg s = syn.seg();
+  return dry_run_bytes([&](Arena a) {
+    Arena e = a, p = a;
+    float* const wanted = reinterpret_cast<float*>(a.base);  // (an output that is asked for; never written)
+    float* const sp = M.sp.ready ? wanted : nullptr;
+    float* const pe = M.pe.ready ? wanted : nullptr;
+    Arena k0 = a, k1 = a, k2 = a;  // each style alone, and the two in one call (refused when their speaker widths differ)
+    (void)speaker_style(c, M, nullptr, n_utt, nullptr, 1 << 30, sp, nullptr, k0);
+    (void)speaker_style(c, M, nullptr, n_utt, nullptr, 1 << 30, nullptr, pe, k1);
+    (void)speaker_style(c, M, nullptr, n_utt, nullptr, 1 << 30, sp, pe, k2);
+    if (frames && M.sp.ready) (void)hubert_encoder_forward(c, M, nullptr, s, nullptr, 0, nullptr, 0, e);
+    if (frames && M.pe.ready) (void)hubert_pitch_energy_forward(c, M, nullptr, s, nullptr, 0, nullptr, nullptr, nullptr, nullptr, p);
+  });
 }
 
 }  // namespace stts

@@ -328,33 +328,6 @@ inline size_t ms_split_floats(const MelStyleW& E, Rows rows) {
   return mx;
 }
 
-// bytes of workspace for rows_T mel frames in n_utt utterances (upper bound over the ways rows_T can be split)
-inline size_t mel_style_workspace_bytes(const MelStyleW& E, int64_t rows_T, int n_utt) {
-  size_t fl = 0;
-  double tr = (double)rows_T;
-  const int levels = E.n_down + 1;
-  size_t lev_rows[kMsMaxBlocks + 2];
-  for (int l = 0; l < levels; ++l) {
-    lev_rows[l] = (size_t)tr * (size_t)(E.n_mels >> l);
-    tr = std::ceil(tr / 2.0) + n_utt;
-  }
-  fl += lev_rows[0] * ms_ld(E.c0);  // conv0
-  int l = 0;
-  for (int i = 0; i < kMsMaxBlocks; ++i) {
-    const MsBlockW& B = E.blk[i];
-    const size_t ri = lev_rows[l], ro = lev_rows[B.down ? l + 1 : l];
-    fl += ri * ms_ld(B.cin);                               // conv1
-    if (B.down) fl += 2 * ro * ms_ld(B.cin);               // depthwise, pooled input
-    if (B.learned_sc) fl += ro * ms_ld(B.cout);            // 1 x 1 shortcut
-    fl += ro * ms_ld(B.cout);                              // block output
-    if (B.down) ++l;
-  }
-  fl += lev_rows[levels - 1] * ms_ld(E.c_last);  // 5 x 5 output (bounded by the last level)
-  fl += ms_split_floats(E, [&](int lv) { return lev_rows[std::min(lv, levels - 1)]; });
-  const size_t ints = (size_t)(kMsMaxBlocks + 2) * (n_utt + 1);
-  return fl * sizeof(float) + ints * sizeof(int) + 64 * 256 + ((size_t)1 << 20);
-}
-
 // ------------------------------------------------------------------------------------------------ MelStyleEncoder.forward
 // P: split-K partials, ms_slices(w) * rows_out * ms_ld(cout) floats (unused when the conv is not split)
 // the base grid is the output level (offOut, Fo columns); the input level (offIn, F columns) differs from it only for the 5 x 5 valid conv
@@ -382,22 +355,34 @@ inline unsigned ms_grid(long n) { return (unsigned)((n + 255) / 256); }
 
 // mel [rows_T, ld >= n_mels] (utterance offsets s) -> style_out [n_utt, ld_style >= style_dim].  taps (optional): the four ResBlk outputs one
 // after the other, each [rows of its level][ms_ld(cout)] channels-last.
-inline int mel_style_forward(const MelStyleW& E, hipStream_t st, const Seg& s, const float* mel, int ld, float* style_out, int ld_style, float* taps, Arena& ws) {
-  MsPlan P;
-  STTS_TRY(ms_plan(E, s.n_utt, s.host, &P));
+// The body takes the plan (the workspace query has a bounding one and no offsets); of `s` it reads n_utt and the device offsets.
+inline int mel_style_planned(const MelStyleW& E, hipStream_t st, const Seg& s, const MsPlan& P, const float* mel, int ld, float* style_out, int ld_style, float* taps,
+                             Arena& ws) {
   const int n = s.n_utt, nl = P.n_lev;
+  // every buffer, from the plan alone and ahead of the first launch
   int* offs = ws.get<int>((size_t)(nl + 1) * (n + 1));
+  float* x = ws.get<float>((size_t)P.rows(0) * ms_ld(E.c0));  // shared.0's output
+  const size_t pf = ms_split_floats(E, [&](int lv) { return (size_t)P.rows(lv); });
+  float* part = pf ? ws.get<float>(pf) : nullptr;
+  struct { float *h1, *out, *hd, *xp, *sc; } buf[kMsMaxBlocks];  // hd / xp / sc: null where the block has no such buffer
+  for (int i = 0, l = 0; i < kMsMaxBlocks; ++i) {
+    const MsBlockW& B = E.blk[i];
+    const int lo = B.down ? l + 1 : l;
+    const size_t ri = (size_t)P.rows(l), ro = (size_t)P.rows(lo), ldi = ms_ld(B.cin), ldo = ms_ld(B.cout);
+    buf[i].h1 = ws.get<float>(ri * ldi);
+    buf[i].out = ws.get<float>(ro * ldo);
+    buf[i].hd = B.down ? ws.get<float>(ro * ldi) : nullptr;
+    buf[i].xp = B.down ? ws.get<float>(ro * ldi) : nullptr;
+    buf[i].sc = B.learned_sc ? ws.get<float>(ro * ldo) : nullptr;
+    l = lo;
+  }
+  float* h5 = ws.get<float>((size_t)P.rows(nl) * ms_ld(E.c_last));  // the 5 x 5 conv's output
   STTS_CHECK(ws.ok, "mel_style_forward: workspace too small");
+  STTS_DRY_RETURN(ws);
   auto off = [&](int l) -> const int* { return l == 0 ? s.dev : offs + l * (n + 1); };
   hipLaunchKernelGGL(ms_offsets_kernel, dim3(1), dim3(64), 0, st, s.dev, n, E.n_down, offs);
-  // shared.0
-  float* x = ws.get<float>((size_t)P.rows(0) * ms_ld(E.c0));
-  STTS_CHECK(ws.ok, "mel_style_forward: workspace too small");
   hipLaunchKernelGGL(ms_conv0_kernel, dim3(ms_grid(P.rows(0) * ms_ld(E.c0))), dim3(256), 0, st, mel, ld, s.dev, n, P.F[0], P.rows(0), E.w0, E.b0, E.c0,
                      ms_ld(E.c0), x);
-  float* part = nullptr;
-  if (const size_t pf = ms_split_floats(E, [&](int lv) { return (size_t)P.rows(lv); })) part = ws.get<float>(pf);
-  STTS_CHECK(ws.ok, "mel_style_forward: workspace too small");
   int l = 0;
   float* tap = taps;
   for (int i = 0; i < kMsMaxBlocks; ++i) {
@@ -405,12 +390,11 @@ inline int mel_style_forward(const MelStyleW& E, hipStream_t st, const Seg& s, c
     const int lo = B.down ? l + 1 : l;
     const long ri = P.rows(l), ro = P.rows(lo);
     const int ldi = ms_ld(B.cin), ldo = ms_ld(B.cout);
-    float* h1 = ws.get<float>((size_t)ri * ldi);
-    float* out = ws.get<float>((size_t)ro * ldo);
-    float* hd = B.down ? ws.get<float>((size_t)ro * ldi) : h1;
-    float* xp = B.down ? ws.get<float>((size_t)ro * ldi) : x;
-    float* sc = B.learned_sc ? ws.get<float>((size_t)ro * ldo) : xp;
-    STTS_CHECK(ws.ok, "mel_style_forward: workspace too small");
+    float* h1 = buf[i].h1;
+    float* out = buf[i].out;
+    float* hd = B.down ? buf[i].hd : h1;
+    float* xp = B.down ? buf[i].xp : x;
+    float* sc = B.learned_sc ? buf[i].sc : xp;
     // residual: conv1(lrelu(x)) [+ downsample_res]; the shortcut: avg-pool first, then the 1 x 1 conv (linear maps commute; 1/4 of its flops)
     STTS_TRY(ms_conv(st, B.conv1, true, x, off(l), off(l), n, P.F[l], P.F[l], ri, nullptr, 1.f, h1, part));
     if (B.down) {
@@ -429,13 +413,33 @@ inline int mel_style_forward(const MelStyleW& E, hipStream_t st, const Seg& s, c
   }
   // LeakyReLU -> shared.6 (5 x 5, valid) -> mean -> LeakyReLU -> unshared
   const long r5 = P.rows(nl);
-  float* h5 = ws.get<float>((size_t)r5 * ms_ld(E.c_last));
-  STTS_CHECK(ws.ok, "mel_style_forward: workspace too small");
   STTS_TRY(ms_conv(st, E.conv5, true, x, off(l), off(nl), n, P.F[l], P.F[nl], r5, nullptr, 1.f, h5, part));
   hipLaunchKernelGGL(ms_tail_kernel, dim3(n), dim3(256), (size_t)E.c_last * sizeof(float), st, h5, ms_ld(E.c_last), off(nl), P.F[nl], E.c_last, E.wl, E.bl,
                      E.style_dim, style_out, ld_style);
   STTS_HIP(hipGetLastError());
   return 0;
+}
+inline int mel_style_forward(const MelStyleW& E, hipStream_t st, const Seg& s, const float* mel, int ld, float* style_out, int ld_style, float* taps, Arena& ws) {
+  MsPlan P;
+  STTS_TRY(ms_plan(E, s.n_utt, s.host, &P));
+  return mel_style_planned(E, st, s, P, mel, ld, style_out, ld_style, taps, ws);
+}
+
+// Bytes of workspace for rows_T mel frames in n_utt utterances, however rows_T is split: a dry run of the forward on a bounding plan.
+// Halving a level rounds every utterance up, so sum over utterances of ceil(T / 2^l) has no single worst split: level l + 1 is bounded
+// by ceil(rows of level l / 2) + n_utt, and the 5 x 5 output by the last level.
+inline size_t mel_style_workspace_bytes(const MelStyleW& E, int64_t rows_T, int n_utt) {
+  if (rows_T <= 0 || n_utt <= 0) return 0;
+  MsPlan P;
+  P.n_lev = E.n_down + 1;
+  P.trows[0] = rows_T;
+  for (int l = 0; l < P.n_lev; ++l) {
+    P.F[l] = E.n_mels >> l;
+    P.trows[l + 1] = l + 1 < P.n_lev ? (P.trows[l] + 1) / 2 + n_utt : P.trows[l];
+  }
+  P.F[P.n_lev] = P.F[P.n_lev - 1] - (kMsMinOut - 1);
+  const Seg s{n_utt, nullptr, nullptr};
+  return dry_run_bytes([&](Arena a) { (void)mel_style_planned(E, nullptr, s, P, nullptr, 0, nullptr, 0, nullptr, a); });
 }
 
 }  // namespace stts

@@ -820,9 +820,11 @@ inline int finalize_frame(stts_ctx* c, int which) {
 // ------------------------------------------------------------------------------------------------
 // workspace bump allocator (caller-owned memory)
 // ------------------------------------------------------------------------------------------------
-// Workspace sizing by dry run (stts_frame_workspace_bytes): the stages carve their buffers from an Arena over a fake address
-// range, stop before their first launch and report how far they got - so the bound is what the stages really request,
-// for any model dims, instead of a hand-derived closed form.
+// Workspace sizing by dry run (every stts_*_workspace_bytes query but the CTC one): a stage carves ALL its buffers from an Arena, checks
+// `ok`, and only then launches; under dry_run().on it is handed an Arena over a fake address range with null device pointers, records how
+// far it got (STTS_DRY_RETURN) and returns before its first launch.  A stage that calls sub-stages walks them over rest() first.  So the
+// bound is what the code asks for, whatever the dims, precision or STTS_* switches; no host code ahead of STTS_DRY_RETURN may read
+// through a device pointer.
 struct DryRun {
   bool on = false;
   size_t peak = 0;
@@ -856,7 +858,28 @@ struct Arena {
     used += bytes;
     return p;
   }
+  // the unused tail, for a sub-stage (or scratch that is released again when the sub-arena goes out of scope)
+  Arena rest() const { return Arena(base + used, cap - used, offset0 + used); }
 };
+
+// Dry mode for a scope; on every exit path it goes back to what it was.  A stage that calls sub-stages walks them under a DryScope over
+// rest() before its own first launch: in a query that records their peak, in a real call a workspace too small for any of them is
+// refused before anything is launched.
+struct DryScope {
+  const bool was = dry_run().on;
+  DryScope() { dry_run().on = true; }
+  ~DryScope() { dry_run().on = was; }
+};
+
+// Bytes that `walk` carves: walk(arena) runs one or more stages in dry mode, each over a copy of the (fake, never touched) arena it is
+// given; what they return is ignored (a stage that refuses its arguments has carved nothing).
+template <typename Walk>
+inline size_t dry_run_bytes(Walk&& walk) {
+  DryScope dry;
+  dry_run().peak = 0;
+  walk(Arena(reinterpret_cast<char*>((uintptr_t)1 << 20), (size_t)1 << 46));
+  return dry_run().peak + 4096;
+}
 
 struct Seg {
   int n_utt;
@@ -873,6 +896,29 @@ struct Seg {
     for (int i = 0; i < n_utt; ++i) m = std::max(m, host[i + 1] - host[i]);
     return m;
   }
+};
+
+// Host offsets for a workspace query that knows only (rows, n_utt, max_len): lengths with that total, count and maximum, every
+// utterance non-empty (max_len is clipped to what the others leave; <= 0 = unknown: one utterance holds all rows the others leave).
+// THE RULE this stands on: a stage's carving may depend on a Seg only through rows(), n_utt and max_len(), and is non-decreasing
+// in each - so any batch with these three numbers, or smaller ones, fits.  (A count that depends on how the rows are split, like
+// sum over utterances of ceil(len / 4), is carved in its capacity form: wino_plane_rows.)
+struct SynthSeg {
+  std::vector<int> off;
+  SynthSeg(int64_t rows, int n_utt, int64_t max_len) : off(std::max(n_utt, 1) + 1, 0) {
+    n_utt = std::max(n_utt, 1);
+    rows = std::max<int64_t>(rows, n_utt);
+    const int64_t most = rows - (n_utt - 1);
+    max_len = max_len <= 0 ? most : std::max(std::min(max_len, most), (rows + n_utt - 1) / n_utt);  // (too small for the total: raised)
+    int64_t rest = rows - max_len;
+    off[1] = (int)max_len;
+    for (int u = 1; u < n_utt; ++u) {
+      const int64_t len = std::max<int64_t>(1, std::min(max_len, rest - (n_utt - 1 - u)));
+      off[u + 1] = off[u] + (int)len;
+      rest -= len;
+    }
+  }
+  Seg seg() const { return Seg{(int)off.size() - 1, off.data(), nullptr}; }
 };
 
 inline GemmArgs gemm_args(const Seg& s) {
@@ -1775,7 +1821,7 @@ inline int vocoder_forward(stts_ctx* c, hipStream_t st, const Seg& s, const floa
   float* headP = ws.get<float>(R * hc);
   STTS_CHECK(ws.ok, "vocoder_forward: workspace too small");
   {
-    Arena tmp(ws.base + ws.used, ws.cap - ws.used, ws.offset0 + ws.used);  // released again before vocoder_body carves its own buffers
+    Arena tmp = ws.rest();  // released again before vocoder_body carves its own buffers
     WinoScratch wino;
     if (c->wino_prior[0].ready) wino.p = tmp.get<float>(wino_scratch_floats(s, c->wino_prior[0]));
     unsigned short* har16 = c->prec != PREC_F32 ? tmp.get<unsigned short>(R * ld_har) : nullptr;
@@ -1815,11 +1861,7 @@ inline int frame_path(stts_ctx* c, hipStream_t st, const Seg& s, const float* as
   const bool side_cfg = c->prec == PREC_F32 && R > side_min_rows && c->wino_prior[0].ready;
   float* side_scratch = side_cfg ? top.get<float>(wino_scratch_floats(s, c->wino_prior[0])) : nullptr;
   STTS_CHECK(top.ok, "frame_path: workspace too small");
-  const size_t mark = top.used;
-  auto stage = [&]() {
-    Arena a((char*)wsp + mark, ws_bytes - mark, mark);
-    return a;
-  };
+  auto stage = [&]() { return top.rest(); };  // (nothing more is carved from `top`: every stage starts at the same mark)
   // Measured: running the (independent) source -> STFT -> prior-conv chain on side streams next to decoder/flow gains
   // < 1 % at B = 8 (7.51 vs 7.57 ms/step): the decoder GEMMs already fill the chip, so the stages stay on one stream.
   // 16-bit operand modes, large batches: the spectra are only read by the prior convs, so the STFT writes them as 16-bit rows
@@ -1898,37 +1940,20 @@ inline int frame_path(stts_ctx* c, hipStream_t st, const Seg& s, const float* as
 }
 
 // Bytes of caller-owned workspace that every frame-rate entry point accepts for a batch of `R` rows in `n_utt` utterances,
-// the longest `max_len` rows: a DRY RUN of the stages themselves over a fake address range (each carves its buffers, records
-// how far it got and returns before its first launch), so the bound follows the model dims and whatever the stages really
-// request.  Buffer sizes depend on the batch only through (R, n_utt, max_len); weights must be finalized (which convs have a
-// Winograd form decides their scratch).
+// the longest `max_len` rows: a dry run of the stages themselves (dry_run_bytes), so the bound follows the model dims and
+// whatever the stages really request.  Weights must be finalized (which convs have a Winograd form decides their scratch).
 inline size_t frame_workspace_bytes(const stts_ctx* cc, int64_t R, int n_utt, int max_len) {
   stts_ctx* c = const_cast<stts_ctx*>(cc);
   if (R <= 0 || n_utt <= 0 || max_len <= 0) return 0;
-  max_len = (int)std::min<int64_t>(max_len, R);
-  std::vector<int> off(n_utt + 1, 0);  // any lengths with this total, count and maximum
-  long rest = R - max_len;
-  off[1] = max_len;
-  for (int u = 1; u < n_utt; ++u) {
-    const long len = std::max<long>(1, std::min<long>(max_len, rest - (n_utt - 1 - u)));
-    off[u + 1] = off[u] + (int)len;
-    rest -= len;
-  }
-  Seg s{n_utt, off.data(), nullptr};
-  DryRun& d = dry_run();
-  d.on = true;
-  d.peak = 0;
-  char* fake = reinterpret_cast<char*>((uintptr_t)1 << 20);
-  const size_t cap = (size_t)1 << 46;
-  (void)frame_path(c, nullptr, s, nullptr, c->d.inter_dim, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, fake, cap);
-  {  // the staged entry points start their carving at offset 0; vocoder_forward with its own head buffers is the largest of them
-    Arena a(fake, cap);
-    (void)vocoder_forward(c, nullptr, s, nullptr, c->d.dec_hidden, nullptr, nullptr, nullptr, har_ld(c), nullptr, nullptr, nullptr, 0, a);
-    Arena b(fake, cap);
-    (void)decoder_forward(c, nullptr, s, nullptr, c->d.inter_dim, nullptr, nullptr, nullptr, nullptr, c->d.dec_hidden, b);
-  }
-  d.on = false;
-  return d.peak + 4096;
+  const SynthSeg syn(R, n_utt, max_len);
+  const Seg s = syn.seg();
+  return dry_run_bytes([&](Arena a) {
+    (void)frame_path(c, nullptr, s, nullptr, c->d.inter_dim, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, a.base, a.cap);
+    // the staged entry points start their carving at offset 0; vocoder_forward with its own head buffers is the largest of them
+    Arena v = a, d = a;
+    (void)vocoder_forward(c, nullptr, s, nullptr, c->d.dec_hidden, nullptr, nullptr, nullptr, har_ld(c), nullptr, nullptr, nullptr, 0, v);
+    (void)decoder_forward(c, nullptr, s, nullptr, c->d.inter_dim, nullptr, nullptr, nullptr, nullptr, c->d.dec_hidden, d);
+  });
 }
 
 }  // namespace stts

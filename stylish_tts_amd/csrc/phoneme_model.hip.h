@@ -357,6 +357,7 @@ inline int text_encoder_forward(stts_ctx* c, hipStream_t st, const TextEncW& W, 
   float* att = ws.get<float>(R * C);
   float* ff = ws.get<float>(R * W.filter);
   STTS_CHECK(ws.ok, "text_encoder_forward: workspace too small");
+  STTS_DRY_RETURN(ws);
   hipLaunchKernelGGL(embed_kernel, dim3((unsigned)std::min<long>(1024, ceil_div((int)(R * C / 4), 256))), dim3(256), 0, st, tokens, W.emb, C, W.tokens,
                      sqrtf((float)C), x, C, (int)R, c->d_err);
   // ConvReluNorm prenet (text_encoder.py:79-86): 3 x (conv k5 -> channel LayerNorm eps 1e-4 -> ReLU), + 1x1 proj residual
@@ -390,6 +391,7 @@ inline int text_style_forward(stts_ctx* c, hipStream_t st, const StyleEncW& W, c
   float* gx = ws.get<float>((size_t)s.n_utt * inter4);
   float* w2u = ws.get<float>((size_t)s.n_utt * W.blk[0].pw2.npad * inter4);
   STTS_CHECK(ws.ok, "text_style_forward: workspace too small");
+  STTS_DRY_RETURN(ws);
   STTS_TRY(gemm_store(st, s, x, ldx, 0, W.conv_in, h, sd, 0));
   for (int i = 0; i < W.n; ++i) {
     const StyleEncW::Blk& B = W.blk[i];
@@ -431,6 +433,7 @@ inline int prosody_forward(hipStream_t st, const ProsodyW& W, const Seg& s, cons
   float* att = ws.get<float>(R * C);
   float* ff = ws.get<float>(R * 2 * C);
   STTS_CHECK(ws.ok, "prosody_forward: workspace too small");
+  STTS_DRY_RETURN(ws);
   STTS_HIP(hipMemcpy2DAsync(x, C * sizeof(float), enc, ld_enc * sizeof(float), d * sizeof(float), R, hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(broadcast_style_kernel, dim3(std::max(1, ceil_div(s.max_len() * sd, 256)), s.n_utt), dim3(256), 0, st, style, sd, sd, x, C, d, s.dev);
   for (int i = 0; i < W.n_layers; ++i) {
@@ -446,15 +449,6 @@ inline int prosody_forward(hipStream_t st, const ProsodyW& W, const Seg& s, cons
   return 0;
 }
 
-inline size_t phoneme_workspace_bytes(const stts_ctx* c, int64_t n_tok, int64_t n_frames, int n_utt) {
-  const stts_model_dims& d = c->d;
-  const size_t C = d.te_hidden, Cp = d.pe_inter + d.style_dim;
-  const size_t tok = (size_t)n_tok * (C * 8 + d.te_filter + Cp * 12 + d.style_dim * 12 + 64) * sizeof(float);
-  const size_t frm = (size_t)n_frames * (Cp * 12 + 16) * sizeof(float) + ((size_t)n_frames / kWinoM + n_utt + 1) * 8 * 2 * Cp * sizeof(float);  // + Winograd scratch
-  const size_t per = (size_t)n_utt * ((size_t)(n_tok / std::max(1, n_utt) / 32 + 16) * 4 * d.style_dim * 8 + 128 * 256 + 8192) * sizeof(float);
-  return tok + frm + per + ((size_t)4 << 20);
-}
-
 // ------------------------------------------------------------------------------------------------ DurationPredictor.forward
 inline int duration_forward(stts_ctx* c, PhonemeModel& M, hipStream_t st, const Seg& s, const long* tokens, float* logits, int ld_logits, int* dur_out,
                             float* mu_out, float* style_out, float* prosody_out, Arena& ws) {
@@ -467,11 +461,22 @@ inline int duration_forward(stts_ctx* c, PhonemeModel& M, hipStream_t st, const 
   float* sty = ws.get<float>((size_t)s.n_utt * D.table.ld());
   int* row_utt = ws.get<int>(R);
   STTS_CHECK(ws.ok, "duration_forward: workspace too small");
+  // the sub-stages, each over the unused tail
+  auto text = [&]() { Arena a = ws.rest(); return text_encoder_forward(c, st, M.te[0], s, tokens, mu, d, nullptr, a); };
+  auto text_style = [&]() { Arena a = ws.rest(); return text_style_forward(c, st, M.se[0], s, mu, d, style, c->d.style_dim, a); };
+  auto prosody = [&]() { Arena a = ws.rest(); return prosody_forward(st, D.pros, s, mu, d, style, sty, D.table.ld(), row_utt, pros, a); };
+  {
+    DryScope dry;
+    STTS_TRY(text());
+    STTS_TRY(text_style());
+    STTS_TRY(prosody());
+  }
+  STTS_DRY_RETURN(ws);
   hipLaunchKernelGGL(row_utt_kernel, dim3(ceil_div(s.max_len(), 256), s.n_utt), dim3(256), 0, st, s.dev, s.n_utt, row_utt);
-  { Arena a(ws.base + ws.used, ws.cap - ws.used); STTS_TRY(text_encoder_forward(c, st, M.te[0], s, tokens, mu, d, nullptr, a)); }
-  { Arena a(ws.base + ws.used, ws.cap - ws.used); STTS_TRY(text_style_forward(c, st, M.se[0], s, mu, d, style, c->d.style_dim, a)); }
+  STTS_TRY(text());
+  STTS_TRY(text_style());
   STTS_TRY(run_style(st, D.table, style, s.n_utt, sty));
-  { Arena a(ws.base + ws.used, ws.cap - ws.used); STTS_TRY(prosody_forward(st, D.pros, s, mu, d, style, sty, D.table.ld(), row_utt, pros, a)); }
+  STTS_TRY(prosody());
   STTS_TRY(gemm_store(st, s, pros, C, 0, D.proj, logits, ld_logits, 0));
   if (dur_out) hipLaunchKernelGGL(duration_decode_kernel, dim3(ceil_div((int)R, 256)), dim3(256), 0, st, logits, ld_logits, 16, (int)R, dur_out);
   STTS_HIP(hipGetLastError());
@@ -513,11 +518,17 @@ inline int pitch_energy_forward(stts_ctx* c, PhonemeModel& M, hipStream_t st, co
   float* ss_mid = wstat_mode ? ws.get<float>(adain_part_floats(sf, C, kWinoStatChunk)) : nullptr;
   float* ss_x = wstat_mode ? ws.get<float>(adain_part_floats(sf, C, kWinoStatChunk)) : nullptr;  // statistics of x: one pass for both branches' first norm
   STTS_CHECK(ws.ok, "pitch_energy_forward: workspace too small");
+  const int lds = P.table.ld();
+  auto prosody = [&]() { Arena a = ws.rest(); return prosody_forward(st, P.pros, sp, pe_enc, ld_enc, pe_style, sty, lds, row_utt_p, pros, a); };
+  {
+    DryScope dry;
+    STTS_TRY(prosody());
+  }
+  STTS_DRY_RETURN(ws);
   hipLaunchKernelGGL(row_utt_kernel, dim3(ceil_div(sp.max_len(), 256), sp.n_utt), dim3(256), 0, st, sp.dev, sp.n_utt, row_utt_p);
   hipLaunchKernelGGL(row_utt_kernel, dim3(ceil_div(sf.max_len(), 256), sf.n_utt), dim3(256), 0, st, sf.dev, sf.n_utt, row_utt_f);
   STTS_TRY(run_style(st, P.table, pe_style, sp.n_utt, sty));
-  const int lds = P.table.ld();
-  { Arena a(ws.base + ws.used, ws.cap - ws.used); STTS_TRY(prosody_forward(st, P.pros, sp, pe_enc, ld_enc, pe_style, sty, lds, row_utt_p, pros, a)); }
+  STTS_TRY(prosody());
   // compute_cross (pitch_energy_predictor.py:83-102): base = prosody^T @ alignment == gather by the frame->token map
   hipLaunchKernelGGL(frame_token_map_kernel, dim3(sp.n_utt), dim3(256), 0, st, dur, sp.dev, sf.dev, 1, src_row);
   hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)std::min<long>(2048, std::max<long>(1, ceil_div((int)(Rf * C / 4), 256)))), dim3(256), 0, st, pros, C,
@@ -562,6 +573,28 @@ inline int pitch_energy_forward(stts_ctx* c, PhonemeModel& M, hipStream_t st, co
   }
   STTS_HIP(hipGetLastError());
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ workspace
+// Bytes that the four phoneme-rate entry points accept for `n_tok` tokens and `n_frames` frames in `n_utt` utterances, the longest of
+// `max_tok` tokens and `max_frames` frames: the largest of their dry runs, every optional output left to the workspace.  Components
+// that are not finalized carve nothing and count nothing.
+inline size_t phoneme_workspace_bytes(const stts_ctx* cc, int64_t n_tok, int64_t n_frames, int n_utt, int max_tok, int max_frames) {
+  stts_ctx* c = const_cast<stts_ctx*>(cc);
+  if (!c || !c->phoneme || n_tok <= 0 || n_utt <= 0 || max_tok <= 0) return 0;
+  PhonemeModel& M = *static_cast<PhonemeModel*>(c->phoneme.get());
+  const SynthSeg tok(n_tok, n_utt, max_tok), frm(n_frames, n_utt, max_frames);
+  const Seg sp = tok.seg(), sf = frm.seg();
+  return dry_run_bytes([&](Arena a) {
+    for (int i = 0; i < 3; ++i) {
+      Arena e = a, s = a;
+      if (M.te[i].ready) (void)text_encoder_forward(c, nullptr, M.te[i], sp, nullptr, nullptr, 0, nullptr, e);
+      if (M.se[i].ready) (void)text_style_forward(c, nullptr, M.se[i], sp, nullptr, 0, nullptr, 0, s);
+    }
+    Arena d = a, p = a;
+    if (M.dur.ready && M.te[0].ready && M.se[0].ready) (void)duration_forward(c, M, nullptr, sp, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, d);
+    if (M.pe.ready && n_frames > 0 && max_frames > 0) (void)pitch_energy_forward(c, M, nullptr, sp, sf, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, p);
+  });
 }
 
 }  // namespace stts

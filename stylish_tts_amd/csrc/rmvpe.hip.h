@@ -563,16 +563,6 @@ inline size_t rv_partial_floats(const RvW& M, long Tp) {
 
 inline size_t rv_level_floats(const RvW& M, long Tp, int l, int C) { return (size_t)(Tp >> l) * (kRvMels >> l) * rv_ld(C); }
 
-inline size_t rmvpe_workspace_bytes(const RvW& M, int n_utt, const int* off) {
-  const long Tp = rv_padded(n_utt, off);
-  size_t fl = 0;
-  for (int l = 0; l < kRvLevels; ++l) fl += rv_level_floats(M, Tp, l, M.d.c0 << l) + 64;  // skips
-  fl += 4 * (rv_level_floats(M, Tp, 0, M.d.c0) + 64);                                    // four rotating buffers, each as large as the largest activation
-  fl += rv_partial_floats(M, Tp) + 64;
-  fl += (size_t)Tp * (4 * kRvMels + 6 * kRvHid + 2 * kRvHid + kRvClasses) + 256;  // cnn, xi, gru, hidden
-  return fl * sizeof(float) + (size_t)(n_utt + 1) * sizeof(int) + ((size_t)64 << 10);
-}
-
 struct RvRun {
   hipStream_t st;
   const int* offP;
@@ -645,6 +635,7 @@ inline int rmvpe_forward(const RvW& M, hipStream_t st, int n_utt, const int* off
   float* gru = ws.get<float>((size_t)Tp * 2 * kRvHid + 64);
   float* hp = ws.get<float>((size_t)Tp * kRvClasses + 64);
   STTS_CHECK(ws.ok, "rmvpe_forward: workspace too small");
+  STTS_DRY_RETURN(ws);
   hipLaunchKernelGGL(rv_offsets_kernel, dim3(1), dim3(64), 0, st, off_dev, n_utt, offP);
   RvRun r{st, offP, n_utt, Tp, part};
   float* tap = taps;
@@ -734,6 +725,11 @@ inline int rmvpe_forward(const RvW& M, hipStream_t st, int n_utt, const int* off
   }
   STTS_HIP(hipGetLastError());
   return 0;
+}
+
+// workspace bytes for these host frame offsets: a dry run of the carving above
+inline size_t rmvpe_workspace_bytes(const RvW& M, int n_utt, const int* off) {
+  return dry_run_bytes([&](Arena a) { (void)rmvpe_forward(M, nullptr, n_utt, off, nullptr, nullptr, 0, 0.f, nullptr, nullptr, nullptr, a); });
 }
 
 }  // namespace stts

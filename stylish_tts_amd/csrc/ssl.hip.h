@@ -502,26 +502,6 @@ inline void ssl_plan(const SslDims& d, int n_utt, const int* samp_off, SslPlan* 
     for (int u = 0; u <= n_utt; ++u) P->lvl_off[i][u] = P->cap_off[u] * g.D[i];
 }
 
-inline size_t ssl_workspace_bytes(const SslW& M, int n_utt, const int* samp_off) {
-  const SslDims& d = M.d;
-  SslPlan P;
-  ssl_plan(d, n_utt, samp_off, &P);
-  const SslGeom g = ssl_geom(d);
-  const size_t cap = P.cap_off[n_utt], F = P.fr_off[n_utt];
-  size_t fl = 0;
-  // two alternating level buffers, each large enough for its biggest level (+ the window overhang of the last view row)
-  size_t a = 0, b = 0;
-  for (int i = 0; i < d.n_conv; ++i) {
-    const size_t n = cap * g.D[i] * d.conv_dim[i] + 16 * (size_t)d.conv_dim[i] + 64;
-    (i % 2 == 0 ? a : b) = std::max(i % 2 == 0 ? a : b, n);
-  }
-  fl += a + b + 512;
-  fl += (size_t)n_utt * 2 * d.conv_dim[0];                                              // GroupNorm statistics
-  fl += F * ((size_t)d.conv_dim[d.n_conv - 1] + 6 * (size_t)d.hidden + d.inter) + 64;   // ln, x, t, qkv (3), att, ff
-  const size_t nchunk = ceil_div(std::max(1, P.max_len0), kSslT0);
-  return fl * sizeof(float) + (size_t)n_utt * nchunk * 2 * d.conv_dim[0] * sizeof(double) + (size_t)(d.n_conv + 2) * (n_utt + 1) * sizeof(int) + ((size_t)64 << 10);
-}
-
 inline int ssl_forward(const SslW& M, hipStream_t st, int n_utt, const int* samp_off_host, const int* samp_off_dev, const float* wave, const Seg& sT, float* feats,
                        int ld_feats, const SslTaps* taps, Arena& ws) {
   const SslDims& d = M.d;
@@ -547,6 +527,7 @@ inline int ssl_forward(const SslW& M, hipStream_t st, int n_utt, const int* samp
   float* att = ws.get<float>(F * H);
   float* ff = ws.get<float>(F * d.inter);
   STTS_CHECK(ws.ok, "ssl_forward: workspace too small");
+  STTS_DRY_RETURN(ws);
   const int* cap_dev = tab;
   const int* fr_dev = tab + n1;
   hipLaunchKernelGGL(ssl_offsets_kernel, dim3(1), dim3(64), 0, st, g, samp_off_dev, n_utt, tab);
@@ -620,6 +601,12 @@ inline int ssl_forward(const SslW& M, hipStream_t st, int n_utt, const int* samp
   }
   STTS_HIP(hipGetLastError());
   return 0;
+}
+
+// workspace bytes for these host sample offsets: a dry run of the carving above
+inline size_t ssl_workspace_bytes(const SslW& M, int n_utt, const int* samp_off) {
+  const Seg none{n_utt, nullptr, nullptr};  // (the time_dim offsets: read after the carving only)
+  return dry_run_bytes([&](Arena a) { (void)ssl_forward(M, nullptr, n_utt, samp_off, nullptr, nullptr, none, nullptr, 0, nullptr, a); });
 }
 
 }  // namespace stts

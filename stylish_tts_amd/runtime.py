@@ -351,22 +351,23 @@ class HipModel:
         return out
 
     # ------------------------------------------------------------------ phoneme-rate stages (packed tokens)
-    def _ph_ws(self, n_tok: int, n_frames: int, n_utt: int) -> torch.Tensor:
-        return self._grow(self._pws, int(self.lib.stts_phoneme_workspace_bytes(self.ctx, n_tok, n_frames, n_utt)))
+    def _ph_ws(self, seg_p: Segments, seg_t: Optional[Segments] = None) -> torch.Tensor:
+        rows_t, max_t = (seg_t.rows, seg_t.max_len) if seg_t is not None else (0, 0)
+        return self._grow(self._pws, int(self.lib.stts_phoneme_workspace_bytes(self.ctx, seg_p.rows, rows_t, seg_p.n, seg_p.max_len, max_t)))
 
     def text_encoder(self, which: int, seg: Segments, tokens: torch.Tensor, return_hidden=False):
         """tokens int64 [n_tok] (packed) -> mu [n_tok, inter] (+ last hidden [n_tok, 128])."""
         inter = self.cfg.pitch_energy_predictor.inter_dim if which == 2 else self.cfg.inter_dim
         mu = self._f32(seg.rows, inter)
         xh = self._f32(seg.rows, self.cfg.text_encoder.hidden_dim) if return_hidden else None
-        ws = self._ph_ws(seg.rows, 0, seg.n)
+        ws = self._ph_ws(seg)
         _lib.check(self.lib.stts_text_encoder_forward(self.ctx, _stream(), which, seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(tokens), _ptr(mu), inter,
                                                       _ptr(xh), _ptr(ws), ws.numel()))
         return (mu, xh) if return_hidden else mu
 
     def text_style(self, which: int, seg: Segments, x: torch.Tensor):
         style = self._f32(seg.n, self.cfg.style_dim)
-        ws = self._ph_ws(seg.rows, 0, seg.n)
+        ws = self._ph_ws(seg)
         _lib.check(self.lib.stts_text_style_forward(self.ctx, _stream(), which, seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(x), x.shape[1], _ptr(style),
                                                     _ptr(ws), ws.numel()))
         return style
@@ -379,7 +380,7 @@ class HipModel:
         if taps:
             t = dict(text_mu=self._f32(seg.rows, self.cfg.inter_dim), style=self._f32(seg.n, self.cfg.style_dim),
                      prosody=self._f32(seg.rows, self.cfg.inter_dim + self.cfg.style_dim))
-        ws = self._ph_ws(seg.rows, 0, seg.n)
+        ws = self._ph_ws(seg)
         _lib.check(self.lib.stts_duration_forward(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(tokens), _ptr(logits), _ptr(dur),
                                                   _ptr(t["text_mu"]) if t else None, _ptr(t["style"]) if t else None,
                                                   _ptr(t["prosody"]) if t else None, _ptr(ws), ws.numel()))
@@ -391,7 +392,7 @@ class HipModel:
         en = self._f32(seg_t.rows)
         C = self.cfg.pitch_energy_predictor.inter_dim + self.cfg.style_dim
         t = dict(prosody=self._f32(seg_p.rows, C), cross=self._f32(seg_t.rows, C)) if taps else None
-        ws = self._ph_ws(seg_p.rows, seg_t.rows, seg_p.n)
+        ws = self._ph_ws(seg_p, seg_t)
         _lib.check(self.lib.stts_pitch_energy_forward(self.ctx, _stream(), seg_p.n, seg_p.host_ptr, _ptr(seg_p.dev), seg_t.host_ptr, _ptr(seg_t.dev),
                                                       _ptr(dur), _ptr(pe_enc), pe_enc.shape[1], _ptr(pe_style), _ptr(f0), _ptr(en),
                                                       _ptr(t["prosody"]) if t else None, _ptr(t["cross"]) if t else None, _ptr(ws), ws.numel(), seg_t.flags))

@@ -1,7 +1,9 @@
 // Sanitizer driver (CPU): loads a weight dump, finalizes every component and walks the stage entry points over the shapes of
 // BASELINE's configs with the HIP runtime stubbed out (hip_stub.cpp).  Exercised under -fsanitize=address,undefined:
-// weight-norm folding, row / Winograd / fragment packing, style tables, the workspace closed forms against what the stages
-// really carve (a stage returns "workspace too small" if the bound is wrong), and the launch planning of every contraction.
+// weight-norm folding, row / Winograd / fragment packing, style tables, the workspace queries (dry runs of the stages' own carving)
+// against the real calls (a stage returns "workspace too small" if the bound is wrong), and the launch planning of every contraction.
+// Every stage walk but the frame path's is then repeated one 256-byte unit below the smallest workspace the stage accepts: it must be
+// refused with "workspace too small" before anything is launched (`refusal <precision> <case> <stage> : ...`).
 // It also says what the packers wrote: after every finalize a line `digest <precision> <what> <hex>` with the stub's digest of the device
 // allocations made since the context was created.  Per precision a second context finalizes the same components in another order, with one
 // finalize in the middle that must fail, and has to end at the first context's digest: packing must not depend on what was packed before.
@@ -47,6 +49,40 @@ static void launchtrace(const char* what, const char* trace) {
   std::string tag = what;
   std::replace(tag.begin(), tag.end(), ' ', '_');
   printf("launchtrace %d %s : %s\n", g_prec, tag.c_str(), trace);
+}
+
+// `call(bytes)` runs one stage entry point on `bytes` of workspace, which the stage's query sized (`query` bytes: accepted, the caller has
+// checked).  Finds the smallest size the stage accepts - acceptance is monotone in the size, so bisection over 256-byte units ends where
+// walking down from the query would - and runs the call once more one unit below: refused, by that message, nothing launched.
+template <typename Call>
+static int refuse_below(const char* what, const char* stage, size_t query, Call call) {
+  size_t lo = 0, hi = query / 256;  // units: lo refused, hi accepted
+  while (hi - lo > 1) {
+    const size_t mid = lo + (hi - lo) / 2;
+    (call(mid * 256) == 0 ? hi : lo) = mid;
+  }
+  const long before = stts_stub_launch_count();
+  const int rc = call((hi - 1) * 256);
+  const long launched = stts_stub_launch_count() - before;
+  if (rc == 0 || !strstr(stts_last_error(), "workspace too small") || launched != 0) {
+    fprintf(stderr, "FAILED %s %s: %zu bytes (one unit below the least accepted size): status %d, %ld launches, \"%s\"\n", what, stage, (hi - 1) * 256, rc, launched,
+            rc ? stts_last_error() : "");
+    return 1;
+  }
+  std::string tag = what;
+  std::replace(tag.begin(), tag.end(), ' ', '_');
+  printf("refusal %d %s %s : query %zu bytes, least accepted %zu, refused below it with nothing launched\n", g_prec, tag.c_str(), stage, query, hi * 256);
+  return 0;
+}
+#define REFUSE(what, query, stage, ...)                                                         \
+  do {                                                                                          \
+    if (refuse_below(what, stage, query, [&](size_t bytes) { return __VA_ARGS__; })) return 1; \
+  } while (0)
+
+static std::vector<int32_t> offsets(const std::vector<int>& lens, int scale = 1) {
+  std::vector<int32_t> off(lens.size() + 1, 0);
+  for (size_t i = 0; i < lens.size(); ++i) off[i + 1] = off[i] + scale * lens[i];
+  return off;
 }
 
 static int frame_case(stts_ctx* c, const std::vector<int>& lens, const char* what) {
@@ -182,7 +218,7 @@ static int phoneme_case(stts_ctx* c, const std::vector<int>& toks, const std::ve
     fo4[i + 1] = fo4[i] + 4 * frames[i];
   }
   const long P = to[n], T = fo[n];
-  const size_t wsb = stts_phoneme_workspace_bytes(c, P, T, n);
+  const size_t wsb = stts_phoneme_workspace_bytes(c, P, T, n, *std::max_element(toks.begin(), toks.end()), *std::max_element(frames.begin(), frames.end()));
   std::vector<char> ws(wsb);
   std::vector<int64_t> tokens(P, 3);
   std::vector<int32_t> dur(P, 1);
@@ -205,7 +241,133 @@ static int phoneme_case(stts_ctx* c, const std::vector<int>& toks, const std::ve
   CK(stts_length_regulate(c, nullptr, n, dur.data(), to.data(), fo4.data(), 4 * T, 4, mu.data(), 256, 128, enc4.data(), 128, idx.data()));
   CK(stts_upsample4(c, nullptr, n, fo.data(), fo.data(), fo4.data(), f0.data(), up.data()));
   launchtrace(what, stts_stub_trace_end());
-  printf("  %-44s tokens %6ld frames %7ld  workspace %8.1f MB\n", what, P, T, wsb / 1048576.0);
+  printf("  %-44s tokens %6ld frames %7ld  workspace %8.1f MB (%zu bytes)\n", what, P, T, wsb / 1048576.0, wsb);
+  REFUSE(what, wsb, "text_encoder", stts_text_encoder_forward(c, nullptr, 0, n, to.data(), to.data(), tokens.data(), mu.data(), 256, xh.data(), ws.data(), bytes));
+  REFUSE(what, wsb, "text_style", stts_text_style_forward(c, nullptr, 0, n, to.data(), to.data(), mu.data(), 256, sty.data(), ws.data(), bytes));
+  REFUSE(what, wsb, "duration", stts_duration_forward(c, nullptr, n, to.data(), to.data(), tokens.data(), logits.data(), dur_out.data(), nullptr, nullptr, nullptr, ws.data(), bytes));
+  REFUSE(what, wsb, "pitch_energy", stts_pitch_energy_forward(c, nullptr, n, to.data(), to.data(), fo.data(), fo.data(), dur.data(), mu.data(), 256, sty.data(), f0.data(), en.data(),
+                                                   nullptr, nullptr, ws.data(), bytes, 0));
+  return 0;
+}
+
+// sizes the driver cannot know from the dims structs: read off the weights
+struct Widths {
+  int hubert_dim, spk_dim, n_mels, pitch_asr;
+};
+
+// The HuBERT voice-conversion stages over `frames` feature frames per utterance, each sized by stts_hubert_workspace_bytes.
+static int hubert_case(stts_ctx* c, const stts_model_dims& d, const Widths& wd, const std::vector<int>& frames, const char* what) {
+  const int n = (int)frames.size();
+  const std::vector<int32_t> off = offsets(frames);
+  const long T = off[n];
+  const int ldf = (wd.hubert_dim + 31) / 32 * 32;
+  const size_t wsb = stts_hubert_workspace_bytes(c, T, n, *std::max_element(frames.begin(), frames.end()));
+  std::vector<char> ws(wsb);
+  auto spk = buf((size_t)n * wd.spk_dim), sty = buf((size_t)n * d.style_dim), pe = buf((size_t)n * d.style_dim), feats = buf(T * ldf), asr = buf(4 * T * d.inter_dim);
+  auto f0 = buf(T), en = buf(T);
+  stts_stub_trace_begin();
+  CK(stts_speaker_style(c, nullptr, n, spk.data(), wd.spk_dim, sty.data(), pe.data(), ws.data(), wsb));
+  CK(stts_hubert_encoder_forward(c, nullptr, n, off.data(), off.data(), feats.data(), ldf, asr.data(), d.inter_dim, ws.data(), wsb));
+  CK(stts_hubert_pitch_energy_forward(c, nullptr, n, off.data(), off.data(), feats.data(), ldf, pe.data(), f0.data(), en.data(), nullptr, ws.data(), wsb));
+  launchtrace(what, stts_stub_trace_end());
+  printf("  %-44s frames %7ld  workspace %8.1f MB (%zu bytes)\n", what, T, wsb / 1048576.0, wsb);
+  REFUSE(what, wsb, "speaker_style", stts_speaker_style(c, nullptr, n, spk.data(), wd.spk_dim, sty.data(), pe.data(), ws.data(), bytes));
+  REFUSE(what, wsb, "hubert_encoder", stts_hubert_encoder_forward(c, nullptr, n, off.data(), off.data(), feats.data(), ldf, asr.data(), d.inter_dim, ws.data(), bytes));
+  REFUSE(what, wsb, "hubert_pitch_energy", stts_hubert_pitch_energy_forward(c, nullptr, n, off.data(), off.data(), feats.data(), ldf, pe.data(), f0.data(), en.data(), nullptr,
+                                                                 ws.data(), bytes));
+  return 0;
+}
+
+// MelStyleEncoder (both of them) and CfmPitchPredictor's network over `frames` mel frames per utterance.
+static int mel_case(stts_ctx* c, const Widths& wd, const std::vector<int>& frames, const char* what) {
+  const int n = (int)frames.size();
+  const std::vector<int32_t> off = offsets(frames);
+  const long T = off[n];
+  auto mel = buf(T * wd.n_mels), style = buf((size_t)n * 256), asr = buf(T * wd.pitch_asr), normed = buf(T), hz = buf(T);
+  for (int which : {STTS_W_PE_MEL_STYLE, STTS_W_CFM_PITCH}) {
+    const size_t wsb = stts_mel_style_workspace_bytes(c, which, T, n);
+    std::vector<char> ws(wsb);
+    const std::string name = std::string(what) + (which == STTS_W_PE_MEL_STYLE ? " pe_mel_style" : " spk_emb");
+    stts_stub_trace_begin();
+    CK(stts_mel_style_forward(c, nullptr, which, n, off.data(), off.data(), mel.data(), wd.n_mels, style.data(), ws.data(), wsb));
+    launchtrace(name.c_str(), stts_stub_trace_end());
+    printf("  %-44s frames %7ld  workspace %8.1f MB (%zu bytes)\n", name.c_str(), T, wsb / 1048576.0, wsb);
+    REFUSE(name.c_str(), wsb, "mel_style", stts_mel_style_forward(c, nullptr, which, n, off.data(), off.data(), mel.data(), wd.n_mels, style.data(), ws.data(), bytes));
+  }
+  const size_t wsb = stts_cfm_pitch_workspace_bytes(c, T, n);
+  std::vector<char> ws(wsb);
+  const std::string name = std::string(what) + " cfm_pitch";
+  stts_stub_trace_begin();
+  CK(stts_cfm_pitch_forward(c, nullptr, n, off.data(), off.data(), asr.data(), wd.pitch_asr, style.data(), normed.data(), hz.data(), 7.f, 1.f, nullptr, ws.data(), wsb));
+  launchtrace(name.c_str(), stts_stub_trace_end());
+  printf("  %-44s frames %7ld  workspace %8.1f MB (%zu bytes)\n", name.c_str(), T, wsb / 1048576.0, wsb);
+  REFUSE(name.c_str(), wsb, "cfm_pitch", stts_cfm_pitch_forward(c, nullptr, n, off.data(), off.data(), asr.data(), wd.pitch_asr, style.data(), normed.data(), hz.data(), 7.f, 1.f, nullptr,
+                                             ws.data(), bytes));
+  return 0;
+}
+
+// AdaptiveHubert over `samples` per utterance, resampled to `frames` feature frames.
+static int ssl_case(stts_ctx* c, const stts_ssl_dims& sd, const std::vector<int>& samples, const std::vector<int>& frames, const char* what) {
+  const int n = (int)samples.size();
+  const std::vector<int32_t> so = offsets(samples), fo = offsets(frames);
+  const int ldf = (sd.hidden_size + 31) / 32 * 32;
+  const size_t wsb = stts_ssl_workspace_bytes(c, n, so.data());
+  std::vector<char> ws(wsb);
+  auto wave = buf(so[n]), feats = buf((size_t)fo[n] * ldf);
+  stts_stub_trace_begin();
+  CK(stts_ssl_forward(c, nullptr, n, so.data(), so.data(), wave.data(), fo.data(), fo.data(), feats.data(), ldf, ws.data(), wsb));
+  launchtrace(what, stts_stub_trace_end());
+  printf("  %-44s samples %7d  workspace %8.1f MB (%zu bytes)\n", what, so[n], wsb / 1048576.0, wsb);
+  REFUSE(what, wsb, "ssl", stts_ssl_forward(c, nullptr, n, so.data(), so.data(), wave.data(), fo.data(), fo.data(), feats.data(), ldf, ws.data(), bytes));
+  return 0;
+}
+
+// One evaluation of the CFM estimator over `frames` rows per utterance (F0 / N curves of the same lengths).
+static int cfm_case(stts_ctx* c, const stts_cfm_dims& cd, const std::vector<int>& frames, const char* what) {
+  const int n = (int)frames.size();
+  const std::vector<int32_t> off = offsets(frames);
+  const long R = off[n];
+  const int lda = (cd.asr_dim + 31) / 32 * 32;
+  const size_t wsb = stts_cfm_workspace_bytes(c, R, n);
+  std::vector<char> ws(wsb);
+  auto x = buf(R * cd.feat_dim), asr = buf(R * lda), f0 = buf(R), nc = buf(R), spk = buf((size_t)n * cd.spk_dim), t = buf(n), noise = buf(R), out = buf(R * cd.feat_dim);
+  stts_stub_trace_begin();
+  CK(stts_cfm_estimator(c, nullptr, n, off.data(), off.data(), x.data(), cd.feat_dim, asr.data(), lda, f0.data(), nc.data(), off.data(), off.data(), spk.data(), t.data(),
+                        noise.data(), out.data(), cd.feat_dim, ws.data(), wsb));
+  launchtrace(what, stts_stub_trace_end());
+  printf("  %-44s rows %7ld  workspace %8.1f MB (%zu bytes)\n", what, R, wsb / 1048576.0, wsb);
+  REFUSE(what, wsb, "cfm_estimator", stts_cfm_estimator(c, nullptr, n, off.data(), off.data(), x.data(), cd.feat_dim, asr.data(), lda, f0.data(), nc.data(), off.data(), off.data(),
+                                             spk.data(), t.data(), noise.data(), out.data(), cd.feat_dim, ws.data(), bytes));
+  return 0;
+}
+
+// The text aligner and RMVPE over `frames` mel frames per utterance (their queries take the real offsets).
+static int aligner_case(stts_ctx* c, const stts_aligner_dims& ad, const std::vector<int>& frames, const char* what) {
+  const int n = (int)frames.size();
+  const std::vector<int32_t> off = offsets(frames);
+  const long R = off[n];
+  const size_t wsb = stts_aligner_workspace_bytes(c, n, off.data());
+  std::vector<char> ws(wsb);
+  auto mel = buf(R * ad.n_mels), lp = buf(R * ad.classes);
+  stts_stub_trace_begin();
+  CK(stts_aligner_forward(c, nullptr, n, off.data(), off.data(), mel.data(), ad.n_mels, lp.data(), ad.classes, ws.data(), wsb));
+  launchtrace(what, stts_stub_trace_end());
+  printf("  %-44s rows %7ld  workspace %8.1f MB (%zu bytes)\n", what, R, wsb / 1048576.0, wsb);
+  REFUSE(what, wsb, "aligner", stts_aligner_forward(c, nullptr, n, off.data(), off.data(), mel.data(), ad.n_mels, lp.data(), ad.classes, ws.data(), bytes));
+  return 0;
+}
+static int rmvpe_case(stts_ctx* c, const std::vector<int>& frames, const char* what) {
+  const int n = (int)frames.size();
+  const std::vector<int32_t> off = offsets(frames);
+  const long R = off[n];
+  const size_t wsb = stts_rmvpe_workspace_bytes(c, n, off.data());
+  std::vector<char> ws(wsb);
+  auto mel = buf(R * 128), hidden = buf(R * 360), f0 = buf(R);
+  stts_stub_trace_begin();
+  CK(stts_rmvpe_forward(c, nullptr, n, off.data(), off.data(), mel.data(), 128, 0.03f, hidden.data(), f0.data(), ws.data(), wsb));
+  launchtrace(what, stts_stub_trace_end());
+  printf("  %-44s rows %7ld  workspace %8.1f MB (%zu bytes)\n", what, R, wsb / 1048576.0, wsb);
+  REFUSE(what, wsb, "rmvpe", stts_rmvpe_forward(c, nullptr, n, off.data(), off.data(), mel.data(), 128, 0.03f, hidden.data(), f0.data(), ws.data(), bytes));
   return 0;
 }
 
@@ -370,14 +532,24 @@ static int new_ctx(const stts_model_dims& d, int prec, const std::vector<Tensor>
   return 0;
 }
 
-// a weight dump: the three dims structs, then (name, shape, fp32 data) per tensor
-static int read_weights(const char* path, stts_model_dims& d, stts_cfm_dims& cd, stts_ssl_dims& sd, std::vector<Tensor>& w) {
+struct Dims {
+  stts_model_dims d;
+  stts_cfm_dims cd;
+  stts_ssl_dims sd;
+  stts_aligner_dims ad;
+  stts_rmvpe_dims rd;
+};
+
+// a weight dump: the five dims structs, then (name, shape, fp32 data) per tensor
+static int read_weights(const char* path, Dims& dims, std::vector<Tensor>& w) {
   FILE* f = fopen(path, "rb");
   if (!f) {
     perror(path);
     return 2;
   }
-  if (fread(&d, sizeof(d), 1, f) != 1 || fread(&cd, sizeof(cd), 1, f) != 1 || fread(&sd, sizeof(sd), 1, f) != 1) return 2;
+  if (fread(&dims.d, sizeof(dims.d), 1, f) != 1 || fread(&dims.cd, sizeof(dims.cd), 1, f) != 1 || fread(&dims.sd, sizeof(dims.sd), 1, f) != 1 ||
+      fread(&dims.ad, sizeof(dims.ad), 1, f) != 1 || fread(&dims.rd, sizeof(dims.rd), 1, f) != 1)
+    return 2;
   for (;;) {
     int32_t name_len = 0;
     Tensor t;
@@ -406,11 +578,23 @@ int main(int argc, char** argv) {
   gemm_section();
   if (argc > 2 && strcmp(argv[2], "gemm") == 0) return 0;
   epi_section();
-  stts_model_dims d;
-  stts_cfm_dims cd;
-  stts_ssl_dims sd;
+  Dims dims;
   std::vector<Tensor> w;
-  if (read_weights(argv[1], d, cd, sd, w)) return 2;
+  if (read_weights(argv[1], dims, w)) return 2;
+  const stts_model_dims& d = dims.d;
+  const stts_cfm_dims& cd = dims.cd;
+  const stts_ssl_dims& sd = dims.sd;
+  const stts_aligner_dims& ad = dims.ad;
+  stts_aligner_dims ad1 = ad;  // the same aligner with one TDNN layer (its Ffn is then layer 1: the dump has those weights too)
+  ad1.n_tdnn = 1;
+  auto width = [&](const char* name, int axis) {
+    for (const Tensor& t : w)
+      if (t.name == name) return (int)t.shape[axis];
+    fprintf(stderr, "FAILED: no tensor %s in the dump\n", name);
+    exit(2);
+  };
+  const Widths wd{width("hubert_speech_predictor.phone_encoder.phone_emb.weight", 1), width("hubert_speech_predictor.style_encoder.0.weight", 1),
+                  width("pe_mel_style_encoder.shared.0.weight_orig", 0), width("cfm_pitch_predictor.asr_emb.0.weight", 1)};
   for (int prec = 0; prec <= 3; ++prec) {  // fp32, fp16 operands (16-bit weight copies are packed too), fp32 on the f32 matrix cores
     if (prec == 1) {  // bf16: the reverse flow alone (its kernel choice has branches of its own; the packing is fp16's with another rounding)
       stts_ctx* cf = nullptr;
@@ -441,6 +625,10 @@ int main(int argc, char** argv) {
     digest("ssl");
     CK(stts_cfm_finalize(c, &cd));
     digest("cfm");
+    CK(stts_aligner_finalize(c, &ad));
+    digest("aligner");
+    CK(stts_rmvpe_finalize(c, &dims.rd));
+    digest("rmvpe");
     printf("precision %d: %zu tensors loaded and packed\n", prec, w.size());
     if (flow_section(c, prec)) return 1;
     if (prec != 3) {  // the stage walks: once per operand width
@@ -459,6 +647,25 @@ int main(int argc, char** argv) {
       if (frame_case(c, std::vector<int>(64, 3200), "cfg5 per GPU: 64 x 10 s")) return 1;
       if (phoneme_case(c, std::vector<int>(64, 50), std::vector<int>(64, 240), "cfg3: 64 x 50 tokens")) return 1;
       if (phoneme_case(c, {510, 2, 160}, {1020, 4, 800}, "token-count extremes")) return 1;
+      // skewed batches: the per-utterance statistics buffers grow with (utterances x longest utterance).  256 utterances, one of 4 000 frames; and 24 with
+      // one of 2 400 frames, just over the row count from which the Winograd branch (and its statistics buffers) is taken
+      std::vector<int> tok256(256, 3), frm256(256, 20), tok24(24, 1), frm24(24, 8), mel24(24, 65);  // (65 frames: the shortest MelStyleEncoder takes)
+      tok256[0] = 500; frm256[0] = 4000; tok24[0] = 300; frm24[0] = mel24[0] = 2400;
+      if (phoneme_case(c, tok256, frm256, "skew256: 1 x 4000 + 255 x 20 frames")) return 1;
+      if (phoneme_case(c, tok24, frm24, "skew24: 1 x 2400 + 23 x 8 frames")) return 1;
+      if (hubert_case(c, d, wd, {240, 17, 96}, "hubert: 3 utterances")) return 1;
+      if (hubert_case(c, d, wd, frm256, "hubert skew256")) return 1;
+      if (hubert_case(c, d, wd, frm24, "hubert skew24")) return 1;
+      if (mel_case(c, wd, {300, 97, 161}, "mel: 3 utterances")) return 1;
+      if (mel_case(c, wd, mel24, "mel skew24")) return 1;
+      if (ssl_case(c, sd, {16000, 4000, 9001}, {50, 12, 28}, "ssl: 3 utterances")) return 1;
+      if (cfm_case(c, cd, {120, 37, 64}, "cfm: 3 utterances")) return 1;
+      if (cfm_case(c, cd, frm24, "cfm skew24")) return 1;
+      if (aligner_case(c, ad, {300, 1, 97}, "aligner: 3 utterances")) return 1;
+      if (rmvpe_case(c, {300, 17, 97}, "rmvpe: 3 utterances")) return 1;
+      CK(stts_aligner_finalize(c, &ad1));
+      if (aligner_case(c, ad1, {300, 1, 97}, "aligner, one tdnn layer")) return 1;
+      CK(stts_aligner_finalize(c, &ad));  // (back to what the digest was taken of)
     }
     stts_ctx_destroy(c);
     // another order, a finalize that fails in the middle (a depth no weights were loaded for), then that component and the frame path again
@@ -475,7 +682,9 @@ int main(int argc, char** argv) {
       return 1;
     }
     CK(stts_finalize_weights(c, kMelStyle));
+    CK(stts_rmvpe_finalize(c, &dims.rd));
     CK(stts_finalize_weights(c, kHubert));
+    CK(stts_aligner_finalize(c, &ad));
     CK(stts_cfm_finalize(c, &cd));
     CK(stts_finalize_weights(c, kTts));
     const uint64_t second = stts_stub_digest() - base;
@@ -487,9 +696,10 @@ int main(int argc, char** argv) {
     printf("order %d: the second order and the failed finalize end at the same digest %016" PRIx64 "\n", prec, second);
   }
   if (argc > 2) {  // a model whose flow is not 128 channels wide: every coupling layer as plain contractions with the gate / split-accumulate / couple epilogues
-    stts_model_dims nd;
+    Dims ndims;
     std::vector<Tensor> nw;
-    if (read_weights(argv[2], nd, cd, sd, nw)) return 2;
+    if (read_weights(argv[2], ndims, nw)) return 2;
+    const stts_model_dims& nd = ndims.d;
     for (int prec : {0, 2, 3}) {
       stts_ctx* cf = nullptr;
       if (new_ctx(nd, prec, nw, &cf)) return 1;

@@ -5,8 +5,8 @@
 
 Steps: (1) hipcc --cuda-host-only -fsanitize=address,undefined -c for every translation unit of the library (no device code is generated or loaded),
 (2) link it with hip_stub.cpp into libstylish_hip_asan.so (the fat-binary symbol the host code references is defined as an
-empty blob), (3) dump the synthetic weights of every inference module, of the voice-conversion models, of the CFM estimator and of a narrow
-AdaptiveHubert to a binary file, (4) run asan_driver on it.
+empty blob), (3) dump the synthetic weights of every inference module, of the voice-conversion models, of the CFM estimator, of a narrow
+AdaptiveHubert, of a narrow text aligner (with three TDNN layers and with one) and of a small RMVPE to a binary file, (4) run asan_driver on it.
 (5) run `asan_driver <weights> gemm` (the contraction cases only) once per setting of GEMM_SETTINGS, each line prefixed with `[setting]`.
 Exit code 0 = no sanitizer report, every stage accepted its workspace for every shape, and the packed bytes did not depend on the order of the
 finalizes.  The driver's `digest <precision> <what> <hex>` lines say what was packed: two builds of the library pack the same bytes exactly when
@@ -26,10 +26,14 @@ GEMM_SETTINGS = ["STTS_NO_X3=1", "STTS_X3_REM=1", "STTS_X3_TILE=5", "STTS_X3_TIL
                  "STTS_SPLITK_MIN_ITERS=2", "STTS_GEMM16_MIN_TILES=1"]
 
 
-def write_tensors(f, m, spec):
+def write_tensors(f, m, spec, seen=None):
     from stylish_tts_amd import params
 
     for k, v in params.synth_state_dict(spec, 0, prefix=m + ".").items():
+        if seen is not None:  # (two specs of one module that share tensors: a name is a tensor, written once)
+            if k in seen:
+                continue
+            seen.add(k)
         name = (m + "." + k).encode()
         shape = v.shape if v.ndim else (1,)
         f.write(struct.pack("<i", len(name)) + name + struct.pack("<i", len(shape)) + struct.pack(f"<{len(shape)}q", *shape))
@@ -61,7 +65,7 @@ def main(build_dir):
     subprocess.check_call([cxx, *san, "-DSTTS_TEST_OPS", os.path.join(HERE, "asan_driver.cpp"), lib, f"-Wl,-rpath,{build_dir}", "-o", exe])
 
     # weights: every module's synthetic state dict under the name modules.py loads it by (module + "." + key); the header is the three dims structs
-    from stylish_tts_amd import _lib, hubert_ssl, params
+    from stylish_tts_amd import _lib, aligner, hubert_ssl, params, rmvpe
     from stylish_tts_amd.config import load_model_config
 
     cfg = load_model_config()
@@ -70,18 +74,27 @@ def main(build_dir):
                                     num_conv_pos_embeddings=32, num_conv_pos_embedding_groups=4))
     specs = [(m, params.module_spec(m, cfg)) for t in (params.MODULE_SPECS, params.HUBERT_MODULE_SPECS, params.MEL_STYLE_MODULE_SPECS) for m in t]
     specs += [("cfm_mel_decoder", params.cfm_mel_decoder_spec()), ("hubert", params.hubert_ssl_spec(ssl_arch))]
+    # a narrow text aligner, and the same with ONE tdnn layer (its Ffn is then encoder.layers.1: the driver finalizes both from one dump); a small RMVPE
+    al_dims = aligner.dims(hidden_dim=128, tdnn_blstm_spec=(("tdnn", 5, 1, 1), ("tdnn", 3, 1, 1), ("tdnn", 3, 1, 1), ("ffn", 2)))
+    al_one = aligner.dims(hidden_dim=128, tdnn_blstm_spec=(("tdnn", 5, 1, 1), ("ffn", 2)))
+    rv_dims = rmvpe.dims(dict(n_blocks=1, inter_layers=1, en_out_channels=4))
+    extra_dims = bytes(aligner.dims_struct(al_dims)) + bytes(rmvpe.dims_struct(rv_dims))
     wpath = os.path.join(build_dir, "weights.bin")
     with open(wpath, "wb") as f:
-        f.write(bytes(_lib.dims_from_config(cfg)) + bytes(_lib.CfmDims(**params.CFM_DEFAULT_DIMS)) + bytes(hubert_ssl.dims_struct(ssl_arch)))
+        f.write(bytes(_lib.dims_from_config(cfg)) + bytes(_lib.CfmDims(**params.CFM_DEFAULT_DIMS)) + bytes(hubert_ssl.dims_struct(ssl_arch)) + extra_dims)
         for m, spec in specs:
             write_tensors(f, m, spec)
+        seen = set()
+        write_tensors(f, "text_aligner", params.text_aligner_spec(al_dims), seen)
+        write_tensors(f, "text_aligner", params.text_aligner_spec(al_one), seen)
+        write_tensors(f, "rmvpe", params.rmvpe_spec(rv_dims))
     # ... and the text-to-speech weights of the narrow model of tests/golden/gen_golden.py (NARROW: decoder / generator width 384): its flow has 96 channels and runs
     # as plain contractions (gate / split-accumulate / couple epilogues)
     narrow = load_model_config(dict(dict(cfg), decoder=dict(cfg["decoder"], hidden_dim=384, residual_dim=32),
                                     generator=dict(cfg["generator"], input_dim=384, hidden_dim=384, conv_intermediate_dim=1152)))
     npath = os.path.join(build_dir, "weights_narrow.bin")
     with open(npath, "wb") as f:
-        f.write(bytes(_lib.dims_from_config(narrow)) + bytes(_lib.CfmDims(**params.CFM_DEFAULT_DIMS)) + bytes(hubert_ssl.dims_struct(ssl_arch)))
+        f.write(bytes(_lib.dims_from_config(narrow)) + bytes(_lib.CfmDims(**params.CFM_DEFAULT_DIMS)) + bytes(hubert_ssl.dims_struct(ssl_arch)) + extra_dims)
         write_tensors(f, "speech_predictor", params.module_spec("speech_predictor", narrow))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([exe, wpath, npath], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

@@ -1,10 +1,13 @@
 """CPU sanitizer pass over the library's host side.
 
-The host code of csrc/ (weight-norm folding, row / Winograd / MFMA-fragment packing, style tables, the workspace closed forms,
-arena carving, the launch planning of every contraction) is compiled with -fsanitize=address,undefined against a stub of the
+The host code of csrc/ (weight-norm folding, row / Winograd / MFMA-fragment packing, style tables, the workspace queries - dry runs of
+the stages' own arena carving - the launch planning of every contraction) is compiled with -fsanitize=address,undefined against a stub of the
 HIP runtime (tests/asan/hip_stub.cpp: device memory = host heap, launches validated and counted, nothing executed) and driven
 over the shapes of BASELINE's configs (cfg2, cfg3's phoneme batch, cfg4's 256 mixed utterances, cfg5's 64 x 10 s per GPU,
-token-count extremes), in fp32 and fp16 operand modes.  GPU AddressSanitizer is not available on this pool; the kernels
+token-count extremes, two skewed batches whose per-utterance statistics buffers outgrow an average-length bound), in fp32 and fp16
+operand modes.  Every stage outside the frame path is walked on a workspace of the size its query returns and then once more one
+256-byte unit below the smallest size it accepts: that call must be refused with "workspace too small" before anything is launched
+(`refusal <precision> <case> <stage> : ...`, STAGE_WALKS).  GPU AddressSanitizer is not available on this pool; the kernels
 themselves are covered by the -m gpu parity tests.
 
 The driver also finalizes every component (text-to-speech, the voice-conversion models, AdaptiveHubert, the CFM estimator) in the f32, f16
@@ -61,6 +64,15 @@ GEMM_PINS.update({(p, c, 100): f for p in (1, 2) for c, f in (("tile15_128", 115
 # ... and just below each threshold the forced tile must NOT be what runs
 GEMM_OFF = ([(0, f"tile22_{b}", 0, 22) for b in (439, 440, 459, 639)]
             + [(p, c, 100, f) for p in (1, 2) for c, f in (("tile15_127", 115), ("tile14_95", 114), ("gemm16_191", 119))])
+# the walks of the stages outside the frame path: case -> the stages whose refusal line must be there (asan_driver.cpp main)
+_PHONEME = ("text_encoder", "text_style", "duration", "pitch_energy")
+_HUBERT = ("speaker_style", "hubert_encoder", "hubert_pitch_energy")
+STAGE_WALKS = {"cfg3:_64_x_50_tokens": _PHONEME, "token-count_extremes": _PHONEME, "skew256:_1_x_4000_+_255_x_20_frames": _PHONEME,
+               "skew24:_1_x_2400_+_23_x_8_frames": _PHONEME, "hubert:_3_utterances": _HUBERT, "hubert_skew256": _HUBERT, "hubert_skew24": _HUBERT,
+               "ssl:_3_utterances": ("ssl",), "cfm:_3_utterances": ("cfm_estimator",), "cfm_skew24": ("cfm_estimator",),
+               "aligner:_3_utterances": ("aligner",), "aligner,_one_tdnn_layer": ("aligner",), "rmvpe:_3_utterances": ("rmvpe",)}
+STAGE_WALKS.update({f"{c}_{e}": ("mel_style",) for c in ("mel:_3_utterances", "mel_skew24") for e in ("pe_mel_style", "spk_emb")})
+STAGE_WALKS.update({f"{c}_cfm_pitch": ("cfm_pitch",) for c in ("mel:_3_utterances", "mel_skew24")})
 LAUNCH_CASES = [(p, c) for p in (0, 2) for c in ("cfg2:_8_x_3_s", "B_=_1_x_3_s", "short_ragged_utterances", "cfg5_per_GPU:_64_x_10_s", "cfg3:_64_x_50_tokens",
                                                  "token-count_extremes")] + [(0, "cfg4:_256_utterances_of_0.25-10_s")]
 
@@ -77,7 +89,7 @@ def test_host_side_under_asan_ubsan(tmp_path):
     assert r.stdout.count("cfg5 per GPU") == 2  # both precisions reached the largest case
     for prec in (0, 2, 3):
         assert f"order {prec}: the second order and the failed finalize end at the same digest" in r.stdout, tail
-        for what in ("tts", "hubert", "mel_style", "cfm_pitch_net", "ssl", "cfm"):
+        for what in ("tts", "hubert", "mel_style", "cfm_pitch_net", "ssl", "cfm", "aligner", "rmvpe"):
             assert re.search(rf"^digest {prec} {what} [0-9a-f]{{16}}$", r.stdout, re.M), (prec, what, tail)
     traces = {(int(p), b, sw): t for p, b, sw, t in re.findall(r"^flowtrace (\d) (\S+) (\S+) : (.+)$", r.stdout, re.M)}
     missing = [k for k in FLOW_CASES + [(p, b, sw) for (p, b), sw in PINS.items()] if k not in traces]
@@ -94,6 +106,13 @@ def test_host_side_under_asan_ubsan(tmp_path):
     assert not missing, missing
     launch = {(int(p), c): t for p, c, t in re.findall(r"^launchtrace (\d) (\S+) : (.+)$", r.stdout, re.M)}
     assert not [k for k in LAUNCH_CASES if k not in launch], sorted(launch)
+    # every stage walk ran on the workspace its query sized (a launchtrace line: the driver stops at a call that fails), and was refused just below the
+    # smallest workspace the stage accepts, before its first launch (the driver prints the line only then)
+    refusals = set(re.findall(r"^refusal (\d) (\S+) (\S+) : query \d+ bytes, least accepted \d+, refused below it with nothing launched$", r.stdout, re.M))
+    for prec in (0, 2):
+        for case, stages in STAGE_WALKS.items():
+            assert (prec, case) in launch, (prec, case)
+            assert not [s for s in stages if (str(prec), case, s) not in refusals], (prec, case, sorted(refusals))
     for (prec, case, unforced), forced in GEMM_PINS.items():
         assert not gemm[(prec, case, forced)].startswith("error") and gemm[(prec, case, unforced)] == gemm[(prec, case, forced)], (prec, case, forced, gemm[(prec, case, unforced)])
     for prec, case, unforced, forced in GEMM_OFF:

@@ -106,6 +106,51 @@ def test_long_token_sequences_vs_oracle(hip, weights, cfg, P, T):
 CFG3_TOL = dict(text=2e-4, style=2e-4, prosody=2e-4, logits=2e-4, f0=2e-4, energy=5e-4, audio_rounded=1.6e-2, audio_fp32=2e-2)
 
 
+def test_skewed_batch_duration_pitch_energy_vs_oracle(hip, weights, cfg):
+    """24 utterances in one packed call, one of 300 tokens / 2 400 frames and 23 of 1 token / 8 frames: 2 584 frames, just over the row count
+    from which pitch / energy takes its Winograd convs and carves their statistics buffers.  Those buffers grow with (utterances x longest
+    utterance), so this is the smallest batch that the workspace query has to size from the longest utterance and not from the average one.
+    fp32 engine, duration -> pitch / energy, judged as the cases above: the long utterance and the first and last short one against the
+    oracle at B = 1 (teacher-forced: the engine's own encoder outputs and styles, durations that split the frames over the tokens)."""
+    from oracle import stylish_oracle as O
+    from stylish_tts_amd import synth
+
+    P, T = [300] + [1] * 23, [2400] + [8] * 23
+    toks = [synth.tokens(f"skew.{i}", 1, p, cfg.text_encoder.tokens)[0] for i, p in enumerate(P)]
+    d = np.concatenate([synth.durations_for(f"skew.d.{i}", p, t) for i, (p, t) in enumerate(zip(P, T))]).astype(np.int32)
+    sp, st = segs(P), segs(T)
+    t_dev = dev(np.concatenate(toks))
+    logits, dur, taps = hip.duration(sp, t_dev, taps=True)
+    pe_enc = hip.text_encoder(2, sp, t_dev)
+    pe_style = hip.text_style(2, sp, pe_enc)
+    f0, en = hip.pitch_energy(sp, st, dev(d), pe_enc, pe_style)
+    hip.check_status()
+    dur_h = dur.cpu().numpy()
+    errs = {k: 0.0 for k in ("text", "style", "prosody", "logits", "f0", "energy")}
+    for u in (0, 1, 23):
+        tk, lengths1 = toks[u][None], np.array([P[u]], np.int64)
+        ps, pt = slice(sp.host[u], sp.host[u + 1]), slice(st.host[u], st.host[u + 1])
+        lo, mid = O.duration_predictor(tk, lengths1, weights["duration_predictor"], cfg, return_intermediates=True)
+        errs["text"] = max(errs["text"], rel(taps["text_mu"][ps].cpu().numpy().T[None], mid["text_mu"]))
+        errs["style"] = max(errs["style"], rel(taps["style"][u : u + 1], mid["style"]))
+        errs["prosody"] = max(errs["prosody"], rel(taps["prosody"][ps].cpu().numpy()[None], mid["prosody"]))
+        errs["logits"] = max(errs["logits"], rel(logits[ps].cpu().numpy()[None], lo))
+        want = O.prediction_to_duration(lo[0]).astype(np.int32)
+        for i in np.nonzero(dur_h[ps] != want)[0]:  # (the licence of the cases above: a logit pair within fp32 noise of a tie)
+            srt = np.sort(lo[0, i])[::-1]
+            assert srt[0] - srt[1] < 1e-3 * np.abs(lo).max(), (u, i, dur_h[ps][i], want[i])
+        pe_mu, _, _ = O.text_encoder(tk, lengths1, weights["pe_text_encoder"], cfg)
+        errs["text"] = max(errs["text"], rel(pe_enc[ps].cpu().numpy().T[None], pe_mu))
+        enc_h, sty_h = pe_enc[ps].cpu().numpy()[:, :256].T[None].copy(), pe_style[u : u + 1].cpu().numpy()
+        errs["style"] = max(errs["style"], rel(pe_style[u : u + 1], O.text_style_encoder(enc_h, lengths1, weights["pe_text_style_encoder"], cfg)))
+        al = synth.alignment_from_durations(d[ps])[None]
+        o_f0, o_n = O.pitch_energy_predictor(enc_h, lengths1, al, sty_h, weights["pitch_energy_predictor"], cfg)
+        errs["f0"], errs["energy"] = max(errs["f0"], rel(f0[pt].cpu().numpy()[None], o_f0)), max(errs["energy"], rel(en[pt].cpu().numpy()[None], o_n))
+    print("\n[skewed batch: 1 x 300 tokens / 2400 frames + 23 x 1 token / 8 frames] max-abs error / max-abs of the oracle's tensor:", {k: f"{v:.1e}" for k, v in errs.items()})
+    for k, v in errs.items():
+        assert v < CFG3_TOL[k], (k, v, errs)
+
+
 def test_cfg3_chain_b64_bf16_vs_rounded_oracle(cfg, weights):
     from oracle import stylish_oracle as O
     from stylish_tts_amd import synth
