@@ -441,6 +441,52 @@ int stts_log_mel_stats(stts_ctx* ctx, void* stream, int n_utt, const int32_t* sa
  * nonzero bins [first, one past the last) of every filter (0, 0: an empty filter).  No context, no GPU. */
 int stts_log_mel_filters(int n_fft, int n_mels, int sample_rate, int32_t* band, float* weights);
 
+/* ---- Validation scores: what every validate_* of the reference logs about its audio (train/stage_type.py).  MultiSpectrogram
+ * (train/multi_spectrogram.py) per resolution (n_fft, hop_length, win_length):
+ *   X = torch.stft(audio, n_fft, hop_length, win_length, periodic Hann(win_length)) (center=True / reflect, one-sided, unnormalised)
+ *   fft_mag = |X|      phase = (fft_mag > 1e-3) * angle(X)      mag = log1p(MelScale(n_mels, sample_rate, n_fft / 2 + 1)(fft_mag))
+ * with MelScale at torchaudio's defaults: the filters of stts_log_mel_filters.  wave: packed mono audio, utterance u = samples
+ * [sample_off[u], sample_off[u+1]), more than n_fft / 2 of them; it has ALL of its samples / hop_length + 1 frames, rows [row_off[u], row_off[u+1]).
+ * Geometry rules: those of stts_log_mel_forward.  One wave per frame, everything in fp64 (window product, transform, sqrt(re^2 + im^2), mel sums
+ * in bin order, log1p, atan2); sums are added in fixed orders without atomics: every result is bit-identical from run to run and independent of the
+ * batch around its utterance.  The caller owns every buffer (stts_val_sizes has the sizes); nothing is allocated per call.  The tables of a
+ * geometry are built on first use and kept in the context.  *_host / *_dev must hold the same offsets. */
+/* Host only (no context, no GPU): sizes[0] = rows = sum of samples / hop_length + 1, sizes[1] = doubles of stts_val_mel_sums' partials (2 rows),
+ * sizes[2] = doubles of stts_val_magphase_sums' partials (4 rows), sizes[3] = doubles of its scratch (rows * (n_fft / 2 + 1)).  A nonzero status
+ * names the rule or the utterance too short for the reflect padding. */
+int stts_val_sizes(int n_utt, const int32_t* sample_off_host, int n_fft, int hop_length, int64_t* sizes);
+/* MultiSpectrogram.calculate_single as time-major rows: mag_rows [rows, ld_mag >= n_mels], fft_mag_rows and phase_rows [rows, ld_bins >= n_fft / 2 + 1];
+ * each value is rounded once from fp64 to fp32, columns beyond the width are not written.  Each of the three may be null, not all; an output's
+ * bits do not depend on which others are asked for. */
+int stts_multi_spectrogram_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev,
+                                   const int32_t* row_off_host, const int32_t* row_off_dev, const float* wave, int n_fft, int win_length, int hop_length,
+                                   int n_mels, int sample_rate, float* mag_rows, int ld_mag, float* fft_mag_rows, float* phase_rows, int ld_bins);
+/* The sums of MultiResolutionSTFTLoss.spectral_convergence_loss (train/losses.py:24-25) at one resolution, without writing a spectrogram: one
+ * launch transforms frame f of the target and of the prediction in the same wave; partials [rows][2] (fp64) = (sum_m |t - p|, sum_m |t|) of the
+ * frame's log1p mel values, sums [n_utt][2] (fp64) = each utterance's partials added in a fixed order.  target / pred: packed alike; an utterance
+ * whose sample counts differ (sample_off_host against pred_off_host) gives a nonzero status naming it.  An identical pair gives a numerator of
+ * exactly 0.  The reference's number over an equal-length batch is sum_u sums[u][0] / (sum_u sums[u][1] + 1e-6), averaged over the resolutions. */
+int stts_val_mel_sums(stts_ctx* ctx, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* pred_off_host, const int32_t* sample_off_dev,
+                      const int32_t* row_off_host, const int32_t* row_off_dev, const float* target, const float* pred, int n_fft, int win_length,
+                      int hop_length, int n_mels, int sample_rate, double* partials, double* sums);
+/* The sums of MagPhaseLoss.forward (train/losses.py:85-154).  gt: the packed recordings; hop_length: the hop of the transform (the reference's
+ * hop_length // 4); logamp_rows / phase_rows: the prediction's log-magnitude and phase as time-major rows [rows, ld >= n_fft / 2 + 1], utterance u
+ * with exactly samples / hop_length + 1 rows (a nonzero status names an utterance with another count).  With Y the transform of gt,
+ * target_mag = |Y| + 1e-14, on = target_mag > 1e-3, tp = on * angle(Y), pp = on * phase_rows (the input is NOT modified),
+ * aw(d) = |d - 2 pi round(d / 2 pi)|, w_k = base^k, base = exp(ln 2.5 / ((n_fft / 2 + 1) / 2)):
+ *   sums[u][0] = sum |logamp - log(target_mag + 1e-9)|                                      "mag" = its mean
+ *   sums[u][1] = sum w_k aw(pp - tp)
+ *   sums[u][2] = sum w_k aw((pp[k-1] - pp[k]) - (tp[k-1] - tp[k])), bin -1 = 0
+ *   sums[u][3] = sum w_k aw((pp[f-1] - pp[f]) - (tp[f-1] - tp[f])), frame -1 = 0            "phase" = the sum of the three means
+ * partials [rows][4] and sums [n_utt][4] in fp64; scratch [rows][n_fft / 2 + 1] fp64 holds the masked target phase between the two launches. */
+int stts_val_magphase_sums(stts_ctx* ctx, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev,
+                           const int32_t* row_off_host, const int32_t* row_off_dev, const float* gt, const float* logamp_rows, const float* phase_rows, int ld,
+                           int n_fft, int win_length, int hop_length, double* scratch, double* partials, double* sums);
+/* sums [n_utt] (fp64) = each utterance's sum of smooth_l1(a - b) at beta 1 (0.5 d^2 below |d| = 1, |d| - 0.5 from there on) over the packed fp32
+ * vectors a and b, utterance u = values [off[u], off[u+1]), at least one; added in a fixed order. */
+int stts_val_smooth_l1_sums(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* a, const float* b,
+                            double* sums);
+
 /* ---- Windowed-sinc sample-rate conversion: torchaudio.transforms.Resample(orig_freq, new_freq, resampling_method, lowpass_filter_width, rolloff,
  * beta) / functional.resample from their published definition, with the float64 result as the target:
  *   o, n = orig_freq, new_freq over their gcd;  base = min(o, n) * rolloff;  width = ceil(lowpass_filter_width * o / base);  taps = 2 width + o

@@ -129,6 +129,11 @@ SIGNATURES = {
     "stts_log_mel_forward": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_double, C.c_double, _P, _I, _P, _P]),
     "stts_log_mel_stats": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "stts_log_mel_filters": (_I, [_I, _I, _I, _P, _P]),
+    "stts_val_sizes": (_I, [_I, _P, _I, _I, _P]),
+    "stts_multi_spectrogram_forward": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I]),
+    "stts_val_mel_sums": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "stts_val_magphase_sums": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "stts_val_smooth_l1_sums": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     "stts_resample_geometry": (_I, [_I, _I, _I, C.c_double, _P, _P, _P, _P]),
     "stts_resample_out_length": (_I64, [_I64, _I, _I]),
     "stts_resample_tile": (_I, [_I, _I]),

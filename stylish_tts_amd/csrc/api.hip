@@ -11,6 +11,7 @@
 #include "aligner.hip.h"
 #include "log_mel.hip.h"
 #include "resample.hip.h"
+#include "val_scores.hip.h"
 
 using namespace stts;
 
@@ -960,6 +961,102 @@ int stts_log_mel_stats(stts_ctx* c, void* stream, int n_utt, const int32_t* samp
   STTS_TRY(log_mel_entry(c, stream, n_utt, sample_off_host, sample_off_dev, row_off_host, row_off_dev, wave, n_fft, win_length, hop_length, n_mels, sample_rate, 0.0, 1.0,
                          nullptr, 0, nullptr, nullptr, partials));
   hipLaunchKernelGGL(log_mel_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (long)row_off_host[n_utt], n_mels, stats);
+  STTS_HIP(hipGetLastError());
+  return 0;
+  API_END
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ validation scores (val_scores.hip.h)
+extern "C" {
+
+int stts_val_sizes(int n_utt, const int32_t* sample_off_host, int n_fft, int hop_length, int64_t* sizes) {
+  API_BEGIN
+  STTS_CHECK(sizes, "val_sizes: null argument");
+  STTS_TRY(log_mel_check_geometry(n_fft, n_fft, hop_length, 1, 2));
+  STTS_CHECK(n_utt > 0 && n_utt <= 65535 && sample_off_host && sample_off_host[0] == 0, "val_sizes: bad offsets");
+  int64_t rows = 0;
+  for (int u = 0; u < n_utt; ++u) {
+    const long n = (long)sample_off_host[u + 1] - sample_off_host[u];
+    STTS_CHECK(n > n_fft / 2, "val_sizes: utterance %d has %ld samples; the reflect padding needs more than n_fft / 2 = %d", u, n, n_fft / 2);
+    rows += n / hop_length + 1;
+  }
+  STTS_CHECK(rows <= INT32_MAX, "val_sizes: %lld frames do not fit 32-bit row offsets", (long long)rows);
+  sizes[0] = rows;
+  sizes[1] = 2 * rows;
+  sizes[2] = 4 * rows;
+  sizes[3] = rows * (n_fft / 2 + 1);
+  return 0;
+  API_END
+}
+
+static int val_spec_entry(stts_ctx* c, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const int32_t* row_off_host,
+                          const int32_t* row_off_dev, const float* a, const float* b, int n_fft, int win_length, int hop_length, int n_mels, int sample_rate,
+                          float* mag, int ld_mag, float* fft_mag, float* phase, int ld_bins, double* partials, double* sums) {
+  STTS_TRY(log_mel_check_geometry(n_fft, win_length, hop_length, n_mels, sample_rate));
+  int max_fr = 0;
+  STTS_TRY(val_check_offsets(b ? "val_mel_sums" : "multi_spectrogram", n_utt, sample_off_host, row_off_host, n_fft, hop_length, &max_fr));
+  STTS_CHECK(c && sample_off_dev && row_off_dev && a, "val_scores: null argument");
+  STTS_CHECK(!mag || ld_mag >= n_mels, "multi_spectrogram: ld_mag %d < %d mel bins", ld_mag, n_mels);
+  STTS_CHECK(!(fft_mag || phase) || ld_bins >= n_fft / 2 + 1, "multi_spectrogram: ld_bins %d < %d bins", ld_bins, n_fft / 2 + 1);
+  STTS_HIP(hipSetDevice(c->device));
+  const LogMelTables* t = nullptr;
+  STTS_TRY(log_mel_tables(c, n_fft, win_length, n_mels, sample_rate, &t));
+  return launch_val_spec((hipStream_t)stream, *t, n_fft, win_length, hop_length, n_mels, n_utt, max_fr, sample_off_dev, row_off_dev, a, b, mag, ld_mag, fft_mag,
+                         phase, ld_bins, partials, sums);
+}
+
+int stts_multi_spectrogram_forward(stts_ctx* c, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev,
+                                   const int32_t* row_off_host, const int32_t* row_off_dev, const float* wave, int n_fft, int win_length, int hop_length,
+                                   int n_mels, int sample_rate, float* mag_rows, int ld_mag, float* fft_mag_rows, float* phase_rows, int ld_bins) {
+  API_BEGIN
+  STTS_CHECK(mag_rows || fft_mag_rows || phase_rows, "multi_spectrogram: no output");
+  return val_spec_entry(c, stream, n_utt, sample_off_host, sample_off_dev, row_off_host, row_off_dev, wave, nullptr, n_fft, win_length, hop_length, n_mels,
+                        sample_rate, mag_rows, ld_mag, fft_mag_rows, phase_rows, ld_bins, nullptr, nullptr);
+  API_END
+}
+
+int stts_val_mel_sums(stts_ctx* c, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* pred_off_host, const int32_t* sample_off_dev,
+                      const int32_t* row_off_host, const int32_t* row_off_dev, const float* target, const float* pred, int n_fft, int win_length,
+                      int hop_length, int n_mels, int sample_rate, double* partials, double* sums) {
+  API_BEGIN
+  STTS_CHECK(n_utt > 0 && sample_off_host && pred_off_host, "val_mel_sums: bad offsets");
+  for (int u = 0; u < n_utt; ++u) {
+    const long nt = (long)sample_off_host[u + 1] - sample_off_host[u], np = (long)pred_off_host[u + 1] - pred_off_host[u];
+    STTS_CHECK(nt == np, "val_mel_sums: utterance %d: the target has %ld samples, the prediction %ld", u, nt, np);
+  }
+  STTS_CHECK(pred && partials && sums, "val_mel_sums: null argument");
+  return val_spec_entry(c, stream, n_utt, sample_off_host, sample_off_dev, row_off_host, row_off_dev, target, pred, n_fft, win_length, hop_length, n_mels,
+                        sample_rate, nullptr, 0, nullptr, nullptr, 0, partials, sums);
+  API_END
+}
+
+int stts_val_magphase_sums(stts_ctx* c, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const int32_t* row_off_host,
+                           const int32_t* row_off_dev, const float* gt, const float* logamp_rows, const float* phase_rows, int ld, int n_fft, int win_length,
+                           int hop_length, double* scratch, double* partials, double* sums) {
+  API_BEGIN
+  STTS_TRY(log_mel_check_geometry(n_fft, win_length, hop_length, 1, 2));
+  int max_fr = 0;
+  STTS_TRY(val_check_offsets("val_magphase_sums", n_utt, sample_off_host, row_off_host, n_fft, hop_length, &max_fr));
+  STTS_CHECK(c && sample_off_dev && row_off_dev && gt && logamp_rows && phase_rows && scratch && partials && sums, "val_magphase_sums: null argument");
+  STTS_CHECK(ld >= n_fft / 2 + 1, "val_magphase_sums: ld %d < %d bins", ld, n_fft / 2 + 1);
+  STTS_HIP(hipSetDevice(c->device));
+  const ValTables* t = nullptr;
+  STTS_TRY(val_tables(c, n_fft, win_length, &t));
+  return launch_val_magphase((hipStream_t)stream, *t, n_fft, win_length, hop_length, n_utt, max_fr, sample_off_dev, row_off_dev, gt, logamp_rows, phase_rows, ld,
+                             scratch, partials, sums);
+  API_END
+}
+
+int stts_val_smooth_l1_sums(stts_ctx* c, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* a, const float* b,
+                            double* sums) {
+  API_BEGIN
+  STTS_CHECK(n_utt > 0 && n_utt <= 65535 && off_host && off_host[0] == 0, "val_smooth_l1_sums: bad offsets");
+  for (int u = 0; u < n_utt; ++u) STTS_CHECK(off_host[u + 1] > off_host[u], "val_smooth_l1_sums: utterance %d has no values", u);
+  STTS_CHECK(c && off_dev && a && b && sums, "val_smooth_l1_sums: null argument");
+  STTS_HIP(hipSetDevice(c->device));
+  hipLaunchKernelGGL(val_smooth_l1_kernel, dim3(n_utt), dim3(256), 0, (hipStream_t)stream, a, b, off_dev, sums);
   STTS_HIP(hipGetLastError());
   return 0;
   API_END

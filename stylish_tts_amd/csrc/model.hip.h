@@ -214,6 +214,9 @@ struct stts_ctx {
   // resampler (resample.hip.h): the fp64 coefficient table per (o, n, lowpass_filter_width, rolloff, method, beta), context lifetime
   std::map<std::tuple<int, int, int, double, int, double>, std::shared_ptr<void>> resample;  // stts::ResampleTable
   std::mutex resample_mu;
+  // validation scores (val_scores.hip.h): window, twiddles and the phase weights w_k per (n_fft, win_length), context lifetime
+  std::map<std::array<int, 2>, std::shared_ptr<void>> val_scores;  // stts::ValTables
+  std::mutex val_scores_mu;
 };
 
 namespace stts {

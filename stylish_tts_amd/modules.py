@@ -21,6 +21,9 @@ Reference classes mirrored (paths relative to /root/reference/src/stylish_tts/tr
   LogMelSpectrogram           torchaudio MelSpectrogram + calculate_mel (stage_type.py:1023-1032), preprocess (dataprep/align_text.py:112-117),
                               log_norm / compute_log_mel_stats (utils.py:71-148)
   Resample                    torchaudio.transforms.Resample as models/ssl.py:21-24 and dataprep/rmvpe/inference.py:50-59 build it
+  MultiSpectrogram            train/multi_spectrogram.py:25-81
+  MultiResolutionSTFTLoss     train/losses.py:14-35 (forward values; fused from the audio behind one MultiSpectrogram.forward call's lists, else on the tensors)
+  MagPhaseLoss                train/losses.py:38-154 (forward values; leaves pred.phase unmodified)
 
 Differences, all additive: forward() of the stochastic modules takes an optional ``noise`` dict with the three draws
 the reference takes from the global torch generator (``prior_noise`` [B,128,4T], ``src_noise`` [B,1,300T],
@@ -524,6 +527,217 @@ class LogMelSpectrogram(torch.nn.Module):
         eng = self.engine
         flat = torch.cat([_f(w, eng.device) for w in ws]).contiguous()
         return eng.log_mel_stats(Segments(L, eng.device), flat, *self._geom(), return_partials=return_partials)
+
+
+# ------------------------------------------------------------------------------------------------ validation scores (csrc/val_scores.hip.h)
+def _wave_batch(x, lengths=None):
+    """[B, samples] / [B, 1, samples] / a list of 1-D recordings (+ lengths [B]) -> (list of 1-D tensors cut to their lengths, their lengths)."""
+    if isinstance(x, (list, tuple)):
+        ws = [torch.as_tensor(w).reshape(-1) for w in x]
+    else:
+        x = torch.as_tensor(x)
+        if x.dim() == 3 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.dim() == 1:
+            x = x[None]
+        if x.dim() != 2:
+            raise ValueError(f"audio must be [B, samples], [B, 1, samples] or a list of 1-D recordings, got shape {tuple(x.shape)}")
+        ws = [x[b] for b in range(x.shape[0])]
+    if lengths is not None:
+        L = [int(v) for v in torch.as_tensor(lengths).tolist()]
+        if len(L) != len(ws) or any(n > w.numel() for n, w in zip(L, ws)):
+            raise ValueError(f"lengths {L} do not fit {len(ws)} recordings of {[int(w.numel()) for w in ws]} samples")
+        ws = [w[:n] for w, n in zip(ws, L)]
+    return ws, [int(w.numel()) for w in ws]
+
+
+def _pack_waves(eng: HipModel, ws):
+    return torch.cat([_f(w, eng.device) for w in ws]).contiguous()
+
+
+def mel_score(sums):
+    """sums [R, B, 2] (HipModel.mel_sums, on the host) -> (mel, [mel_r], [mel_utt]): per resolution sum_u numerators / (sum_u denominators + 1e-6)
+    - MultiResolutionSTFTLoss' number for an equal-length batch - and their mean; per utterance the same of its own sums.  Plain float64
+    arithmetic in a fixed order."""
+    R, B = len(sums), len(sums[0])
+    mel_r = []
+    for r in range(R):
+        num = den = 0.0
+        for u in range(B):
+            num += float(sums[r][u][0])
+            den += float(sums[r][u][1])
+        mel_r.append(num / (den + 1e-6))
+    mel_utt = []
+    for u in range(B):
+        s = 0.0
+        for r in range(R):
+            s += float(sums[r][u][0]) / (float(sums[r][u][1]) + 1e-6)
+        mel_utt.append(s / R)
+    return sum(mel_r) / R, mel_r, mel_utt
+
+
+def magphase_score(sums, rows: int, n_bins: int):
+    """sums [B, 4] (HipModel.magphase_sums, on the host), the batch's rows and bins -> (mag, phase, the three phase terms): the means over every
+    (utterance, bin, frame) and, for "phase", the sum of the three."""
+    tot = [0.0] * 4
+    for u in range(len(sums)):
+        for c in range(4):
+            tot[c] += float(sums[u][c])
+    count = float(rows) * float(n_bins)
+    terms = [tot[1] / count, tot[2] / count, tot[3] / count]
+    return tot[0] / count, (terms[0] + terms[1]) + terms[2], terms
+
+
+class _SpectrogramList(list):
+    """A list MultiSpectrogram.forward returned.  It remembers the audio it came from and its tensors as they were, so that MultiResolutionSTFTLoss
+    can score an untouched pair of lists on the fused path (fp64 from the samples to the sums) instead of from these fp32 tensors."""
+
+    source = None
+    stamp = None
+
+    def untouched(self) -> bool:
+        return self.stamp is not None and self.stamp == [(id(t), t._version) for t in self]
+
+
+class MultiSpectrogram(torch.nn.Module):
+    """train/multi_spectrogram.py:25-81 on the engine, same constructor and forward: per resolution the log1p mel spectrogram, the masked phase and
+    the magnitude of torch.stft (periodic Hann).  ``forward`` runs the resolutions given to the constructor (the reference's forward reads the
+    module-level list, which is the constructor's default).  Only the Hann window is built; MelScale at torchaudio's defaults with 128 mels."""
+
+    def __init__(self, resolutions=None, window=torch.hann_window, *, sample_rate, engine=None, cfg=None):
+        from . import val_scores
+
+        super().__init__()
+        if window is not torch.hann_window:
+            raise NotImplementedError("the HIP MultiSpectrogram is built for torch.hann_window")
+        self.resolutions = [val_scores.as_tuple(r) for r in (val_scores.resolutions if resolutions is None else resolutions)]
+        self.sample_rate, self.n_mels = int(sample_rate), val_scores.N_MELS
+        for fft, hop, window_length in self.resolutions:
+            val_scores.check_geometry(fft, window_length, hop, self.n_mels, self.sample_rate)
+        self._engine = engine
+        self._cfg = cfg
+
+    @property
+    def engine(self) -> HipModel:
+        if self._engine is None:
+            self._engine = get_engine(self._cfg, 0)
+        return self._engine
+
+    def calculate_single(self, audio, index, item=None):
+        """audio [B, samples] -> (mag [B, 1, 128, F], phase [B, n_bins, F], fft_mag [B, 1, n_bins, F]) at resolution ``index``."""
+        fft, hop, window_length = self.resolutions[index]
+        ws, L = _wave_batch(audio)
+        if len(set(L)) != 1:
+            raise ValueError("MultiSpectrogram takes an equal-length batch [B, samples], as the reference does (HipModel.multi_spectrogram runs ragged ones)")
+        eng = self.engine
+        seg = Segments(L, eng.device)
+        seg_m, mag, phase, fft_mag = eng.multi_spectrogram(seg, _pack_waves(eng, ws), fft, window_length, hop, self.n_mels, self.sample_rate, mag=True, phase=True,
+                                                           fft_mag=True)
+        B, F, nb = seg.n, seg_m.lengths[0], fft // 2 + 1
+        return (eng.to_channel_major(mag, B, self.n_mels, F).unsqueeze(1), eng.to_channel_major(phase, B, nb, F),
+                eng.to_channel_major(fft_mag, B, nb, F).unsqueeze(1))
+
+    def forward(self, *, target, pred):
+        out = [_SpectrogramList() for _ in range(6)]
+        for index in range(len(self.resolutions)):
+            t = self.calculate_single(target, index)
+            p = self.calculate_single(pred, index)
+            for dst, v in zip(out, (t[0], p[0], t[1], p[1], t[2], p[2])):
+                dst.append(v)
+        out[0].source = out[1].source = dict(target=target, pred=pred, resolutions=self.resolutions, sample_rate=self.sample_rate, n_mels=self.n_mels,
+                                             engine=self.engine)
+        for lst in out[:2]:
+            lst.stamp = [(id(t), t._version) for t in lst]
+        return tuple(out)
+
+
+class MultiResolutionSTFTLoss(torch.nn.Module):
+    """train/losses.py:14-35: mean over the resolutions of ||t - p||_1 / (||t||_1 + 1e-6), logged as "mel".  Two forms, and which one runs shows in
+    ``last_path``:
+      "fused"    ``target_list`` / ``pred_list`` are the two lists of ONE MultiSpectrogram.forward call, as it returned them (same tensors, none
+                 edited in place since): the score is formed on the engine from the audio behind them (HipModel.mel_sums: fp64 from the samples to
+                 the sums, what pipeline.validation_scores reports), not from their fp32 tensors;
+      "tensors"  any other lists of tensors - sliced, copied, edited, built elsewhere: the reference's own arithmetic on the tensors given, summed in
+                 float64 by torch on their device.  It differs from the fused number by the tensors' rounding to fp32 (a few 1e-8 of the score)."""
+
+    def __init__(self, *, sample_rate):
+        super().__init__()
+        self.sample_rate = int(sample_rate)
+        self.last_path = None
+
+    def spectral_convergence_loss(self, target, pred):
+        t, p = torch.as_tensor(target).double(), torch.as_tensor(pred).double()
+        return (t - p).abs().sum() / (t.abs().sum() + 1e-6)
+
+    def forward(self, *, target_list, pred_list, log):
+        src = getattr(target_list, "source", None)
+        if src is not None and getattr(pred_list, "source", None) is src and target_list.untouched() and pred_list.untouched():
+            eng = src["engine"]
+            tw, L = _wave_batch(src["target"])
+            pw, Lp = _wave_batch(src["pred"])
+            sums = eng.mel_sums(Segments(L, eng.device), _pack_waves(eng, tw), _pack_waves(eng, pw), src["resolutions"], src["n_mels"], src["sample_rate"],
+                                seg_pred=Segments(Lp, eng.device))
+            loss = torch.tensor(mel_score(sums.cpu().tolist())[0], dtype=torch.float64)
+            self.last_path = "fused"
+        else:
+            if len(target_list) != len(pred_list) or len(target_list) == 0:
+                raise ValueError(f"{len(target_list)} target spectrograms, {len(pred_list)} predictions")
+            loss = sum(self.spectral_convergence_loss(t, p) for t, p in zip(target_list, pred_list)) / len(target_list)
+            self.last_path = "tensors"
+        log.add_loss("mel", loss)
+        return loss
+
+
+def _magphase_sums(eng: HipModel, gt_waves, L, logamp_rows, phase_rows, seg_rows, n_fft, win, hop):
+    """MagPhaseLoss' sums [B, 4] (float64, on the device) from packed prediction rows; nothing is read back."""
+    return eng.magphase_sums(Segments(L, eng.device), _pack_waves(eng, gt_waves), seg_rows, logamp_rows, phase_rows, logamp_rows.shape[1], n_fft, win, hop)
+
+
+class MagPhaseLoss(torch.nn.Module):
+    """train/losses.py:85-154 on the engine, same constructor and forward: ``pred`` has .magnitude (log-magnitude) and .phase [B, n_bins, F], ``gt``
+    is the recording [B, samples] with F = samples // (hop_length // 4) + 1; logs "mag" and "phase".  Unlike the reference, which overwrites
+    ``pred.phase`` with its masked copy, this leaves ``pred`` as it was."""
+
+    def __init__(self, *, n_fft, hop_length, win_length, engine=None, cfg=None):
+        from . import val_scores
+
+        super().__init__()
+        self.n_fft, self.hop_length, self.win_length = int(n_fft), int(hop_length) // 4, int(win_length)
+        val_scores.check_geometry(self.n_fft, self.win_length, self.hop_length)
+        self._engine = engine
+        self._cfg = cfg
+
+    @property
+    def engine(self) -> HipModel:
+        if self._engine is None:
+            self._engine = get_engine(self._cfg, 0)
+        return self._engine
+
+    def sums(self, pred, gt):
+        """(sums [B, 4] float64 on the device, the batch's rows): HipModel.magphase_sums of the prediction; nothing is read back."""
+        from . import val_scores
+
+        ws, L = _wave_batch(gt)
+        mg, ph = torch.as_tensor(pred.magnitude), torch.as_tensor(pred.phase)
+        nb = self.n_fft // 2 + 1
+        if mg.dim() != 3 or mg.shape != ph.shape or mg.shape[0] != len(L) or mg.shape[1] != nb:
+            raise ValueError(f"pred.magnitude / pred.phase must be [{len(L)}, {nb}, frames], got {tuple(mg.shape)} / {tuple(ph.shape)}")
+        val_scores.frame_counts(L, self.n_fft, self.hop_length)
+        val_scores.check_rows(L, [mg.shape[2]] * len(L), self.hop_length)
+        eng = self.engine
+        la, pr = eng.to_time_major(_f(mg, eng.device)), eng.to_time_major(_f(ph, eng.device))
+        seg_rows = Segments([mg.shape[2]] * len(L), eng.device)
+        return _magphase_sums(eng, ws, L, la, pr, seg_rows, self.n_fft, self.win_length, self.hop_length), seg_rows.rows
+
+    def scores(self, pred, gt):
+        """(mag, phase, [instantaneous, frequency, time]) as Python floats; one host read."""
+        sums, rows = self.sums(pred, gt)
+        return magphase_score(sums.cpu().tolist(), rows, self.n_fft // 2 + 1)
+
+    def forward(self, pred, gt, log):
+        mag, phase, _ = self.scores(pred, gt)
+        log.add_loss("mag", torch.tensor(mag, dtype=torch.float64))
+        log.add_loss("phase", torch.tensor(phase, dtype=torch.float64))
 
 
 class Resample(torch.nn.Module):

@@ -375,3 +375,76 @@ class VoiceConverter:
             for i, smp in enumerate(samples):
                 write_wav(f"{out_prefix}_{i}.wav", smp, self.cfg.sample_rate)
         return samples
+
+
+def _curve_pair(pair, what):
+    """(predicted, recorded) curves [B, T] / lists of 1-D curves -> (list of 1-D predicted, list of 1-D recorded, their lengths)."""
+    from .modules import _wave_batch
+
+    if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+        raise ValueError(f"{what} must be a pair (predicted, recorded)")
+    (a, La), (b, Lb) = _wave_batch(pair[0]), _wave_batch(pair[1])
+    if La != Lb:
+        raise ValueError(f"{what}: the predicted curves have {La} values, the recorded ones {Lb}")
+    return a, b, La
+
+
+@torch.no_grad()
+def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, prediction=None, pitch=None, energy=None) -> dict:
+    """What the reference's validate_* functions log about a batch (train/stage_type.py), on the engine's fused kernels (nothing is materialised):
+    audio / audio_gt: the synthesised waveforms and the recordings, [B, samples], [B, 1, samples] or lists of 1-D tensors (``lengths`` [B] cuts a
+    padded batch).  -> dict of Python numbers, read from the device once:
+      mel        MultiResolutionSTFTLoss over MultiSpectrogram: per resolution sum of the numerators / (sum of the denominators + 1e-6) over the
+                 batch - the reference's number for an equal-length batch - averaged; mel_r the per-resolution values, mel_utt every
+                 utterance's own score (what a ragged batch can report)
+      mag, phase MagPhaseLoss at the engine's model.yml geometry, with ``prediction``: a DecoderPrediction (magnitude / phase [B, n_bins, F]) or the
+                 time-major rows (logamp_rows, phase_rows[, Segments]) of ``HipModel.vocoder(return_spec=True)``, whose last row of every utterance is
+                 repeated like the reference's replicate padding; phase_terms the three means "phase" adds up
+      pitch, energy  smooth_l1_loss (beta 1, mean) of the pairs (predicted, recorded) given as ``pitch`` / ``energy``
+    ValueError naming the utterance whose lengths do not agree, or the geometry rule a length breaks."""
+    from .modules import MagPhaseLoss, _magphase_sums, _pack_waves, _wave_batch, magphase_score, mel_score
+
+    eng = engine
+    pw, Lp = _wave_batch(audio, lengths)
+    gw, Lg = _wave_batch(audio_gt, lengths)
+    seg_g, seg_p = Segments(Lg, eng.device), Segments(Lp, eng.device)
+    parts = [eng.mel_sums(seg_g, _pack_waves(eng, gw), _pack_waves(eng, pw), sample_rate=eng.cfg.sample_rate, seg_pred=seg_p)]  # [R, B, 2]
+    R, B = parts[0].shape[0], seg_g.n
+    mp_rows = None
+    if prediction is not None:
+        n_fft, win, hop = eng.n_fft, eng.win_length, eng.hop4
+        if hasattr(prediction, "magnitude"):
+            mp, mp_rows = MagPhaseLoss(n_fft=n_fft, hop_length=4 * hop, win_length=win, engine=eng).sums(prediction, gw)
+        else:
+            la, ph = prediction[0], prediction[1]
+            rows = [n // hop for n in Lg]
+            seg_v = prediction[2] if len(prediction) > 2 else Segments(rows, eng.device)
+            if seg_v.lengths != rows or la.shape[0] != seg_v.rows or ph.shape != la.shape:
+                raise ValueError(f"the vocoder rows describe {seg_v.lengths} frames; the recordings' {Lg} samples at hop {hop} make {rows}")
+            idx = torch.cat([torch.cat([torch.arange(seg_v.host[b], seg_v.host[b + 1]), torch.tensor([seg_v.host[b + 1] - 1])]) for b in range(seg_v.n)])
+            idx = idx.to(eng.device)
+            seg_r = Segments([r + 1 for r in rows], eng.device)
+            mp = _magphase_sums(eng, gw, Lg, la.index_select(0, idx).contiguous(), ph.index_select(0, idx).contiguous(), seg_r, n_fft, win, hop)
+            mp_rows = seg_r.rows
+        parts.append(mp)  # [B, 4]
+    curves = []
+    for name, pair in (("pitch", pitch), ("energy", energy)):
+        if pair is not None:
+            a, b, L = _curve_pair(pair, name)
+            parts.append(eng.smooth_l1_sums(Segments(L, eng.device), _pack_waves(eng, a), _pack_waves(eng, b)))  # [len(L)]
+            curves.append((name, len(L), sum(L)))
+    host = torch.cat([p.reshape(-1) for p in parts]).cpu().tolist()  # the one host read
+    at = 2 * R * B
+    mel, mel_r, mel_utt = mel_score([[host[2 * (r * B + u) : 2 * (r * B + u) + 2] for u in range(B)] for r in range(R)])
+    out = dict(mel=mel, mel_r=mel_r, mel_utt=mel_utt)
+    if mp_rows is not None:
+        mag, phase, terms = magphase_score([host[at + 4 * u : at + 4 * u + 4] for u in range(B)], mp_rows, eng.n_bins)
+        out.update(mag=mag, phase=phase, phase_terms=terms)
+        at += 4 * B
+    for name, n_utt, n in curves:
+        tot = 0.0
+        for v in host[at : at + n_utt]:
+            tot += v
+        out[name] = tot / n
+        at += n_utt
+    return out

@@ -643,6 +643,118 @@ class HipModel:
         m, s, n = stats.cpu().tolist()
         return (m, s, int(n)) + ((part, seg_m) if return_partials else ())
 
+    # ------------------------------------------------------------------ validation scores (packed waveforms; csrc/val_scores.hip.h)
+    def _packed_wave(self, seg: Segments, wave: torch.Tensor, what: str = "waveform") -> torch.Tensor:
+        wave = wave.to(self.device, torch.float32).contiguous()
+        if wave.dim() != 1 or wave.numel() != seg.rows:
+            raise ValueError(f"packed {what} of {wave.numel()} samples, the offsets describe {seg.rows}")
+        return wave
+
+    def multi_spectrogram(self, seg: Segments, wave: torch.Tensor, n_fft: int, win: int, hop: int, n_mels: int = 128, sample_rate: Optional[int] = None,
+                          mag: bool = True, phase: bool = False, fft_mag: bool = False, ld_mag: Optional[int] = None, ld_bins: Optional[int] = None,
+                          out: Optional[Dict[str, torch.Tensor]] = None):
+        """MultiSpectrogram.calculate_single (train/multi_spectrogram.py:40-55) of the packed recordings as time-major rows over all samples // hop + 1
+        frames of each: -> (their Segments, mag [rows, ld_mag >= n_mels] = log1p of the mel of |X|, phase [rows, ld_bins >= n_fft / 2 + 1] =
+        (|X| > 1e-3) * angle(X), fft_mag [rows, ld_bins] = |X|), None for what was not asked.  out: {"mag" | "phase" | "fft_mag": rows to write into}
+        (columns beyond the width keep their values).  fp64 arithmetic, one rounding (include/stylish_hip.h, stts_multi_spectrogram_forward).
+        ValueError for a geometry or a length the transform refuses.  Nothing is read back by the host."""
+        from . import val_scores
+
+        sr = int(self.cfg.sample_rate if sample_rate is None else sample_rate)
+        val_scores.check_geometry(n_fft, win, hop, n_mels, sr)
+        seg_m = Segments(val_scores.frame_counts(seg.lengths, int(n_fft), int(hop)), self.device)
+        wave = self._packed_wave(seg, wave)
+        out = dict(out or {})
+        if not (mag or phase or fft_mag or out):
+            raise ValueError("multi_spectrogram: no output asked for")
+        bins = int(n_fft) // 2 + 1
+        ld_mag = int(n_mels) if ld_mag is None else int(ld_mag)
+        ld_bins = bins if ld_bins is None else int(ld_bins)
+        for k, t in out.items():
+            if k not in ("mag", "phase", "fft_mag"):
+                raise ValueError(f"out has no {k!r}")
+            if t.dtype != torch.float32 or t.device != self.device or t.dim() != 2 or t.shape[0] != seg_m.rows or not t.is_contiguous():
+                raise ValueError(f"out[{k!r}] must be contiguous float32 [{seg_m.rows}, ld] on {self.device}, got {tuple(t.shape)}")
+        if "mag" in out:
+            ld_mag = out["mag"].shape[1]
+        if "phase" in out or "fft_mag" in out:
+            ld_bins = out.get("phase", out.get("fft_mag")).shape[1]
+            if any(out[k].shape[1] != ld_bins for k in ("phase", "fft_mag") if k in out):
+                raise ValueError("out['phase'] and out['fft_mag'] must share one row stride")
+        if ld_mag < int(n_mels) or ld_bins < bins:
+            raise ValueError(f"ld_mag {ld_mag} < n_mels {n_mels} or ld_bins {ld_bins} < {bins} bins")
+        mg = out["mag"] if "mag" in out else (self._f32(seg_m.rows, ld_mag) if mag else None)
+        ph = out["phase"] if "phase" in out else (self._f32(seg_m.rows, ld_bins) if phase else None)
+        fm = out["fft_mag"] if "fft_mag" in out else (self._f32(seg_m.rows, ld_bins) if fft_mag else None)
+        _lib.check(self.lib.stts_multi_spectrogram_forward(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), seg_m.host_ptr, _ptr(seg_m.dev), _ptr(wave),
+                                                           int(n_fft), int(win), int(hop), int(n_mels), sr, _ptr(mg), ld_mag, _ptr(fm), _ptr(ph), ld_bins))
+        return seg_m, mg, ph, fm
+
+    def mel_sums(self, seg: Segments, target: torch.Tensor, pred: torch.Tensor, resolutions=None, n_mels: int = 128, sample_rate: Optional[int] = None,
+                 seg_pred: Optional[Segments] = None, return_partials: bool = False):
+        """The sums of MultiResolutionSTFTLoss (train/losses.py:14-35) over the packed pairs (target, pred), one fused launch per resolution and no
+        spectrogram written: -> [R, B, 2] float64 on the device, [r, u] = (sum |t - p|, sum |t|) of utterance u's log1p mel spectrogram at resolution r
+        (include/stylish_hip.h, stts_val_mel_sums).  resolutions: Resolution-like objects or (fft, hop, window) tuples, default the reference's three.
+        seg_pred: the prediction's own offsets when they were built apart; ValueError naming an utterance whose sample counts differ.
+        return_partials=True appends the list of per-frame partials [rows_r, 2] and of their Segments."""
+        from . import val_scores
+
+        sr = int(self.cfg.sample_rate if sample_rate is None else sample_rate)
+        res = [val_scores.as_tuple(r) for r in (val_scores.resolutions if resolutions is None else resolutions)]
+        seg_pred = seg if seg_pred is None else seg_pred
+        val_scores.check_pair(seg.lengths, seg_pred.lengths)
+        target, pred = self._packed_wave(seg, target, "target"), self._packed_wave(seg_pred, pred, "prediction")
+        sums = torch.empty(len(res), seg.n, 2, dtype=torch.float64, device=self.device)
+        parts, segs = [], []
+        for i, (fft, hop, window) in enumerate(res):
+            val_scores.check_geometry(fft, window, hop, n_mels, sr)
+            sz = val_scores.sizes(seg.lengths, fft, hop)
+            seg_m = Segments(val_scores.frame_counts(seg.lengths, fft, hop), self.device)
+            part = torch.empty(sz["mel_partials"], dtype=torch.float64, device=self.device)
+            _lib.check(self.lib.stts_val_mel_sums(self.ctx, _stream(), seg.n, seg.host_ptr, seg_pred.host_ptr, _ptr(seg.dev), seg_m.host_ptr, _ptr(seg_m.dev),
+                                                  _ptr(target), _ptr(pred), fft, window, hop, int(n_mels), sr, _ptr(part), _ptr(sums[i])))
+            parts.append(part.view(-1, 2))
+            segs.append(seg_m)
+        return (sums, parts, segs) if return_partials else sums
+
+    def magphase_sums(self, seg_samples: Segments, gt: torch.Tensor, seg_rows: Segments, logamp_rows: torch.Tensor, phase_rows: torch.Tensor, ld: int,
+                      n_fft: int, win: int, hop: int) -> torch.Tensor:
+        """The sums of MagPhaseLoss.forward (train/losses.py:85-154) over the packed recordings gt and the prediction's log-magnitude / phase as
+        time-major rows [rows, ld >= n_fft / 2 + 1] (what vocoder(return_spec=True) returns, plus the reference's repeated last frame): hop is the
+        transform's (the reference's hop_length // 4).  -> [B, 4] float64 on the device: the L1 sum of "mag" and the three weighted anti-wrapping
+        sums of "phase" (include/stylish_hip.h, stts_val_magphase_sums).  phase_rows is not modified.  ValueError naming an utterance whose row
+        count is not samples // hop + 1."""
+        from . import val_scores
+
+        val_scores.check_geometry(n_fft, win, hop)
+        val_scores.frame_counts(seg_samples.lengths, int(n_fft), int(hop))
+        val_scores.check_rows(seg_samples.lengths, seg_rows.lengths, hop)
+        gt = self._packed_wave(seg_samples, gt, "recording")
+        ld = int(ld)
+        for name, t in (("logamp_rows", logamp_rows), ("phase_rows", phase_rows)):
+            if t.dtype != torch.float32 or t.device != self.device or t.dim() != 2 or tuple(t.shape) != (seg_rows.rows, ld) or not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous float32 [{seg_rows.rows}, {ld}] on {self.device}, got {tuple(t.shape)}")
+        if ld < int(n_fft) // 2 + 1:
+            raise ValueError(f"ld {ld} < {int(n_fft) // 2 + 1} bins")
+        sz = val_scores.sizes(seg_samples.lengths, n_fft, hop)
+        scratch = torch.empty(sz["magphase_scratch"], dtype=torch.float64, device=self.device)
+        part = torch.empty(sz["magphase_partials"], dtype=torch.float64, device=self.device)
+        sums = torch.empty(seg_samples.n, 4, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.stts_val_magphase_sums(self.ctx, _stream(), seg_samples.n, seg_samples.host_ptr, _ptr(seg_samples.dev), seg_rows.host_ptr,
+                                                   _ptr(seg_rows.dev), _ptr(gt), _ptr(logamp_rows), _ptr(phase_rows), ld, int(n_fft), int(win), int(hop),
+                                                   _ptr(scratch), _ptr(part), _ptr(sums)))
+        return sums
+
+    def smooth_l1_sums(self, seg: Segments, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        """[B] float64 on the device: each utterance's sum of smooth_l1(a - b), beta 1, over the packed fp32 vectors a and b (utterance offsets seg),
+        added in a fixed order (include/stylish_hip.h, stts_val_smooth_l1_sums).  The reference's mean is sums.sum() / seg.rows."""
+        a, b = self._packed_wave(seg, a, "vector a"), self._packed_wave(seg, b, "vector b")
+        if min(seg.lengths) < 1:
+            raise ValueError(f"utterance {seg.lengths.index(min(seg.lengths))} has no values")
+        sums = torch.empty(seg.n, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.stts_val_smooth_l1_sums(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(a), _ptr(b), _ptr(sums)))
+        return sums
+
     # ------------------------------------------------------------------ windowed-sinc resampler (packed waveforms at any rate)
     def resample(self, seg_in: Segments, wave: torch.Tensor, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99,
                  resampling_method: str = "sinc_interp_hann", beta: Optional[float] = None):
