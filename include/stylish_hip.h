@@ -592,6 +592,110 @@ typedef struct stts_conv_epi_args {
   int32_t force_tile, tune, precision;
 } stts_conv_epi_args;
 int stts_op_conv1d_epi(void* stream, const stts_conv_epi_args* args);
+/* The kernels BETWEEN the contractions, one at a time (tests/test_hip_norm_kernels.py).  Like stts_op_conv1d_epi: one args struct per operator, every
+ * tensor caller-owned and on the device unless named *_host, *_elems the element count of the caller's buffer; a launch that could reach beyond one of
+ * them, or a shape outside a kernel's stated domain, is refused before anything is launched.  Host and device offsets must agree (no capacity form).
+ *
+ * stts_op_adain: chunk statistics -> merge -> apply of AdaIN (models/ada_norm.py:129-139), each step selectable.
+ *   producer 0: adain_partial_kernel, chunks of 128 rows; 1: the same kernel, chunks of 24 rows (the Winograd statistics' chunking);
+ *            2: adain_partial_reduce_kernel: x (channels < split_n) is FINISHED here from ksplit partial slices [ksplit][slice_rows][ld_part] as
+ *               (act(sum_k + bias) [+ r]) * alpha and written, the statistics come from the values in flight (chunks of 128 rows).
+ *   consumer 0: none; 1: adain_affine_kernel (serial merge); 2: adain_affine_lanes_kernel (16 lanes) -> aff [n_utt][2][ld_aff];
+ *            3: adain_apply_kernel through run_adain on the table the producer left (producer 0 or 2; ldp == round_up(C, 32), nchunk ==
+ *               ceil(max_len / 128)) -> y [rows, ldy] (out16: 0 fp32, STTS_PREC_BF16 / _F16: 16-bit elements), rb 64 or 256, act, snake (null: none).
+ *   part [((u * nchunk + chunk) * 2 + {mean, M2})][ldp]; gb [n_utt][ld_gb]: gamma at gcol0 + c, beta at gcol0 + C + c. */
+typedef struct stts_adain_args {
+  const int32_t* seg_off_host;
+  const int32_t* seg_off_dev;
+  float* x;
+  float* part;
+  const float* partial;
+  const float* bias;
+  const float* r;
+  const float* gb;
+  const float* snake;
+  float* aff;
+  void* y;
+  int64_t x_elems, part_elems, partial_elems, bias_elems, r_elems, gb_elems, snake_elems, aff_elems, y_elems;
+  int32_t n_utt, producer, consumer, C, ldx, ldp, nchunk;
+  int32_t ksplit, slice_rows, ld_part, split_n, split_act, ldr, rcol0;
+  float split_alpha;
+  int32_t ld_gb, gcol0, ld_aff, ldy, rb, act, out16;
+} stts_adain_args;
+int stts_op_adain(void* stream, const stts_adain_args* args);
+/* F.conv1d (k 3 or 7, dilation 1) in Winograd form as stts_op_conv1d's force_tile -4, with the AdaIN statistics winograd_output_kernel<N, true> leaves
+ * next to Y: stat [((u * stat_nchunk + 24-row chunk) * 2 + {mean, M2})][ld_stat], stat_nchunk == ceil(ceil(max_len / 6) / 4).  x, y, stat on the device. */
+typedef struct stts_wino_stat_args {
+  const int32_t* seg_off_host;
+  const int32_t* seg_off_dev;
+  const float* x;
+  const float* w_host;
+  const float* bias_host;
+  float* y;
+  float* stat;
+  int64_t x_elems, y_elems, stat_elems;
+  int32_t n_utt, ldx, cin, cout, k, act, ldy, ld_stat, stat_nchunk, precision;
+} stts_wino_stat_args;
+int stts_op_wino_stat(void* stream, const stts_wino_stat_args* args);
+/* row_layernorm_kernel through ln_launch: LayerNorm over C channels (C % 4 == 0, C <= 2048) of n_rows rows, one or two outputs.
+ * static: out.g / out.b = gamma / beta [C]; adaptive: out.g = style table [n_utt][ld_g], gamma at gcol0 + c, beta at gcol0 + C + c (the offsets are then
+ * needed and must sum to n_rows).  partial != null: the row is finished from ksplit split-K slices [ksplit][slice_rows][ld_part] as
+ * (act(sum_k + bias) [+ r]) * alpha (LnIn), x is not read.  n_rows_real >= 0: passed as the device-side row count (rows from there on are skipped). */
+typedef struct stts_ln_out {
+  void* y;
+  const float* g;
+  const float* b;
+  int64_t y_elems, g_elems, b_elems;
+  int32_t ldy, ycol0, ld_g, gcol0, prec16;
+} stts_ln_out;
+typedef struct stts_row_layernorm_args {
+  const int32_t* seg_off_host;
+  const int32_t* seg_off_dev;
+  const float* x;
+  const float* partial;
+  const float* bias;
+  const float* r;
+  int64_t x_elems, partial_elems, bias_elems, r_elems;
+  stts_ln_out out[2];
+  int32_t n_utt, n_rows, n_rows_real, C, ldx, adaptive, nout, act;
+  float eps;
+  int32_t ksplit, slice_rows, ld_part, in_act, ldr, rcol0;
+  float in_alpha;
+} stts_row_layernorm_args;
+int stts_op_row_layernorm(void* stream, const stts_row_layernorm_args* args);
+/* Depthwise Conv1d along time, zero padding inside the utterance (w_host [C][K] = the reference's [C, 1, K], bias_host [C]; C % 4 == 0).
+ *   form 0: dwconv_kernel<31> (K odd, <= 31) with act -> y fp32;
+ *   form 1: dwconv_ln_kernel<K, 16>: + adaptive LayerNorm (eps 1e-6), C <= 512, K in {3, 7, 15, 31} - the dispatch of convnext_block_forward;
+ *   form 2: form 0 into a scratch, then row_layernorm_kernel: that function's fallback.
+ * forms 1, 2: style [n_utt][ld_style], gamma at gcol0 + c, beta at gcol0 + C + c; y fp32 or (prec16) 16-bit elements. */
+typedef struct stts_dwconv_args {
+  const int32_t* seg_off_host;
+  const int32_t* seg_off_dev;
+  const float* x;
+  const float* w_host;
+  const float* bias_host;
+  const float* style;
+  void* y;
+  int64_t x_elems, style_elems, y_elems;
+  int32_t n_utt, form, C, K, act, ldx, ldy, ld_style, gcol0, prec16;
+} stts_dwconv_args;
+int stts_op_dwconv(void* stream, const stts_dwconv_args* args);
+/* GRN (models/generator.py:496-499) from a caller-supplied table of per-32-row-slot sums of squares part [n_utt][ss_stride][ld_ss]:
+ * grn_gx_kernel -> gx [n_utt][ld_gx], then mode 0: nothing; 1: grn_xaff_kernel -> xaff [n_utt][2][ld_xaff]; 2: launch_scale_weight (prec 0 / _BF16 / _F16)
+ * of w [npad][kc] -> wu [n_utt][npad][kc] (fp32 or 16-bit elements; kc == C, C % 4 == 0: the kernel averages gx over kc columns). */
+typedef struct stts_grn_args {
+  const int32_t* seg_off_host;
+  const int32_t* seg_off_dev;
+  const float* part;
+  const float* gamma;
+  const float* w;
+  float* gx;
+  float* xaff;
+  void* wu;
+  int64_t part_elems, gamma_elems, w_elems, gx_elems, xaff_elems, wu_elems;
+  int32_t n_utt, mode, C, ld_ss, ss_stride, ld_gx, ld_xaff, npad, kc, prec;
+} stts_grn_args;
+int stts_op_grn(void* stream, const stts_grn_args* args);
 /* AdaptiveDecoderBlock.forward (models/ada_norm.py:166-182) with weights named `prefix` + reference keys. */
 int stts_op_adain_block(stts_ctx* ctx, void* stream, const char* prefix, int n_utt, const int32_t* seg_off_host,
                         const int32_t* seg_off_dev, const float* x, int ldx, int cin, int cout, const float* style, float* y, int ldy,

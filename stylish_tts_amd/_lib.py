@@ -67,6 +67,51 @@ class ConvEpiArgs(C.Structure):
                 + [(n, C.c_int32) for n in ("ldr", "rcol0", "ldy", "ycol0", "ldy16", "ycol16", "ld_ss", "ss_stride", "ld_stat", "stat_nchunk",
                                             "force_tile", "tune", "precision")])
 
+def _fields(*groups):
+    """(type, "a b c") groups -> ctypes _fields_, in order."""
+    return [(n, t) for t, names in groups for n in names.split()]
+
+
+_I32, _F = C.c_int32, C.c_float
+
+
+class AdainArgs(C.Structure):
+    """include/stylish_hip.h: stts_adain_args (test surface)."""
+    _fields_ = _fields((_P, "seg_off_host seg_off_dev x part partial bias r gb snake aff y"),
+                       (_I64, "x_elems part_elems partial_elems bias_elems r_elems gb_elems snake_elems aff_elems y_elems"),
+                       (_I32, "n_utt producer consumer C ldx ldp nchunk ksplit slice_rows ld_part split_n split_act ldr rcol0"), (_F, "split_alpha"),
+                       (_I32, "ld_gb gcol0 ld_aff ldy rb act out16"))
+
+
+class WinoStatArgs(C.Structure):
+    """include/stylish_hip.h: stts_wino_stat_args (test surface)."""
+    _fields_ = _fields((_P, "seg_off_host seg_off_dev x w_host bias_host y stat"), (_I64, "x_elems y_elems stat_elems"),
+                       (_I32, "n_utt ldx cin cout k act ldy ld_stat stat_nchunk precision"))
+
+
+class LnOutArgs(C.Structure):
+    """include/stylish_hip.h: stts_ln_out (test surface)."""
+    _fields_ = _fields((_P, "y g b"), (_I64, "y_elems g_elems b_elems"), (_I32, "ldy ycol0 ld_g gcol0 prec16"))
+
+
+class RowLayerNormArgs(C.Structure):
+    """include/stylish_hip.h: stts_row_layernorm_args (test surface)."""
+    _fields_ = (_fields((_P, "seg_off_host seg_off_dev x partial bias r"), (_I64, "x_elems partial_elems bias_elems r_elems")) + [("out", LnOutArgs * 2)]
+                + _fields((_I32, "n_utt n_rows n_rows_real C ldx adaptive nout act"), (_F, "eps"), (_I32, "ksplit slice_rows ld_part in_act ldr rcol0"), (_F, "in_alpha")))
+
+
+class DwconvArgs(C.Structure):
+    """include/stylish_hip.h: stts_dwconv_args (test surface)."""
+    _fields_ = _fields((_P, "seg_off_host seg_off_dev x w_host bias_host style y"), (_I64, "x_elems style_elems y_elems"),
+                       (_I32, "n_utt form C K act ldx ldy ld_style gcol0 prec16"))
+
+
+class GrnArgs(C.Structure):
+    """include/stylish_hip.h: stts_grn_args (test surface)."""
+    _fields_ = _fields((_P, "seg_off_host seg_off_dev part gamma w gx xaff wu"), (_I64, "part_elems gamma_elems w_elems gx_elems xaff_elems wu_elems"),
+                       (_I32, "n_utt mode C ld_ss ss_stride ld_gx ld_xaff npad kc prec"))
+
+
 # name -> (restype, argtypes); mirrors include/stylish_hip.h one to one
 SIGNATURES = {
     "stts_last_error": (C.c_char_p, []),
@@ -156,6 +201,11 @@ TEST_SIGNATURES = {
     "stts_op_conv1d": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P, _I, _I, _I]),
     "stts_op_conv1d_x3": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P, _I, _I, _I, _P, _I, C.c_float, _I, _P, _I, _I, _I]),
     "stts_op_conv1d_epi": (_I, [_P, C.POINTER(ConvEpiArgs)]),
+    "stts_op_adain": (_I, [_P, C.POINTER(AdainArgs)]),
+    "stts_op_wino_stat": (_I, [_P, C.POINTER(WinoStatArgs)]),
+    "stts_op_row_layernorm": (_I, [_P, C.POINTER(RowLayerNormArgs)]),
+    "stts_op_dwconv": (_I, [_P, C.POINTER(DwconvArgs)]),
+    "stts_op_grn": (_I, [_P, C.POINTER(GrnArgs)]),
     "stts_op_adain_block": (_I, [_P, _P, C.c_char_p, _I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _SZ]),
     "stts_op_attention": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I]),
     "stts_op_stft_geom": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I]),

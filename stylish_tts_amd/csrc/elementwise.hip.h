@@ -259,7 +259,9 @@ __global__ void __launch_bounds__(64) adain_affine_kernel(const float* __restric
   const int u = blockIdx.y, c = blockIdx.x * 64 + threadIdx.x;
   if (c >= ld_aff) return;
   float sc = 0.f, sh = 0.f;
-  if (c < C) adain_scale_shift(part, ldp, nchunk, u, c, seg_off[u + 1] - seg_off[u], gb, ld_gb, gcol0, C, eps, &sc, &sh, chunk_rows);
+  const int len = seg_off[u + 1] - seg_off[u];
+  // (an utterance of zero rows has no statistics: zeros, as adain_affine_lanes_kernel writes - the merge would divide 0 by 0)
+  if (c < C && len > 0) adain_scale_shift(part, ldp, nchunk, u, c, len, gb, ld_gb, gcol0, C, eps, &sc, &sh, chunk_rows);
   aff[((long)u * 2) * ld_aff + c] = sc;
   aff[((long)u * 2 + 1) * ld_aff + c] = sh;
 }

@@ -356,6 +356,283 @@ int stts_op_istft_geom(void* stream, int n_utt, const int32_t* seg_off_host, con
 
 }  // extern "C"
 
+// ------------------------------------------------------------------------------------------------ the kernels between the contractions
+// stts_op_adain / _wino_stat / _row_layernorm / _dwconv / _grn (include/stylish_hip.h; tests/test_hip_norm_kernels.py).  Each follows stts_op_conv1d_epi:
+// the checks come first and are complete - every index a launch can form is bounded by the caller's element counts - and only then is anything launched.
+namespace {
+// offsets: start at 0, non-decreasing, the same on both sides (read back here: the operators are no hot path)
+int norm_op_offsets(hipStream_t st, const char* op, int n_utt, const int32_t* host, const int32_t* dev) {
+  STTS_CHECK(host && dev && n_utt > 0, "%s: null / empty offsets", op);
+  std::vector<int> d(n_utt + 1);
+  STTS_HIP(hipStreamSynchronize(st));
+  STTS_HIP(hipMemcpy(d.data(), dev, d.size() * sizeof(int), hipMemcpyDeviceToHost));
+  STTS_CHECK(host[0] == 0, "%s: offsets start at 0", op);
+  for (int u = 0; u <= n_utt; ++u) STTS_CHECK(d[u] == host[u] && (u == 0 || host[u] >= host[u - 1]), "%s: offsets decrease, or host and device offsets differ (utterance %d)", op, u);
+  return 0;
+}
+// rows x [col0, col0 + cols) of a [rows, ld] buffer of `elems` elements
+bool norm_op_fits(long rows, int ld, int col0, int cols, long elems) { return col0 >= 0 && cols >= 0 && ld >= col0 + cols && (rows <= 0 || (rows - 1) * (long)ld + col0 + cols <= elems); }
+struct NormOpTemps {  // every exit path waits for the stream and frees the temporaries
+  stts_ctx tmp;
+  hipStream_t st;
+  explicit NormOpTemps(hipStream_t s) : st(s) {}
+  ~NormOpTemps() {
+    (void)hipStreamSynchronize(st);
+    for (void* q : tmp.allocs) (void)hipFree(q);
+  }
+};
+}  // namespace
+
+extern "C" {
+
+int stts_op_adain(void* stream, const stts_adain_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p, "op_adain: null argument");
+  STTS_TRY(norm_op_offsets(st, "op_adain", p->n_utt, p->seg_off_host, p->seg_off_dev));
+  Seg s{p->n_utt, p->seg_off_host, p->seg_off_dev};
+  const long R = s.rows();
+  const int n_utt = p->n_utt, C = p->C, ml = s.max_len();
+  STTS_CHECK(p->producer >= 0 && p->producer <= 2 && p->consumer >= 0 && p->consumer <= 3, "op_adain: producer 0 - 2, consumer 0 - 3");
+  const int chunk_rows = p->producer == 1 ? kWinoStatChunk : kStatChunk;
+  STTS_CHECK(chunk_rows <= kStatChunk, "op_adain: chunk_rows above kStatChunk");
+  STTS_CHECK(C > 0 && p->x && p->part, "op_adain: C, x and part are required");
+  STTS_CHECK(p->ldx % 4 == 0 && norm_op_fits(R, p->ldx, 0, round_up(C, 4), p->x_elems), "op_adain: x [%ld, ldx %d] (ldx %% 4 == 0, covering C = %d rounded up to 4) outside %ld elements", R, p->ldx, C,
+             (long)p->x_elems);
+  STTS_CHECK(p->ldp >= C && p->nchunk >= ceil_div(ml, chunk_rows) && (long)n_utt * p->nchunk * 2 * p->ldp <= p->part_elems,
+             "op_adain: part needs ldp >= C, nchunk >= ceil(max_len / %d) and n_utt * nchunk * 2 * ldp elements", chunk_rows);
+  SplitSrc src{};
+  if (p->producer == 2) {
+    STTS_CHECK(p->partial && p->ksplit >= 1 && p->split_n > 0 && p->split_n <= C, "op_adain: producer 2 needs partial slices and 0 < split_n <= C");
+    STTS_CHECK(p->slice_rows >= R && p->ld_part >= p->split_n && (long)p->ksplit * p->slice_rows * p->ld_part <= p->partial_elems,
+               "op_adain: partial [ksplit][slice_rows >= rows][ld_part >= split_n] outside its buffer");
+    STTS_CHECK(!p->bias || p->bias_elems >= p->split_n, "op_adain: bias shorter than split_n");
+    STTS_CHECK(!p->r || norm_op_fits(R, p->ldr, p->rcol0, p->split_n, p->r_elems), "op_adain: residual window outside its buffer");
+    STTS_CHECK(p->split_act >= ACT_NONE && p->split_act <= ACT_LRELU, "op_adain: split_act out of range");
+    src = SplitSrc{p->partial, p->ksplit, p->slice_rows, p->ld_part, p->split_n, p->bias, p->split_act, p->r, p->ldr, p->rcol0, p->split_alpha};
+  }
+  if (p->consumer) STTS_CHECK(p->gb && p->ld_gb >= 0 && p->gcol0 >= 0 && (long)(n_utt - 1) * p->ld_gb + p->gcol0 + 2 * C <= p->gb_elems, "op_adain: style rows (gamma, beta at gcol0) outside gb");
+  if (p->consumer == 1 || p->consumer == 2)
+    STTS_CHECK(p->aff && p->ld_aff >= C && (long)n_utt * 2 * p->ld_aff <= p->aff_elems, "op_adain: aff needs ld_aff >= C and n_utt * 2 * ld_aff elements");
+  if (p->consumer == 3) {
+    STTS_CHECK(p->producer != 1, "op_adain: adain_apply_kernel merges chunks of %d rows", kStatChunk);
+    STTS_CHECK(p->ldp == round_up(C, 32) && p->nchunk == ceil_div(ml, kStatChunk), "op_adain: run_adain lays the table out as [ceil(max_len / 128)][2][round_up(C, 32)]");
+    STTS_CHECK(p->rb == 64 || p->rb == 256, "op_adain: rb is 64 or 256");
+    STTS_CHECK(p->act >= ACT_NONE && p->act <= ACT_LRELU, "op_adain: act out of range");
+    STTS_CHECK(p->out16 == 0 || p->out16 == PREC_BF16 || p->out16 == PREC_F16, "op_adain: out16 is 0, STTS_PREC_BF16 or _F16");
+    STTS_CHECK(p->y && p->ldy % 4 == 0 && norm_op_fits(R, p->ldy, 0, std::max(p->ldy, C), p->y_elems), "op_adain: y [rows, ldy] (ldy %% 4 == 0, ldy >= C) outside its buffer");
+    STTS_CHECK(!p->snake || p->snake_elems >= C, "op_adain: snake alpha shorter than C");
+  }
+  if (R == 0) return 0;
+  const dim3 pg(ceil_div(C, 32), std::max(1, ceil_div(ml, chunk_rows)), n_utt);
+  if (p->producer == 2)
+    hipLaunchKernelGGL(adain_partial_reduce_kernel, pg, dim3(256), 0, st, p->x, p->ldx, C, s.dev, p->part, p->ldp, p->nchunk, src);
+  else
+    hipLaunchKernelGGL(adain_partial_kernel, pg, dim3(256), 0, st, (const float*)p->x, p->ldx, C, s.dev, p->part, p->ldp, p->nchunk, chunk_rows);
+  if (p->consumer == 1)
+    hipLaunchKernelGGL(adain_affine_kernel, dim3(ceil_div(p->ld_aff, 64), n_utt), dim3(64), 0, st, (const float*)p->part, p->ldp, p->nchunk, s.dev, p->gb, p->ld_gb, p->gcol0, C, 1e-5f, p->aff,
+                       p->ld_aff, chunk_rows);
+  else if (p->consumer == 2)
+    hipLaunchKernelGGL(adain_affine_lanes_kernel, dim3(ceil_div(p->ld_aff, 16), n_utt), dim3(256), 0, st, (const float*)p->part, p->ldp, p->nchunk, s.dev, p->gb, p->ld_gb, p->gcol0, C, 1e-5f,
+                       p->aff, p->ld_aff, chunk_rows);
+  else if (p->consumer == 3)
+    STTS_TRY(run_adain(st, s, p->x, p->ldx, C, reinterpret_cast<float*>(p->y), p->ldy, p->gb, p->ld_gb, p->gcol0, p->act, p->snake, p->part, p->out16, true, p->rb));
+  STTS_HIP(hipGetLastError());
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
+int stts_op_wino_stat(void* stream, const stts_wino_stat_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p, "op_wino_stat: null argument");
+  STTS_TRY(norm_op_offsets(st, "op_wino_stat", p->n_utt, p->seg_off_host, p->seg_off_dev));
+  Seg s{p->n_utt, p->seg_off_host, p->seg_off_dev};
+  const long R = s.rows();
+  STTS_CHECK(R > 0 && p->x && p->w_host && p->y && p->stat && p->cin > 0 && p->cout > 0, "op_wino_stat: null / empty argument");
+  STTS_CHECK(p->k == 3 || p->k == 7, "op_wino_stat: the Winograd forms are F(6, 3) and F(6, 7)");
+  STTS_CHECK(p->precision == 0 || p->precision == 3, "op_wino_stat: precision must be STTS_PREC_F32 or _F32_NATIVE");
+  STTS_CHECK(p->act >= ACT_NONE && p->act <= ACT_LRELU, "op_wino_stat: act out of range");
+  STTS_CHECK(p->ldx % 32 == 0 && norm_op_fits(R, p->ldx, 0, p->ldx, p->x_elems) && p->ldx >= p->cin, "op_wino_stat: ldx must be a multiple of 32 covering cin, x [rows, ldx]");
+  STTS_CHECK(p->ldy % 4 == 0 && norm_op_fits(R, p->ldy, 0, round_up(p->cout, 4), p->y_elems), "op_wino_stat: y [rows, ldy] (ldy %% 4 == 0, covering cout rounded up to 4) outside its buffer");
+  STTS_CHECK(p->ld_stat % 4 == 0 && p->ld_stat >= round_up(p->cout, 4) && p->stat_nchunk == wino_stat_chunks(s) && (long)p->n_utt * p->stat_nchunk * 2 * p->ld_stat <= p->stat_elems,
+             "op_wino_stat: stat needs ld_stat %% 4 == 0 covering cout, stat_nchunk == %d and n_utt * stat_nchunk * 2 * ld_stat elements", wino_stat_chunks(s));
+  NormOpTemps t(st);
+  stts_ctx& tmp = t.tmp;
+  tmp.prec = 0;
+  tmp.allow_x3 = p->precision != 3;
+  PackScope scope(&tmp, engine_mode(&tmp));
+  HostTensor w;
+  w.shape = {p->cout, p->cin, p->k};
+  w.data.assign(p->w_host, p->w_host + (size_t)p->cout * p->cin * p->k);
+  HostTensor b;
+  b.shape = {p->cout};
+  if (p->bias_host) b.data.assign(p->bias_host, p->bias_host + p->cout);
+  WinoConv wc;
+  STTS_TRY(pack_winograd(&tmp, w, p->bias_host ? &b : nullptr, 0, p->cin, p->cout, &wc));
+  float* scratch = nullptr;
+  STTS_HIP(hipMalloc(&scratch, wino_scratch_floats(s, wc) * sizeof(float)));
+  tmp.allocs.push_back(scratch);
+  WinoScratch wz;
+  wz.p = scratch;
+  STTS_TRY(run_winograd(st, s, p->x, p->ldx, wc, p->y, p->ldy, p->act, nullptr, 0, 1.0f, wz, nullptr, 0, p->stat, p->ld_stat));
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
+int stts_op_row_layernorm(void* stream, const stts_row_layernorm_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p, "op_row_layernorm: null argument");
+  const int C = p->C;
+  const long R = p->n_rows;
+  STTS_CHECK(C > 0 && C % 4 == 0 && C <= 2048, "op_row_layernorm: C must be a multiple of 4, at most 2048");
+  STTS_CHECK(R > 0 && (p->nout == 1 || p->nout == 2) && p->act >= ACT_NONE && p->act <= ACT_LRELU, "op_row_layernorm: n_rows, nout (1 or 2) or act out of range");
+  STTS_CHECK(p->n_rows_real <= R, "op_row_layernorm: n_rows_real above n_rows");
+  if (p->adaptive) {
+    STTS_TRY(norm_op_offsets(st, "op_row_layernorm", p->n_utt, p->seg_off_host, p->seg_off_dev));
+    STTS_CHECK(p->seg_off_host[p->n_utt] == R, "op_row_layernorm: the offsets must cover n_rows");
+  }
+  LnIn in{};
+  if (p->partial) {
+    STTS_CHECK(p->ksplit >= 1 && p->slice_rows >= R && p->ld_part % 4 == 0 && p->ld_part >= C && (long)p->ksplit * p->slice_rows * p->ld_part <= p->partial_elems,
+               "op_row_layernorm: partial [ksplit][slice_rows >= n_rows][ld_part >= C, %% 4 == 0] outside its buffer");
+    STTS_CHECK(!p->bias || p->bias_elems >= C, "op_row_layernorm: bias shorter than C");
+    STTS_CHECK(!p->r || norm_op_fits(R, p->ldr, p->rcol0, C, p->r_elems), "op_row_layernorm: residual window outside its buffer");
+    STTS_CHECK(p->in_act >= ACT_NONE && p->in_act <= ACT_LRELU, "op_row_layernorm: in_act out of range");
+    in = LnIn{p->partial, p->ksplit, p->slice_rows, p->ld_part, p->bias, p->in_act, p->r, p->ldr, p->rcol0, p->in_alpha};
+  } else {
+    STTS_CHECK(p->x && p->ldx % 4 == 0 && norm_op_fits(R, p->ldx, 0, C, p->x_elems), "op_row_layernorm: x [n_rows, ldx] (ldx %% 4 == 0, ldx >= C) outside its buffer");
+  }
+  LnOut o[2] = {};
+  for (int k = 0; k < p->nout; ++k) {
+    const stts_ln_out& q = p->out[k];
+    STTS_CHECK(q.y && q.g && (q.prec16 == 0 || q.prec16 == PREC_BF16 || q.prec16 == PREC_F16), "op_row_layernorm: output %d: null tensor or prec16 out of range", k);
+    STTS_CHECK(q.ldy % 4 == 0 && q.ycol0 % 4 == 0 && norm_op_fits(R, q.ldy, q.ycol0, C, q.y_elems), "op_row_layernorm: output %d: window [%d, %d) of ldy %d (multiples of 4) outside its buffer", k,
+               q.ycol0, q.ycol0 + C, q.ldy);
+    if (p->adaptive)
+      STTS_CHECK(q.ld_g % 4 == 0 && q.gcol0 % 4 == 0 && q.gcol0 >= 0 && q.ld_g >= 0 && (long)(p->n_utt - 1) * q.ld_g + q.gcol0 + 2 * C <= q.g_elems,
+                 "op_row_layernorm: output %d: style rows (ld_g, gcol0 multiples of 4) outside g", k);
+    else
+      STTS_CHECK(q.b && q.g_elems >= C && q.b_elems >= C, "op_row_layernorm: output %d: gamma / beta shorter than C", k);
+    o[k] = LnOut{reinterpret_cast<float*>(q.y), q.ldy, q.ycol0, q.g, q.b, q.ld_g, q.gcol0, q.prec16};
+  }
+  NormOpTemps t(st);
+  int* row_utt = nullptr;
+  if (p->adaptive) {
+    STTS_HIP(hipMalloc(&row_utt, R * sizeof(int)));
+    t.tmp.allocs.push_back(row_utt);
+    Seg s{p->n_utt, p->seg_off_host, p->seg_off_dev};
+    hipLaunchKernelGGL(row_utt_kernel, dim3(std::max(1, ceil_div(s.max_len(), 256)), p->n_utt), dim3(256), 0, st, p->seg_off_dev, p->n_utt, row_utt);
+  }
+  int* rows_dev = nullptr;
+  if (p->n_rows_real >= 0) {
+    STTS_HIP(hipMalloc(&rows_dev, sizeof(int)));
+    t.tmp.allocs.push_back(rows_dev);
+    STTS_HIP(hipMemcpy(rows_dev, &p->n_rows_real, sizeof(int), hipMemcpyHostToDevice));
+  }
+  STTS_TRY(ln_launch(st, p->x, p->ldx, C, R, row_utt, p->eps, p->adaptive != 0, p->nout, o[0], o[1], p->act, in, rows_dev));
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
+int stts_op_dwconv(void* stream, const stts_dwconv_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p, "op_dwconv: null argument");
+  STTS_TRY(norm_op_offsets(st, "op_dwconv", p->n_utt, p->seg_off_host, p->seg_off_dev));
+  Seg s{p->n_utt, p->seg_off_host, p->seg_off_dev};
+  const long R = s.rows();
+  const int C = p->C, K = p->K, ml = s.max_len(), n_utt = p->n_utt;
+  STTS_CHECK(R > 0 && p->x && p->w_host && p->bias_host && p->y, "op_dwconv: null / empty argument");
+  STTS_CHECK(p->form >= 0 && p->form <= 2, "op_dwconv: form 0 - 2");
+  STTS_CHECK(C > 0 && C % 4 == 0 && K >= 1 && K % 2 == 1 && K <= 31, "op_dwconv: C must be a multiple of 4, K odd and at most 31");
+  STTS_CHECK(p->form != 1 || (C <= kDwLnMaxC && (K == 3 || K == 7 || K == 15 || K == 31)), "op_dwconv: the fused form takes C <= %d and K in {3, 7, 15, 31}", kDwLnMaxC);
+  STTS_CHECK(p->form != 2 || C <= 2048, "op_dwconv: the LayerNorm takes C <= 2048");
+  STTS_CHECK(p->ldx % 4 == 0 && norm_op_fits(R, p->ldx, 0, C, p->x_elems), "op_dwconv: x [rows, ldx] (ldx %% 4 == 0, ldx >= C) outside its buffer");
+  STTS_CHECK(p->ldy % 4 == 0 && norm_op_fits(R, p->ldy, 0, C, p->y_elems), "op_dwconv: y [rows, ldy] (ldy %% 4 == 0, ldy >= C) outside its buffer");
+  if (p->form == 0) {
+    STTS_CHECK(p->act >= ACT_NONE && p->act <= ACT_LRELU && p->prec16 == 0, "op_dwconv: form 0 writes fp32 rows with an activation of the contraction's set");
+  } else {
+    STTS_CHECK(p->act == ACT_NONE && (p->prec16 == 0 || p->prec16 == PREC_BF16 || p->prec16 == PREC_F16), "op_dwconv: forms 1, 2 have no activation; prec16 is 0, STTS_PREC_BF16 or _F16");
+    STTS_CHECK(p->style && p->ld_style % 4 == 0 && p->gcol0 % 4 == 0 && p->gcol0 >= 0 && p->ld_style >= 0 && (long)(n_utt - 1) * p->ld_style + p->gcol0 + 2 * C <= p->style_elems,
+               "op_dwconv: style rows (ld_style, gcol0 multiples of 4) outside their buffer");
+  }
+  NormOpTemps t(st);
+  stts_ctx& tmp = t.tmp;
+  PackScope scope(&tmp, engine_mode(&tmp));
+  std::vector<float> wt((size_t)K * C), bv(p->bias_host, p->bias_host + C);  // tap-major [K][C]
+  for (int c = 0; c < C; ++c)
+    for (int k = 0; k < K; ++k) wt[(size_t)k * C + c] = p->w_host[(size_t)c * K + k];
+  float *dwt = nullptr, *db = nullptr;
+  STTS_TRY(dev_upload(&tmp, wt, &dwt));
+  STTS_TRY(dev_upload(&tmp, bv, &db));
+  if (p->form == 1) {
+    const dim3 fg(ceil_div(ml, 16), n_utt);
+#define STTS_OP_DWLN(KK) hipLaunchKernelGGL((dwconv_ln_kernel<KK, 16>), fg, dim3(256), 0, st, p->x, p->ldx, C, s.dev, (const float*)dwt, (const float*)db, 1e-6f, p->style, p->ld_style, p->gcol0, \
+                                            reinterpret_cast<float*>(p->y), p->ldy, p->prec16)
+    if (K == 3) STTS_OP_DWLN(3);
+    else if (K == 7) STTS_OP_DWLN(7);
+    else if (K == 15) STTS_OP_DWLN(15);
+    else STTS_OP_DWLN(31);
+#undef STTS_OP_DWLN
+  } else {
+    float* dw = reinterpret_cast<float*>(p->y);
+    int ld_dw = p->ldy;
+    int* row_utt = nullptr;
+    if (p->form == 2) {
+      STTS_HIP(hipMalloc(&dw, (size_t)R * C * sizeof(float)));
+      tmp.allocs.push_back(dw);
+      ld_dw = C;
+      STTS_HIP(hipMalloc(&row_utt, R * sizeof(int)));
+      tmp.allocs.push_back(row_utt);
+      hipLaunchKernelGGL(row_utt_kernel, dim3(ceil_div(ml, 256), n_utt), dim3(256), 0, st, s.dev, n_utt, row_utt);
+    }
+    hipLaunchKernelGGL((dwconv_kernel<31>), dim3(ceil_div(C, 64), ceil_div(ml, 64), n_utt), dim3(256), 0, st, p->x, p->ldx, dw, ld_dw, C, s.dev, (const float*)dwt, (const float*)db, K, p->act);
+    if (p->form == 2) {
+      LnOut o0{reinterpret_cast<float*>(p->y), p->ldy, 0, p->style, nullptr, p->ld_style, p->gcol0, p->prec16}, o1{};
+      STTS_TRY(ln_launch(st, dw, ld_dw, C, R, row_utt, 1e-6f, 1, 1, o0, o1, ACT_NONE, LnIn{}, nullptr));
+    }
+  }
+  STTS_HIP(hipGetLastError());
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
+int stts_op_grn(void* stream, const stts_grn_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p, "op_grn: null argument");
+  STTS_TRY(norm_op_offsets(st, "op_grn", p->n_utt, p->seg_off_host, p->seg_off_dev));
+  Seg s{p->n_utt, p->seg_off_host, p->seg_off_dev};
+  const int C = p->C, n_utt = p->n_utt;
+  STTS_CHECK(C > 0 && p->part && p->gx && p->mode >= 0 && p->mode <= 2, "op_grn: null argument, or mode outside 0 - 2");
+  STTS_CHECK(p->ld_ss >= C && p->ss_stride >= ceil_div(s.max_len(), 32) && (long)n_utt * p->ss_stride * p->ld_ss <= p->part_elems,
+             "op_grn: part needs ld_ss >= C, ss_stride >= ceil(max_len / 32) and n_utt * ss_stride * ld_ss elements");
+  STTS_CHECK(p->ld_gx >= C && (long)n_utt * p->ld_gx <= p->gx_elems, "op_grn: gx needs ld_gx >= C and n_utt * ld_gx elements");
+  if (p->mode == 1) {
+    STTS_CHECK(p->gamma && p->gamma_elems >= C && p->xaff && p->ld_xaff >= C && (long)n_utt * 2 * p->ld_xaff <= p->xaff_elems, "op_grn: xaff needs gamma [C], ld_xaff >= C and n_utt * 2 * ld_xaff elements");
+  } else if (p->mode == 2) {
+    STTS_CHECK(p->prec == PREC_F32 || p->prec == PREC_BF16 || p->prec == PREC_F16, "op_grn: prec is STTS_PREC_F32, _BF16 or _F16");
+    STTS_CHECK(p->kc == C && C % 4 == 0 && p->ld_gx % 4 == 0, "op_grn: scale_weight_kernel averages gx over kc columns, four at a time: kc == C, C %% 4 == 0, ld_gx %% 4 == 0");
+    STTS_CHECK(p->gamma && p->gamma_elems >= C && p->w && p->wu && p->npad > 0 && (long)p->npad * p->kc <= p->w_elems && (long)n_utt * p->npad * p->kc <= p->wu_elems,
+               "op_grn: scale_weight needs gamma [kc], w [npad][kc] and wu [n_utt][npad][kc]");
+  }
+  hipLaunchKernelGGL(grn_gx_kernel, dim3(ceil_div(C, 32), n_utt), dim3(256), 0, st, p->part, p->ld_ss, p->ss_stride, s.dev, C, p->gx, p->ld_gx);
+  if (p->mode == 1) hipLaunchKernelGGL(grn_xaff_kernel, dim3(n_utt), dim3(256), 0, st, (const float*)p->gx, p->ld_gx, p->gamma, p->xaff, p->ld_xaff, C);
+  else if (p->mode == 2) launch_scale_weight(st, dim3(128, n_utt), p->prec, p->w, p->gx, p->ld_gx, p->gamma, p->wu, p->npad, p->kc);
+  STTS_HIP(hipGetLastError());
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
+}  // extern "C"
+
 // ------------------------------------------------------------------------------------------------ kernel microbench
 // Times `iters` back-to-back launches of conv_gemm_f32 on synthetic data (tuning aid for tools/gemm_bench.py).
 extern "C" int stts_bench_gemm(void* stream, int n_utt, int rows_per_utt, int cin, int cout, int k, int tile, int iters, double* avg_ms, int tune) {

@@ -298,6 +298,63 @@ class HipModel:
             a.stat, a.stat_elems, a.stat_nchunk, a.ld_stat = _ptr(stat), stat.numel(), stat.shape[1], stat.shape[3]
         _lib.check(self.lib.stts_op_conv1d_epi(_stream(), C.byref(a)))
 
+    # ------------------------------------------------------------------ the kernels between the contractions (test surface)
+    @staticmethod
+    def _fill_args(a, seg: Optional[Segments], fields: dict, keep: list):
+        """Fill an args struct of include/stylish_hip.h by field name: a CUDA tensor sets the pointer and, where the struct has one, `<name>_elems`;
+        a numpy array (the *_host fields) is passed as contiguous fp32; everything else is assigned as it is.  Nothing is allocated or cleared."""
+        if seg is not None:
+            a.seg_off_host, a.seg_off_dev, a.n_utt = seg.host_ptr, _ptr(seg.dev), seg.n
+        names = {n for n, _ in a._fields_}
+        for k, v in fields.items():
+            if v is None:
+                continue
+            if isinstance(v, torch.Tensor):
+                assert v.is_cuda and v.is_contiguous(), k
+                setattr(a, k, _ptr(v))
+                if k + "_elems" in names:
+                    setattr(a, k + "_elems", v.numel())
+            elif isinstance(v, np.ndarray):
+                v = np.ascontiguousarray(v, np.float32)
+                keep.append(v)
+                setattr(a, k, v.ctypes.data_as(C.c_void_p))
+            else:
+                setattr(a, k, v)
+        return a
+
+    def op_adain(self, seg: Segments, **fields):
+        """stts_op_adain (fields of stts_adain_args by name): chunk statistics -> merge -> apply of AdaIN, into the caller's tensors."""
+        keep = []
+        a = self._fill_args(_lib.AdainArgs(), seg, fields, keep)
+        _lib.check(self.lib.stts_op_adain(_stream(), C.byref(a)))
+
+    def op_wino_stat(self, seg: Segments, **fields):
+        """stts_op_wino_stat (fields of stts_wino_stat_args): the Winograd-form conv with the statistics its output transform leaves."""
+        keep = []
+        a = self._fill_args(_lib.WinoStatArgs(), seg, fields, keep)
+        _lib.check(self.lib.stts_op_wino_stat(_stream(), C.byref(a)))
+
+    def op_row_layernorm(self, seg: Optional[Segments], outs, **fields):
+        """stts_op_row_layernorm (fields of stts_row_layernorm_args; outs: one or two dicts of stts_ln_out fields)."""
+        keep = []
+        a = self._fill_args(_lib.RowLayerNormArgs(), seg, fields, keep)
+        a.nout = len(outs)
+        for i, o in enumerate(outs):
+            self._fill_args(a.out[i], None, o, keep)
+        _lib.check(self.lib.stts_op_row_layernorm(_stream(), C.byref(a)))
+
+    def op_dwconv(self, seg: Segments, **fields):
+        """stts_op_dwconv (fields of stts_dwconv_args): depthwise conv, alone or with the adaptive LayerNorm (fused / two launches)."""
+        keep = []
+        a = self._fill_args(_lib.DwconvArgs(), seg, fields, keep)
+        _lib.check(self.lib.stts_op_dwconv(_stream(), C.byref(a)))
+
+    def op_grn(self, seg: Segments, **fields):
+        """stts_op_grn (fields of stts_grn_args): GRN factor from a slot table, then the input-affine table or the scaled weight copies."""
+        keep = []
+        a = self._fill_args(_lib.GrnArgs(), seg, fields, keep)
+        _lib.check(self.lib.stts_op_grn(_stream(), C.byref(a)))
+
     def op_adain_block(self, prefix: str, seg: Segments, x, cin, cout, style):
         y = self._f32(seg.rows, cout)
         ws = self.workspace(seg)

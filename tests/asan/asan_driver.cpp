@@ -515,6 +515,100 @@ static void epi_section() {
   epi_case("refuse_overflow", 1, 19, lens, caps, {{64, 1, 1}}, 256, 256, 0, 0, 0, 0, 0, false, 0);
 }
 
+// stts_op_adain / _wino_stat / _row_layernorm / _dwconv / _grn (the kernels between the contractions, tests/test_hip_norm_kernels.py): per operator one call
+// that goes through and one that is refused before anything is launched (a buffer one element short, or a shape outside the kernel's domain).
+// `normtrace <case> : [error ]<trace>`.
+template <typename Call>
+static void norm_case(const char* what, Call call) {
+  stts_stub_trace_begin();
+  const int rc = call();
+  const char* trace = stts_stub_trace_end();
+  printf("normtrace %s : %s%s\n", what, rc ? "error " : "", trace);
+}
+
+static void norm_section() {
+  const int n = 3;
+  const std::vector<int32_t> off = {0, 130, 130, 171};  // (an utterance of zero rows in the middle)
+  const long R = off[n];
+  for (int refuse = 0; refuse < 2; ++refuse) {
+    const char* tag = refuse ? "refuse_" : "";
+    auto name = [&](const char* s) { return std::string(tag) + s; };
+    {  // producer 2 + the apply through run_adain; refused: the chunk table one element short
+      const int C = 130, ldx = 160, ldp = 160, nchunk = 2, ksplit = 3, ld_part = 104, Nf = 100;
+      auto x = buf(R * ldx), part = buf((size_t)n * nchunk * 2 * ldp - refuse), partial = buf((size_t)ksplit * R * ld_part), bias = buf(Nf), r = buf(R * 136), gb = buf(n * 2 * C),
+           snake = buf(C), y = buf(R * 192);
+      stts_adain_args a;
+      memset(&a, 0, sizeof(a));
+      a.seg_off_host = a.seg_off_dev = off.data();
+      a.n_utt = n; a.producer = 2; a.consumer = 3; a.C = C; a.ldx = ldx; a.ldp = ldp; a.nchunk = nchunk;
+      a.x = x.data(); a.x_elems = (int64_t)x.size(); a.part = part.data(); a.part_elems = (int64_t)part.size();
+      a.partial = partial.data(); a.partial_elems = (int64_t)partial.size(); a.ksplit = ksplit; a.slice_rows = (int)R; a.ld_part = ld_part; a.split_n = Nf;
+      a.bias = bias.data(); a.bias_elems = Nf; a.split_act = 4; a.r = r.data(); a.r_elems = (int64_t)r.size(); a.ldr = 136; a.rcol0 = 8; a.split_alpha = 0.5f;
+      a.gb = gb.data(); a.gb_elems = (int64_t)gb.size(); a.ld_gb = 2 * C; a.snake = snake.data(); a.snake_elems = C;
+      a.y = y.data(); a.y_elems = (int64_t)y.size(); a.ldy = 192; a.rb = 256; a.out16 = 0;
+      norm_case(name("adain_reduce_apply").c_str(), [&] { return stts_op_adain(nullptr, &a); });
+      // the 24-row chunking with the 16-lane merge; refused: an affine table narrower than C
+      auto aff = buf((size_t)n * 2 * ldx);
+      a.producer = 1; a.consumer = 2; a.nchunk = 6; part = buf((size_t)n * 6 * 2 * ldp); a.part = part.data(); a.part_elems = (int64_t)part.size();
+      a.aff = aff.data(); a.aff_elems = (int64_t)aff.size(); a.ld_aff = refuse ? C - 2 : ldx;
+      norm_case(name("adain_lanes24").c_str(), [&] { return stts_op_adain(nullptr, &a); });
+    }
+    {  // refused: a statistics table with the wrong chunk count
+      const int cin = 64, cout = 132, ldy = 160, ld_stat = 136, nchunk = 6;
+      auto x = buf(R * cin), w = buf((size_t)cout * cin * 3), b = buf(cout), y = buf(R * ldy), stat = buf((size_t)n * nchunk * 2 * ld_stat);
+      stts_wino_stat_args a;
+      memset(&a, 0, sizeof(a));
+      a.seg_off_host = a.seg_off_dev = off.data();
+      a.n_utt = n; a.x = x.data(); a.x_elems = (int64_t)x.size(); a.ldx = cin; a.cin = cin; a.w_host = w.data(); a.bias_host = b.data(); a.cout = cout; a.k = 3;
+      a.y = y.data(); a.y_elems = (int64_t)y.size(); a.ldy = ldy; a.stat = stat.data(); a.stat_elems = (int64_t)stat.size(); a.ld_stat = ld_stat; a.stat_nchunk = nchunk - refuse;
+      norm_case(name("wino_stat").c_str(), [&] { return stts_op_wino_stat(nullptr, &a); });
+    }
+    {  // adaptive, two outputs (the second 16-bit in a window), LnIn, a device-side row count; refused: C not a multiple of 4
+      const int C = refuse ? 130 : 260, ksplit = 3, ld_part = 264;
+      auto partial = buf((size_t)ksplit * (R + 2) * ld_part), bias = buf(C), r = buf(R * 272), sty = buf((size_t)n * (4 * C + 8)), y0 = buf(R * (C + 8));
+      std::vector<uint16_t> y1(R * (C + 40), 0);
+      stts_row_layernorm_args a;
+      memset(&a, 0, sizeof(a));
+      a.seg_off_host = a.seg_off_dev = off.data();
+      a.n_utt = n; a.n_rows = (int)R; a.n_rows_real = (int)R - 3; a.C = C; a.adaptive = 1; a.nout = 2; a.act = 3; a.eps = 1e-5f;
+      a.partial = partial.data(); a.partial_elems = (int64_t)partial.size(); a.ksplit = ksplit; a.slice_rows = (int)R + 2; a.ld_part = ld_part;
+      a.bias = bias.data(); a.bias_elems = C; a.in_act = 4; a.r = r.data(); a.r_elems = (int64_t)r.size(); a.ldr = 272; a.rcol0 = 4; a.in_alpha = 0.5f;
+      a.out[0].y = y0.data(); a.out[0].y_elems = (int64_t)y0.size(); a.out[0].ldy = C + 8; a.out[0].g = sty.data(); a.out[0].g_elems = (int64_t)sty.size();
+      a.out[0].ld_g = 4 * C + 8; a.out[0].gcol0 = 4;
+      a.out[1] = a.out[0];
+      a.out[1].y = y1.data(); a.out[1].y_elems = (int64_t)y1.size(); a.out[1].ldy = C + 40; a.out[1].ycol0 = 32; a.out[1].gcol0 = 4 + 2 * C; a.out[1].prec16 = 1;
+      norm_case(name("row_layernorm").c_str(), [&] { return stts_op_row_layernorm(nullptr, &a); });
+    }
+    for (int form = 0; form < 3; ++form) {  // refused: K = 5 in the fused form, C above 512 there, an output one element short elsewhere
+      const int C = (refuse && form == 1) ? 516 : 260, K = 15;
+      auto x = buf(R * (C + 4)), w = buf((size_t)C * K), b = buf(C), sty = buf((size_t)n * (2 * C + 8)), y = buf(R * (C + 4) - ((refuse && form != 1) ? 5 : 0));
+      stts_dwconv_args a;
+      memset(&a, 0, sizeof(a));
+      a.seg_off_host = a.seg_off_dev = off.data();
+      a.n_utt = n; a.form = form; a.C = C; a.K = K; a.x = x.data(); a.x_elems = (int64_t)x.size(); a.ldx = C + 4; a.w_host = w.data(); a.bias_host = b.data();
+      a.style = sty.data(); a.style_elems = (int64_t)sty.size(); a.ld_style = 2 * C + 8; a.gcol0 = 4; a.y = y.data(); a.y_elems = (int64_t)y.size(); a.ldy = C + 4;
+      a.act = form == 0 ? 1 : 0;
+      norm_case((name("dwconv_form") + std::to_string(form)).c_str(), [&] { return stts_op_dwconv(nullptr, &a); });
+      if (refuse && form == 1) {
+        a.C = 260; a.K = 5;
+        norm_case("refuse_dwconv_form1_k5", [&] { return stts_op_dwconv(nullptr, &a); });
+      }
+    }
+    for (int mode = 1; mode < 3; ++mode) {  // refused: a slot table with too few slots per utterance; scaled weights with kc != C
+      const int C = 132, ld = 160, ss = 5, npad = 8;
+      auto part = buf((size_t)n * ss * ld), gamma = buf(C), gx = buf((size_t)n * ld), xaff = buf((size_t)n * 2 * ld), w = buf((size_t)npad * C), wu = buf((size_t)n * npad * C);
+      stts_grn_args a;
+      memset(&a, 0, sizeof(a));
+      a.seg_off_host = a.seg_off_dev = off.data();
+      a.n_utt = n; a.mode = mode; a.C = C; a.part = part.data(); a.part_elems = (int64_t)part.size(); a.ld_ss = ld; a.ss_stride = (refuse && mode == 1) ? ss - 1 : ss;
+      a.gamma = gamma.data(); a.gamma_elems = C; a.gx = gx.data(); a.gx_elems = (int64_t)gx.size(); a.ld_gx = ld;
+      a.xaff = xaff.data(); a.xaff_elems = (int64_t)xaff.size(); a.ld_xaff = ld;
+      a.w = w.data(); a.w_elems = (int64_t)w.size(); a.wu = wu.data(); a.wu_elems = (int64_t)wu.size(); a.npad = npad; a.kc = (refuse && mode == 2) ? C - 4 : C; a.prec = 1;
+      norm_case((name("grn_mode") + std::to_string(mode)).c_str(), [&] { return stts_op_grn(nullptr, &a); });
+    }
+  }
+}
+
 struct Tensor {
   std::string name;
   int ndim;
@@ -578,6 +672,7 @@ int main(int argc, char** argv) {
   gemm_section();
   if (argc > 2 && strcmp(argv[2], "gemm") == 0) return 0;
   epi_section();
+  norm_section();
   Dims dims;
   std::vector<Tensor> w;
   if (read_weights(argv[1], dims, w)) return 2;
