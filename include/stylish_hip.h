@@ -696,6 +696,36 @@ typedef struct stts_grn_args {
   int32_t n_utt, mode, C, ld_ss, ss_stride, ld_gx, ld_xaff, npad, kc, prec;
 } stts_grn_args;
 int stts_op_grn(void* stream, const stts_grn_args* args);
+/* The 2-D implicit-GEMM convolution (csrc/conv2d.hip.h; tests/test_hip_conv2d.py): conv2d_pack of w_host [cout][cin0 + cin1][ntap] (bias_host [cout] or
+ * null) at width npad (16 / 32 / a multiple of 64: the tile), then one conv2d_launch.  Channels-last packed rows: x0 [((off_in[u] >> sh) + t) * Fin + f][ld0],
+ * x1 the same with ld1 (null when ld1 == 0); base grid of (off_out[u + 1] - off_out[u]) >> sh rows of F columns per utterance; tap i of base position
+ * (t, f) reads input position (t + dt[i], f + df[i]), zeros outside the utterance's [0, T_u) x [0, Fin); the result goes to row
+ * (t' * up + pt) * (F * up) + f * up + pf of y [.][ldy] (t' the base time row within the batch), columns cout .. ldy - 1 written as 0:
+ *   y = (act(sum + bias) + r) / div, act 0 none, 1 ReLU, 2 sigmoid; r [output rows][ldy] or null; lrelu 1: LeakyReLU(0.2) on the operand (npad % 64 == 0).
+ * K = ntap * (ld0 + ld1) is summed in chains of `chunk` (a multiple of 16); sliced 0: the chunk sums are added in the kernel, 1: one chunk per grid slice
+ * into a scratch the operator allocates, added by conv2d_reduce_kernel (the launch has slices only when there is more than one chunk).
+ * Refused before anything is launched: whatever conv2d_pack / conv2d_launch refuse (row strides not multiples of 16, cout > ldy, ldy > npad, ...),
+ * offsets that decrease, differ between host and device or are no multiples of 1 << sh, up outside {1, 2}, pt / pf outside [0, up), ntap > 25, and
+ * every buffer shorter than the rows a launch can reach: (off_in[n_utt] >> sh) * Fin * ld for x0 / x1, (largest output row + 1) * ldy for y and r. */
+typedef struct stts_conv2d_args {
+  const float* w_host;
+  const float* bias_host;
+  const int32_t* off_in_host;
+  const int32_t* off_in_dev;
+  const int32_t* off_out_host;
+  const int32_t* off_out_dev;
+  const float* x0;
+  const float* x1;
+  const float* r;
+  float* y;
+  int64_t x0_elems, x1_elems, r_elems, y_elems;
+  int32_t dt[25], df[25];
+  int32_t ntap, cout, cin0, cin1, ld0, ld1, npad, lrelu, chunk, sliced;
+  int32_t n_utt, sh, Fin, F, up, pt, pf, act;
+  float div;
+  int32_t ldy;
+} stts_conv2d_args;
+int stts_op_conv2d(void* stream, const stts_conv2d_args* args);
 /* AdaptiveDecoderBlock.forward (models/ada_norm.py:166-182) with weights named `prefix` + reference keys. */
 int stts_op_adain_block(stts_ctx* ctx, void* stream, const char* prefix, int n_utt, const int32_t* seg_off_host,
                         const int32_t* seg_off_dev, const float* x, int ldx, int cin, int cout, const float* style, float* y, int ldy,

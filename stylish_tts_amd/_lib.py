@@ -112,6 +112,13 @@ class GrnArgs(C.Structure):
                        (_I32, "n_utt mode C ld_ss ss_stride ld_gx ld_xaff npad kc prec"))
 
 
+class Conv2dArgs(C.Structure):
+    """include/stylish_hip.h: stts_conv2d_args (test surface)."""
+    _fields_ = (_fields((_P, "w_host bias_host off_in_host off_in_dev off_out_host off_out_dev x0 x1 r y"), (_I64, "x0_elems x1_elems r_elems y_elems"))
+                + [("dt", _I32 * 25), ("df", _I32 * 25)]
+                + _fields((_I32, "ntap cout cin0 cin1 ld0 ld1 npad lrelu chunk sliced n_utt sh Fin F up pt pf act"), (_F, "div"), (_I32, "ldy")))
+
+
 # name -> (restype, argtypes); mirrors include/stylish_hip.h one to one
 SIGNATURES = {
     "stts_last_error": (C.c_char_p, []),
@@ -206,6 +213,7 @@ TEST_SIGNATURES = {
     "stts_op_row_layernorm": (_I, [_P, C.POINTER(RowLayerNormArgs)]),
     "stts_op_dwconv": (_I, [_P, C.POINTER(DwconvArgs)]),
     "stts_op_grn": (_I, [_P, C.POINTER(GrnArgs)]),
+    "stts_op_conv2d": (_I, [_P, C.POINTER(Conv2dArgs)]),
     "stts_op_adain_block": (_I, [_P, _P, C.c_char_p, _I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _SZ]),
     "stts_op_attention": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I]),
     "stts_op_stft_geom": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I]),

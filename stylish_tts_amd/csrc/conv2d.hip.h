@@ -13,6 +13,10 @@
 // order, either in the kernel (a second accumulator) or, when the launch has slices, one chunk per grid z with conv2d_reduce_kernel adding the slices
 // in the same order.  Then bias, activation, + residual, / div.  Nothing depends on the batch: an utterance's result is the same bits alone and in any
 // batch.
+//
+// Domain (conv2d_pack and conv2d_launch refuse the rest): ld0, ld1 multiples of kConvBK = 16 (a K step never straddles a tap or a segment), npad 16, 32 or
+// a multiple of 64, N <= ldy <= npad (both summation paths then write channels 0 .. N - 1 and zeros up to ldy), chunk a multiple of 16, offsets
+// multiples of 1 << sh.  tests/test_hip_conv2d.py holds every tile, both summation paths and every row map to float64 through stts_op_conv2d.
 #pragma once
 
 namespace stts {
@@ -248,9 +252,11 @@ inline int conv2d_pack(stts_ctx* c, int cout, int npad, int cin0, int cin1, int 
   o->ntap = ntap;
   o->npad = npad;
   o->K = ntap * (ld0 + ld1);
-  STTS_CHECK(o->K % kConvBK == 0 && ld0 % 4 == 0 && ld1 % 4 == 0 && cin0 <= ld0 && cin1 <= ld1 && ntap >= 1 && ntap <= kConvMaxTaps && cout <= npad &&
-                 (npad == 16 || npad == 32 || npad % 64 == 0),
-             "conv2d: a conv of %d x (%d + %d) -> %d (padded to %d) does not pack", ntap, ld0, ld1, cout, npad);
+  // a K step is one tap and kConvBK channels of ONE segment, so each segment's row stride is a whole number of steps (and a row a whole number of float4)
+  STTS_CHECK(ld0 > 0 && ld0 % kConvBK == 0 && ld1 >= 0 && ld1 % kConvBK == 0 && cin0 >= 0 && cin0 <= ld0 && cin1 >= 0 && cin1 <= ld1 && ntap >= 1 && ntap <= kConvMaxTaps &&
+                 cout >= 1 && cout <= npad && (npad == 16 || npad == 32 || (npad > 0 && npad % 64 == 0)),
+             "conv2d: a conv of %d x (%d + %d) -> %d (padded to %d) does not pack: row strides are multiples of %d, the width is 16, 32 or a multiple of 64", ntap, ld0, ld1, cout,
+             npad, kConvBK);
   for (int i = 0; i < ntap; ++i) {
     o->dt[i] = dt[i];
     o->df[i] = df[i];
@@ -297,6 +303,8 @@ inline int conv2d_launch(hipStream_t st, const Conv2dArgs& g, bool lrelu, int sl
   STTS_CHECK(slices == 1 ? !g.P : g.P && slices == ceil_div(g.K, g.chunk), "conv2d: %d slices without their scratch", slices);
   STTS_CHECK(g.ld1 == 0 || g.X1, "conv2d: a two-segment conv without its second input");
   STTS_CHECK(g.chunk > 0 && g.chunk % kConvBK == 0 && (!lrelu || g.npad % 64 == 0), "conv2d: chunk %d, npad %d%s", g.chunk, g.npad, lrelu ? " (LeakyReLU operand)" : "");
+  // the tiles cover columns 0 .. npad - 1 and write those below ldy, so a row of Y is written whole (channels, then zeros) only when it is no wider than npad
+  STTS_CHECK(g.N >= 1 && g.N <= g.ldy && g.ldy <= g.npad, "conv2d: %d channels into rows of %d floats from tiles %d wide (N <= ldy <= npad)", g.N, g.ldy, g.npad);
   if (g.rows == 0) return 0;
 #define STTS_CONV2D(MT, NT, WM, WN, LRELU)                                                                                                                       \
   hipLaunchKernelGGL((conv2d_kernel<MT, NT, WM, WN, LRELU>), dim3((unsigned)((g.rows + 16 * MT * WM - 1) / (16 * MT * WM)), g.npad / (16 * NT * WN), slices), \

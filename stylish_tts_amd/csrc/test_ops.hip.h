@@ -631,6 +631,72 @@ int stts_op_grn(void* stream, const stts_grn_args* p) {
   API_END
 }
 
+// conv2d_kernel's four instances and conv2d_reduce_kernel through conv2d_pack and conv2d_launch (csrc/conv2d.hip.h; tests/test_hip_conv2d.py).  The extents
+// are the kernel's: the load reads input time rows below offIn[n_utt] >> sh only (ti < T_u), conv2d_row forms output rows up to that of the last base position.
+int stts_op_conv2d(void* stream, const stts_conv2d_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p, "op_conv2d: null argument");
+  STTS_TRY(norm_op_offsets(st, "op_conv2d (input level)", p->n_utt, p->off_in_host, p->off_in_dev));
+  STTS_TRY(norm_op_offsets(st, "op_conv2d (base grid)", p->n_utt, p->off_out_host, p->off_out_dev));
+  const int n_utt = p->n_utt, sh = p->sh, up = p->up;
+  STTS_CHECK(sh >= 0 && sh <= 16, "op_conv2d: level shift %d", sh);
+  for (int u = 0; u <= n_utt; ++u)
+    STTS_CHECK(p->off_in_host[u] % (1 << sh) == 0 && p->off_out_host[u] % (1 << sh) == 0, "op_conv2d: the offsets of utterance %d are no multiples of %d", u, 1 << sh);
+  STTS_CHECK((up == 1 || up == 2) && p->pt >= 0 && p->pt < up && p->pf >= 0 && p->pf < up, "op_conv2d: up %d (1 or 2), pt %d, pf %d (below up)", up, p->pt, p->pf);
+  STTS_CHECK(p->ntap >= 1 && p->ntap <= kConvMaxTaps, "op_conv2d: %d taps (1 .. %d)", p->ntap, kConvMaxTaps);
+  STTS_CHECK(p->w_host && p->x0 && p->y && p->cout >= 1 && p->cin0 >= 1 && p->cin1 >= 0 && p->ld0 >= 1 && p->ld1 >= 0 && p->Fin >= 1 && p->F >= 1 && p->ldy >= 1 && p->chunk >= 1,
+             "op_conv2d: null / empty argument");
+  STTS_CHECK(p->act >= CONV_ACT_NONE && p->act <= CONV_ACT_SIGMOID && p->div != 0.f, "op_conv2d: act 0 - 2, div not 0");
+  const long Tin = p->off_in_host[n_utt] >> sh, Tb = p->off_out_host[n_utt] >> sh, rows = Tb * p->F;
+  const long orows = rows == 0 ? 0 : ((Tb - 1) * up + p->pt) * ((long)p->F * up) + (long)(p->F - 1) * up + p->pf + 1;  // the largest orow of conv2d_row, + 1
+  STTS_CHECK(Tin * p->Fin * p->ld0 <= p->x0_elems && (uintptr_t)p->x0 % 16 == 0, "op_conv2d: x0 [%ld rows][%d] (16-byte aligned) outside its %ld elements", Tin * p->Fin, p->ld0,
+             (long)p->x0_elems);
+  if (p->ld1 > 0)
+    STTS_CHECK(p->x1 && Tin * p->Fin * p->ld1 <= p->x1_elems && (uintptr_t)p->x1 % 16 == 0, "op_conv2d: x1 [%ld rows][%d] (16-byte aligned) outside its %ld elements", Tin * p->Fin,
+               p->ld1, (long)p->x1_elems);
+  STTS_CHECK(orows * p->ldy <= p->y_elems, "op_conv2d: y [%ld rows][%d] outside its %ld elements", orows, p->ldy, (long)p->y_elems);
+  STTS_CHECK(!p->r || orows * p->ldy <= p->r_elems, "op_conv2d: r [%ld rows][%d] outside its %ld elements", orows, p->ldy, (long)p->r_elems);
+  NormOpTemps t(st);
+  stts_ctx& tmp = t.tmp;
+  PackScope scope(&tmp, engine_mode(&tmp));
+  const int cin = p->cin0 + p->cin1, ntap = p->ntap;
+  std::vector<double> bias;
+  if (p->bias_host) bias.assign(p->bias_host, p->bias_host + p->cout);
+  Conv2dW w;
+  STTS_TRY(conv2d_pack(&tmp, p->cout, p->npad, p->cin0, p->cin1, p->ld0, p->ld1, ntap, p->dt, p->df,
+                       [&](int n, int ci, int tap) { return (double)p->w_host[((size_t)n * cin + ci) * ntap + tap]; }, p->bias_host ? &bias : nullptr, &w));
+  Conv2dArgs g = conv2d_args(w);
+  g.X0 = p->x0;
+  g.X1 = p->ld1 > 0 ? p->x1 : nullptr;
+  g.offIn = p->off_in_dev;
+  g.offOut = p->off_out_dev;
+  g.n_utt = n_utt;
+  g.sh = sh;
+  g.Fin = p->Fin;
+  g.F = p->F;
+  g.up = up;
+  g.pt = p->pt;
+  g.pf = p->pf;
+  g.rows = rows;
+  g.chunk = p->chunk;
+  g.act = p->act;
+  g.R = p->r;
+  g.div = p->div;
+  g.Y = p->y;
+  g.ldy = p->ldy;
+  const int slices = p->sliced ? ceil_div(w.K, p->chunk) : 1;
+  if (slices > 1 && rows > 0) {
+    STTS_HIP(hipMalloc(&g.P, (size_t)slices * rows * p->ldy * sizeof(float)));
+    tmp.allocs.push_back(g.P);
+  }
+  STTS_TRY(conv2d_launch(st, g, p->lrelu != 0, g.P ? slices : 1));
+  STTS_HIP(hipGetLastError());
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ kernel microbench

@@ -355,6 +355,18 @@ class HipModel:
         a = self._fill_args(_lib.GrnArgs(), seg, fields, keep)
         _lib.check(self.lib.stts_op_grn(_stream(), C.byref(a)))
 
+    def op_conv2d(self, seg_in: Segments, seg_out: Segments, dt, df, **fields):
+        """stts_op_conv2d (fields of stts_conv2d_args): the 2-D implicit-GEMM convolution, one launch; seg_in / seg_out: the offsets of the input level and of
+        the base grid (used >> sh), dt / df: the taps."""
+        assert seg_in.n == seg_out.n and len(dt) == len(df) <= 25
+        keep = []
+        a = self._fill_args(_lib.Conv2dArgs(), None, fields, keep)
+        a.off_in_host, a.off_in_dev, a.off_out_host, a.off_out_dev, a.n_utt = seg_in.host_ptr, _ptr(seg_in.dev), seg_out.host_ptr, _ptr(seg_out.dev), seg_in.n
+        a.ntap = len(dt)
+        for i, (t, f) in enumerate(zip(dt, df)):
+            a.dt[i], a.df[i] = int(t), int(f)
+        _lib.check(self.lib.stts_op_conv2d(_stream(), C.byref(a)))
+
     def op_adain_block(self, prefix: str, seg: Segments, x, cin, cout, style):
         y = self._f32(seg.rows, cout)
         ws = self.workspace(seg)

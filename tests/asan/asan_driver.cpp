@@ -515,7 +515,8 @@ static void epi_section() {
   epi_case("refuse_overflow", 1, 19, lens, caps, {{64, 1, 1}}, 256, 256, 0, 0, 0, 0, 0, false, 0);
 }
 
-// stts_op_adain / _wino_stat / _row_layernorm / _dwconv / _grn (the kernels between the contractions, tests/test_hip_norm_kernels.py): per operator one call
+// stts_op_adain / _wino_stat / _row_layernorm / _dwconv / _grn (the kernels between the contractions, tests/test_hip_norm_kernels.py) and stts_op_conv2d (the 2-D
+// convolution, tests/test_hip_conv2d.py): per operator one call
 // that goes through and one that is refused before anything is launched (a buffer one element short, or a shape outside the kernel's domain).
 // `normtrace <case> : [error ]<trace>`.
 template <typename Call>
@@ -605,6 +606,20 @@ static void norm_section() {
       a.xaff = xaff.data(); a.xaff_elems = (int64_t)xaff.size(); a.ld_xaff = ld;
       a.w = w.data(); a.w_elems = (int64_t)w.size(); a.wu = wu.data(); a.wu_elems = (int64_t)wu.size(); a.npad = npad; a.kc = (refuse && mode == 2) ? C - 4 : C; a.prec = 1;
       norm_case((name("grn_mode") + std::to_string(mode)).c_str(), [&] { return stts_op_grn(nullptr, &a); });
+    }
+    {  // stts_op_conv2d: 3 x 3 on 171 x 4 positions, two segments, three grid slices and the reduce; refused: a row stride that is no multiple of 16
+      const int F = 4, cin0 = 5, cin1 = 20, ld0 = refuse ? 8 : 16, ld1 = 32, cout = 33, ldy = 48;
+      auto x0 = buf(R * F * ld0), x1 = buf(R * F * ld1), w = buf((size_t)cout * (cin0 + cin1) * 9), b = buf(cout), r = buf(R * F * ldy), y = buf(R * F * ldy);
+      stts_conv2d_args a;
+      memset(&a, 0, sizeof(a));
+      a.off_in_host = a.off_in_dev = a.off_out_host = a.off_out_dev = off.data();
+      a.n_utt = n; a.w_host = w.data(); a.bias_host = b.data(); a.x0 = x0.data(); a.x0_elems = (int64_t)x0.size(); a.x1 = x1.data(); a.x1_elems = (int64_t)x1.size();
+      a.r = r.data(); a.r_elems = (int64_t)r.size(); a.y = y.data(); a.y_elems = (int64_t)y.size(); a.ldy = ldy;
+      a.ntap = 9;
+      for (int i = 0; i < 9; ++i) { a.dt[i] = i / 3 - 1; a.df[i] = i % 3 - 1; }
+      a.cout = cout; a.cin0 = cin0; a.cin1 = cin1; a.ld0 = ld0; a.ld1 = ld1; a.npad = 64; a.lrelu = 1; a.chunk = 192; a.sliced = 1;
+      a.Fin = a.F = F; a.up = 1; a.act = 1; a.div = 1.5f;
+      norm_case(name("conv2d_sliced").c_str(), [&] { return stts_op_conv2d(nullptr, &a); });
     }
   }
 }

@@ -147,12 +147,12 @@ def test_host_side_under_asan_ubsan(tmp_path):
     assert not any(epi[k].startswith("error") for k in ("two_segments", "capacity", "windows_tile15")), epi
     refused = [k for k in epi if k.startswith("refuse_")]
     assert len(refused) == 6 and all(epi[k].strip() == "error" for k in refused), epi
-    # the operators of the kernels between the contractions (asan_driver.cpp norm_section): each accepted call launches the kernels it names, each refused one NOTHING
+    # the operators of the kernels between the contractions and of the 2-D convolution (asan_driver.cpp norm_section): each accepted call launches the kernels it names, each refused one NOTHING
     norm = dict(re.findall(r"^normtrace (\S+) : (.*)$", r.stdout, re.M))
     accepted = {"adain_reduce_apply": ("adain_partial_reduce_kernel", "adain_apply_kernel"), "adain_lanes24": ("adain_partial_kernel", "adain_affine_lanes_kernel"),
                 "wino_stat": ("winograd_output_kernel<8, true>",), "row_layernorm": ("row_utt_kernel", "row_layernorm_kernel"), "dwconv_form0": ("dwconv_kernel<31>",),
                 "dwconv_form1": ("dwconv_ln_kernel<15, 16>",), "dwconv_form2": ("dwconv_kernel<31>", "row_layernorm_kernel"), "grn_mode1": ("grn_gx_kernel", "grn_xaff_kernel"),
-                "grn_mode2": ("grn_gx_kernel", "scale_weight_kernel<1>")}
+                "grn_mode2": ("grn_gx_kernel", "scale_weight_kernel<1>"), "conv2d_sliced": ("conv2d_kernel<2, 2, 2, 2, true>", "(11,1,3)", "conv2d_reduce_kernel")}
     for case, kernels in accepted.items():
         assert not norm[case].startswith("error") and all(k in norm[case] for k in kernels), (case, norm[case])
     refused = [k for k in norm if k.startswith("refuse_")]
