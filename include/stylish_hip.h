@@ -726,6 +726,80 @@ typedef struct stts_conv2d_args {
   int32_t ldy;
 } stts_conv2d_args;
 int stts_op_conv2d(void* stream, const stts_conv2d_args* args);
+/* The flow-matching estimator's row kernels (csrc/cfm.hip.h) and the sequence rotary embedding (csrc/phoneme.hip.h), one launch per call through the launch
+ * helpers the estimator itself uses (tests/test_hip_cfm_kernels.py).  Conventions of the operators above: every tensor caller-owned and on the device,
+ * *_elems the element count of the caller's buffer, refusal before anything is launched, host and device offsets must agree.
+ *
+ * stts_op_cfm_elem   kind 0: mish_kernel in place on x, n float4s;  1: swiglu_kernel, x = A [n rows][2 C] -> y [n rows][C] = silu(A[:, :C]) * A[:, C:];
+ *                    2: gated_residual_kernel, y = x + t * (ada[u][2 C + c] + 1) over packed rows [rows, C], ada [n_utt][3 C].  C % 4 == 0. */
+typedef struct stts_cfm_elem_args {
+  const int32_t* seg_off_host;
+  const int32_t* seg_off_dev;
+  float* x;
+  const float* t;
+  const float* ada;
+  float* y;
+  int64_t x_elems, t_elems, ada_elems, y_elems, n;
+  int32_t n_utt, kind, C;
+} stts_cfm_elem_args;
+int stts_op_cfm_elem(void* stream, const stts_cfm_elem_args* args);
+/* rms_adaln_kernel: y = x' / rms(x') * w * (ada[u][c] + 1) + ada[u][C + c] with x' = x, or (t != null) x' = x + t * (ada_prev[u][2 C + c] + 1); xout (optional)
+ * receives x'.  x [rows, ldx], y [rows, ldy] (y may be x itself with ldy == ldx), t and xout [rows, C], w [C], ada / ada_prev [n_utt][3 C].  C <= 1024. */
+typedef struct stts_rms_adaln_args {
+  const int32_t* seg_off_host;
+  const int32_t* seg_off_dev;
+  const float* x;
+  const float* w;
+  const float* ada;
+  float* y;
+  const float* t;
+  const float* ada_prev;
+  float* xout;
+  int64_t x_elems, w_elems, ada_elems, y_elems, t_elems, ada_prev_elems, xout_elems;
+  int32_t n_utt, C, ldx, ldy;
+} stts_rms_adaln_args;
+int stts_op_rms_adaln(void* stream, const stts_rms_adaln_args* args);
+/* Rotary embeddings in place on the column block [col0, col0 + heads * kc) of x [rows, ldx], and on the block at col1 (-1: none).
+ *   kind 0: axial_rope_kernel, interleaved pairs of whole heads (kc == d), position linspace(-1, 1, n), freq [heads][d / 2];
+ *   kind 1: rope_kernel through run_rope, half-split pairs on the first d = int(kc / 2) features of every head, position = row in the utterance.
+ * d even and <= kc; both blocks inside ldx and apart. */
+typedef struct stts_rope_args {
+  const int32_t* seg_off_host;
+  const int32_t* seg_off_dev;
+  float* x;
+  const float* freq;
+  int64_t x_elems, freq_elems;
+  int32_t n_utt, kind, ldx, col0, col1, heads, kc, d;
+} stts_rope_args;
+int stts_op_rope(void* stream, const stts_rope_args* args);
+/* One row per utterance.  kind 0: small_linear_kernel, y [n_rows, ldy] = act(x [n_rows, ldx] w [N][K]^T + b) (b optional; act 0 none, 1 Mish);
+ *   1: small_layernorm_kernel over N channels (eps 1e-5), w = gamma, b = beta;  2: cfm_time_embed_kernel, x = t [n_rows], w = freqs [N] -> y = cos | sin (ldy >= 2 N). */
+typedef struct stts_cfm_small_args {
+  const float* x;
+  const float* w;
+  const float* b;
+  float* y;
+  int64_t x_elems, w_elems, b_elems, y_elems;
+  int32_t kind, n_rows, N, K, act, ldx, ldy;
+} stts_cfm_small_args;
+int stts_op_cfm_small(void* stream, const stts_cfm_small_args* args);
+/* cfm_source_kernel: har [rows, 32] = (tanh(merge_w * sine source), N resampled to the frames, t[u], 0 ...) from f0 / ncurve packed by the curve offsets and
+ * the SineGenerator's noise draw [rows].  An utterance with frames needs a curve of at least one point; ldh must be 32. */
+typedef struct stts_cfm_source_args {
+  const int32_t* seg_off_host;
+  const int32_t* seg_off_dev;
+  const int32_t* curve_off_host;
+  const int32_t* curve_off_dev;
+  const float* f0;
+  const float* ncurve;
+  const float* t;
+  const float* noise;
+  float* har;
+  int64_t f0_elems, ncurve_elems, t_elems, noise_elems, har_elems;
+  int32_t n_utt, ldh;
+  float merge_w;
+} stts_cfm_source_args;
+int stts_op_cfm_source(void* stream, const stts_cfm_source_args* args);
 /* AdaptiveDecoderBlock.forward (models/ada_norm.py:166-182) with weights named `prefix` + reference keys. */
 int stts_op_adain_block(stts_ctx* ctx, void* stream, const char* prefix, int n_utt, const int32_t* seg_off_host,
                         const int32_t* seg_off_dev, const float* x, int ldx, int cin, int cout, const float* style, float* y, int ldy,

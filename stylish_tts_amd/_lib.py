@@ -119,6 +119,33 @@ class Conv2dArgs(C.Structure):
                 + _fields((_I32, "ntap cout cin0 cin1 ld0 ld1 npad lrelu chunk sliced n_utt sh Fin F up pt pf act"), (_F, "div"), (_I32, "ldy")))
 
 
+class CfmElemArgs(C.Structure):
+    """include/stylish_hip.h: stts_cfm_elem_args (test surface)."""
+    _fields_ = _fields((_P, "seg_off_host seg_off_dev x t ada y"), (_I64, "x_elems t_elems ada_elems y_elems n"), (_I32, "n_utt kind C"))
+
+
+class RmsAdalnArgs(C.Structure):
+    """include/stylish_hip.h: stts_rms_adaln_args (test surface)."""
+    _fields_ = _fields((_P, "seg_off_host seg_off_dev x w ada y t ada_prev xout"), (_I64, "x_elems w_elems ada_elems y_elems t_elems ada_prev_elems xout_elems"),
+                       (_I32, "n_utt C ldx ldy"))
+
+
+class RopeArgs(C.Structure):
+    """include/stylish_hip.h: stts_rope_args (test surface)."""
+    _fields_ = _fields((_P, "seg_off_host seg_off_dev x freq"), (_I64, "x_elems freq_elems"), (_I32, "n_utt kind ldx col0 col1 heads kc d"))
+
+
+class CfmSmallArgs(C.Structure):
+    """include/stylish_hip.h: stts_cfm_small_args (test surface)."""
+    _fields_ = _fields((_P, "x w b y"), (_I64, "x_elems w_elems b_elems y_elems"), (_I32, "kind n_rows N K act ldx ldy"))
+
+
+class CfmSourceArgs(C.Structure):
+    """include/stylish_hip.h: stts_cfm_source_args (test surface)."""
+    _fields_ = _fields((_P, "seg_off_host seg_off_dev curve_off_host curve_off_dev f0 ncurve t noise har"), (_I64, "f0_elems ncurve_elems t_elems noise_elems har_elems"),
+                       (_I32, "n_utt ldh"), (_F, "merge_w"))
+
+
 # name -> (restype, argtypes); mirrors include/stylish_hip.h one to one
 SIGNATURES = {
     "stts_last_error": (C.c_char_p, []),
@@ -214,6 +241,11 @@ TEST_SIGNATURES = {
     "stts_op_dwconv": (_I, [_P, C.POINTER(DwconvArgs)]),
     "stts_op_grn": (_I, [_P, C.POINTER(GrnArgs)]),
     "stts_op_conv2d": (_I, [_P, C.POINTER(Conv2dArgs)]),
+    "stts_op_cfm_elem": (_I, [_P, C.POINTER(CfmElemArgs)]),
+    "stts_op_rms_adaln": (_I, [_P, C.POINTER(RmsAdalnArgs)]),
+    "stts_op_rope": (_I, [_P, C.POINTER(RopeArgs)]),
+    "stts_op_cfm_small": (_I, [_P, C.POINTER(CfmSmallArgs)]),
+    "stts_op_cfm_source": (_I, [_P, C.POINTER(CfmSourceArgs)]),
     "stts_op_adain_block": (_I, [_P, _P, C.c_char_p, _I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _SZ]),
     "stts_op_attention": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I]),
     "stts_op_stft_geom": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I]),

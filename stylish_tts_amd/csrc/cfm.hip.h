@@ -269,6 +269,53 @@ __global__ void __launch_bounds__(256) swiglu_kernel(const float* __restrict__ A
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- launches
+// One helper per kernel above: cfm_estimator and the test operators (test_ops.hip.h, stts_op_cfm_* / _rms_adaln / _rope) launch through these and
+// nothing else, so a test runs the product's grid.  Each returns the grid it launched.
+inline dim3 launch_time_embed(hipStream_t st, const float* t, const float* freqs, int half, float* E, int lde, int n_utt) {
+  const dim3 g(ceil_div(n_utt * half, 256));
+  hipLaunchKernelGGL(cfm_time_embed_kernel, g, dim3(256), 0, st, t, freqs, half, E, lde, n_utt);
+  return g;
+}
+inline dim3 launch_small_layernorm(hipStream_t st, const float* X, int ldx, int C, const float* g, const float* b, float* Y, int ldy, int n_utt) {
+  const dim3 grid(n_utt);
+  hipLaunchKernelGGL(small_layernorm_kernel, grid, dim3(64), 0, st, X, ldx, C, g, b, Y, ldy);
+  return grid;
+}
+inline dim3 launch_cfm_source(hipStream_t st, const Seg& s, const float* f0, const float* ncurve, const int* curve_off_dev, const float* t, const float* noise, float merge_w,
+                              float* har, int ldh) {
+  const dim3 g(s.n_utt);
+  hipLaunchKernelGGL(cfm_source_kernel, g, dim3(256), 0, st, f0, ncurve, curve_off_dev, s.dev, t, noise, merge_w, har, ldh);
+  return g;
+}
+// X rows have ldx, Y rows ldy, T and Xout rows are C wide (the kernel's contract: C <= 1024)
+inline dim3 launch_rms_adaln(hipStream_t st, const Seg& s, const float* X, int ldx, int C, const float* w, const float* ada, float* Y, int ldy, const float* T,
+                             const float* ada_prev, float* Xout) {
+  const dim3 g(ceil_div(s.max_len(), 4), s.n_utt);
+  hipLaunchKernelGGL(rms_adaln_kernel, g, dim3(256), 0, st, X, ldx, C, w, ada, s.dev, Y, ldy, T, ada_prev, Xout);
+  return g;
+}
+inline dim3 launch_axial_rope(hipStream_t st, const Seg& s, float* X, int ldx, int col0, int col1, int heads, int d, const float* freq) {
+  const dim3 g(std::max(1, std::min(1024, ceil_div(s.max_len() * heads * (d / 2), 256))), s.n_utt);
+  hipLaunchKernelGGL(axial_rope_kernel, g, dim3(256), 0, st, X, ldx, col0, col1, heads, d, freq, s.dev);
+  return g;
+}
+inline dim3 launch_gated_residual(hipStream_t st, const Seg& s, const float* H, const float* T, int C, const float* ada, float* Y) {
+  const dim3 g(std::max(1, std::min(1024, ceil_div(s.max_len() * (C / 4), 256))), s.n_utt);
+  hipLaunchKernelGGL(gated_residual_kernel, g, dim3(256), 0, st, H, T, C, ada, s.dev, Y);
+  return g;
+}
+inline dim3 launch_mish(hipStream_t st, float* X, long n4) {
+  const dim3 g((unsigned)std::min<long>(2048, ceil_div(n4, 256L)));
+  hipLaunchKernelGGL(mish_kernel, g, dim3(256), 0, st, X, n4);
+  return g;
+}
+inline dim3 launch_swiglu(hipStream_t st, const float* A, int M, float* U, long rows) {
+  const dim3 g((unsigned)std::min<long>(2048, ceil_div(rows * (M / 4), 256L)));
+  hipLaunchKernelGGL(swiglu_kernel, g, dim3(256), 0, st, A, M, U, rows);
+  return g;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- weights
 inline int pack_small(stts_ctx* c, const std::string& p, SmallLinear* o) {
   STTS_GET(w, p + ".weight");
@@ -314,6 +361,7 @@ inline int finalize_cfm(stts_ctx* c, const CfmDims& d, CfmModel* M) {
   STTS_CHECK(d.hidden % d.head_dim == 0 && d.head_dim % 4 == 0 && d.head_dim <= kAttnMaxKc, "cfm: hidden_dim %d / head_dim %d unsupported", d.hidden, d.head_dim);
   STTS_CHECK(d.hidden % 32 == 0 && d.emb % 32 == 0 && d.feat >= 1 && d.depth >= 1 && d.enc_blocks >= 1 && d.dec_blocks >= 1 && d.prev_depth >= 0 && d.post_depth >= 0,
              "cfm: bad dimensions (hidden_dim and emb_dim must be multiples of 32)");
+  STTS_CHECK(d.hidden <= 1024, "cfm: hidden_dim %d > 1024 (rms_adaln_kernel keeps a row in 16 registers per lane)", d.hidden);
   M->d = d;
   STTS_TRY(pack_plain(c, P + "asr_emb.1", true, 0, -1, &M->asr1));
   STTS_TRY(pack_plain(c, P + "asr_emb.3", true, 0, -1, &M->asr3));
@@ -334,6 +382,9 @@ inline int finalize_cfm(stts_ctx* c, const CfmDims& d, CfmModel* M) {
   STTS_CHECK(M->asr1.cin_real == d.asr && M->asr3.N == d.emb && M->spk0.K == d.spk && M->spk2.N == d.emb && M->prior.N == d.feat && M->out_proj.N == d.feat &&
                  M->in_x.N == d.hidden && M->time_proj.N == d.hidden,
              "cfm: tensor shapes do not match the given dimensions");
+  // the inner widths cfm_estimator carves its scratch rows by (a wider layer would write, a deeper one read, past a row)
+  STTS_CHECK(M->asr1.N == 4 * d.emb && M->asr3.cin_real == 4 * d.emb && M->spk0.N == 4 * d.emb && M->spk2.K == 4 * d.emb && M->time_proj.K == d.hidden,
+             "cfm: asr_emb / spk_emb must be emb_dim -> 4 emb_dim -> emb_dim and time_emb.proj.0 hidden_dim -> hidden_dim");
   const char* ad[3] = {"shared_adaln_attn", "shared_adaln_xattn", "shared_adaln_ffw"};
   for (int k = 0; k < 3; ++k) {
     STTS_TRY(upload_vec(c, P + ad[k] + ".0.weight", d.hidden, &M->ad_g[k]));
@@ -341,6 +392,7 @@ inline int finalize_cfm(stts_ctx* c, const CfmDims& d, CfmModel* M) {
     STTS_TRY(pack_small(c, P + ad[k] + ".1", &M->ad1[k]));
     STTS_TRY(pack_small(c, P + ad[k] + ".3", &M->ad3[k]));
     STTS_CHECK(M->ad3[k].N == 3 * d.hidden, "cfm: %s must produce scale | shift | gate", ad[k]);
+    STTS_CHECK(M->ad1[k].K == d.hidden && M->ad1[k].N == 4 * d.hidden && M->ad3[k].K == 4 * d.hidden, "cfm: %s must be hidden_dim -> 4 hidden_dim -> 3 hidden_dim", ad[k]);
   }
   M->blocks.clear();
   M->role.clear();
@@ -406,12 +458,12 @@ inline int cfm_estimator(stts_ctx* c, const CfmModel& M, hipStream_t st, const S
              kAttnMaxKeys, s.max_len());
   // conditioning that does not depend on x
   STTS_TRY(cfm_linear(st, s, asr, ld_asr, M.asr1, ACT_NONE, a1, 4 * d.emb));
-  hipLaunchKernelGGL(mish_kernel, dim3((unsigned)std::min<long>(2048, ceil_div(R * d.emb, 256L))), dim3(256), 0, st, a1, R * d.emb);  // R * 4 emb / 4 float4s
+  launch_mish(st, a1, R * d.emb);  // R * 4 emb / 4 float4s
   STTS_TRY(cfm_linear(st, s, a1, 4 * d.emb, M.asr3, ACT_NONE, ae, d.emb));
   STTS_TRY(run_small(st, M.spk0, spk, d.spk, 1, s1, 4 * d.emb, U));
   STTS_TRY(run_small(st, M.spk2, s1, 4 * d.emb, 0, se, d.emb, U));
   hipLaunchKernelGGL(broadcast_style_kernel, dim3(std::max(1, ceil_div(s.max_len() * d.emb, 256)), U), dim3(256), 0, st, se, d.emb, d.emb, sb, d.emb, 0, s.dev);
-  hipLaunchKernelGGL(cfm_source_kernel, dim3(U), dim3(256), 0, st, f0, ncurve, curve_off_dev, s.dev, t, noise, M.merge_w, har, 32);
+  launch_cfm_source(st, s, f0, ncurve, curve_off_dev, t, noise, M.merge_w, har, 32);
   // x + prior_generator(har) (k = 7 conv over the three source features), then in_proj over [x | asr_emb | spk_emb] as three K segments
   // (xp's pad columns meet zero weights in in_proj, but the contraction reads them: they must be finite)
   if (ldf > d.feat) STTS_HIP(hipMemsetAsync(xp, 0, (size_t)R * ldf * sizeof(float), st));
@@ -425,22 +477,20 @@ inline int cfm_estimator(stts_ctx* c, const CfmModel& M, hipStream_t st, const S
     STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, M.in_x.npad, U, s.max_len()));
   }
   // time embedding and the three shared AdaLN states (scale | shift | gate per utterance)
-  hipLaunchKernelGGL(cfm_time_embed_kernel, dim3(ceil_div(U * (dim / 2), 256)), dim3(256), 0, st, t, M.time_freqs, dim / 2, te0, dim, U);
+  launch_time_embed(st, t, M.time_freqs, dim / 2, te0, dim, U);
   STTS_TRY(run_small(st, M.time_proj, te0, dim, 1, te, dim, U));
   for (int k = 0; k < 3; ++k) {
-    hipLaunchKernelGGL(small_layernorm_kernel, dim3(U), dim3(64), 0, st, te, dim, dim, M.ad_g[k], M.ad_b[k], tl, dim);
+    launch_small_layernorm(st, te, dim, dim, M.ad_g[k], M.ad_b[k], tl, dim, U);
     STTS_TRY(run_small(st, M.ad1[k], tl, dim, 1, tm, 4 * dim, U));
     STTS_TRY(run_small(st, M.ad3[k], tm, 4 * dim, 0, ada + (size_t)k * U * 3 * dim, 3 * dim, U));
   }
-  const dim3 rgrid(ceil_div(s.max_len(), 4), U), egrid(std::max(1, std::min(1024, ceil_div(s.max_len() * (dim / 4), 256))), U);
   STTS_CHECK(dim <= 1024, "cfm_estimator: hidden_dim %d > 1024", dim);
   auto rope2 = [&](float* X, int ldx, int col0, int col1, const float* fr) {  // queries and keys of a q | k | v buffer
-    hipLaunchKernelGGL(axial_rope_kernel, dim3(std::max(1, std::min(1024, ceil_div(s.max_len() * heads * (d.head_dim / 2), 256))), U), dim3(256), 0, st, X, ldx, col0,
-                       col1, heads, d.head_dim, fr, s.dev);
+    launch_axial_rope(st, s, X, ldx, col0, col1, heads, d.head_dim, fr);
   };
   // norm(x) for the next branch, fused with the gated residual of the branch that just finished (t != nullptr): hn <- adaln(hn + t * gate)
   auto norm = [&](const float* x, const float* w, const float* a_next, const float* t, const float* a_prev, float* xout) {
-    hipLaunchKernelGGL(rms_adaln_kernel, rgrid, dim3(256), 0, st, x, dim, dim, w, a_next, s.dev, hn, dim, t, a_prev, xout);
+    launch_rms_adaln(st, s, x, dim, dim, w, a_next, hn, dim, t, a_prev, xout);
   };
   const float* a_attn = ada;
   const float* a_x = ada + (size_t)1 * U * 3 * dim;
@@ -468,12 +518,12 @@ inline int cfm_estimator(stts_ctx* c, const CfmModel& M, hipStream_t st, const S
     // SwiGLU branch
     norm(hn, B.n_mlp, a_mlp, other, a_prev, nullptr);
     STTS_TRY(cfm_linear(st, s, hn, dim, B.w12, ACT_NONE, a12, 2 * mlp));
-    hipLaunchKernelGGL(swiglu_kernel, dim3((unsigned)std::min<long>(2048, ceil_div(R * (mlp / 4), 256L))), dim3(256), 0, st, a12, mlp, um, R);
+    launch_swiglu(st, a12, mlp, um, R);
     STTS_TRY(cfm_linear(st, s, um, mlp, B.w3, ACT_NONE, other, dim));
   }
   // the last block's SwiGLU residual: x = hn + other * (gate + 1)
   float* cur = h;
-  hipLaunchKernelGGL(gated_residual_kernel, egrid, dim3(256), 0, st, hn, other, dim, a_mlp, s.dev, cur);
+  launch_gated_residual(st, s, hn, other, dim, a_mlp, cur);
   STTS_TRY(cfm_linear(st, s, cur, dim, M.out_proj, ACT_NONE, out, ld_out));
   STTS_HIP(hipGetLastError());
   return 0;

@@ -697,6 +697,149 @@ int stts_op_conv2d(void* stream, const stts_conv2d_args* p) {
   API_END
 }
 
+// The flow-matching estimator's row kernels (csrc/cfm.hip.h) and the sequence rotary embedding (csrc/phoneme.hip.h), one launch per call through the launch
+// helpers cfm_estimator itself uses (launch_* / run_small / run_rope): tests/test_hip_cfm_kernels.py.  As above: every check before any launch, every index a
+// launch can form bounded by the caller's element counts, host and device offsets compared, the stream synchronised on exit.
+static bool cfm_op_disjoint(const float* a, long na, const float* b, long nb) { return !a || !b || a + na <= b || b + nb <= a; }
+
+int stts_op_cfm_elem(void* stream, const stts_cfm_elem_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p && p->kind >= 0 && p->kind <= 2, "op_cfm_elem: null argument, or kind outside 0 - 2");
+  if (p->kind == 0) {  // mish_kernel in place over n float4s
+    STTS_CHECK(p->x && p->n > 0 && p->n <= p->x_elems / 4 && (uintptr_t)p->x % 16 == 0, "op_cfm_elem: mish needs x (16-byte aligned) of at least 4 n = %ld elements", 4 * (long)p->n);
+    launch_mish(st, p->x, (long)p->n);
+  } else if (p->kind == 1) {  // swiglu_kernel: x = A [n rows][2 C] -> y [n rows][C]
+    const long rows = (long)p->n, M = p->C;
+    STTS_CHECK(M > 0 && M % 4 == 0, "op_cfm_elem: swiglu reads four columns at a time: C %% 4 == 0 (C = %d)", p->C);
+    STTS_CHECK(p->x && p->y && rows > 0 && rows <= (1L << 40) / M && rows * 2 * M <= p->x_elems && rows * M <= p->y_elems && (uintptr_t)p->x % 16 == 0 && (uintptr_t)p->y % 16 == 0,
+               "op_cfm_elem: swiglu needs x [n, 2 C] and y [n, C] (16-byte aligned) inside their buffers");
+    STTS_CHECK(cfm_op_disjoint(p->x, rows * 2 * M, p->y, rows * M), "op_cfm_elem: swiglu's output overlaps its input");
+    launch_swiglu(st, p->x, p->C, p->y, rows);
+  } else {  // gated_residual_kernel: y = x + t * (gate_u + 1), gate = ada[u][2 C ..]
+    STTS_TRY(norm_op_offsets(st, "op_cfm_elem", p->n_utt, p->seg_off_host, p->seg_off_dev));
+    Seg s{p->n_utt, p->seg_off_host, p->seg_off_dev};
+    const long R = s.rows(), C = p->C;
+    STTS_CHECK(C > 0 && C % 4 == 0, "op_cfm_elem: the gated residual reads four columns at a time: C %% 4 == 0 (C = %d)", p->C);
+    STTS_CHECK((long)s.max_len() * (C / 4) < (1L << 31), "op_cfm_elem: max_len * C / 4 beyond the grid arithmetic");
+    STTS_CHECK(p->x && p->t && p->ada && p->y && R * C <= p->x_elems && R * C <= p->t_elems && R * C <= p->y_elems && (long)p->n_utt * 3 * C <= p->ada_elems,
+               "op_cfm_elem: the gated residual needs x, t, y [rows, C] and ada [n_utt, 3 C] inside their buffers");
+    STTS_CHECK((uintptr_t)p->x % 16 == 0 && (uintptr_t)p->t % 16 == 0 && (uintptr_t)p->y % 16 == 0 && (uintptr_t)p->ada % 16 == 0, "op_cfm_elem: 16-byte alignment");
+    STTS_CHECK(cfm_op_disjoint(p->x, R * C, p->y, R * C) && cfm_op_disjoint(p->t, R * C, p->y, R * C), "op_cfm_elem: the gated residual's output overlaps an input");
+    if (R > 0) launch_gated_residual(st, s, p->x, p->t, p->C, p->ada, p->y);
+  }
+  STTS_HIP(hipGetLastError());
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
+int stts_op_rms_adaln(void* stream, const stts_rms_adaln_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p, "op_rms_adaln: null argument");
+  STTS_TRY(norm_op_offsets(st, "op_rms_adaln", p->n_utt, p->seg_off_host, p->seg_off_dev));
+  Seg s{p->n_utt, p->seg_off_host, p->seg_off_dev};
+  const long R = s.rows(), C = p->C;
+  STTS_CHECK(C > 0 && C <= 1024, "op_rms_adaln: rms_adaln_kernel keeps a row in 16 registers per lane: 0 < C <= 1024 (C = %d)", p->C);
+  STTS_CHECK(p->x && p->w && p->ada && p->y, "op_rms_adaln: x, w, ada and y are required");
+  STTS_CHECK(norm_op_fits(R, p->ldx, 0, p->C, p->x_elems), "op_rms_adaln: x [%ld, ldx %d] (ldx >= C = %d) outside %ld elements", R, p->ldx, p->C, (long)p->x_elems);
+  STTS_CHECK(norm_op_fits(R, p->ldy, 0, p->C, p->y_elems), "op_rms_adaln: y [%ld, ldy %d] (ldy >= C = %d) outside %ld elements", R, p->ldy, p->C, (long)p->y_elems);
+  STTS_CHECK(p->w_elems >= C && (long)p->n_utt * 3 * C <= p->ada_elems, "op_rms_adaln: w [C] or ada [n_utt, 3 C] shorter than that");
+  STTS_CHECK((p->t == nullptr) == (p->ada_prev == nullptr), "op_rms_adaln: t and ada_prev come together");
+  STTS_CHECK(!p->t || (R * C <= p->t_elems && (long)p->n_utt * 3 * C <= p->ada_prev_elems), "op_rms_adaln: t [rows, C] or ada_prev [n_utt, 3 C] shorter than that");
+  STTS_CHECK(!p->xout || R * C <= p->xout_elems, "op_rms_adaln: xout [rows, C] shorter than that");
+  const long xspan = R > 0 ? (R - 1) * p->ldx + C : 0, yspan = R > 0 ? (R - 1) * p->ldy + C : 0;
+  STTS_CHECK((p->y == p->x && p->ldy == p->ldx) || cfm_op_disjoint(p->x, xspan, p->y, yspan), "op_rms_adaln: y may alias x row for row (the same pointer and leading dimension), not overlap it");
+  STTS_CHECK(cfm_op_disjoint(p->xout, R * C, p->x, xspan) && cfm_op_disjoint(p->xout, R * C, p->y, yspan) && cfm_op_disjoint(p->xout, R * C, p->t, R * C) &&
+                 cfm_op_disjoint(p->t, R * C, p->y, yspan),
+             "op_rms_adaln: xout or t overlaps another tensor");
+  if (R > 0) launch_rms_adaln(st, s, p->x, p->ldx, p->C, p->w, p->ada, p->y, p->ldy, p->t, p->ada_prev, p->xout);
+  STTS_HIP(hipGetLastError());
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
+int stts_op_rope(void* stream, const stts_rope_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p && (p->kind == 0 || p->kind == 1), "op_rope: null argument, or kind outside 0 (axial) / 1 (sequence)");
+  STTS_TRY(norm_op_offsets(st, "op_rope", p->n_utt, p->seg_off_host, p->seg_off_dev));
+  Seg s{p->n_utt, p->seg_off_host, p->seg_off_dev};
+  const long R = s.rows();
+  const int heads = p->heads, kc = p->kc, d = p->d;
+  STTS_CHECK(heads > 0 && kc > 0 && d > 0 && d % 2 == 0 && d <= kc, "op_rope: the rotated features come in pairs inside a head: d even, 0 < d <= kc (d = %d, kc = %d)", d, kc);
+  STTS_CHECK(p->kind != 0 || (kc == d && p->freq && (long)heads * (d / 2) <= p->freq_elems), "op_rope: the axial form turns whole heads (kc == d) by freq [heads, d / 2]");
+  STTS_CHECK(p->kind != 1 || d == (int)(kc * 0.5), "op_rope: the sequence form turns the first int(kc / 2) features of a head (d = %d, kc = %d)", d, kc);
+  const long width = (long)heads * kc;
+  STTS_CHECK(p->col0 >= 0 && p->col0 + width <= p->ldx, "op_rope: column block [%d, %ld) outside ldx %d", p->col0, p->col0 + width, p->ldx);
+  STTS_CHECK(p->col1 == -1 || (p->col1 >= 0 && p->col1 + width <= p->ldx && (p->col1 >= p->col0 + width || p->col0 >= p->col1 + width)),
+             "op_rope: second column block at %d outside ldx %d, or overlapping the first (-1: none)", p->col1, p->ldx);
+  STTS_CHECK(p->x && (R == 0 || (R - 1) * (long)p->ldx + std::max(p->col0, p->col1) + width <= p->x_elems), "op_rope: x [%ld, ldx %d] outside %ld elements", R, p->ldx, (long)p->x_elems);
+  STTS_CHECK((long)s.max_len() * heads * (d / 2) * 2 < (1L << 31), "op_rope: max_len * heads * d beyond the grid arithmetic");
+  if (R > 0) {
+    if (p->kind == 0) launch_axial_rope(st, s, p->x, p->ldx, p->col0, p->col1, heads, d, p->freq);
+    else run_rope(st, s, p->x, p->ldx, p->col0, heads, kc, p->col1);
+  }
+  STTS_HIP(hipGetLastError());
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
+int stts_op_cfm_small(void* stream, const stts_cfm_small_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p && p->kind >= 0 && p->kind <= 2, "op_cfm_small: null argument, or kind outside 0 - 2");
+  const long rows = p->n_rows, N = p->N, K = p->K;
+  STTS_CHECK(rows > 0 && N > 0 && p->x && p->w && p->y && rows * N < (1L << 31), "op_cfm_small: null / empty argument");
+  if (p->kind == 0) {  // small_linear_kernel: y [rows, N] = act(x [rows, K] w[N, K]^T + b)
+    STTS_CHECK(K > 0 && (p->act == 0 || p->act == 1), "op_cfm_small: linear needs K > 0 and act 0 (none) or 1 (Mish)");
+    STTS_CHECK(norm_op_fits(rows, p->ldx, 0, p->K, p->x_elems) && norm_op_fits(rows, p->ldy, 0, p->N, p->y_elems), "op_cfm_small: x [rows, ldx >= K] or y [rows, ldy >= N] outside its buffer");
+    STTS_CHECK(N * K <= p->w_elems && (!p->b || N <= p->b_elems), "op_cfm_small: w [N, K] or b [N] shorter than that");
+    SmallLinear w;
+    w.W = const_cast<float*>(p->w);
+    w.b = const_cast<float*>(p->b);
+    w.N = p->N;
+    w.K = p->K;
+    STTS_TRY(run_small(st, w, p->x, p->ldx, p->act, p->y, p->ldy, p->n_rows));
+  } else if (p->kind == 1) {  // small_layernorm_kernel over N channels: w = gamma, b = beta
+    STTS_CHECK(p->b && N <= p->w_elems && N <= p->b_elems, "op_cfm_small: layernorm needs gamma (w) and beta (b) of N elements");
+    STTS_CHECK(norm_op_fits(rows, p->ldx, 0, p->N, p->x_elems) && norm_op_fits(rows, p->ldy, 0, p->N, p->y_elems), "op_cfm_small: x [rows, ldx >= N] or y [rows, ldy >= N] outside its buffer");
+    launch_small_layernorm(st, p->x, p->ldx, p->N, p->w, p->b, p->y, p->ldy, p->n_rows);
+  } else {  // cfm_time_embed_kernel: x = t [rows], w = freqs [N = half] -> y [rows, ldy] = cos | sin
+    STTS_CHECK(rows <= p->x_elems && N <= p->w_elems, "op_cfm_small: time embedding needs t (x) [rows] and freqs (w) [N]");
+    STTS_CHECK(norm_op_fits(rows, p->ldy, 0, 2 * p->N, p->y_elems), "op_cfm_small: y [rows, ldy >= 2 N] outside its buffer");
+    launch_time_embed(st, p->x, p->w, p->N, p->y, p->ldy, p->n_rows);
+  }
+  STTS_HIP(hipGetLastError());
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
+int stts_op_cfm_source(void* stream, const stts_cfm_source_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p, "op_cfm_source: null argument");
+  STTS_TRY(norm_op_offsets(st, "op_cfm_source (frames)", p->n_utt, p->seg_off_host, p->seg_off_dev));
+  STTS_TRY(norm_op_offsets(st, "op_cfm_source (curves)", p->n_utt, p->curve_off_host, p->curve_off_dev));
+  Seg s{p->n_utt, p->seg_off_host, p->seg_off_dev};
+  const long R = s.rows(), Lc = p->curve_off_host[p->n_utt];
+  STTS_CHECK(p->ldh == 32, "op_cfm_source: the source rows are 32 columns wide (ldh = %d)", p->ldh);
+  for (int u = 0; u < p->n_utt; ++u)
+    STTS_CHECK(p->seg_off_host[u + 1] == p->seg_off_host[u] || p->curve_off_host[u + 1] > p->curve_off_host[u], "op_cfm_source: utterance %d has frames but a curve of zero points", u);
+  STTS_CHECK(p->f0 && p->ncurve && p->t && p->noise && p->har, "op_cfm_source: null tensor");
+  STTS_CHECK(Lc <= p->f0_elems && Lc <= p->ncurve_elems && p->n_utt <= p->t_elems && R <= p->noise_elems && R * 32 <= p->har_elems,
+             "op_cfm_source: f0 / ncurve [%ld], t [%d], noise [%ld] or har [%ld, 32] shorter than that", Lc, p->n_utt, R, R);
+  launch_cfm_source(st, s, p->f0, p->ncurve, p->curve_off_dev, p->t, p->noise, p->merge_w, p->har, p->ldh);
+  STTS_HIP(hipGetLastError());
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ kernel microbench

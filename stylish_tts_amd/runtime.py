@@ -367,6 +367,39 @@ class HipModel:
             a.dt[i], a.df[i] = int(t), int(f)
         _lib.check(self.lib.stts_op_conv2d(_stream(), C.byref(a)))
 
+    # ------------------------------------------------------------------ the flow-matching estimator's row kernels (test surface)
+    def op_cfm_elem(self, seg: Optional[Segments], **fields):
+        """stts_op_cfm_elem (fields of stts_cfm_elem_args): kind 0 Mish in place, 1 SwiGLU, 2 the gated residual (the only one with offsets)."""
+        keep = []
+        a = self._fill_args(_lib.CfmElemArgs(), seg, fields, keep)
+        _lib.check(self.lib.stts_op_cfm_elem(_stream(), C.byref(a)))
+
+    def op_rms_adaln(self, seg: Segments, **fields):
+        """stts_op_rms_adaln (fields of stts_rms_adaln_args): RMSNorm + AdaLN, optionally fused with the previous branch's gated residual."""
+        keep = []
+        a = self._fill_args(_lib.RmsAdalnArgs(), seg, fields, keep)
+        _lib.check(self.lib.stts_op_rms_adaln(_stream(), C.byref(a)))
+
+    def op_rope(self, seg: Segments, **fields):
+        """stts_op_rope (fields of stts_rope_args): kind 0 the estimator's axial RoPE, 1 the encoders' sequence RoPE, in place."""
+        keep = []
+        a = self._fill_args(_lib.RopeArgs(), seg, fields, keep)
+        _lib.check(self.lib.stts_op_rope(_stream(), C.byref(a)))
+
+    def op_cfm_small(self, **fields):
+        """stts_op_cfm_small (fields of stts_cfm_small_args): kind 0 the per-utterance Linear, 1 its LayerNorm, 2 the timestep embedding."""
+        keep = []
+        a = self._fill_args(_lib.CfmSmallArgs(), None, fields, keep)
+        _lib.check(self.lib.stts_op_cfm_small(_stream(), C.byref(a)))
+
+    def op_cfm_source(self, seg: Segments, curves: Segments, **fields):
+        """stts_op_cfm_source (fields of stts_cfm_source_args): the sine source; seg: frames, curves: the points of F0 / N per utterance."""
+        assert seg.n == curves.n
+        keep = []
+        a = self._fill_args(_lib.CfmSourceArgs(), seg, fields, keep)
+        a.curve_off_host, a.curve_off_dev = curves.host_ptr, _ptr(curves.dev)
+        _lib.check(self.lib.stts_op_cfm_source(_stream(), C.byref(a)))
+
     def op_adain_block(self, prefix: str, seg: Segments, x, cin, cout, style):
         y = self._f32(seg.rows, cout)
         ws = self.workspace(seg)

@@ -624,6 +624,88 @@ static void norm_section() {
   }
 }
 
+// stts_op_cfm_elem / _rms_adaln / _rope / _cfm_small / _cfm_source (the flow-matching estimator's row kernels, tests/test_hip_cfm_kernels.py): every kind of every
+// operator once, and per operator one call that is refused before anything is launched.  `cfmtrace <case> : [error ]<trace>`.
+template <typename Call>
+static void cfm_op_case(const char* what, Call call) {
+  stts_stub_trace_begin();
+  const int rc = call();
+  const char* trace = stts_stub_trace_end();
+  printf("cfmtrace %s : %s%s\n", what, rc ? "error " : "", trace);
+}
+
+static void cfm_ops_section() {
+  const int n = 3;
+  const std::vector<int32_t> off = {0, 1100, 1100, 1103}, coff = {0, 300, 300, 303}, coff0 = {0, 300, 300, 300};  // (an utterance of zero rows in the middle)
+  const long R = off[n];
+  {
+    const int C = 1024, M = 2048;
+    auto x = buf(R * 2 * M), t = buf(R * C), ada = buf((size_t)n * 3 * C), y = buf(R * M);
+    stts_cfm_elem_args a;
+    memset(&a, 0, sizeof(a));
+    a.seg_off_host = a.seg_off_dev = off.data();
+    a.n_utt = n; a.x = x.data(); a.x_elems = (int64_t)x.size(); a.t = t.data(); a.t_elems = (int64_t)t.size(); a.ada = ada.data(); a.ada_elems = (int64_t)ada.size();
+    a.y = y.data(); a.y_elems = (int64_t)y.size();
+    a.kind = 0; a.n = 2048 * 256 + 3;  // the capped grid
+    cfm_op_case("elem_mish", [&] { return stts_op_cfm_elem(nullptr, &a); });
+    a.kind = 1; a.C = M; a.n = R;
+    cfm_op_case("elem_swiglu", [&] { return stts_op_cfm_elem(nullptr, &a); });
+    a.kind = 2; a.C = C;
+    cfm_op_case("elem_gated", [&] { return stts_op_cfm_elem(nullptr, &a); });
+    a.kind = 1; a.C = 6;  // refused: four columns at a time
+    cfm_op_case("refuse_elem", [&] { return stts_op_cfm_elem(nullptr, &a); });
+  }
+  for (int refuse = 0; refuse < 2; ++refuse) {  // refused: C above the 16 registers per lane
+    const int C = refuse ? 1028 : 1024, ldx = 1060;
+    auto x = buf(R * ldx), w = buf(C), ada = buf((size_t)n * 3 * C), ap = buf((size_t)n * 3 * C), t = buf(R * C), xo = buf(R * C);
+    stts_rms_adaln_args a;
+    memset(&a, 0, sizeof(a));
+    a.seg_off_host = a.seg_off_dev = off.data();
+    a.n_utt = n; a.C = C; a.ldx = a.ldy = ldx; a.x = x.data(); a.y = x.data(); a.x_elems = a.y_elems = (int64_t)x.size(); a.w = w.data(); a.w_elems = C;
+    a.ada = ada.data(); a.ada_elems = (int64_t)ada.size(); a.ada_prev = ap.data(); a.ada_prev_elems = (int64_t)ap.size(); a.t = t.data(); a.t_elems = (int64_t)t.size();
+    a.xout = xo.data(); a.xout_elems = (int64_t)xo.size();
+    cfm_op_case(refuse ? "refuse_rms_adaln" : "rms_adaln", [&] { return stts_op_rms_adaln(nullptr, &a); });
+  }
+  {
+    const int heads = 8, d = 64, dim = heads * d;
+    auto x = buf(R * 3 * dim), freq = buf(heads * d / 2);
+    stts_rope_args a;
+    memset(&a, 0, sizeof(a));
+    a.seg_off_host = a.seg_off_dev = off.data();
+    a.n_utt = n; a.x = x.data(); a.x_elems = (int64_t)x.size(); a.freq = freq.data(); a.freq_elems = (int64_t)freq.size(); a.ldx = 3 * dim; a.col0 = 0; a.col1 = dim;
+    a.kind = 0; a.heads = heads; a.kc = a.d = d;
+    cfm_op_case("rope_axial", [&] { return stts_op_rope(nullptr, &a); });
+    a.kind = 1; a.heads = 16; a.kc = 32; a.d = 16;
+    cfm_op_case("rope_sequence", [&] { return stts_op_rope(nullptr, &a); });
+    a.kc = 6; a.d = 3;  // refused: an odd number of rotated features
+    cfm_op_case("refuse_rope", [&] { return stts_op_rope(nullptr, &a); });
+  }
+  {
+    const int N = 5, K = 100, rows = 3;
+    auto x = buf(rows * (K + 8)), w = buf(N * K), b = buf(N), y = buf(rows * (2 * N + 4));
+    stts_cfm_small_args a;
+    memset(&a, 0, sizeof(a));
+    a.x = x.data(); a.x_elems = (int64_t)x.size(); a.w = w.data(); a.w_elems = (int64_t)w.size(); a.b = b.data(); a.b_elems = N; a.y = y.data(); a.y_elems = (int64_t)y.size();
+    a.n_rows = rows; a.N = N; a.K = K; a.act = 1; a.ldx = K + 8; a.ldy = 2 * N + 4;
+    for (int kind = 0; kind < 3; ++kind) {
+      a.kind = kind;
+      cfm_op_case(("small_kind" + std::to_string(kind)).c_str(), [&] { return stts_op_cfm_small(nullptr, &a); });
+    }
+    a.ldy = 2 * N - 1;  // refused: cos | sin do not fit a row
+    cfm_op_case("refuse_small", [&] { return stts_op_cfm_small(nullptr, &a); });
+  }
+  for (int refuse = 0; refuse < 2; ++refuse) {  // refused: an utterance with frames and a curve of zero points
+    auto f0 = buf(303), nc = buf(303), t = buf(n), noise = buf(R), har = buf(R * 32);
+    stts_cfm_source_args a;
+    memset(&a, 0, sizeof(a));
+    a.seg_off_host = a.seg_off_dev = off.data();
+    a.curve_off_host = a.curve_off_dev = refuse ? coff0.data() : coff.data();
+    a.n_utt = n; a.ldh = 32; a.merge_w = 0.8f; a.f0 = f0.data(); a.f0_elems = 303; a.ncurve = nc.data(); a.ncurve_elems = 303; a.t = t.data(); a.t_elems = n;
+    a.noise = noise.data(); a.noise_elems = R; a.har = har.data(); a.har_elems = (int64_t)har.size();
+    cfm_op_case(refuse ? "refuse_source" : "source", [&] { return stts_op_cfm_source(nullptr, &a); });
+  }
+}
+
 struct Tensor {
   std::string name;
   int ndim;
@@ -688,6 +770,7 @@ int main(int argc, char** argv) {
   if (argc > 2 && strcmp(argv[2], "gemm") == 0) return 0;
   epi_section();
   norm_section();
+  cfm_ops_section();
   Dims dims;
   std::vector<Tensor> w;
   if (read_weights(argv[1], dims, w)) return 2;

@@ -157,6 +157,17 @@ def test_host_side_under_asan_ubsan(tmp_path):
         assert not norm[case].startswith("error") and all(k in norm[case] for k in kernels), (case, norm[case])
     refused = [k for k in norm if k.startswith("refuse_")]
     assert sorted(refused) == sorted(["refuse_" + k for k in accepted] + ["refuse_dwconv_form1_k5"]) and all(norm[k].strip() == "error" for k in refused), norm
+    # the operators of the flow-matching estimator's row kernels (asan_driver.cpp cfm_ops_section): the product's grids - capped at 2048 / 1024 blocks where the
+    # shapes exceed them -, each refused call launches NOTHING
+    cfm = dict(re.findall(r"^cfmtrace (\S+) : (.*)$", r.stdout, re.M))
+    cfm_accepted = {"elem_mish": ("mish_kernel", "(2048,1,1)(256,1,1)"), "elem_swiglu": ("swiglu_kernel", "(2048,1,1)(256,1,1)"), "elem_gated": ("gated_residual_kernel", "(1024,3,1)(256,1,1)"),
+                    "rms_adaln": ("rms_adaln_kernel", "(275,3,1)(256,1,1)"), "rope_axial": ("axial_rope_kernel", "(1024,3,1)(256,1,1)"), "rope_sequence": ("rope_kernel", "(1100,3,1)(256,1,1)"),
+                    "small_kind0": ("small_linear_kernel", "(4,1,1)(256,1,1)"), "small_kind1": ("small_layernorm_kernel", "(3,1,1)(64,1,1)"),
+                    "small_kind2": ("cfm_time_embed_kernel", "(1,1,1)(256,1,1)"), "source": ("cfm_source_kernel", "(3,1,1)(256,1,1)")}
+    for case, parts in cfm_accepted.items():
+        assert not cfm[case].startswith("error") and cfm[case].startswith("1x ") and " | " not in cfm[case] and all(k in cfm[case] for k in parts), (case, cfm[case])
+    refused = [k for k in cfm if k.startswith("refuse_")]
+    assert sorted(refused) == ["refuse_elem", "refuse_rms_adaln", "refuse_rope", "refuse_small", "refuse_source"] and all(cfm[k].strip() == "error" for k in refused), cfm
     # every switch setting ran every case
     per_setting = {}
     for sw in re.findall(r"^\[(STTS_\w+=\d+)\] gemmtrace ", r.stdout, re.M):
