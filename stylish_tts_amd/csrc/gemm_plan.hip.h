@@ -136,7 +136,7 @@ inline bool gemm16_route(const GemmArgs& a, int epi, int npad, int n_utt, int fo
   if (force_tile != 0 && force_tile != 19) return false;
   return gemm16_eligible(a, epi, npad) && (force_tile == 19 || gemm16_tiles(a, npad, n_utt) >= sw.gemm16_min_tiles);
 }
-// would launch_conv_gemm pick conv_gemm16_kernel for this call?  (run_adain_block asks before it sets stat_part)
+// would launch_conv_gemm pick conv_gemm16_kernel for this call?  (plan_adain_block asks before the runner sets stat_part)
 inline bool gemm16_will_run(const GemmArgs& a, int epi, int npad, int n_utt) { return gemm16_route(a, epi, npad, n_utt, 0, gemm_switches()); }
 
 constexpr int kCUs = 256;

@@ -266,12 +266,16 @@ inline int hubert_pitch_energy_forward(stts_ctx* c, const HubertModel& M, hipStr
   int* row_utt = ws.get<int>(R);
   float* t1 = ws.get<float>(R * C);
   float* t2 = ws.get<float>(R * C);
-  float* act1 = ws.get<float>(R * C);
-  float* hb = ws.get<float>(R * C);
-  float* act2 = ws.get<float>(R * C);
-  float* ss = ws.get<float>(adain_part_floats(s, C));
-  WinoScratch wino;  // large batches: Winograd convs (as the text predictor's blocks)
-  if (R > fold_rows() && P.f0[0].w1.ready) wino.p = ws.get<float>(wino_scratch_floats(s, P.f0[0].w1));
+  BlockIO io;
+  io.act1 = ws.get<float>(R * C);
+  io.hbuf = ws.get<float>(R * C);
+  io.act2 = ws.get<float>(R * C);
+  io.ss = ws.get<float>(adain_part_floats(s, C));
+  // large batches: Winograd convs (as the text predictor's blocks), every norm on its own statistics pass
+  const BlockSwitches sw = block_switches();
+  const ChainPlan plan = plan_adain_chain(s, PREC_F32, P.f0, 3, 0, ChainOffer{false, false, false, false}, sw);
+  WinoScratch wino;
+  if (plan.wino) wino.p = ws.get<float>(wino_scratch_floats(s, P.f0[0].w1));
   STTS_CHECK(ws.ok, "hubert_pitch_energy_forward: workspace too small");
   const int lds = P.table.ld();
   auto prosody = [&]() { Arena a = ws.rest(); return prosody_forward(st, P.pros, s, q, d, pe_style, sty, lds, row_utt, pros, a); };
@@ -284,12 +288,15 @@ inline int hubert_pitch_energy_forward(stts_ctx* c, const HubertModel& M, hipStr
   STTS_TRY(gemm_store(st, s, feats, ld_f, 0, P.quant, q, d, 0));
   STTS_TRY(run_style(st, P.table, pe_style, s.n_utt, sty));
   STTS_TRY(prosody());
+  io.style = sty; io.ld_style = lds; io.ldx = io.ldy = C; io.wino = &wino;
+  BlockChain chain(plan, nullptr);
   for (int br = 0; br < 2; ++br) {
     const AdainBlockW* blocks = br == 0 ? P.f0 : P.n;
     const float* cur = pros;
     float* bufs[2] = {t1, t2};
     for (int i = 0; i < 3; ++i) {
-      STTS_TRY(run_adain_block(st, s, blocks[i], sty, lds, cur, C, bufs[i & 1], C, act1, hb, act2, ss, 0, &wino));
+      io.x = cur; io.y = bufs[i & 1];
+      STTS_TRY(adain_block(st, s, blocks[i], io, chain, sw));
       cur = bufs[i & 1];
     }
     const ChanConvSet cs{cur, br == 0 ? P.f0_w : P.n_w, br == 0 ? P.f0_b : P.n_b, br == 0 ? f0 : nrg};

@@ -1131,445 +1131,9 @@ inline dim3 rows_grid(const Seg& s, int per_row_work) {
   return dim3((unsigned)std::min<long>(std::max<long>(1, ceil_div((int)std::min<long>(total, 1 << 30), 256)), 512), s.n_utt);
 }
 
-// rows from which the 16-bit operand modes keep contraction inputs as 16-bit rows in HBM (B = 4 x 3 s; measured bf16, 3-s utterances:
-// B = 1: 827 vs 739 utt/s without / with 16-bit rows, B = 2: 1 424 vs 1 313, B = 4: 2 272 vs 2 304, B = 8: 3 442 vs 3 522)
-inline long rows16_threshold() {
-  static const long v = getenv("STTS_ROWS16") ? atol(getenv("STTS_ROWS16")) : 3840;
-  return v;
-}
-
-// AdaIN + activation: Y[:, :ldy] = act((1+gamma) * InstanceNorm(X[:, :C]) + beta), zeros in the pad columns.
-// part: scratch of adain_part_floats(s, C) floats.
-inline size_t adain_part_floats(const Seg& s, int C, int chunk_rows = kStatChunk) { return (size_t)s.n_utt * ceil_div(s.max_len(), chunk_rows) * 2 * round_up(C, 32); }
-// out16: PREC_BF16 / PREC_F16 = Y is a 16-bit row buffer (ldy in elements), the input of a contraction in that operand mode
-inline int run_adain(hipStream_t st, const Seg& s, const float* X, int ldx, int C, float* Y, int ldy, const float* style_out, int ld_style,
-                     int gcol0, int act, const float* alpha, float* part, int out16 = 0, bool have_stats = false, int force_rb = 0) {
-  // force_rb (tests: stts_op_adain): 64 or 256 rows per apply block whatever the batch; have_stats: `part` already holds the chunk statistics of X (written by the producing contraction's epilogue, GemmArgs::stat_part)
-  const int nchunk = ceil_div(s.max_len(), kStatChunk), ldp = round_up(C, 32);
-  if (!have_stats)
-    STTS_LAUNCH_PROF("adain_partial_kernel", (size_t)s.rows() * C * 4, adain_partial_kernel, dim3(ceil_div(C, 32), nchunk, s.n_utt), dim3(256), st, X, ldx, C, s.dev, part, ldp, nchunk, kStatChunk);
-  const int rb = force_rb ? force_rb : (long)ceil_div(ldy, 64) * ceil_div(s.rows(), 64) >= 4096 ? 256 : 64;  // rows per block
-  STTS_LAUNCH_PROF("adain_apply_kernel", (size_t)s.rows() * (C * 4 + ldy * (out16 ? 2 : 4)), adain_apply_kernel, dim3(ceil_div(ldy, 64), ceil_div(s.max_len(), rb), s.n_utt), dim3(256), st, X, ldx, Y, ldy, C, s.dev,
-                     part, ldp, nchunk, style_out, ld_style, gcol0, 1e-5f, act, alpha, out16, rb);
-  STTS_HIP(hipGetLastError());
-  return 0;
-}
-
-// A contraction whose split-K reduce pass is left to the consumer of its output (small batches: the next AdaIN's statistics kernel finishes it).
-struct PendingReduce {
-  SplitSrc src{};   // src.partial == nullptr: nothing pending
-  float* Y = nullptr;
-  int ldy = 0;
-};
-inline void pending_from(PendingReduce* p, const SplitInfo& info, const GemmArgs& a) {
-  p->src = SplitSrc{};
-  if (info.ksplit > 1) {
-    p->src = SplitSrc{info.partial, info.ksplit, info.slice_rows, info.ld_part, a.N, a.bias, a.act, a.R, a.ldr, a.rcol0, a.alpha};
-    p->Y = a.Y + a.ycol0;
-    p->ldy = a.ldy;
-  }
-}
-// finishes a pending reduce on its own (no consumer took it)
-inline int pending_finish(hipStream_t st, PendingReduce* p) {
-  if (!p || !p->src.partial) return 0;
-  const SplitSrc& r = p->src;
-  const long work = (long)r.slice_rows * ((r.N + 3) / 4);
-  STTS_LAUNCH_PROF("splitk_reduce_kernel", (size_t)work * 4 * 4 * (r.ksplit + 1), splitk_reduce_kernel, dim3((unsigned)std::min<long>(2048, (work + 255) / 256)), dim3(256), st, r.partial,
-                   r.ksplit, r.slice_rows, 0, r.ld_part, r.N, r.bias, r.act, r.R, r.ldr, r.rcol0, r.alpha, p->Y, p->ldy, 0);
-  p->src = SplitSrc{};
-  STTS_HIP(hipGetLastError());
-  return 0;
-}
-// batches up to this many rows fold AdaIN into the consuming contraction's staging (run_adain_block); above it the decoder convs run in Winograd form
-inline long fold_rows() {
-  static const long v = getenv("STTS_FOLD_ROWS") ? atol(getenv("STTS_FOLD_ROWS")) : 2500;
-  return v;
-}
-// fp32 Winograd branch of the decoder: the slab width of winograd_bridge_kernel (one launch between an AdaIN block's chained convs), or 0 for the three
-// launches (output transform with statistics, affine table, input transform).  A bridge block holds the whole time axis of its utterance, so the launch
-// pays only when (utterances x slabs) covers a good part of the chip, and stops paying once there are more blocks than the chip holds at a time (two of
-// ten waves per CU at 3-s utterances).  Rule: 96 <= utterances x (hidden_dim / 16) <= 384, i.e. 3 to 12 utterances at 512 channels, every utterance at most 1 536 rows.
-// Measured per step, three launches -> bridge, 3-s utterances, same box, same build, alternated: B = 3: 2.112 -> 2.057 ms (-2.6 %), B = 4: 2.312 -> 2.241
-// (-3.1 %), B = 6: 2.737 -> 2.665 (-2.6 %), B = 8: 3.246 -> 3.198 (-1.5 %), B = 12: 4.349 -> 4.317 (-0.7 %), B = 16: 5.538 -> 5.546 (+0.1 %: stays); cfg4
-// (256 ragged utterances, calls of more than 12): 150.0 vs 149.8 ms forced on (stays); B = 1, 2 and a single 10-s utterance never reach the Winograd
-// branch or exceed a block.  STTS_ADAIN_BRIDGE (read per call): 0 = never, 1 = wherever the kernel can run.
-constexpr int kBridgeSlab = 16;
-constexpr int kBridgeMinBlocks = 96, kBridgeMaxBlocks = 384;
-inline int adain_bridge_slab(const Seg& s, const AdainBlockW* blocks, int nblocks) {
-  const char* env = getenv("STTS_ADAIN_BRIDGE");
-  const int forced = env ? (atoi(env) != 0) : -1;
-  if (forced == 0) return 0;
-  if (getenv("STTS_X3_PRESPLIT") && atoi(getenv("STTS_X3_PRESPLIT")) != 0) return 0;  // (pre-split input planes: another layout)
-  const int slab = kBridgeSlab;
-  for (int i = 0; i < nblocks; ++i) {
-    const AdainBlockW& B = blocks[i];
-    if (!wino_bridge_fits(s, B.w1, B.w2, slab) || B.w2.planes.kc != B.cout) return 0;
-    if (i + 1 < nblocks && (!wino_bridge_fits(s, B.w2, blocks[i + 1].w1, slab) || blocks[i + 1].cin < B.cout)) return 0;
-  }
-  if (forced == 1) return slab;
-  const long nb = (long)s.n_utt * (blocks[0].cout / slab);
-  return nb >= kBridgeMinBlocks && nb <= kBridgeMaxBlocks ? slab : 0;
-}
-// A second stream for a contraction that is independent of the launches around it (run_adain_block: the learned 1x1 shortcut next to conv1), with the
-// fork / join events that order it against the caller's stream and an output buffer of its own ([rows, cout]).
-struct SideWork {
-  hipStream_t stream = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-  float* out = nullptr;
-};
-struct AdainStats {
-  float* in = nullptr;   // statistics of x for norm1 (layout of adain_partial_kernel, round_up(cin, 32) columns)
-  bool in_ready = false;
-  float* mid = nullptr;  // scratch: statistics of conv1's output for norm2
-  float* out = nullptr;  // where conv2 writes the statistics of y
-  int out_ld = 0;
-  bool out_ready = false;
-  int chunk_rows = kStatChunk;  // kWinoStatChunk: fp32 Winograd branch, the statistics come out of the convs' output transforms (winograd_output_kernel<N, true>)
-  // fp32 Winograd branch, chained (decoder_forward, adain_bridge_slab): ONE launch between two convs (winograd_bridge_kernel) instead of output transform,
-  // affine table and input transform - the statistics never leave the block that reduces them, `mid` and `out` stay unused
-  int bridge_w = 0;                   // slab width, 0: off
-  const AdainBlockW* next = nullptr;  // the block whose conv1 consumes this block's output (null: the output transform writes y, nothing follows)
-  const float* cst = nullptr;         // chunk statistics of the next block's constant input columns (layout of `in`, cst_ld columns)
-  int cst_ld = 0;
-  bool planes_ready = false;          // the previous block's bridge has written conv1's input planes
-};
-// AdaptiveDecoderBlock (models/ada_norm.py:166-182).  x [rows, ldx] (cols >= cin may hold anything when
-// kcin == round_up(cin) because the packed weights are zero there, but AdaIN writes zeros anyway).
-// scratch: act1 [rows, kcin], h [rows, cout], act2 [rows, cout], ss [adain_part_floats(s, max(kcin, cout))]
-inline int run_adain_block(hipStream_t st, const Seg& s, const AdainBlockW& B, const float* style_out, int ld_style, const float* x, int ldx,
-                           float* y, int ldy, float* act1, float* hbuf, float* act2, float* ss, int force_tile = 0, WinoScratch* wino = nullptr,
-                           unsigned short* xs16 = nullptr, bool xs16_ready = false, unsigned short* y16 = nullptr, int ldy16 = 0,
-                           AdainStats* stats = nullptr, PendingReduce* pend_in = nullptr, PendingReduce* pend_out = nullptr, const SideWork* side = nullptr) {
-  // side (fp32 Winograd branch, learned shortcut): the 1x1 shortcut contraction - it reads the block's input only - runs on side->stream next to conv1's three
-  // launches (whose plane contraction fills the chip 1.25 times and whose transforms leave the matrix cores idle) instead of between conv1 and conv2.
-  // pend_in / pend_out (small batches, fold path): x's first columns may still be the split-K partial sums of the contraction that produced them
-  // (pend_in: finished by norm1's statistics launch, which also writes them to x); conv2's own reduce pass is left to the caller's next consumer
-  // (pend_out).  Without them every contraction finishes its own output.
-  // stats (16-bit modes, large batches; decoder_forward): statistics written by the producing contractions' epilogues (conv_gemm16_kernel,
-  // GemmArgs::stat_part) instead of a pass of adain_partial_kernel per norm - norm1's come from the previous block's conv2 (`in`, if `in_ready`),
-  // norm2's from this block's conv1 (`mid`), and conv2 leaves those of y for the next block's norm1 in `out` (`out_ld` columns per row, the
-  // next block's padded input width; its constant columns are filled once by the caller); `out_ready` reports whether it did.
-  // xs16: [rows, ldx] 16-bit scratch for the rounded copy of x a learned shortcut reads (16-bit modes, large batches);
-  // xs16_ready: it already holds that copy (the previous block's conv2 wrote it).  y16: also write y rounded, as [rows, ldy16].
-  const int ml = s.max_len();
-  // Small batches (launch-latency bound): AdaIN -> LeakyReLU is folded into the staging of the contraction that consumes
-  // it (conv_gemm_f32<..., XAFF>): the statistics pass stays, a 64-thread kernel turns them into per-(utterance, channel)
-  // scale / shift tables (kept in act1 / act2), and the normalised tensor is never written: B = 1 frame path -4 %.
-  // Large batches keep the separate apply pass: the affine in the K loop costs the 512-channel contractions ~14 % at
-  // B = 8 (142 vs 125 us), more than the 11 us pass it removes.  fp32: from 2 500 rows on both convs run in Winograd form instead (AdaIN rides in
-  // their input transforms): 3-s utterances, same box: B = 3: 2.78 -> 2.63 ms, B = 4: 2.88 -> 2.83; B = 2: 2.16 -> 2.26 and B = 1: 1.77 -> 1.92 (fold stays).
-  const bool fold = s.rows() <= (B.conv1.prec == PREC_F32 ? fold_rows() : 4096);  // (16-bit modes: measured at 4 096 only)
-  STTS_CHECK(ldx >= B.kcin, "adain block: input leading dimension %d < padded channels %d", ldx, B.kcin);
-  static const bool affine_lanes = getenv("STTS_AFFINE_SERIAL") == nullptr;  // experiments: the one-thread-per-channel merge (adain_affine_kernel)
-  auto affine = [&](const float* X, int ld, int C, int ld_aff, int gcol0, float* aff, PendingReduce* pend = nullptr) {
-    const int nchunk = ceil_div(ml, kStatChunk), ldp = round_up(C, 32);
-    if (pend && pend->src.partial) {  // the producer's reduce pass rides in the statistics launch (X's first columns are written here)
-      STTS_LAUNCH_PROF("adain_partial_reduce_kernel", (size_t)s.rows() * C * 4 * (1 + pend->src.ksplit), adain_partial_reduce_kernel, dim3(ceil_div(C, 32), nchunk, s.n_utt), dim3(256), st,
-                       const_cast<float*>(X), ld, C, s.dev, ss, ldp, nchunk, pend->src);
-      pend->src = SplitSrc{};
-    } else
-    STTS_LAUNCH_PROF("adain_partial_kernel", (size_t)s.rows() * C * 4, adain_partial_kernel, dim3(ceil_div(C, 32), nchunk, s.n_utt), dim3(256), st, X, ld, C, s.dev, ss, ldp, nchunk, kStatChunk);
-    if (affine_lanes)
-      STTS_LAUNCH_PROF("adain_affine_lanes_kernel", (size_t)s.n_utt * nchunk * 2 * ldp * 4, adain_affine_lanes_kernel, dim3(ceil_div(ld_aff, 16), s.n_utt), dim3(256), st, ss, ldp, nchunk, s.dev, style_out, ld_style,
-                       gcol0, C, 1e-5f, aff, ld_aff, kStatChunk);
-    else
-    STTS_LAUNCH_PROF("adain_affine_kernel", (size_t)s.n_utt * nchunk * 2 * ldp * 4, adain_affine_kernel, dim3(ceil_div(ld_aff, 64), s.n_utt), dim3(64), st, ss, ldp, nchunk, s.dev, style_out, ld_style, gcol0, C,
-                       1e-5f, aff, ld_aff, kStatChunk);
-  };
-  // norm1 -> LeakyReLU -> conv1
-  GemmArgs a = gemm_args(s);
-  PendingReduce pend_mid;
-  if (pend_in && pend_in->src.partial) STTS_CHECK(pend_in->Y == x && pend_in->ldy == ldx, "adain block: the pending reduce does not belong to this input");
-  if (!fold) STTS_TRY(pending_finish(st, pend_in));
-  if (fold) {
-    affine(x, ldx, B.cin, B.kcin, B.n1.col0, act1, pend_in);
-    set_seg(a, 0, x, ldx, 0, B.conv1);
-    a.xaff = act1;
-    a.ld_xaff = B.kcin;
-  }
-  const bool wino1 = !fold && wino && *wino && B.w1.ready && force_tile == 0;
-  // (learned shortcut: conv2 in Winograd form + the 1x1 shortcut as a contraction of its own, added as the Winograd conv's residual)
-  static const bool wino2_sc = getenv("STTS_NO_WINO_CONV2SC") == nullptr;
-  const bool wino2 = !fold && wino && *wino && B.w2.ready && (!B.sc.W || wino2_sc) && force_tile == 0;
-  // fp32 Winograd branch: every normalised tensor is the output of a Winograd conv (conv1 -> norm2, conv2 -> the next block's norm1), whose output
-  // transform leaves the chunk statistics behind: the norms keep only their 64-thread affine launch (no adain_partial_kernel pass)
-  const bool wstats = stats && stats->chunk_rows == kWinoStatChunk && wino1 && wino2;
-  const int bw = wstats ? stats->bridge_w : 0;
-  auto affine_from = [&](const float* part, int C, int ld_aff, int gcol0, float* aff) {
-    const int wch = wino_stat_chunks(s), ldp = round_up(C, 32);
-    STTS_LAUNCH_PROF("adain_affine_lanes_kernel", (size_t)s.n_utt * wch * 2 * ldp * 4, adain_affine_lanes_kernel, dim3(ceil_div(ld_aff, 16), s.n_utt), dim3(256), st, part, ldp, wch, s.dev, style_out, ld_style,
-                     gcol0, C, 1e-5f, aff, ld_aff, kWinoStatChunk);
-  };
-  // 16-bit operand modes, large batches: the normalised activations are WRITTEN as 16-bit rows (act1 / act2 reinterpreted),
-  // so the contractions stage half the bytes and convert nothing; a learned shortcut reads a rounded copy of x (xs16)
-  const int h16 = (s.rows() >= rows16_threshold() && B.conv1.prec != PREC_F32 && force_tile == 0 && (!B.sc.W || xs16) && ldx % 8 == 0) ? B.conv1.prec : 0;
-  const int nchunk = ceil_div(ml, kStatChunk);
-  const bool fuse_stats = stats && h16 && !fold && !wino1 && !wino2;
-  if (!fold && !wino1) {
-    const bool ready = fuse_stats && stats->in_ready;
-    STTS_TRY(run_adain(st, s, x, ldx, B.cin, act1, B.kcin, style_out, ld_style, B.n1.col0, ACT_LRELU, nullptr, ready ? stats->in : ss, h16, ready));
-    set_seg(a, 0, act1, B.kcin, 0, B.conv1);
-    a.x16 = h16 != 0;
-  }
-  if (stats) stats->out_ready = false;
-  a.N = B.cout;
-  a.bias = B.conv1.bias;
-  a.Y = hbuf;
-  a.ldy = B.cout;
-  auto shortcut = [&](hipStream_t sst, float* out) -> int {
-    GemmArgs g = gemm_args(s);
-    set_seg(g, 0, x, ldx, 0, B.sc);
-    g.N = B.cout; g.bias = nullptr; g.Y = out; g.ldy = B.cout;
-    return launch_conv_gemm(sst, g, EPI_STORE, B.sc.npad, s.n_utt, ml, 0);
-  };
-  const bool sc_side = side && side->stream && side->out && wino1 && wino2 && B.sc.W && !gemm_profiler().on;
-  if (sc_side) {  // x is complete in st's order here; side->out was last read by the previous block's conv2, which st has queued before this event
-    STTS_HIP(hipEventRecord(side->fork, st));
-    STTS_HIP(hipStreamWaitEvent(side->stream, side->fork, 0));
-    const int rc = shortcut(side->stream, side->out);
-    STTS_HIP(hipEventRecord(side->join, side->stream));  // (recorded whatever rc is: st joins below or at the caller's error path via stream order)
-    if (rc) { (void)hipStreamWaitEvent(st, side->join, 0); return rc; }
-  }
-  if (wino1) {
-    // large batches: conv1 (k = 3) in Winograd F(6,3) form, 8 instead of 18 multiplies per 6 outputs (winograd.hip.h); AdaIN + LeakyReLU ride
-    // in its input transform (an elementwise, bandwidth-bound kernel: there the affine is free, unlike in the K loop)
-    if (bw && stats->planes_ready) {  // the previous block's bridge has normalised and transformed x
-      STTS_TRY(run_winograd(st, s, nullptr, 0, B.w1, nullptr, 0, ACT_NONE, nullptr, 0, 1.0f, *wino, nullptr, 0, nullptr, 0, WinoForm{true, true}));
-    } else {
-    if (wstats && stats->in_ready) affine_from(stats->in, B.cin, B.kcin, B.n1.col0, act1);
-    else affine(x, ldx, B.cin, B.kcin, B.n1.col0, act1);
-    STTS_TRY(run_winograd(st, s, x, ldx, B.w1, hbuf, B.cout, ACT_NONE, nullptr, 0, 1.0f, *wino, act1, B.kcin, wstats && !bw ? stats->mid : nullptr, round_up(B.cout, 32),
-                          WinoForm{false, bw != 0}));
-    }
-  } else {
-    if (fuse_stats && gemm16_will_run(a, EPI_STORE, B.conv1.npad, s.n_utt)) {
-      a.stat_part = stats->mid; a.ld_stat = round_up(B.cout, 32); a.stat_nchunk = nchunk;
-    }
-    SplitInfo info1{};
-    if (fold) a.defer = &info1;  // norm2's statistics launch finishes a split-K conv1
-    STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, B.conv1.npad, s.n_utt, ml, force_tile));
-    if (fold) pending_from(&pend_mid, info1, a);
-  }
-  const bool mid_ready = a.stat_part != nullptr;
-  // norm2 -> LeakyReLU -> conv2 (+ learned 1x1 shortcut as a second K segment | + identity residual), / sqrt(2)
-  GemmArgs b = gemm_args(s);
-  if (fold) {
-    affine(hbuf, B.cout, B.cout, B.cout, B.n2.col0, act2, &pend_mid);
-    set_seg(b, 0, hbuf, B.cout, 0, B.conv2);
-    b.xaff = act2;
-    b.ld_xaff = B.cout;
-  } else if (wino2) {
-    if (bw) {  // norm2 rides in the bridge below
-    } else if (wstats) affine_from(stats->mid, B.cout, B.cout, B.n2.col0, act2);
-    else affine(hbuf, B.cout, B.cout, B.cout, B.n2.col0, act2);
-  } else {
-    STTS_TRY(run_adain(st, s, hbuf, B.cout, B.cout, act2, B.cout, style_out, ld_style, B.n2.col0, ACT_LRELU, nullptr, mid_ready ? stats->mid : ss, h16, mid_ready));
-    set_seg(b, 0, act2, B.cout, 0, B.conv2);
-    b.x16 = h16 != 0;
-  }
-  if (B.sc.W) {
-    if (h16) {
-      if (!xs16_ready) launch_cast_rows(st, h16, x, ldx, B.cin, xs16, ldx, s.rows());
-      set_seg(b, 1, reinterpret_cast<const float*>(xs16), ldx, 0, B.sc);
-    } else {
-      set_seg(b, 1, x, ldx, 0, B.sc);
-    }
-  } else {
-    b.R = x;
-    b.ldr = ldx;
-  }
-  b.N = B.cout;
-  b.bias = B.conv2.bias;
-  b.Y = y;
-  b.ldy = ldy;
-  b.alpha = 0.70710678118654752440f;
-  const bool y16_epi = y16 && h16 && !wino2;  // the 16-bit contraction's epilogue rounds y for the next block's shortcut
-  if (y16_epi) {
-    b.Y16 = y16;
-    b.ldy16 = ldy16;
-  }
-  if (wino2) {
-    const float* res = x;
-    int ld_res = ldx;
-    if (B.sc.W && sc_side) {
-      STTS_HIP(hipStreamWaitEvent(st, side->join, 0));
-      res = side->out;
-      ld_res = B.cout;
-    } else if (B.sc.W) {  // act1 is free again (conv1 has consumed it): the shortcut's output lives there
-      STTS_TRY(shortcut(st, act1));
-      res = act1;
-      ld_res = B.cout;
-    }
-    if (bw) {
-      // conv1 -> norm2 -> conv2: contraction, bridge, contraction (conv1's output is needed by nobody else: hbuf stays unwritten); with a next block, conv2 ->
-      // its norm1 -> its conv1 the same way - that bridge writes y (+ residual, / sqrt 2), the next block's shortcut and residual input
-      STTS_TRY(run_wino_bridge(st, s, B.w1, nullptr, 0, 1.0f, nullptr, 0, B.w2, style_out, ld_style, B.n2.col0, B.cout, nullptr, 0, nullptr, 0, *wino, bw));
-      const AdainBlockW* nb = stats->next;
-      STTS_TRY(run_winograd(st, s, nullptr, 0, B.w2, y, ldy, ACT_NONE, res, ld_res, b.alpha, *wino, nullptr, 0, nullptr, 0, WinoForm{true, nb != nullptr}));
-      if (nb) STTS_TRY(run_wino_bridge(st, s, B.w2, res, ld_res, b.alpha, y, ldy, nb->w1, style_out, ld_style, nb->n1.col0, nb->cin, stats->cst, stats->cst_ld, y, ldy, *wino, bw));
-      stats->planes_ready = nb != nullptr;
-      STTS_HIP(hipGetLastError());
-      return 0;
-    }
-    const bool leave = wstats && stats->out;  // the statistics of y for the next block's norm1 (its hidden columns)
-    STTS_TRY(run_winograd(st, s, hbuf, B.cout, B.w2, y, ldy, ACT_NONE, res, ld_res, b.alpha, *wino, act2, B.cout, leave ? stats->out : nullptr, leave ? stats->out_ld : 0));
-    if (leave) stats->out_ready = true;
-  } else {
-    if (fuse_stats && stats->out && gemm16_will_run(b, EPI_STORE, B.conv2.npad, s.n_utt)) {
-      b.stat_part = stats->out; b.ld_stat = stats->out_ld; b.stat_nchunk = nchunk;
-      stats->out_ready = true;
-    }
-    SplitInfo info2{};
-    if (fold && pend_out && !y16) b.defer = &info2;  // (a rounded copy of y is cast from y right below: y must exist then)
-    STTS_TRY(launch_conv_gemm(st, b, EPI_STORE, B.conv2.npad, s.n_utt, ml, force_tile));
-    if (fold && pend_out && !y16) pending_from(pend_out, info2, b);
-  }
-  if (y16 && !y16_epi) launch_cast_rows(st, B.conv1.prec, y, ldy, B.cout, y16, ldy16, s.rows(), B.cout);  // (cout % 8 == 0: caller)
-  STTS_HIP(hipGetLastError());
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// stage: Decoder.forward (models/decoder.py:47-60)
-// ------------------------------------------------------------------------------------------------
-inline int decoder_forward(stts_ctx* c, hipStream_t st, const Seg& s, const float* asr, int ld_asr, const float* pitch, const float* energy,
-                           const float* style, float* x_out, int ld_x, Arena& ws, const SideWork* side_lane = nullptr) {
-  const stts_model_dims& d = c->d;
-  const long R = s.rows();
-  const int ccat = d.dec_hidden + d.dec_residual + 2, ldcat = c->dec[1].kcin;  // 578 -> 608 (640 in the 16-bit modes): the packed input width
-  const int cenc = d.inter_dim + 2, ldenc = c->dec[0].kcin;                    // 130 -> 160 (192)
-  STTS_CHECK(ldcat >= ccat && ldenc >= cenc, "decoder_forward: packed widths %d / %d do not cover %d / %d channels", ldcat, ldenc, ccat, cenc);
-  // (dec[0] runs on the encoder-input width, the other blocks on the concat width: scratch is sized by the wider of the two - a config
-  //  with inter_dim > hidden_dim + residual_dim is legal)
-  const int ldwide = std::max(ldenc, ldcat);
-  float* enc_in = ws.get<float>(R * ldenc);
-  float* xa = ws.get<float>(R * ldcat);
-  float* xb = ws.get<float>(R * ldcat);
-  float* act1 = ws.get<float>(R * ldwide);
-  float* hbuf = ws.get<float>(R * d.dec_hidden);
-  float* act2 = ws.get<float>(R * d.dec_hidden);
-  float* ss = ws.get<float>(adain_part_floats(s, ldwide));
-  float* ss_in = ws.get<float>(adain_part_floats(s, ldwide, kWinoStatChunk));   // statistics from the producers' epilogues (AdainStats): 16-bit contractions, or
-  float* ss_mid = ws.get<float>(adain_part_floats(s, ldwide, kWinoStatChunk));  // the fp32 Winograd output transforms (chunks of 24 rows: the larger footprint)
-  float* sty = ws.get<float>((size_t)s.n_utt * c->dec_style.ld());
-  // conv1 of every block in Winograd form once the batch is large enough to be throughput-bound (B = 1: 35 vs 30 us)
-  WinoScratch wino;
-  if (R > fold_rows() && c->dec[1].w1.ready) wino.p = ws.get<float>(wino_scratch_floats(s, c->dec[1].w1));
-  // the learned shortcuts' outputs when they run on the side lane (run_adain_block; carved whenever the Winograd branch may run, so the size does not depend on the caller's streams)
-  float* sc_out = wino.p && c->dec[1].sc.W ? ws.get<float>(R * d.dec_hidden) : nullptr;
-  // 16-bit modes, large batches: rounded copies of the blocks' inputs for the learned shortcuts, ping-pong like xa / xb: a block's
-  // conv2 epilogue writes the hidden columns of the next block's copy, the constant columns (asr_res, F0, N) are rounded once
-  const bool x16 = R >= rows16_threshold() && c->prec != PREC_F32 && d.dec_hidden % 8 == 0;
-  unsigned short* xs16a = x16 ? ws.get<unsigned short>(R * ldwide) : nullptr;
-  unsigned short* xs16b = x16 ? ws.get<unsigned short>(R * ldwide) : nullptr;
-  STTS_CHECK(ws.ok, "decoder_forward: workspace too small");
-  STTS_DRY_RETURN(ws);
-  STTS_TRY(run_style(st, c->dec_style, style, s.n_utt, sty));
-  FrontArgs fa;
-  fa.asr = asr; fa.ld_asr = ld_asr; fa.pitch = pitch; fa.energy = energy;
-  for (int i = 0; i < 3; ++i) { fa.wf[i] = c->front_wf[i]; fa.wn[i] = c->front_wn[i]; }
-  fa.bf = c->front_bf; fa.bn = c->front_bn;
-  fa.enc_in = enc_in; fa.ld_enc = ldenc; fa.xa = xa; fa.xb = xb; fa.ld_x = ldcat;
-  fa.c_asr = d.inter_dim; fa.c_hidden = d.dec_hidden; fa.c_res = d.dec_residual;
-  STTS_LAUNCH_PROF("decoder_front_kernel", (size_t)R * (d.inter_dim + 2 + ldenc + 2 * 4) * 4, decoder_front_kernel, rows_grid(s, ldenc / 4), dim3(256), st, fa, s.dev);
-  // asr_res = wn-conv1x1(asr) into the residual columns of both concat buffers (decoder.py:54)
-  for (float* dst : {xa, xb}) {
-    GemmArgs a = gemm_args(s);
-    set_seg(a, 0, asr, ld_asr, 0, c->asr_res);
-    a.N = d.dec_residual; a.bias = c->asr_res.bias; a.Y = dst; a.ldy = ldcat; a.ycol0 = d.dec_hidden;
-    STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, c->asr_res.npad, s.n_utt, s.max_len()));
-  }
-  const int lds = c->dec_style.ld();
-  const int ctail = d.dec_hidden & ~7, ntail = ldcat - ctail;  // constant columns (from the 8-aligned column at or below dec_hidden)
-  auto cast_tail = [&](const float* src, unsigned short* dst) {
-    launch_cast_rows(st, c->prec, src + ctail, ldcat, ccat - ctail, dst + ctail, ldcat, R, ntail);
-  };
-  // dec[0] rounds its own (narrow) input into xs16b as scratch, so xs16b's constant columns are filled after it
-  // 16-bit modes, large batches: the statistics of a block's input come out of the previous block's conv2 epilogue (its 512 hidden columns) and,
-  // for the constant columns [asr_res | F0 | N] that every decode block sees, from ONE statistics pass here
-  static const bool no_stat_fuse = getenv("STTS_NO_STAT_FUSE") != nullptr;  // experiments: every norm runs its own statistics pass
-  static const bool no_wino_stats = getenv("STTS_NO_WINO_STATS") != nullptr;  // experiments: the fp32 Winograd branch runs a statistics pass per norm
-  const bool wstat_mode = c->prec == PREC_F32 && wino && !no_wino_stats;
-  const bool use_stats = (x16 && !no_stat_fuse) || wstat_mode;
-  AdainStats stats;
-  if (wstat_mode) stats.chunk_rows = kWinoStatChunk;
-  stats.mid = ss_mid;
-  stats.out = ss_in;
-  stats.out_ld = round_up(ccat, 32);
-  // one launch between the chained convs where the batch covers the chip with (utterance, slab) blocks (adain_bridge_slab); hbuf, ss_mid and the hidden columns
-  // of ss_in are then unused
-  const int bridge_w = wstat_mode ? adain_bridge_slab(s, c->dec, 5) : 0;
-  if (bridge_w) {
-    stats.bridge_w = bridge_w;
-    stats.cst = ss_in;
-    stats.cst_ld = stats.out_ld;
-    wino.mp_kc = c->dec[1].w1.planes.kc;  // (the scratch is sized by this conv)
-  }
-  // small batches: a block's conv2 leaves its split-K reduce pass to the next block's first statistics launch (PendingReduce)
-  PendingReduce pend;
-  bool const_ready = false;
-  // the chunk statistics of the constant columns [asr_res | F0 | N] of every later block's input, ONCE (xa and xb hold the same constant columns)
-  auto const_columns = [&]() -> int {
-    if (!(stats.out_ready || bridge_w) || const_ready) return 0;
-    const int nchunk = ceil_div(s.max_len(), stats.chunk_rows), cc0 = d.dec_hidden, ncst = ccat - cc0;
-    STTS_CHECK(cc0 % 32 == 0, "decoder_forward: hidden_dim must be a multiple of 32");
-    STTS_LAUNCH_PROF("adain_partial_kernel", (size_t)R * ncst * 4, adain_partial_kernel, dim3(ceil_div(ncst, 32), nchunk, s.n_utt), dim3(256), st, xa + cc0, ldcat, ncst, s.dev,
-                     ss_in + cc0, stats.out_ld, nchunk, stats.chunk_rows);
-    const_ready = true;
-    return 0;
-  };
-  if (bridge_w) {  // (block 0's second bridge already merges them)
-    STTS_CHECK(c->dec[0].cout == d.dec_hidden, "decoder_forward: the blocks' width %d is not hidden_dim %d", c->dec[0].cout, d.dec_hidden);
-    STTS_TRY(const_columns());
-    stats.next = &c->dec[1];
-  }
-  STTS_TRY(run_adain_block(st, s, c->dec[0], sty, lds, enc_in, ldenc, xa, ldcat, act1, hbuf, act2, ss, 0, &wino, xs16b, false, xs16a, ldcat, use_stats ? &stats : nullptr,
-                           nullptr, &pend));
-  if (x16) {
-    cast_tail(xa, xs16a);
-    cast_tail(xb, xs16b);
-  }
-  // (once, as soon as a block has left statistics of its output: whichever block that is, the constant columns must be there before the next norm1 merges them)
-  STTS_TRY(const_columns());
-  float* cur = xa;
-  float* nxt = xb;
-  unsigned short* cur16 = xs16a;
-  unsigned short* nxt16 = xs16b;
-  // Measured (3-s utterances, same box, alternated): B = 16: 5.82 -> 5.74 ms per step (+1.4 %); B = 8: 3.505 -> 3.52 (-0.5 %), B = 4: 2.39 -> 2.42 (-1.3 %): below
-  // ~12 000 rows the two cross-queue waits per block cost what the overlap gains, and the shortcuts stay on the caller's stream (STTS_SC_SIDE_MIN_ROWS).
-  static const long sc_side_min_rows = getenv("STTS_SC_SIDE_MIN_ROWS") ? atol(getenv("STTS_SC_SIDE_MIN_ROWS")) : 12000;
-  SideWork side;
-  if (side_lane && sc_out && R >= sc_side_min_rows) {
-    side = *side_lane;
-    side.out = sc_out;
-  }
-  auto blocks = [&]() -> int {
-    for (int i = 1; i <= 4; ++i) {
-      float* dst = i == 4 ? x_out : nxt;
-      const int ldd = i == 4 ? ld_x : ldcat;
-      STTS_TRY(const_columns());
-      stats.in = ss_in;
-      stats.in_ready = stats.out_ready;  // (the previous block's conv2 - conv_gemm16_kernel's epilogue or the fp32 Winograd output transform - left the statistics of its output)
-      stats.out = i == 4 ? nullptr : ss_in;
-      stats.next = bridge_w && i < 4 ? &c->dec[i + 1] : nullptr;
-      STTS_TRY(run_adain_block(st, s, c->dec[i], sty, lds, cur, ldcat, dst, ldd, act1, hbuf, act2, ss, 0, &wino, cur16, x16, i == 4 ? nullptr : nxt16, ldcat,
-                               use_stats ? &stats : nullptr, &pend, &pend, side.stream ? &side : nullptr));
-      std::swap(cur, nxt);
-      std::swap(cur16, nxt16);
-    }
-    return 0;
-  };
-  const int rc = blocks();
-  if (rc && side.stream) {  // an error path may have left a shortcut running on the side lane: the caller's stream must not outrun it (it reads x and writes the workspace)
-    (void)hipEventRecord(side.join, side.stream);
-    (void)hipStreamWaitEvent(st, side.join, 0);
-  }
-  if (rc) return rc;
-  return pending_finish(st, &pend);  // the last block's output has no AdaIN behind it
-}
-
 }  // namespace stts
 
+#include "adain_block.hip.h"
 #include "flow.hip.h"
 
 namespace stts {

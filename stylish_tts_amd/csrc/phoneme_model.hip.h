@@ -505,15 +505,17 @@ inline int pitch_energy_forward(stts_ctx* c, PhonemeModel& M, hipStream_t st, co
   float* t1 = ws.get<float>(Rf * C);
   float* t2 = ws.get<float>(Rf * C);
   float* x = cross_out ? cross_out : ws.get<float>(Rf * C);
-  float* act1 = ws.get<float>(Rf * C);
-  float* hb = ws.get<float>(Rf * C);
-  float* act2 = ws.get<float>(Rf * C);
-  float* ss = ws.get<float>(adain_part_floats(sf, C));
-  WinoScratch wino;  // large batches: Winograd convs
-  if (Rf > fold_rows() && P.f0[0].w1.ready) wino.p = ws.get<float>(wino_scratch_floats(sf, P.f0[0].w1));
-  // ... whose output transforms leave the AdaIN statistics of what they write (decoder_forward's scheme: AdainStats with 24-row chunks)
-  static const bool no_wino_stats = getenv("STTS_NO_WINO_STATS") != nullptr;
-  const bool wstat_mode = wino && !no_wino_stats;
+  BlockIO io;
+  io.act1 = ws.get<float>(Rf * C);
+  io.hbuf = ws.get<float>(Rf * C);
+  io.act2 = ws.get<float>(Rf * C);
+  io.ss = ws.get<float>(adain_part_floats(sf, C));
+  // large batches: Winograd convs, whose output transforms leave the AdaIN statistics of what they write (decoder_forward's scheme: a BlockChain with 24-row chunks)
+  const BlockSwitches sw = block_switches();
+  const ChainPlan plan = plan_adain_chain(sf, PREC_F32, P.f0, 3, 0, ChainOffer{true, false, false, false}, sw);
+  WinoScratch wino;
+  if (plan.wino) wino.p = ws.get<float>(wino_scratch_floats(sf, P.f0[0].w1));
+  const bool wstat_mode = plan.wino_stats;
   float* ss_in = wstat_mode ? ws.get<float>(adain_part_floats(sf, C, kWinoStatChunk)) : nullptr;
   float* ss_mid = wstat_mode ? ws.get<float>(adain_part_floats(sf, C, kWinoStatChunk)) : nullptr;
   float* ss_x = wstat_mode ? ws.get<float>(adain_part_floats(sf, C, kWinoStatChunk)) : nullptr;  // statistics of x: one pass for both branches' first norm
@@ -546,25 +548,20 @@ inline int pitch_energy_forward(stts_ctx* c, PhonemeModel& M, hipStream_t st, co
                      P.cp_dw_b, 5, (int)ACT_SILU);
   STTS_TRY(gemm_store(st, sf, t2, C, 0, P.cp2, x, C, 0, ACT_NONE, base, C, 0.70710678118654752440f));
   // F0 and N branches: 3 AdaptiveDecoderBlocks each + 1x1 projection to one channel
+  io.style = sty; io.ld_style = lds; io.ldx = io.ldy = C; io.wino = &wino;
   for (int br = 0; br < 2; ++br) {
     const AdainBlockW* blocks = br == 0 ? P.f0 : P.n;
     const float* cur = x;
     float* bufs[2] = {t1, t2};
-    AdainStats stats;
-    stats.chunk_rows = kWinoStatChunk;
-    stats.mid = ss_mid;
+    BlockChain chain(plan, ss_mid);
     const bool x_stats = wstat_mode && blocks[0].cin == C && C % 32 == 0;
-    if (x_stats && br == 0) {
-      const int nchunk = wino_stat_chunks(sf);
-      STTS_LAUNCH_PROF("adain_partial_kernel", (size_t)Rf * C * 4, adain_partial_kernel, dim3(ceil_div(C, 32), nchunk, sf.n_utt), dim3(256), st, x, C, C, sf.dev, ss_x, C, nchunk, kWinoStatChunk);
-    }
+    if (x_stats && br == 0) launch_adain_partial(st, sf, x, C, C, ss_x, C, kWinoStatChunk);
     for (int i = 0; i < 3; ++i) {
       // norm1 of blocks 1, 2: statistics left by the previous block's conv2; norm2: by this block's conv1 (both Winograd output transforms)
-      stats.in = i == 0 ? ss_x : ss_in;
-      stats.in_ready = i == 0 ? x_stats : (stats.out_ready && blocks[i].cin == blocks[i - 1].cout);
-      stats.out = (i < 2 && blocks[i].cout <= C) ? ss_in : nullptr;
-      stats.out_ld = round_up(blocks[i].cout, 32);
-      STTS_TRY(run_adain_block(st, sf, blocks[i], sty, lds, cur, C, bufs[i & 1], C, act1, hb, act2, ss, 0, &wino, nullptr, false, nullptr, 0, wstat_mode ? &stats : nullptr));
+      chain.link(i == 0 ? ss_x : ss_in, i == 0 ? x_stats : (chain.out_ready && blocks[i].cin == blocks[i - 1].cout), (i < 2 && blocks[i].cout <= C) ? ss_in : nullptr,
+                 round_up(blocks[i].cout, 32), nullptr);
+      io.x = cur; io.y = bufs[i & 1];
+      STTS_TRY(adain_block(st, sf, blocks[i], io, chain, sw));
       cur = bufs[i & 1];
     }
     const ChanConvSet cs{cur, br == 0 ? P.f0_w : P.n_w, br == 0 ? P.f0_b : P.n_b, br == 0 ? f0 : nrg};

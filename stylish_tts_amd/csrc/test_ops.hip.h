@@ -262,10 +262,13 @@ int stts_op_adain_block(stts_ctx* c, void* stream, const char* prefix, int n_utt
   STTS_CHECK(ldx == B.kcin, "op_adain_block: ldx must equal cin padded to 32 (%d)", B.kcin);
   Seg s{n_utt, seg_off_host, seg_off_dev};
   Arena a(ws, ws_bytes);
-  float *act1, *h, *act2, *ss, *sty;
-  STTS_TRY(op_scratch(a, s, B.kcin, B.cout, &act1, &h, &act2, &ss, &sty, T.ld()));
+  BlockIO io;  // (no Winograd scratch, no chain: the folded form or the apply pass)
+  float* sty;
+  STTS_TRY(op_scratch(a, s, B.kcin, B.cout, &io.act1, &io.hbuf, &io.act2, &io.ss, &sty, T.ld()));
   STTS_TRY(run_style(st, T, style, n_utt, sty));
-  return run_adain_block(st, s, B, sty, T.ld(), x, ldx, y, ldy, act1, h, act2, ss);
+  io.style = sty; io.ld_style = T.ld(); io.x = x; io.ldx = ldx; io.y = y; io.ldy = ldy;
+  BlockChain chain;
+  return adain_block(st, s, B, io, chain, block_switches());
   API_END
 }
 

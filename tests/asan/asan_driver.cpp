@@ -15,6 +15,8 @@
 // `launchtrace <precision> <case> : <trace>` around every stage walk.  In the compact grid of conv_gemm_f32, grid.y is the row-tile count and grid.z the split-K factor.
 // A second weight dump (a model with 96 flow channels) adds `flowtrace <precision> generic96* -` lines: the flow as plain contractions with the gate,
 // split-accumulate and couple epilogues.
+// The AdaptiveDecoderBlock chains the same way: `blocktrace <precision> <case> <switches> : <trace>` per case of block_section below, in all four precisions;
+// `asan_driver <weights> block` prints those lines only (fp32 and bf16), for one process per setting of the block's process-wide switches.
 // `asan_driver <weights> gemm` prints the gemmtrace lines only (no finalize): the STTS_* switches of the contractions are read once per process, so
 // tests/asan/build_and_run.py starts one process per setting.
 #include <algorithm>
@@ -706,6 +708,108 @@ static void cfm_ops_section() {
   }
 }
 
+// The AdaptiveDecoderBlock chains (csrc/adain_block.hip.h: plan_adain_block / plan_adain_chain): `blocktrace <precision> <case> <switches> : [error ]<trace>` of one
+// entry-point call under `switches` ("STTS_ADAIN_BRIDGE=0|1" or "-": the switch is read per call).  The block's other switches are read once per process:
+// `asan_driver <weights> block` prints these lines alone and tests/asan/build_and_run.py starts one such process per setting.
+template <typename Call>
+static void block_case(int prec, const std::string& what, const char* switches, Call call) {
+  unsetenv("STTS_ADAIN_BRIDGE");
+  if (strcmp(switches, "-") != 0) setenv("STTS_ADAIN_BRIDGE", strchr(switches, '=') + 1, 1);
+  stts_stub_trace_begin();
+  const int rc = call();
+  const char* trace = stts_stub_trace_end();
+  unsetenv("STTS_ADAIN_BRIDGE");
+  if (rc) fprintf(stderr, "blocktrace %d %s %s: %s\n", prec, what.c_str(), switches, stts_last_error());
+  printf("blocktrace %d %s %s : %s%s\n", prec, what.c_str(), switches, rc ? "error " : "", trace);
+}
+
+struct Workspace {  // untouched: the host code only computes pointers into it
+  char* p;
+  size_t bytes;
+  explicit Workspace(size_t n) : p((char*)malloc(n ? n : 1)), bytes(n) {}
+  ~Workspace() { free(p); }
+};
+
+// stts_decoder_forward (frame: stts_frame_path, whose decoder may put the learned shortcuts on a side lane) over utterances of `lens` rows
+static void decoder_block_case(stts_ctx* c, int prec, const std::vector<int>& lens, const std::string& what, const char* switches, bool frame = false) {
+  const int n = (int)lens.size();
+  const std::vector<int32_t> off = offsets(lens);
+  const long R = off[n];
+  Workspace ws(stts_frame_workspace_bytes(c, R, n, *std::max_element(lens.begin(), lens.end())));
+  auto asr = buf(R * 128), pitch = buf(R), energy = buf(R), style = buf((size_t)n * 64), x = buf(frame ? 0 : R * 512);
+  auto pn = buf(frame ? R * 128 : 0), sn = buf(frame ? R * 75 : 0), ph = buf(1), audio = buf(frame ? R * 75 : 0);
+  block_case(prec, (frame ? "frame_" : "dec_") + what, switches, [&] {
+    return frame ? stts_frame_path(c, nullptr, n, off.data(), off.data(), asr.data(), 128, pitch.data(), energy.data(), style.data(), pn.data(), sn.data(), ph.data(), 0,
+                                   audio.data(), ws.p, ws.bytes, 0)
+                 : stts_decoder_forward(c, nullptr, n, off.data(), off.data(), asr.data(), 128, pitch.data(), energy.data(), style.data(), x.data(), 512, ws.p, ws.bytes);
+  });
+}
+
+static void block_section(stts_ctx* c, int prec, const Widths& wd, const stts_model_dims& d, bool phoneme_rate) {
+  auto uni = [](int b, int len) { return std::vector<int>(b, len); };
+  const bool f32 = prec == 0 || prec == 3;
+  if (f32) {
+    // fold -> Winograd: AdaIN rides in the contractions' staging up to fold_rows() = 2 500 rows
+    for (int len : {300, 2500, 2501}) decoder_block_case(c, prec, {len}, "1x" + std::to_string(len), "-");
+    // the bridge: 96 <= utterances x 32 slabs <= 384 and every utterance within the 256 groups of six rows (1 536) a bridge block holds
+    const std::vector<std::pair<std::string, std::vector<int>>> shapes = {{"2x1300", uni(2, 1300)}, {"3x960", uni(3, 960)},   {"4x700", uni(4, 700)},
+                                                                          {"12x960", uni(12, 960)}, {"13x960", uni(13, 960)}, {"1537+2x960", {1537, 960, 960}}};
+    for (const auto& sh : shapes)
+      for (const char* sw : {"-", "STTS_ADAIN_BRIDGE=0", "STTS_ADAIN_BRIDGE=1"}) decoder_block_case(c, prec, sh.second, sh.first, sw);
+  } else {
+    // 16-bit rows from rows16_threshold() = 3 840 rows, folded up to 4 096: two long utterances around both; the 110 x (30 .. 50) batch of
+    // tests/test_hip_gemm16_epilogues.py (4 400 rows: conv_gemm16_kernel with the statistics from its epilogues) and its first 100 utterances (3 960 rows: folded)
+    decoder_block_case(c, prec, {300}, "1x300", "-");
+    for (int rows : {3839, 3840, 4096, 4097}) decoder_block_case(c, prec, {rows - rows / 2, rows / 2}, std::to_string(rows) + "rows", "-");
+    std::vector<int> lens;
+    for (int i = 0; i < 110; ++i) lens.push_back(30 + i % 21);
+    decoder_block_case(c, prec, lens, "110utt", "-");
+    lens.resize(100);
+    decoder_block_case(c, prec, lens, "100utt", "-");
+  }
+  if (prec == 0)  // the learned shortcuts on the caller's stream below 12 000 rows, on the side lane from there
+    for (int b : {12, 13})
+      for (const char* sw : {"-", "STTS_ADAIN_BRIDGE=0"}) decoder_block_case(c, prec, uni(b, 960), std::to_string(b) + "x960", sw, true);
+  {  // stts_op_adain_block: one block with neither Winograd scratch nor a chain (folded, then the apply pass)
+    const int cin = d.inter_dim + 2, ldx = (cin + 31) / 32 * 32;
+    for (const std::vector<int>& lens : {uni(1, 300), uni(2, 2049)}) {
+      const int n = (int)lens.size();
+      const std::vector<int32_t> off = offsets(lens);
+      const long R = off[n];
+      Workspace ws(stts_frame_workspace_bytes(c, R, n, lens[0]));
+      auto x = buf(R * ldx), style = buf((size_t)n * 64), y = buf(R * d.dec_hidden);
+      block_case(prec, "op_" + std::to_string(n) + "x" + std::to_string(lens[0]), "-", [&] {
+        return stts_op_adain_block(c, nullptr, "speech_predictor.decoder.encode", n, off.data(), off.data(), x.data(), ldx, cin, d.dec_hidden, style.data(), y.data(), d.dec_hidden,
+                                   ws.p, ws.bytes);
+      });
+    }
+  }
+  if (!phoneme_rate) return;
+  // the pitch/energy predictor's two branches of three blocks (always fp32 operands): three utterances of 2 500 and of 2 501 frames
+  for (int last : {840, 841}) {
+    const std::vector<int> toks = uni(3, 50), frames = {830, 830, last};
+    const std::vector<int32_t> to = offsets(toks), fo = offsets(frames);
+    const long P = to[3], T = fo[3];
+    Workspace ws(stts_phoneme_workspace_bytes(c, P, T, 3, 50, last));
+    std::vector<int32_t> dur(P, 1);
+    auto mu = buf(P * 256), sty = buf(3 * 64), f0 = buf(T), en = buf(T);
+    block_case(prec, "pe_" + std::to_string(T) + "frames", "-", [&] {
+      return stts_pitch_energy_forward(c, nullptr, 3, to.data(), to.data(), fo.data(), fo.data(), dur.data(), mu.data(), 256, sty.data(), f0.data(), en.data(), nullptr, nullptr,
+                                       ws.p, ws.bytes, 0);
+    });
+  }
+  for (const std::vector<int>& frames : {std::vector<int>{240, 17, 96}, uni(2, 1300)}) {  // HubertPitchEnergyPredictor: no statistics chain
+    const int n = (int)frames.size(), ldf = (wd.hubert_dim + 31) / 32 * 32;
+    const std::vector<int32_t> off = offsets(frames);
+    const long T = off[n];
+    Workspace ws(stts_hubert_workspace_bytes(c, T, n, frames[0]));
+    auto pe = buf((size_t)n * d.style_dim), feats = buf(T * ldf), f0 = buf(T), en = buf(T);
+    block_case(prec, "hubert_" + std::to_string(T) + "frames", "-", [&] {
+      return stts_hubert_pitch_energy_forward(c, nullptr, n, off.data(), off.data(), feats.data(), ldf, pe.data(), f0.data(), en.data(), nullptr, ws.p, ws.bytes);
+    });
+  }
+}
+
 struct Tensor {
   std::string name;
   int ndim;
@@ -763,14 +867,17 @@ static int read_weights(const char* path, Dims& dims, std::vector<Tensor>& w) {
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    fprintf(stderr, "usage: asan_driver <weights.bin> [gemm | <narrow weights.bin>]\n");
+    fprintf(stderr, "usage: asan_driver <weights.bin> [gemm | block | <narrow weights.bin>]\n");
     return 2;
   }
-  gemm_section();
-  if (argc > 2 && strcmp(argv[2], "gemm") == 0) return 0;
-  epi_section();
-  norm_section();
-  cfm_ops_section();
+  const bool block_only = argc > 2 && strcmp(argv[2], "block") == 0;
+  if (!block_only) {
+    gemm_section();
+    if (argc > 2 && strcmp(argv[2], "gemm") == 0) return 0;
+    epi_section();
+    norm_section();
+    cfm_ops_section();
+  }
   Dims dims;
   std::vector<Tensor> w;
   if (read_weights(argv[1], dims, w)) return 2;
@@ -788,12 +895,23 @@ int main(int argc, char** argv) {
   };
   const Widths wd{width("hubert_speech_predictor.phone_encoder.phone_emb.weight", 1), width("hubert_speech_predictor.style_encoder.0.weight", 1),
                   width("pe_mel_style_encoder.shared.0.weight_orig", 0), width("cfm_pitch_predictor.asr_emb.0.weight", 1)};
+  if (block_only) {  // the block cases alone, fp32 and bf16: one process per setting of the block's once-per-process switches
+    for (int prec : {0, 1}) {
+      stts_ctx* cb = nullptr;
+      if (new_ctx(d, prec, w, &cb)) return 1;
+      CK(stts_finalize_weights(cb, prec == 0 ? STTS_W_FRAME_PATH | STTS_W_PITCH_ENERGY | STTS_W_HUBERT_PE : STTS_W_DECODER));
+      block_section(cb, prec, wd, d, prec == 0);
+      stts_ctx_destroy(cb);
+    }
+    return 0;
+  }
   for (int prec = 0; prec <= 3; ++prec) {  // fp32, fp16 operands (16-bit weight copies are packed too), fp32 on the f32 matrix cores
-    if (prec == 1) {  // bf16: the reverse flow alone (its kernel choice has branches of its own; the packing is fp16's with another rounding)
+    if (prec == 1) {  // bf16: the reverse flow and the decoder alone (their kernel choices have branches of their own; the packing is fp16's with another rounding)
       stts_ctx* cf = nullptr;
       if (new_ctx(d, prec, w, &cf)) return 1;
-      CK(stts_finalize_weights(cf, STTS_W_FLOW));
+      CK(stts_finalize_weights(cf, STTS_W_FLOW | STTS_W_DECODER));
       if (flow_section(cf, prec)) return 1;
+      block_section(cf, prec, wd, d, false);
       stts_ctx_destroy(cf);
       continue;
     }
@@ -824,6 +942,7 @@ int main(int argc, char** argv) {
     digest("rmvpe");
     printf("precision %d: %zu tensors loaded and packed\n", prec, w.size());
     if (flow_section(c, prec)) return 1;
+    block_section(c, prec, wd, d, true);
     if (prec != 3) {  // the stage walks: once per operand width
       if (frame_case(c, std::vector<int>(8, 960), "cfg2: 8 x 3 s")) return 1;
       if (frame_case(c, {960}, "B = 1 x 3 s")) return 1;

@@ -7,7 +7,8 @@ Steps: (1) hipcc --cuda-host-only -fsanitize=address,undefined -c for every tran
 (2) link it with hip_stub.cpp into libstylish_hip_asan.so (the fat-binary symbol the host code references is defined as an
 empty blob), (3) dump the synthetic weights of every inference module, of the voice-conversion models, of the CFM estimator, of a narrow
 AdaptiveHubert, of a narrow text aligner (with three TDNN layers and with one) and of a small RMVPE to a binary file, (4) run asan_driver on it.
-(5) run `asan_driver <weights> gemm` (the contraction cases only) once per setting of GEMM_SETTINGS, each line prefixed with `[setting]`.
+(5) run `asan_driver <weights> gemm` (the contraction cases only) once per setting of GEMM_SETTINGS, and `asan_driver <weights> block` (the AdaptiveDecoderBlock
+cases only) once per setting of BLOCK_SETTINGS, each line prefixed with `[setting]`.
 Exit code 0 = no sanitizer report, every stage accepted its workspace for every shape, and the packed bytes did not depend on the order of the
 finalizes.  The driver's `digest <precision> <what> <hex>` lines say what was packed: two builds of the library pack the same bytes exactly when
 these lines are the same."""
@@ -24,6 +25,8 @@ sys.path.insert(0, ROOT)
 # the process-wide switches of the contractions (csrc/gemm_plan.hip.h gemm_switches)
 GEMM_SETTINGS = ["STTS_NO_X3=1", "STTS_X3_REM=1", "STTS_X3_TILE=5", "STTS_X3_TILE=6", "STTS_X3_TILE=22", "STTS_X3P_GLDS=0", "STTS_TILE16=14", "STTS_TILE16=16", "STTS_TILE16=18",
                  "STTS_SPLITK_MIN_ITERS=2", "STTS_GEMM16_MIN_TILES=1"]
+# the process-wide switches of the AdaptiveDecoderBlock chains (csrc/adain_block.hip.h block_switches)
+BLOCK_SETTINGS = ["STTS_NO_WINO_STATS=1", "STTS_NO_STAT_FUSE=1", "STTS_NO_WINO_CONV2SC=1", "STTS_AFFINE_SERIAL=1", "STTS_FOLD_ROWS=0", "STTS_SC_SIDE_MIN_ROWS=0"]
 
 
 def write_tensors(f, m, spec, seen=None):
@@ -97,6 +100,9 @@ def main(build_dir):
         f.write(bytes(_lib.dims_from_config(narrow)) + bytes(_lib.CfmDims(**params.CFM_DEFAULT_DIMS)) + bytes(hubert_ssl.dims_struct(ssl_arch)) + extra_dims)
         write_tensors(f, "speech_predictor", params.module_spec("speech_predictor", narrow))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    # the block cases under each of the block's process-wide switches, one fresh process per setting, next to the whole run (they are independent of it)
+    blocks = [(s, subprocess.Popen([exe, wpath, "block"], env=dict(env, **dict([s.split("=")])), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True))
+              for s in BLOCK_SETTINGS]
     r = subprocess.run([exe, wpath, npath], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     # the contraction cases once more under each experiment switch, one fresh process per setting (gemm_switches() reads them once per process); printed first,
     # so that the output still ends with the whole run's last lines
@@ -108,6 +114,10 @@ def main(build_dir):
         g = subprocess.run([exe, wpath, "gemm"], env=dict(env, **{k: v}), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         print("".join(f"[{setting}] {line}\n" for line in g.stdout.splitlines()))
         rc = g.returncode
+    for setting, p in blocks:
+        out = p.communicate()[0]
+        print("".join(f"[{setting}] {line}\n" for line in out.splitlines()))
+        rc = rc or p.returncode
     print(r.stdout)
     return rc
 

@@ -25,7 +25,12 @@ The same for the dense contractions (csrc/gemm_plan.hip.h plan_conv_gemm): `gemm
 table forced in each operand form it exists in, the shapes around every threshold of the plan with the tile left to it, and the remainder launch; and
 `launchtrace <precision> <case> : <trace>` around every stage walk, and `flowtrace <precision> generic96* -` for a second model whose flow is 96 channels wide
 (every coupling layer as plain contractions with the gate / split-accumulate / couple epilogues).  The tile the plan is meant to take is pinned the same way: against the forced trace on the
-same shape.  build_and_run.py repeats the gemmtrace cases under each experiment switch (lines prefixed `[NAME=value]`, compared between builds only)."""
+same shape.  build_and_run.py repeats the gemmtrace cases under each experiment switch (lines prefixed `[NAME=value]`, compared between builds only).
+
+And for the AdaptiveDecoderBlock chains (csrc/adain_block.hip.h plan_adain_chain / plan_adain_block): `blocktrace <precision> <case> <switches> : <trace>` of the decoder, the
+frame path, the pitch/energy predictors and stts_op_adain_block on the batch shapes around every threshold of the plan (2 500 rows fold -> Winograd, 96 .. 384 bridge
+blocks, 3 840 / 4 096 rows in the 16-bit modes, 12 000 rows for the side lane), under STTS_ADAIN_BRIDGE (read per call) and, one process per setting, under the block's
+process-wide switches.  The unforced trace must equal the forced one on its side of a threshold and differ from it on the other (check_blocktraces)."""
 import os
 import re
 import shutil
@@ -73,6 +78,59 @@ STAGE_WALKS = {"cfg3:_64_x_50_tokens": _PHONEME, "token-count_extremes": _PHONEM
                "aligner:_3_utterances": ("aligner",), "aligner,_one_tdnn_layer": ("aligner",), "rmvpe:_3_utterances": ("rmvpe",)}
 STAGE_WALKS.update({f"{c}_{e}": ("mel_style",) for c in ("mel:_3_utterances", "mel_skew24") for e in ("pe_mel_style", "spk_emb")})
 STAGE_WALKS.update({f"{c}_cfm_pitch": ("cfm_pitch",) for c in ("mel:_3_utterances", "mel_skew24")})
+# blocktrace cases: (precision, case, switches); tests/asan/asan_driver.cpp block_section has the shapes
+_BRIDGE = ("-", "STTS_ADAIN_BRIDGE=0", "STTS_ADAIN_BRIDGE=1")
+BRIDGE_ON, BRIDGE_OFF, BRIDGE_TOO_LONG = ("3x960", "4x700", "12x960"), ("2x1300", "13x960"), "1537+2x960"  # what the rule of plan_adain_chain takes with the switch unset
+BLOCK_CASES = ([(p, f"dec_1x{n}", "-") for p in (0, 3) for n in (300, 2500, 2501)]
+               + [(p, f"dec_{b}", sw) for p in (0, 3) for b in BRIDGE_ON + BRIDGE_OFF + (BRIDGE_TOO_LONG,) for sw in _BRIDGE]
+               + [(p, f"dec_{c}", "-") for p in (1, 2) for c in ("1x300", "3839rows", "3840rows", "4096rows", "4097rows", "110utt", "100utt")]
+               + [(0, f"frame_{b}x960", sw) for b in (12, 13) for sw in _BRIDGE[:2]] + [(p, c, "-") for p in (0, 1, 2, 3) for c in ("op_1x300", "op_2x2049")]
+               + [(p, c, "-") for p in (0, 2, 3) for c in ("pe_2500frames", "pe_2501frames", "hubert_353frames", "hubert_2600frames")])
+# the block's process-wide switches (tests/asan/build_and_run.py BLOCK_SETTINGS): setting -> the (precision, case, switches) whose trace it must change and those it
+# must leave alone.  STTS_FOLD_ROWS=0 forces the Winograd form and STTS_SC_SIDE_MIN_ROWS=0 the side lane, so what they leave alone is the unforced choice pinned.
+BLOCK_SETTINGS = {
+    "STTS_FOLD_ROWS=0": ([(0, "dec_1x2500", "-"), (0, "pe_2500frames", "-"), (0, "dec_1x300", "-")], [(0, "dec_1x2501", "-"), (0, "pe_2501frames", "-"), (0, "dec_13x960", "-")]),
+    "STTS_SC_SIDE_MIN_ROWS=0": ([(0, "frame_12x960", sw) for sw in _BRIDGE[:2]], [(0, "frame_13x960", sw) for sw in _BRIDGE[:2]] + [(0, "dec_13x960", "-")]),
+    "STTS_NO_WINO_STATS=1": ([(0, "dec_2x1300", "-"), (0, "dec_3x960", "-"), (0, "pe_2501frames", "-")], [(0, "dec_1x2500", "-"), (0, "hubert_2600frames", "-"), (1, "dec_110utt", "-")]),
+    "STTS_NO_STAT_FUSE=1": ([(1, "dec_110utt", "-")], [(1, "dec_100utt", "-"), (0, "dec_2x1300", "-")]),
+    "STTS_NO_WINO_CONV2SC=1": ([(0, "dec_2x1300", "-")], [(0, "dec_1x2500", "-"), (0, "pe_2501frames", "-")]),
+    "STTS_AFFINE_SERIAL=1": ([(0, "dec_1x300", "-"), (0, "op_1x300", "-")], [(0, "op_2x2049", "-")]),
+}
+
+
+def check_blocktraces(stdout):
+    """The blocktrace lines of a driver run: every case there and accepted, the unforced choice equal to the forced one on its side of each threshold."""
+    block = {(int(p), c, sw): t for p, c, sw, t in re.findall(r"^blocktrace (\d) (\S+) (\S+) : (.*)$", stdout, re.M)}
+    missing = [k for k in BLOCK_CASES if k not in block]
+    assert not missing, missing
+    assert not [k for k, t in block.items() if t.startswith("error") or not t.strip()], block
+    for p in (0, 3):
+        auto, off, on = ({b: block[(p, f"dec_{b}", sw)] for b in BRIDGE_ON + BRIDGE_OFF + (BRIDGE_TOO_LONG,)} for sw in _BRIDGE)
+        for b in BRIDGE_ON:  # 96 <= utterances x 32 <= 384: the bridge, as forced on
+            assert auto[b] == on[b] != off[b], (p, b, auto[b])
+        for b in BRIDGE_OFF:  # outside: three launches, as forced off; the kernel could run
+            assert auto[b] == off[b] != on[b], (p, b, auto[b])
+        assert auto[BRIDGE_TOO_LONG] == off[BRIDGE_TOO_LONG] == on[BRIDGE_TOO_LONG], p  # an utterance beyond a bridge block: not even forced
+        assert "winograd_bridge_kernel" in on["3x960"] and "winograd_bridge_kernel" not in off["3x960"], on["3x960"]
+        # fold -> Winograd above 2 500 rows
+        assert "winograd" not in block[(p, "dec_1x2500", "-")] and "winograd_input_kernel" in block[(p, "dec_1x2501", "-")], p
+    assert "winograd" not in block[(0, "pe_2500frames", "-")] and "winograd_input_kernel" in block[(0, "pe_2501frames", "-")]
+    for p in (1, 2):  # 4 400 rows: conv_gemm16_kernel with the statistics from its epilogues; 3 960 rows: folded, no apply pass
+        assert "conv_gemm16_kernel<" in block[(p, "dec_110utt", "-")] and "conv_gemm16_kernel<" not in block[(p, "dec_100utt", "-")], p
+        assert "adain_apply_kernel" in block[(p, "dec_4097rows", "-")] and "adain_apply_kernel" not in block[(p, "dec_4096rows", "-")], p
+    per_setting = {}
+    for sw, p, c, s, t in re.findall(r"^\[(STTS_\w+=\d+)\] blocktrace (\d) (\S+) (\S+) : (.*)$", stdout, re.M):
+        per_setting.setdefault(sw, {})[(int(p), c, s)] = t
+    assert sorted(per_setting) == sorted(BLOCK_SETTINGS), sorted(per_setting)
+    n_cases = len([k for k in block if k[0] in (0, 1)])
+    for sw, (changed, same) in BLOCK_SETTINGS.items():
+        forced = per_setting[sw]
+        assert len(forced) == n_cases and not [k for k, t in forced.items() if t.startswith("error")], (sw, len(forced), n_cases)
+        assert not [k for k in changed if forced[k] == block[k]], (sw, "changes nothing in", [k for k in changed if forced[k] == block[k]])
+        assert not [k for k in same if forced[k] != block[k]], (sw, "changes", [k for k in same if forced[k] != block[k]])
+    assert len({tuple(sorted(f.items())) for f in per_setting.values()}) == len(per_setting)  # (the settings differ from one another)
+
+
 LAUNCH_CASES = [(p, c) for p in (0, 2) for c in ("cfg2:_8_x_3_s", "B_=_1_x_3_s", "short_ragged_utterances", "cfg5_per_GPU:_64_x_10_s", "cfg3:_64_x_50_tokens",
                                                  "token-count_extremes")] + [(0, "cfg4:_256_utterances_of_0.25-10_s")]
 
@@ -168,6 +226,7 @@ def test_host_side_under_asan_ubsan(tmp_path):
         assert not cfm[case].startswith("error") and cfm[case].startswith("1x ") and " | " not in cfm[case] and all(k in cfm[case] for k in parts), (case, cfm[case])
     refused = [k for k in cfm if k.startswith("refuse_")]
     assert sorted(refused) == ["refuse_elem", "refuse_rms_adaln", "refuse_rope", "refuse_small", "refuse_source"] and all(cfm[k].strip() == "error" for k in refused), cfm
+    check_blocktraces(r.stdout)
     # every switch setting ran every case
     per_setting = {}
     for sw in re.findall(r"^\[(STTS_\w+=\d+)\] gemmtrace ", r.stdout, re.M):
