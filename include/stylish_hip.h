@@ -71,7 +71,8 @@ enum {
   STTS_W_CFM_PITCH_NET = 8192, /* cfm_pitch_predictor.{asr_emb, blocks, out_proj} (in_proj.* is accepted and ignored; not part of STTS_W_ALL) */
   STTS_W_SSL = 16384,        /* hubert.model.* = AdaptiveHubert (finalized by stts_ssl_finalize, not part of STTS_W_ALL)      train/models/ssl.py:16-31 */
   STTS_W_RMVPE = 32768,      /* rmvpe.* = the RMVPE pitch extractor E2E0 (finalized by stts_rmvpe_finalize, not part of STTS_W_ALL) train/dataprep/rmvpe/model.py:49-86 */
-  STTS_W_ALIGNER = 65536     /* text_aligner.* = the TDNN CTC aligner (finalized by stts_aligner_finalize, not part of STTS_W_ALL)           train/models/text_aligner.py */
+  STTS_W_ALIGNER = 65536,    /* text_aligner.* = the TDNN CTC aligner (finalized by stts_aligner_finalize, not part of STTS_W_ALL)           train/models/text_aligner.py */
+  STTS_W_WAVLM = 131072      /* wavlm.* = transformers' WavLMModel, the network of the "slm" distance (finalized by stts_wavlm_finalize, not part of STTS_W_ALL) train/losses.py:408-426 */
 };
 int stts_finalize_weights(stts_ctx* ctx, int which);
 /* Operand precision of the FRAME-RATE Conv1d / Linear contractions (call before the first stts_finalize_weights).
@@ -279,6 +280,35 @@ int stts_ssl_forward_taps(stts_ctx* ctx, void* stream, int n_utt, const int32_t*
                           float* conv_last, float* proj, float* pos, float* layers, float* hidden, void* ws, size_t ws_bytes);
 /* rows of the conv0 tap buffer of a call (its utterances start at multiples of the later strides' product) */
 int64_t stts_ssl_tap_rows(const stts_ssl_dims* dims, int n_utt, const int32_t* sample_off_host);
+
+/* ---- WavLM and the reference's perceptual distance over its hidden states (WavLMLoss, train/losses.py:408-426, logged as "slm"): transformers'
+ * WavLMModel in eval mode with feat_extract_norm "group", do_stable_layer_norm false, conv_bias false, exact GELU and heads of 64.  Front end and
+ * layer body are AdaptiveHubert's (above); every layer's attention adds gate[query][head] * rel_attn_embed[bucket(key - query)][head] to its scores
+ * (the gate from gru_rel_pos_linear / gru_rel_pos_const of the layer's input, the table from layer 0; num_buckets a multiple of 4,
+ * num_buckets / 4 < max_bucket_distance <= 2048).  Weights: stts_load_weight(ctx, "wavlm.<WavLMModel state_dict key>", ...) (masked_spec_embed is
+ * accepted and ignored), then stts_wavlm_finalize.  fp32 whatever stts_set_precision chose; an utterance's results are the same bit for bit alone
+ * and packed with others.  An utterance below the feature extractor's receptive field (400 samples for the base model), or a pair of unequal
+ * lengths, is an error status before any launch. */
+typedef struct stts_wavlm_dims {
+  stts_ssl_dims ssl;
+  int32_t num_buckets, max_bucket_distance;
+} stts_wavlm_dims;
+int stts_wavlm_finalize(stts_ctx* ctx, const stts_wavlm_dims* dims);
+/* pairs 0: a stts_wavlm_forward_states call of n_utt utterances; pairs > 0: a stts_wavlm_l1_sums call (n_utt = 2 pairs).  0 on bad arguments. */
+size_t stts_wavlm_workspace_bytes(const stts_ctx* ctx, int n_utt, const int32_t* sample_off_host, int pairs);
+/* wave: packed mono samples at 16 kHz -> states [num_hidden_layers + 1][frames, hidden_size]: state 0 is the encoder LayerNorm's output, state l + 1
+ * layer l's (transformers' hidden_states), rows packed at the utterances' frame counts (stts_ssl_frames).  gate0 (may be null): layer 0's gate
+ * [frames, num_attention_heads]. */
+int stts_wavlm_forward_states(stts_ctx* ctx, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const float* wave,
+                              float* states, float* gate0, void* ws, size_t ws_bytes);
+/* 2 * pairs packed waveforms, utterances u and u + pairs of equal length -> sums [pairs][num_hidden_layers + 1] (device doubles): the sum of
+ * |state(u) - state(u + pairs)| over the pair's frames and channels, accumulated in double in a fixed order (no atomics; two calls give the same
+ * bits), and frames [pairs] (device int32).  No hidden state is kept and nothing is read back by the host. */
+int stts_wavlm_l1_sums(stts_ctx* ctx, void* stream, int pairs, const int32_t* sample_off_host, const int32_t* sample_off_dev, const float* wave, double* sums,
+                       int32_t* frames, void* ws, size_t ws_bytes);
+/* out [2 max_d + 1] (host): the bucket of rel_attn_embed the attention reads at distance d = key - query, for d = -max_d .. max_d (beyond
+ * max_bucket_distance the distance is clamped: the buckets have saturated by then) */
+int stts_wavlm_bucket_table(const stts_ctx* ctx, int max_d, int32_t* out);
 
 /* ---- RMVPE pitch extractor (train/dataprep/rmvpe/: E2E0 of model.py / deepunet.py / seq.py in eval mode, mel2hidden of inference.py:28-35, the decode
  * of utils.py:114-131, the log-mel of spec.py:39-71, the resampling of dataprep/pitch_extractor.py:136-141).  Weights are loaded under "rmvpe." with the
@@ -812,6 +842,10 @@ int stts_op_adain_block(stts_ctx* ctx, void* stream, const char* prefix, int n_u
 int stts_op_attention(void* stream, int n_utt, const int32_t* q_off_host, const int32_t* q_off_dev, const int32_t* k_off_host,
                       const int32_t* k_off_dev, const float* q, const float* k, const float* v, float* o, int heads, int kc,
                       const int32_t* band_centre, int window, int kernel);
+/* wavlm_l1_kernel alone: sums[u] (device double) = sum |a - b| over utterance u's rows of two row buffers packed alike ([rows, ld], C real columns);
+ * part: device scratch of n_utt * ceil(max_len / 8) doubles; frames (may be null): device int32 [n_utt]. */
+int stts_op_wavlm_l1(void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* a, const float* b, int ld, int C, double* part,
+                     double* sums, int32_t* frames);
 /* The vocoder's STFT / iSTFT at a geometry (n_fft, win, vocoder hop h = hop_length / 4; the rules of stts_finalize_weights) without a model.
  * Utterance u has seg_off[u+1] - seg_off[u] frames and h samples per frame, packed.  generic 0: the kernels the engine would run (the
  * specialised ones at 2048 / 1200 / 75), 1: the run-time-geometry kernels always.

@@ -190,6 +190,11 @@ SIGNATURES = {
     "stts_ssl_forward": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _SZ]),
     "stts_ssl_forward_taps": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _SZ]),
     "stts_ssl_tap_rows": (_I64, [_P, _I, _P]),
+    "stts_wavlm_finalize": (_I, [_P, _P]),
+    "stts_wavlm_workspace_bytes": (_SZ, [_P, _I, _P, _I]),
+    "stts_wavlm_forward_states": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
+    "stts_wavlm_l1_sums": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
+    "stts_wavlm_bucket_table": (_I, [_P, _I, _P]),
     "stts_rmvpe_finalize": (_I, [_P, _P]),
     "stts_rmvpe_workspace_bytes": (_SZ, [_P, _I, _P]),
     "stts_rmvpe_forward": (_I, [_P, _P, _I, _P, _P, _P, _I, C.c_float, _P, _P, _P, _SZ]),
@@ -248,6 +253,7 @@ TEST_SIGNATURES = {
     "stts_op_cfm_source": (_I, [_P, C.POINTER(CfmSourceArgs)]),
     "stts_op_adain_block": (_I, [_P, _P, C.c_char_p, _I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _SZ]),
     "stts_op_attention": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I]),
+    "stts_op_wavlm_l1": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "stts_op_stft_geom": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I]),
     "stts_op_istft_geom": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I]),
 }

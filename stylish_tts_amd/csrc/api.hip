@@ -7,6 +7,7 @@
 #include "mel_style.hip.h"
 #include "cfm_pitch.hip.h"
 #include "ssl.hip.h"
+#include "wavlm.hip.h"
 #include "rmvpe.hip.h"
 #include "aligner.hip.h"
 #include "log_mel.hip.h"
@@ -660,6 +661,86 @@ int stts_ssl_forward_taps(stts_ctx* c, void* stream, int n_utt, const int32_t* s
   SslTaps t;
   t.conv0 = conv0; t.conv0_off = conv0_off; t.conv_last = conv_last; t.proj = proj; t.pos = pos; t.layers = layers; t.hidden = hidden;
   return ssl_entry(c, stream, n_utt, sample_off_host, sample_off_dev, wave, off_T_host, off_T_dev, feats, ld_feats, &t, ws, ws_bytes);
+  API_END
+}
+
+// ------------------------------------------------------------------------------------------------ WavLM and its perceptual distance (wavlm.hip.h)
+int stts_wavlm_finalize(stts_ctx* c, const stts_wavlm_dims* dims) {
+  API_BEGIN
+  STTS_CHECK(c && dims, "null argument");
+  STTS_HIP(hipSetDevice(c->device));
+  c->ready &= ~STTS_W_WAVLM;
+  free_component_allocs(c, STTS_W_WAVLM);
+  SslDims d;
+  STTS_TRY(ssl_dims_from(&dims->ssl, &d));
+  auto m = std::make_shared<WavlmW>();
+  // fp32 whatever the precision, packed as the AdaptiveHubert weights are
+  PackScope scope(c, {PREC_F32, true, 32, STTS_W_WAVLM});
+  STTS_TRY(finalize_wavlm(c, d, dims->num_buckets, dims->max_bucket_distance, m.get()));
+  m->ssl.ready = true;
+  c->wavlm = m;
+  c->ready |= STTS_W_WAVLM;
+  STTS_HIP(hipDeviceSynchronize());
+  return 0;
+  API_END
+}
+
+// pairs > 0: n_utt = 2 pairs and utterances u, u + pairs must have one length
+static int wavlm_check_offsets(const SslDims& d, int n_utt, const int32_t* sample_off_host, int pairs) {
+  STTS_CHECK(n_utt > 0 && sample_off_host && sample_off_host[0] == 0, "wavlm: bad sample offsets");
+  for (int u = 0; u < n_utt; ++u) {
+    const long n = (long)sample_off_host[u + 1] - sample_off_host[u];
+    STTS_CHECK(n > 0 && ssl_frames_host(d, n) > 0, "wavlm: utterance %d has %ld samples, fewer than one frame of the feature extractor needs", u, n);
+  }
+  for (int u = 0; u < pairs; ++u) {
+    const long a = (long)sample_off_host[u + 1] - sample_off_host[u], b = (long)sample_off_host[u + pairs + 1] - sample_off_host[u + pairs];
+    STTS_CHECK(a == b, "wavlm: pair %d has waveforms of unequal lengths (%ld and %ld samples)", u, a, b);
+  }
+  return 0;
+}
+
+size_t stts_wavlm_workspace_bytes(const stts_ctx* c, int n_utt, const int32_t* sample_off_host, int pairs) {
+  if (!c || !c->wavlm || !(c->ready & STTS_W_WAVLM) || pairs < 0 || (pairs > 0 && n_utt != 2 * pairs)) return 0;
+  const WavlmW& M = *static_cast<const WavlmW*>(c->wavlm.get());
+  if (wavlm_check_offsets(M.ssl.d, n_utt, sample_off_host, pairs) != 0) return 0;
+  return wavlm_workspace_bytes(M, n_utt, sample_off_host, pairs);
+}
+
+int stts_wavlm_forward_states(stts_ctx* c, void* stream, int n_utt, const int32_t* sample_off_host, const int32_t* sample_off_dev, const float* wave, float* states,
+                              float* gate0, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  STTS_CHECK(c && c->wavlm && (c->ready & STTS_W_WAVLM), "the WavLM weights are not finalized (stts_wavlm_finalize)");
+  const WavlmW& M = *static_cast<const WavlmW*>(c->wavlm.get());
+  STTS_CHECK(sample_off_dev && wave && states && ws, "wavlm: null argument");
+  STTS_TRY(wavlm_check_offsets(M.ssl.d, n_utt, sample_off_host, 0));
+  STTS_HIP(hipSetDevice(c->device));
+  Arena a(ws, ws_bytes);
+  return wavlm_forward(M, (hipStream_t)stream, n_utt, sample_off_host, sample_off_dev, wave, states, gate0, 0, nullptr, nullptr, a);
+  API_END
+}
+
+int stts_wavlm_l1_sums(stts_ctx* c, void* stream, int pairs, const int32_t* sample_off_host, const int32_t* sample_off_dev, const float* wave, double* sums,
+                       int32_t* frames, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  STTS_CHECK(c && c->wavlm && (c->ready & STTS_W_WAVLM), "the WavLM weights are not finalized (stts_wavlm_finalize)");
+  const WavlmW& M = *static_cast<const WavlmW*>(c->wavlm.get());
+  STTS_CHECK(pairs > 0, "wavlm: no pairs");
+  STTS_TRY(wavlm_check_offsets(M.ssl.d, 2 * pairs, sample_off_host, pairs));
+  STTS_CHECK(sample_off_dev && wave && sums && frames && ws, "wavlm: null argument");
+  STTS_HIP(hipSetDevice(c->device));
+  Arena a(ws, ws_bytes);
+  return wavlm_forward(M, (hipStream_t)stream, 2 * pairs, sample_off_host, sample_off_dev, wave, nullptr, nullptr, pairs, sums, frames, a);
+  API_END
+}
+
+int stts_wavlm_bucket_table(const stts_ctx* c, int max_d, int32_t* out) {
+  API_BEGIN
+  STTS_CHECK(c && c->wavlm && (c->ready & STTS_W_WAVLM), "the WavLM weights are not finalized (stts_wavlm_finalize)");
+  STTS_CHECK(max_d >= 0 && out, "wavlm: bad argument");
+  const WavlmW& M = *static_cast<const WavlmW*>(c->wavlm.get());
+  const int D = M.max_dist;
+  for (int d = -max_d; d <= max_d; ++d) out[d + max_d] = M.bucket[std::max(-D, std::min(D, d)) + D];  // the clamp the attention applies
+  return 0;
   API_END
 }
 

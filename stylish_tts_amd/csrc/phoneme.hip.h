@@ -156,12 +156,39 @@ inline bool attn_mfma_kc(int kc) { return kc == 16 || kc == 32 || kc == 40 || kc
 // SPLIT = 2 (long sequences): two wave groups per query tile take the even / odd key blocks, each with its own running maximum / sum / accumulator,
 // merged through LDS at the end - a problem of 8 x 800 frames x 4 heads is 896 wave tiles for 1 024 SIMDs, i.e. less than one wave per SIMD, and a wave
 // alone on its SIMD alternates dependent MFMA chains with the softmax's vector work; with the keys split the SIMDs hold two waves that interleave.
-template <int KC, int SPLIT = 1>
+// BIAS (WavLM's gated relative-position bias, csrc/wavlm.hip.h): one more argument, an AttnBias, and score += gate[query][head] * tab[head][key - query],
+// the head's slice of the bias-by-distance table staged in LDS once per block (dynamic, (2 dmax + 1) floats; |key - query| is clamped to dmax, where the
+// buckets have saturated).  For one score register a half-wave reads 32 consecutive distances (query l & 31 descending), so every ds_read_b32 group hits
+// 32 distinct banks.  A compile-time switch: the plain instantiations take no such argument and contain none of it.  Never key-split.
+struct AttnBias {
+  const float* gate;  // [query rows][ldg], column = head
+  int ldg;
+  const float* tab;  // [heads][2 dmax + 1]: bias of head h at distance d in tab[h][d + dmax]
+  int dmax;
+};
+template <class... A>
+__device__ __forceinline__ AttnBias attn_bias_arg(A... a) {
+  const AttnBias r[] = {a...};
+  return r[0];
+}
+template <int KC, int SPLIT = 1, bool BIAS = false, class... BiasArg>
 __global__ void __launch_bounds__(256 * SPLIT) attention_mfma_kernel(const float* __restrict__ Q, int ldq, int qcol0, const float* __restrict__ K, int ldk,
                                                              int kcol0, const float* __restrict__ V, int ldv, int vcol0, float* __restrict__ O, int ldo,
                                                              const int* __restrict__ q_off, const int* __restrict__ k_off,
-                                                             const int* __restrict__ band_centre, int window, float scale) {
+                                                             const int* __restrict__ band_centre, int window, float scale, BiasArg... bias_arg) {
   static_assert(KC % 8 == 0 && KC <= 160, "head size");
+  static_assert(sizeof...(BiasArg) == (BIAS ? 1 : 0) && (!BIAS || SPLIT == 1), "the biased form takes one AttnBias and is never key-split");
+  [[maybe_unused]] const float* btab = nullptr;  // the head's table slice in LDS, at distance 0
+  [[maybe_unused]] int bdmax = 0;
+  if constexpr (BIAS) {
+    extern __shared__ float bias_s[];
+    const AttnBias ba = attn_bias_arg(bias_arg...);
+    const int n = 2 * ba.dmax + 1;
+    for (int i = threadIdx.x; i < n; i += 256) bias_s[i] = ba.tab[(long)blockIdx.y * n + i];
+    __syncthreads();  // (ahead of the early exit below: every thread of the block gets here)
+    btab = bias_s + ba.dmax;
+    bdmax = ba.dmax;
+  }
   // KCP: the head size padded to whole 32-channel output tiles (the text encoders' heads of 16 and the predictors' heads of 40 / 160 channels: the
   // pad columns of the V stage are zeros, written once); row strides (floats): K rows KC + 2, V rows KCP + 8; G float4 groups per staged row
   constexpr int KCP = (KC + 31) / 32 * 32, NT = KCP / 32, KS = KC + 2, VS = KCP + 8, G = KC / 4, NE = (32 * G + 255) / 256;
@@ -189,6 +216,11 @@ __global__ void __launch_bounds__(256 * SPLIT) attention_mfma_kernel(const float
     }
   }
   const int centre = band_centre ? band_centre[qlo + ql] : 0;
+  [[maybe_unused]] float gq = 0.f;
+  if constexpr (BIAS) {
+    const AttnBias ba = attn_bias_arg(bias_arg...);
+    gq = ba.gate[(long)(qlo + ql) * ba.ldg + h];
+  }
   f32x16 o[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
@@ -247,6 +279,7 @@ __global__ void __launch_bounds__(256 * SPLIT) attention_mfma_kernel(const float
       const int j = kb * 32 + 8 * (i >> 2) + 4 * lh + (i & 3);
       float v = sacc[i] * scale;
       if (band_centre && j >= centre - window && j <= centre + window) v += -1e4f;
+      if constexpr (BIAS) v += gq * btab[max(-bdmax, min(bdmax, j - ql))];
       if (j >= nk) v = -INFINITY;
       sacc[i] = v;
       mx = fmaxf(mx, v);

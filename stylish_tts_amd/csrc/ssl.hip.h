@@ -366,10 +366,10 @@ inline void ssl_fold_pos_weight(const HostTensor& g, const HostTensor& v, std::v
   }
 }
 
-inline int finalize_ssl(stts_ctx* c, const SslDims& d, SslW* M) {
+// p: the key prefix of the transformers model ("hubert.model." for AdaptiveHubert; WavLM, whose front end and layer body are the same, has its own)
+inline int finalize_ssl(stts_ctx* c, const SslDims& d, SslW* M, const std::string& p = "hubert.model.") {
   *M = SslW();
   M->d = d;
-  const std::string p = "hubert.model.";
   STTS_CHECK(d.n_conv >= 1 && d.n_conv <= kSslMaxConv, "ssl: conv layers %d outside [1, %d]", d.n_conv, kSslMaxConv);
   STTS_CHECK(d.layers >= 1 && d.layers <= kSslMaxLayers, "ssl: num_hidden_layers %d outside [1, %d]", d.layers, kSslMaxLayers);
   STTS_CHECK(d.hidden > 0 && d.hidden % 32 == 0 && d.hidden <= 2048, "ssl: hidden_size %d must be a multiple of 32, at most 2048", d.hidden);
@@ -502,11 +502,25 @@ inline void ssl_plan(const SslDims& d, int n_utt, const int* samp_off, SslPlan* 
     for (int u = 0; u <= n_utt; ++u) P->lvl_off[i][u] = P->cap_off[u] * g.D[i];
 }
 
-inline int ssl_forward(const SslW& M, hipStream_t st, int n_utt, const int* samp_off_host, const int* samp_off_dev, const float* wave, const Seg& sT, float* feats,
-                       int ld_feats, const SslTaps* taps, Arena& ws) {
+// What a network built on this encoder adds to it (WavLM, wavlm.hip.h); the defaults are HuBERT.
+struct SslPlain {
+  void carve(Arena&, long /*frames*/) {}                                                  // its own buffers, after the encoder's
+  int state(hipStream_t, int /*k*/, const float* /*x*/, const Seg& /*sF*/) { return 0; }  // hidden state k (0: after the encoder LayerNorm) is in x
+  // the attention of layer i over q | k | v rows (x: the layer's input)
+  int attention(hipStream_t st, int /*i*/, const float* /*x*/, const Seg& sF, const float* qkv, int H, int heads, float* att) {
+    // (matrix cores, keys never split over wave groups: the split depends on the longest utterance of the call)
+    return run_attention(st, sF, sF, qkv, 3 * H, 0, qkv, 3 * H, H, qkv, 3 * H, 2 * H, att, H, heads, H / heads, nullptr, 0, 3);
+  }
+};
+
+// The shared graph: feature extractor, projection, positional conv, encoder LayerNorm, post-LN layers.  Leaves the last hidden state in *x_out
+// (packed rows at the frame offsets *fr_dev_out, host plan *P); in a dry run it returns after the carving with *x_out null.
+template <class Ext>
+inline int ssl_encode(const SslW& M, hipStream_t st, int n_utt, const int* samp_off_host, const int* samp_off_dev, const float* wave, const SslTaps* taps, Arena& ws,
+                      Ext& ext, SslPlan& P, const float** x_out, const int** fr_dev_out) {
   const SslDims& d = M.d;
   const SslGeom g = ssl_geom(d);
-  SslPlan P;
+  *x_out = nullptr;
   ssl_plan(d, n_utt, samp_off_host, &P);
   const int n1 = n_utt + 1, C0 = d.conv_dim[0], CL = d.conv_dim[d.n_conv - 1], H = d.hidden;
   const long cap = P.cap_off[n_utt], F = P.fr_off[n_utt];
@@ -526,6 +540,7 @@ inline int ssl_forward(const SslW& M, hipStream_t st, int n_utt, const int* samp
   float* qkv = ws.get<float>(F * 3 * H);
   float* att = ws.get<float>(F * H);
   float* ff = ws.get<float>(F * d.inter);
+  ext.carve(ws, F);
   STTS_CHECK(ws.ok, "ssl_forward: workspace too small");
   STTS_DRY_RETURN(ws);
   const int* cap_dev = tab;
@@ -578,21 +593,36 @@ inline int ssl_forward(const SslW& M, hipStream_t st, int n_utt, const int* samp
     STTS_TRY(static_ln(st, t, H, H, F, d.eps, M.enc_g, M.enc_b, x, H, ACT_NONE));
     if (taps && taps->pos) STTS_HIP(hipMemcpyAsync(taps->pos, x, F * H * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
+  STTS_TRY(ext.state(st, 0, x, sF));
   // ---- post-LN transformer layers
-  const int kc = H / d.heads;
   for (int i = 0; i < d.layers; ++i) {
     const SslW::Layer& L = M.layer[i];
     STTS_TRY(ssl_gemm(st, sF, x, H, L.qkv, qkv, 3 * H, ACT_NONE));
-    // (matrix cores, keys never split over wave groups: the split depends on the longest utterance of the call)
-    STTS_TRY(run_attention(st, sF, sF, qkv, 3 * H, 0, qkv, 3 * H, H, qkv, 3 * H, 2 * H, att, H, d.heads, kc, nullptr, 0, 3));
+    STTS_TRY(ext.attention(st, i, x, sF, qkv, H, d.heads, att));
     STTS_TRY(ssl_gemm(st, sF, att, H, L.o, t, H, ACT_NONE, x, H));
     STTS_TRY(static_ln(st, t, H, H, F, d.eps, L.g1, L.b1, x, H, ACT_NONE));
     STTS_TRY(ssl_gemm(st, sF, x, H, L.f1, ff, d.inter, ACT_GELU));
     STTS_TRY(ssl_gemm(st, sF, ff, d.inter, L.f2, t, H, ACT_NONE, x, H));
     STTS_TRY(static_ln(st, t, H, H, F, d.eps, L.g2, L.b2, x, H, ACT_NONE));
     if (taps && taps->layers) STTS_HIP(hipMemcpyAsync(taps->layers + (size_t)i * F * H, x, F * H * sizeof(float), hipMemcpyDeviceToDevice, st));
+    STTS_TRY(ext.state(st, i + 1, x, sF));
   }
   if (taps && taps->hidden) STTS_HIP(hipMemcpyAsync(taps->hidden, x, F * H * sizeof(float), hipMemcpyDeviceToDevice, st));
+  STTS_HIP(hipGetLastError());
+  *x_out = x;
+  *fr_dev_out = fr_dev;
+  return 0;
+}
+
+inline int ssl_forward(const SslW& M, hipStream_t st, int n_utt, const int* samp_off_host, const int* samp_off_dev, const float* wave, const Seg& sT, float* feats,
+                       int ld_feats, const SslTaps* taps, Arena& ws) {
+  SslPlain plain;
+  SslPlan P;
+  const float* x = nullptr;
+  const int* fr_dev = nullptr;
+  STTS_TRY(ssl_encode(M, st, n_utt, samp_off_host, samp_off_dev, wave, taps, ws, plain, P, &x, &fr_dev));
+  if (!x) return 0;  // a dry run: sized, nothing launched
+  const int H = M.d.hidden;
   // ---- rate conversion straight into the packed feature rows
   {
     const long work = (long)sT.max_len() * (ld_feats / 4);

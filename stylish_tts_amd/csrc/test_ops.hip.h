@@ -283,6 +283,22 @@ int stts_op_attention(void* stream, int n_utt, const int32_t* q_off_host, const 
   API_END
 }
 
+// wavlm_l1_kernel + wavlm_l1_finish_kernel (wavlm.hip.h) on two row buffers packed alike: sums[u] = sum |a - b| over utterance u's rows, in double.
+// part: device scratch of n_utt * ceil(max_len / 8) doubles.
+int stts_op_wavlm_l1(void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* a, const float* b, int ld, int C, double* part,
+                     double* sums, int32_t* frames) {
+  API_BEGIN
+  STTS_CHECK(n_utt > 0 && off_host && off_dev && a && b && part && sums && C > 0 && ld >= C, "null / empty argument");
+  Seg s{n_utt, off_host, off_dev};
+  const int ml = s.max_len();
+  STTS_TRY(launch_wavlm_l1((hipStream_t)stream, a, b, ld, C, n_utt, off_dev, ml, part));
+  hipLaunchKernelGGL(wavlm_l1_finish_kernel, dim3(ceil_div(n_utt, 64)), dim3(64), 0, (hipStream_t)stream, part, 1, n_utt, ceil_div(std::max(1, ml), kWavlmL1Rows), off_dev, sums,
+                     frames);
+  STTS_HIP(hipGetLastError());
+  return 0;
+  API_END
+}
+
 // The vocoder's STFT / iSTFT kernels at a geometry (n_fft, win, hop 4h) without a model: the launches of harmonic_stft / vocoder_body, with
 // this geometry's tables.  generic 0: the kernels the engine picks (signal.hip.h at 2048 / 1200 / 300), 1: signal_geom.hip.h always.
 struct GeomOpTables {

@@ -50,6 +50,7 @@ W_CFM_PITCH_NET = 8192  # cfm_pitch_predictor.{asr_emb, blocks, out_proj}
 W_SSL = 16384  # hubert.model.* (AdaptiveHubert; finalized by stts_ssl_finalize)
 W_RMVPE = 32768  # rmvpe.* (RmvpePitchExtractor; finalized by stts_rmvpe_finalize)
 W_ALIGNER = 65536  # text_aligner.* (TextAligner; finalized by stts_aligner_finalize)
+W_WAVLM = 131072  # wavlm.* (WavLM; finalized by stts_wavlm_finalize)
 
 _ENGINES: Dict[int, HipModel] = {}
 
@@ -1223,6 +1224,152 @@ class AdaptiveHubert(HipModule):
         B, T = wave.shape[0], int(time_dim)
         rows = self.packed(wave, [T] * B, lengths, sample_rate=sample_rate)
         return rows[:, : self.hidden].reshape(B, T, self.hidden).permute(0, 2, 1).contiguous()
+
+
+class WavLM(HipModule):
+    """transformers' WavLMModel in eval mode on the engine (csrc/wavlm.hip.h): ``config`` holds WavLMConfig fields (wavlm.arch; the base model when
+    None), load_state_dict takes ``WavLMModel.state_dict()`` keys (masked_spec_embed is stored and unused).  ``model_path``: a LOCAL directory with
+    config.json and model.safetensors (or pytorch_model.bin); nothing is ever downloaded and no pretrained weights ship with the engine.
+    Audio is mono at 16 kHz.  ``lengths`` runs a ragged batch in which every utterance gets what it gets alone, bit for bit (the reference's
+    padded batch would let GroupNorm, the positional conv and the attention see the padding).  Forward values only: no gradients."""
+
+    module_name = "wavlm"
+    components = W_WAVLM
+    sr = 16000
+
+    def __init__(self, config=None, engine=None, cfg=None, model_path=None):
+        from . import wavlm
+
+        sd = None
+        if model_path is not None:
+            import json
+            import os
+
+            with open(os.path.join(model_path, "config.json"), "r", encoding="utf-8") as f:
+                config = json.load(f)
+            st = os.path.join(model_path, "model.safetensors")
+            if os.path.exists(st):
+                from safetensors.torch import load_file
+
+                sd = load_file(st)
+            else:
+                sd = torch.load(os.path.join(model_path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
+        self.arch = wavlm.arch(config)
+        self.hidden = self.arch["hidden_size"]
+        self.n_states = self.arch["num_hidden_layers"] + 1
+        super().__init__(params.wavlm_spec(self.arch), cfg or load_model_config(), engine)
+        if sd is not None:
+            self.load_state_dict({(k[len("wavlm."):] if k.startswith("wavlm.") else k): v for k, v in sd.items()}, strict=False)
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        # older checkpoints spell the positional conv's weight norm weight_g / weight_v
+        q = "encoder.pos_conv_embed.conv."
+        sd = dict(state_dict)
+        if q + "weight_g" in sd:
+            sd[q + "parametrizations.weight.original0"] = sd.pop(q + "weight_g")
+            sd[q + "parametrizations.weight.original1"] = sd.pop(q + "weight_v")
+        return super().load_state_dict(sd, strict=strict, assign=assign)
+
+    def _bind(self):
+        eng = self._engine
+        owners = eng.__dict__.setdefault("_owners", {})
+        if self._dirty or owners.get(W_WAVLM) is not self:
+            self._load_into(eng)
+            eng.wavlm_finalize(self.arch)
+            owners[W_WAVLM] = self
+            self._dirty = False
+
+    def frames(self, samples: int) -> int:
+        from . import wavlm
+
+        return wavlm.frames(samples, self.arch)
+
+    def _pack(self, wave, lengths):
+        """(packed samples on the device, their Segments) of wave [B, samples] or a list of 1-D waveforms."""
+        eng = self.engine
+        if isinstance(wave, (list, tuple)):
+            ws = [_f(torch.as_tensor(w).reshape(-1), eng.device) for w in wave]
+            L = [int(w.numel()) for w in ws] if lengths is None else [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()]
+            if len(L) != len(ws) or any(n < 1 or n > w.numel() for n, w in zip(L, ws)):
+                raise ValueError(f"lengths {L} do not fit the {len(ws)} waveforms given")
+            flat = torch.cat([w[:n] for w, n in zip(ws, L)]).contiguous()
+        else:
+            w = torch.as_tensor(wave)
+            if w.dim() == 3 and w.shape[1] == 1:
+                w = w[:, 0]
+            if w.dim() != 2:
+                raise ValueError(f"WavLM input must be [B, samples] or [B, 1, samples], got shape {tuple(w.shape)}")
+            B, S = w.shape
+            L = [S] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()]
+            if len(L) != B or any(n < 1 or n > S for n in L):
+                raise ValueError(f"lengths {L} do not fit a batch of {B} x {S} samples")
+            wd = _f(w, eng.device)
+            flat = wd.reshape(-1) if lengths is None else torch.cat([wd[b, : L[b]] for b in range(B)]).contiguous()
+        return flat, Segments(L, eng.device)
+
+    def hidden_states(self, wave, lengths=None, gate: bool = False):
+        """wave [B, samples] (or [B, 1, samples], or a list) at 16 kHz -> a tuple of num_hidden_layers + 1 packed tensors [sum frames, hidden]:
+        transformers' ``hidden_states`` (state 0 is the encoder LayerNorm's output), utterance after utterance."""
+        flat, seg = self._pack(wave, lengths)
+        for n in seg.lengths:
+            self.frames(n)  # ValueError below the receptive field, where the reference raises
+        res = self.engine.wavlm_states(seg, flat, gate=gate)
+        states = res[0] if gate else res
+        tup = tuple(states[k] for k in range(states.shape[0]))
+        return (tup, res[1]) if gate else tup
+
+    def forward(self, wave, lengths=None):
+        """last_hidden_state as [B, frames, hidden] for a dense batch."""
+        last = self.hidden_states(wave, lengths)[-1]
+        B = len(wave) if isinstance(wave, (list, tuple)) else torch.as_tensor(wave).shape[0]
+        if last.shape[0] % B or lengths is not None:
+            raise ValueError("forward() returns a dense [B, frames, hidden]: use hidden_states() for a ragged batch")
+        return last.reshape(B, -1, self.hidden)
+
+
+class WavLMLoss(torch.nn.Module):
+    """train/losses.py:408-426 on the engine, same constructor shape: ``model`` is a modules.WavLM (or a LOCAL checkpoint directory; nothing is
+    downloaded), ``forward(wav, y_rec)`` resamples both from ``model_sr`` to ``slm_sr`` (Resample at torchaudio's defaults: Hann, width 6), runs
+    both through WavLM and returns the mean absolute difference over all hidden states as a 0-d float64 tensor - what the stages log as "slm".
+    Inputs: [B, L], [B, 1, L], or lists of 1-D waveforms; ``lengths`` [B] for ragged batches, where every utterance is its own run and the mean is
+    over real frames only (the reference would run the padding through the network).  The value is
+    sum of all sums / (states * total frames * hidden); forward value only, no gradients.  The two waveforms of a pair run as utterances u and
+    u + B of one call; no hidden state leaves the device, and ``sums`` does not read anything back."""
+
+    def __init__(self, model, model_sr, slm_sr: int = 16000, engine=None):
+        super().__init__()
+        self.wavlm = model if isinstance(model, WavLM) else WavLM(model_path=model, engine=engine)
+        if int(slm_sr) != self.wavlm.sr:
+            raise ValueError(f"WavLM takes audio at {self.wavlm.sr} Hz, got slm_sr = {slm_sr}")
+        self.model_sr, self.slm_sr = int(model_sr), int(slm_sr)
+        self.resample = None if self.model_sr == self.slm_sr else Resample(self.model_sr, self.slm_sr, engine=self.wavlm._engine, cfg=self.wavlm.cfg)
+
+    def sums(self, wav, y_rec, lengths=None):
+        """(sums [B, states] float64, frames [B] int32) on the device; nothing is read back."""
+        m = self.wavlm
+        a, sa = m._pack(wav, lengths)
+        b, sb = m._pack(y_rec, lengths)
+        if sa.lengths != sb.lengths:
+            raise ValueError(f"the recordings have {sa.lengths} samples, the synthesised waveforms {sb.lengths}: a pair must have one length")
+        eng = m.engine
+        if self.resample is not None:
+            self.resample._engine = eng
+            a, sa = self.resample.packed_rows(a, sa)
+            b, sb = self.resample.packed_rows(b, sb)
+        for n in sa.lengths:
+            m.frames(n)  # ValueError below the receptive field
+        return eng.wavlm_l1(Segments(sa.lengths + sb.lengths, eng.device), torch.cat([a, b]))
+
+    def scores(self, wav, y_rec, lengths=None):
+        """(slm, [per-utterance slm]) as Python floats; one host read."""
+        from . import wavlm
+
+        sums, fr = self.sums(wav, y_rec, lengths)
+        both = torch.cat([sums, fr.to(torch.float64)[:, None]], dim=1).cpu().tolist()
+        return wavlm.score([r[:-1] for r in both], [int(r[-1]) for r in both], self.wavlm.hidden)
+
+    def forward(self, wav, y_rec, lengths=None):
+        return torch.tensor(self.scores(wav, y_rec, lengths)[0], dtype=torch.float64)
 
 
 class RmvpePitchExtractor(HipModule):

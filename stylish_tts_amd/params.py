@@ -478,6 +478,31 @@ def hubert_ssl_spec(arch=None, weight_norm: str = "parametrizations", p: str = "
     return s
 
 
+def wavlm_spec(arch=None, p: str = "") -> Spec:
+    """transformers' WavLMModel.state_dict() in registration order.  ``arch``: wavlm.arch() fields (base when None).  The kinds of the shared
+    layers are hubert_ssl_spec's; gru_rel_pos_const is near 1 (its initial value), gru_rel_pos_linear and rel_attn_embed are scaled so that the
+    gate varies from frame to frame and the bias is a real share of the scores (the fixture generator asserts both)."""
+    from .wavlm import ARCH_DEFAULTS
+
+    a = dict(ARCH_DEFAULTS if arch is None else arch)
+    h, inter, heads = a["hidden_size"], a["intermediate_size"], a["num_attention_heads"]
+    hub = hubert_ssl_spec(dict(a, classifier_proj_size=1), p=p)
+    s: Spec = []
+    for name, shape, kind in hub:
+        if name.startswith(p + "final_proj."):
+            continue
+        m = name[len(p):]
+        if m.startswith("encoder.layers.") and m.endswith(".attention.k_proj.weight"):
+            s.append((name[: -len("k_proj.weight")] + "gru_rel_pos_const", (1, heads, 1, 1), "gate_const"))
+        s.append((name, shape, kind))
+        if m.startswith("encoder.layers.") and m.endswith(".attention.out_proj.bias"):
+            q = name[: -len("out_proj.bias")]
+            s += [(q + "gru_rel_pos_linear.weight", (8, h // heads), "w_gate"), (q + "gru_rel_pos_linear.bias", (8,), "b")]
+            if m.startswith("encoder.layers.0."):
+                s.append((q + "rel_attn_embed.weight", (a["num_buckets"], heads), "rel_embed"))
+    return s
+
+
 def _bn2d(p: str, c: int) -> Spec:
     """BatchNorm2d's five state_dict entries; num_batches_tracked (a 0-dim counter) is accepted and ignored by the engine."""
     return [(p + ".weight", (c,), "ln_g"), (p + ".bias", (c,), "ln_b"), (p + ".running_mean", (c,), "ln_b"), (p + ".running_var", (c,), "bn_var"),
@@ -616,6 +641,12 @@ def synth_tensor(name: str, shape: Tuple[int, ...], kind: str, seed: int = 0) ->
         v = u * np.sqrt(3.0 / fan_in)
     elif kind == "wn_g_pos":  # per-tap gain of the positional conv: the fold makes every tap's [cout, cin] slice this norm
         v = 1.2 + 0.3 * u
+    elif kind == "gate_const":  # WavLM's gru_rel_pos_const (initialised to ones)
+        v = 1.0 + 0.1 * u
+    elif kind == "w_gate":  # WavLM's gru_rel_pos_linear: unit-scale pre-activations after the sum of four, so the sigmoids move
+        v = u * 0.5 * np.sqrt(3.0 / fan_in)
+    elif kind == "rel_embed":  # WavLM's rel_attn_embed: a bias of the order of the scores themselves
+        v = u * 1.5
     elif kind == "w_small":
         v = u * 0.5 * np.sqrt(3.0 / fan_in)
     elif kind == "w_tiny":

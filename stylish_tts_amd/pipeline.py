@@ -390,7 +390,7 @@ def _curve_pair(pair, what):
 
 
 @torch.no_grad()
-def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, prediction=None, pitch=None, energy=None) -> dict:
+def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, prediction=None, pitch=None, energy=None, slm=None) -> dict:
     """What the reference's validate_* functions log about a batch (train/stage_type.py), on the engine's fused kernels (nothing is materialised):
     audio / audio_gt: the synthesised waveforms and the recordings, [B, samples], [B, 1, samples] or lists of 1-D tensors (``lengths`` [B] cuts a
     padded batch).  -> dict of Python numbers, read from the device once:
@@ -401,6 +401,8 @@ def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, predictio
                  time-major rows (logamp_rows, phase_rows[, Segments]) of ``HipModel.vocoder(return_spec=True)``, whose last row of every utterance is
                  repeated like the reference's replicate padding; phase_terms the three means "phase" adds up
       pitch, energy  smooth_l1_loss (beta 1, mean) of the pairs (predicted, recorded) given as ``pitch`` / ``energy``
+      slm        with ``slm``: a modules.WavLMLoss - the mean absolute difference of WavLM's hidden states of the recordings and the synthesised
+                 waveforms (the value of ``slm(audio_gt, audio)``, bit for bit); slm_utt every utterance's own value
     ValueError naming the utterance whose lengths do not agree, or the geometry rule a length breaks."""
     from .modules import MagPhaseLoss, _magphase_sums, _pack_waves, _wave_batch, magphase_score, mel_score
 
@@ -433,6 +435,10 @@ def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, predictio
             a, b, L = _curve_pair(pair, name)
             parts.append(eng.smooth_l1_sums(Segments(L, eng.device), _pack_waves(eng, a), _pack_waves(eng, b)))  # [len(L)]
             curves.append((name, len(L), sum(L)))
+    if slm is not None:
+        slm.wavlm._engine = slm.wavlm._engine or eng
+        s_sums, s_fr = slm.sums(gw, pw)  # [B, states] float64, [B] int32
+        parts += [s_sums, s_fr.to(torch.float64)]
     host = torch.cat([p.reshape(-1) for p in parts]).cpu().tolist()  # the one host read
     at = 2 * R * B
     mel, mel_r, mel_utt = mel_score([[host[2 * (r * B + u) : 2 * (r * B + u) + 2] for u in range(B)] for r in range(R)])
@@ -447,4 +453,10 @@ def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, predictio
             tot += v
         out[name] = tot / n
         at += n_utt
+    if slm is not None:
+        from . import wavlm
+
+        ns = slm.wavlm.n_states
+        fr = [int(v) for v in host[at + ns * B : at + ns * B + B]]
+        out["slm"], out["slm_utt"] = wavlm.score([host[at + ns * u : at + ns * u + ns] for u in range(B)], fr, slm.wavlm.hidden)
     return out

@@ -634,6 +634,57 @@ class HipModel:
         t["frames"] = fr
         return feats, t
 
+    # ------------------------------------------------------------------ WavLM and its perceptual distance (packed waveforms at 16 kHz)
+    def wavlm_finalize(self, arch) -> None:
+        """Pack the weights loaded under "wavlm." for the WavLMConfig fields ``arch`` (wavlm.arch); include/stylish_hip.h, stts_wavlm_finalize."""
+        from . import wavlm
+
+        self._wavlm_arch = dict(arch)
+        self._wavlm_dims = wavlm.dims_struct(arch)
+        _lib.check(self.lib.stts_wavlm_finalize(self.ctx, C.byref(self._wavlm_dims)))
+
+    def _wavlm_ws(self, seg_s: Segments, wave: torch.Tensor, pairs: int):
+        if getattr(self, "_wavlm_dims", None) is None:
+            _lib.check(self.lib.stts_wavlm_forward_states(self.ctx, _stream(), 0, None, None, None, None, None, None, 0))  # not finalized: the library's message
+        # 0: too short an utterance, an unequal pair or bad offsets - the entry point names it, it fails before any launch
+        need = int(self.lib.stts_wavlm_workspace_bytes(self.ctx, seg_s.n, seg_s.host_ptr, pairs)) or 256
+        wave = wave.to(self.device, torch.float32).contiguous()
+        if wave.dim() != 1 or wave.numel() != seg_s.rows:
+            raise ValueError(f"packed waveform of {wave.numel()} samples, the offsets describe {seg_s.rows}")
+        return self._grow(self._sslws, need), wave
+
+    def wavlm_states(self, seg_s: Segments, wave: torch.Tensor, gate: bool = False):
+        """wave [sum samples] packed mono audio at 16 kHz -> states [layers + 1, sum frames, hidden]: transformers' hidden_states, packed rows.
+        gate=True also returns layer 0's gate [sum frames, heads] (a test tap).  Nothing is read back by the host."""
+        from . import hubert_ssl
+
+        ws, wave = self._wavlm_ws(seg_s, wave, 0)
+        a = self._wavlm_arch
+        F = sum(hubert_ssl.frames(n, a) if n >= hubert_ssl.min_samples(a) else 0 for n in seg_s.lengths)
+        states = self._f32(a["num_hidden_layers"] + 1, max(F, 1), a["hidden_size"])
+        g0 = self._f32(max(F, 1), a["num_attention_heads"]) if gate else None
+        _lib.check(self.lib.stts_wavlm_forward_states(self.ctx, _stream(), seg_s.n, seg_s.host_ptr, _ptr(seg_s.dev), _ptr(wave), _ptr(states),
+                                                      _ptr(g0) if gate else None, _ptr(ws), ws.numel()))
+        return (states, g0) if gate else states
+
+    def wavlm_l1(self, seg_s: Segments, wave: torch.Tensor):
+        """2 B packed waveforms, utterances u and u + B of equal length -> (sums [B, layers + 1] float64, frames [B] int32), both on the device:
+        the sums of |difference| of every hidden state over the pair's frames and channels (stts_wavlm_l1_sums).  Nothing is read back."""
+        if seg_s.n % 2:
+            raise ValueError(f"{seg_s.n} utterances do not form pairs")
+        B = seg_s.n // 2
+        ws, wave = self._wavlm_ws(seg_s, wave, B)
+        sums = torch.empty(max(B, 1), self._wavlm_arch["num_hidden_layers"] + 1, dtype=torch.float64, device=self.device)
+        fr = torch.empty(max(B, 1), dtype=torch.int32, device=self.device)
+        _lib.check(self.lib.stts_wavlm_l1_sums(self.ctx, _stream(), B, seg_s.host_ptr, _ptr(seg_s.dev), _ptr(wave), _ptr(sums), _ptr(fr), _ptr(ws), ws.numel()))
+        return sums, fr
+
+    def wavlm_bucket_table(self, max_d: int) -> "np.ndarray":
+        """The bucket of rel_attn_embed the attention reads at every distance -max_d .. max_d (int32 [2 max_d + 1]); stts_wavlm_bucket_table."""
+        out = np.zeros(2 * int(max_d) + 1, np.int32)
+        _lib.check(self.lib.stts_wavlm_bucket_table(self.ctx, int(max_d), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     # ------------------------------------------------------------------ RMVPE pitch extractor (packed log-mel frames at 100 frames / s)
     def rmvpe_finalize(self, dims) -> None:
         """Pack the weights loaded under "rmvpe." for E2E0's constructor arguments ``dims`` (rmvpe.dims); include/stylish_hip.h, stts_rmvpe_finalize."""

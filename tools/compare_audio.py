@@ -10,7 +10,12 @@ arguments but another --precision compare output for output:
 
 Prints the score per resolution, their mean, the worst utterance and the waveform max-abs difference, then one JSON line.
 
-    python tools/compare_audio.py A.npy B.npy [--sample-rate 24000] [--lengths 72000,72000]
+    python tools/compare_audio.py A.npy B.npy [--sample-rate 24000] [--lengths 72000,72000] [--slm DIR]
+
+--slm DIR adds the reference's "slm" score (WavLMLoss, train/losses.py:408-426: the mean absolute difference of WavLM's 13 hidden states, both
+files resampled from --sample-rate to 16 kHz on the engine) from the LOCAL WavLM checkpoint directory DIR (config.json + model.safetensors or
+pytorch_model.bin; nothing is downloaded, no weights ship with the engine).  ``--slm synthetic`` runs the base network with the engine's synthetic
+weights: the arithmetic of the score, not a perceptual number.
 """
 from __future__ import annotations
 
@@ -46,6 +51,7 @@ def main():
     ap.add_argument("b", help="the waveforms scored against them (.npy)")
     ap.add_argument("--sample-rate", type=int, default=None, help="of both files (default: the model config's)")
     ap.add_argument("--lengths", default="", help="comma-separated sample counts of the utterances in a flat file")
+    ap.add_argument("--slm", default=None, metavar="DIR", help="also print the WavLM distance, from this local checkpoint directory ('synthetic': synthetic weights)")
     args = ap.parse_args()
     import torch
 
@@ -62,13 +68,22 @@ def main():
     seg = Segments([w.size for w in A], eng.device)
     sums = eng.mel_sums(seg, torch.from_numpy(np.concatenate(A)), torch.from_numpy(np.concatenate(B)), sample_rate=sr)
     mel, mel_r, mel_utt = mel_score(sums.cpu().tolist())
+    extra = {}
+    if args.slm:
+        from stylish_tts_amd import modules
+
+        net = modules.WavLM(engine=eng).load_synthetic(0) if args.slm == "synthetic" else modules.WavLM(model_path=args.slm, engine=eng)
+        slm, slm_utt = modules.WavLMLoss(net, sr).scores([torch.from_numpy(w) for w in A], [torch.from_numpy(w) for w in B])
+        extra = dict(slm=slm, slm_utt_max=max(slm_utt))
     eng.close()
     for (fft, hop, window), v in zip((val_scores.as_tuple(r) for r in val_scores.resolutions), mel_r):
         print(f"mel at fft {fft:4d} hop {hop:3d} window {window:4d}: {v:.6e}")
     worst = int(np.argmax(mel_utt))
     max_abs = max(float(np.abs(x - y).max()) for x, y in zip(A, B))
     print(f"mel: {mel:.6e}   worst utterance {worst}: {mel_utt[worst]:.6e}   waveform max-abs difference: {max_abs:.3e}")
-    print(json.dumps(dict(mel=mel, mel_r=mel_r, mel_utt_max=mel_utt[worst], utterances=len(A), sample_rate=sr, max_abs=max_abs)))
+    if extra:
+        print(f"slm: {extra['slm']:.6e}   worst utterance: {extra['slm_utt_max']:.6e}")
+    print(json.dumps(dict(mel=mel, mel_r=mel_r, mel_utt_max=mel_utt[worst], utterances=len(A), sample_rate=sr, max_abs=max_abs, **extra)))
 
 
 if __name__ == "__main__":
