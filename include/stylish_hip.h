@@ -830,6 +830,58 @@ typedef struct stts_cfm_source_args {
   float merge_w;
 } stts_cfm_source_args;
 int stts_op_cfm_source(void* stream, const stts_cfm_source_args* args);
+/* The small kernels between the stages, one at a time through the launch functions the stages themselves call (tests/test_hip_glue_kernels.py).  Conventions as
+ * above: every tensor caller-owned and on the device (w_host / b_host excepted), *_elems the element count of the caller's buffer, refusal before any launch.
+ *   kind 0  decoder_front_kernel: x = phoneme encoding [rows, ldx >= C], x2 = pitch, x3 = energy [rows]; F0 = wf . pitch + bf, N = wn . energy + bn (3 taps, zero
+ *           outside the utterance) -> y = encode input [rows, ldy] = [x | F0 | N | 0 ..], y2 / y3 = concat buffers [rows, ld2]: columns from c_hidden + c_res on
+ *           = [F0 | N | 0 ..], the columns before them untouched.
+ *   kind 1  run_style (style_fc_kernel / style_fc_batch_kernel, the launcher's own choice): y [n_utt, ldy = J rounded up to 4] = x [n_utt, K] w_host [J, K]^T + b_host.
+ *   kind 2  embed_kernel: y [n_rows, ldy] = x [vocab = J, C] rows picked by tokens (int64 [n_rows]) times sqrt(C); an id outside the vocabulary sets bit 1 of *err.
+ *   kind 3  mean_rows_kernel: y [n_utt, ldy] = mean over utterance u's rows of x [rows, ldx] (C columns).
+ *   kind 4  broadcast_style_kernel: y [rows, ldy] columns [col0, col0 + C) = x [n_utt, ldx] of the row's utterance.
+ *   kind 5  row_utt_kernel: iy [rows] = utterance of the row.
+ *   kind 6  frame_token_map_kernel, then local_token_kernel: seg_off = frame offsets, tok_off = token offsets, dur [tokens] -> iy [frames] = token row of
+ *           every frame at rate `rep`, iy2 [frames] = iy - tok_off[u]. */
+typedef struct stts_glue_args {
+  const int32_t* seg_off_host;
+  const int32_t* seg_off_dev;
+  const int32_t* tok_off_host;
+  const int32_t* tok_off_dev;
+  const float* x;
+  const float* x2;
+  const float* x3;
+  const float* w_host;
+  const float* b_host;
+  const int64_t* tokens;
+  const int32_t* dur;
+  float* y;
+  float* y2;
+  float* y3;
+  int32_t* iy;
+  int32_t* iy2;
+  int32_t* err;
+  int64_t x_elems, x2_elems, x3_elems, tokens_elems, dur_elems, y_elems, y2_elems, y3_elems, iy_elems, iy2_elems;
+  int32_t n_utt, kind, n_rows, C, K, J, ldx, ldy, ld2, col0, rep, c_hidden, c_res;
+  float wf[3], bf, wn[3], bn;
+} stts_glue_args;
+int stts_op_glue(void* stream, const stts_glue_args* args);
+/* single_channel_conv_kernel: y[r][ycol] = bias + sum over taps t and channels c of w[t][c] x[r + t - (ntaps - 1) / 2][c], zero outside the utterance, for one or two
+ * (x, w, bias, y) sets in one launch.  prec16 0: x fp32 [rows, ldx]; STTS_PREC_BF16 / _F16: 16-bit rows (x_elems counts 16-bit elements).  w fp32 [ntaps][C] on the
+ * device, y [rows, ldy].  C and ldx multiples of 4, ntaps odd and at most 7. */
+typedef struct stts_chan_conv_args {
+  const int32_t* seg_off_host;
+  const int32_t* seg_off_dev;
+  const void* x0;
+  const void* x1;
+  const float* w0;
+  const float* w1;
+  float* y0;
+  float* y1;
+  int64_t x0_elems, x1_elems, w0_elems, w1_elems, y0_elems, y1_elems;
+  int32_t n_utt, prec16, nsets, ntaps, C, ldx, ldy, ycol;
+  float bias0, bias1;
+} stts_chan_conv_args;
+int stts_op_chan_conv(void* stream, const stts_chan_conv_args* args);
 /* AdaptiveDecoderBlock.forward (models/ada_norm.py:166-182) with weights named `prefix` + reference keys. */
 int stts_op_adain_block(stts_ctx* ctx, void* stream, const char* prefix, int n_utt, const int32_t* seg_off_host,
                         const int32_t* seg_off_dev, const float* x, int ldx, int cin, int cout, const float* style, float* y, int ldy,

@@ -146,6 +146,20 @@ class CfmSourceArgs(C.Structure):
                        (_I32, "n_utt ldh"), (_F, "merge_w"))
 
 
+class GlueArgs(C.Structure):
+    """include/stylish_hip.h: stts_glue_args (test surface)."""
+    _fields_ = (_fields((_P, "seg_off_host seg_off_dev tok_off_host tok_off_dev x x2 x3 w_host b_host tokens dur y y2 y3 iy iy2 err"),
+                        (_I64, "x_elems x2_elems x3_elems tokens_elems dur_elems y_elems y2_elems y3_elems iy_elems iy2_elems"),
+                        (_I32, "n_utt kind n_rows C K J ldx ldy ld2 col0 rep c_hidden c_res"))
+                + [("wf", _F * 3), ("bf", _F), ("wn", _F * 3), ("bn", _F)])
+
+
+class ChanConvArgs(C.Structure):
+    """include/stylish_hip.h: stts_chan_conv_args (test surface)."""
+    _fields_ = _fields((_P, "seg_off_host seg_off_dev x0 x1 w0 w1 y0 y1"), (_I64, "x0_elems x1_elems w0_elems w1_elems y0_elems y1_elems"),
+                       (_I32, "n_utt prec16 nsets ntaps C ldx ldy ycol"), (_F, "bias0 bias1"))
+
+
 # name -> (restype, argtypes); mirrors include/stylish_hip.h one to one
 SIGNATURES = {
     "stts_last_error": (C.c_char_p, []),
@@ -251,6 +265,8 @@ TEST_SIGNATURES = {
     "stts_op_rope": (_I, [_P, C.POINTER(RopeArgs)]),
     "stts_op_cfm_small": (_I, [_P, C.POINTER(CfmSmallArgs)]),
     "stts_op_cfm_source": (_I, [_P, C.POINTER(CfmSourceArgs)]),
+    "stts_op_glue": (_I, [_P, C.POINTER(GlueArgs)]),
+    "stts_op_chan_conv": (_I, [_P, C.POINTER(ChanConvArgs)]),
     "stts_op_adain_block": (_I, [_P, _P, C.c_char_p, _I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _SZ]),
     "stts_op_attention": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I]),
     "stts_op_wavlm_l1": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P]),

@@ -487,7 +487,7 @@ inline int decoder_forward(stts_ctx* c, hipStream_t st, const Seg& s, const floa
   fa.bf = c->front_bf; fa.bn = c->front_bn;
   fa.enc_in = enc_in; fa.ld_enc = ldenc; fa.xa = xa; fa.xb = xb; fa.ld_x = ldcat;
   fa.c_asr = d.inter_dim; fa.c_hidden = d.dec_hidden; fa.c_res = d.dec_residual;
-  STTS_LAUNCH_PROF("decoder_front_kernel", (size_t)R * (d.inter_dim + 2 + ldenc + 2 * 4) * 4, decoder_front_kernel, rows_grid(s, ldenc / 4), dim3(256), st, fa, s.dev);
+  launch_decoder_front(st, s, fa);
   // asr_res = wn-conv1x1(asr) into the residual columns of both concat buffers (decoder.py:54)
   for (float* dst : {xa, xb}) {
     GemmArgs a = gemm_args(s);

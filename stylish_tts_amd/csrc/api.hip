@@ -252,7 +252,7 @@ int stts_length_regulate(stts_ctx* c, void* stream, int n_utt, const int32_t* du
   hipStream_t st = (hipStream_t)stream;
   STTS_CHECK(dur && tok_off && frm_off && enc && out && src_row_ws && n_utt > 0 && n_frames >= 0 && rep >= 1, "length_regulate: bad argument");
   STTS_CHECK(C % 4 == 0 && ld_enc % 4 == 0 && ld_out % 4 == 0, "length_regulate: channel counts must be multiples of 4");
-  hipLaunchKernelGGL(frame_token_map_kernel, dim3(n_utt), dim3(256), 0, st, dur, tok_off, frm_off, rep, src_row_ws);
+  launch_frame_token_map(st, n_utt, dur, tok_off, frm_off, rep, src_row_ws);
   const long work = n_frames * (C / 4);
   hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)std::min<long>(2048, std::max<long>(1, (work + 255) / 256))), dim3(256), 0, st, enc, ld_enc,
                      src_row_ws, out, ld_out, 0, C, (int)n_frames, frm_off + n_utt);  // n_frames may be a capacity: the real count is frm_off[n_utt]

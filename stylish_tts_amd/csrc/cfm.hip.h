@@ -462,7 +462,7 @@ inline int cfm_estimator(stts_ctx* c, const CfmModel& M, hipStream_t st, const S
   STTS_TRY(cfm_linear(st, s, a1, 4 * d.emb, M.asr3, ACT_NONE, ae, d.emb));
   STTS_TRY(run_small(st, M.spk0, spk, d.spk, 1, s1, 4 * d.emb, U));
   STTS_TRY(run_small(st, M.spk2, s1, 4 * d.emb, 0, se, d.emb, U));
-  hipLaunchKernelGGL(broadcast_style_kernel, dim3(std::max(1, ceil_div(s.max_len() * d.emb, 256)), U), dim3(256), 0, st, se, d.emb, d.emb, sb, d.emb, 0, s.dev);
+  launch_broadcast_style(st, s, se, d.emb, d.emb, sb, d.emb, 0);
   launch_cfm_source(st, s, f0, ncurve, curve_off_dev, t, noise, M.merge_w, har, 32);
   // x + prior_generator(har) (k = 7 conv over the three source features), then in_proj over [x | asr_emb | spk_emb] as three K segments
   // (xp's pad columns meet zero weights in in_proj, but the contraction reads them: they must be finite)

@@ -284,7 +284,7 @@ inline int hubert_pitch_energy_forward(stts_ctx* c, const HubertModel& M, hipStr
     STTS_TRY(prosody());
   }
   STTS_DRY_RETURN(ws);
-  hipLaunchKernelGGL(row_utt_kernel, dim3(ceil_div(s.max_len(), 256), s.n_utt), dim3(256), 0, st, s.dev, s.n_utt, row_utt);
+  launch_row_utt(st, s, row_utt);
   STTS_TRY(gemm_store(st, s, feats, ld_f, 0, P.quant, q, d, 0));
   STTS_TRY(run_style(st, P.table, pe_style, s.n_utt, sty));
   STTS_TRY(prosody());
@@ -300,8 +300,7 @@ inline int hubert_pitch_energy_forward(stts_ctx* c, const HubertModel& M, hipStr
       cur = bufs[i & 1];
     }
     const ChanConvSet cs{cur, br == 0 ? P.f0_w : P.n_w, br == 0 ? P.f0_b : P.n_b, br == 0 ? f0 : nrg};
-    hipLaunchKernelGGL(single_channel_conv_kernel<0>, dim3((unsigned)ceil_div(s.max_len(), 4 * kChanRows), 1, s.n_utt), dim3(256), 0, st, cs, cs, C, C, s.dev, 1,
-                       1, 0);
+    STTS_TRY(launch_single_channel_conv(st, s, 0, 1, cs, cs, C, C, 1, 1, 0));
   }
   STTS_HIP(hipGetLastError());
   return 0;

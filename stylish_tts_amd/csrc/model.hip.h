@@ -1116,6 +1116,8 @@ inline int run_wino_bridge(hipStream_t st, const Seg& s, const WinoConv& A, cons
 }
 
 inline int run_style(hipStream_t st, const StyleTable& t, const float* style, int n_utt, float* out) {
+  // both kernels hold a weight row in two registers per lane (style_fc_kernel) / 128 floats of LDS (style_fc_batch_kernel): a wider table would lose its columns from 128 on
+  STTS_CHECK(t.K > 0 && t.K <= 128, "run_style: a style table of K = %d columns (the style kernels cover 1 .. 128)", t.K);
   if (n_utt >= 16 && t.K % 4 == 0 && t.K <= 128) {  // lane = utterance: no per-utterance reduction (same sums, other order: ~1e-7)
     STTS_LAUNCH_PROF("style_fc_batch_kernel", (size_t)t.J * (t.K + n_utt) * 4, style_fc_batch_kernel, dim3(ceil_div(t.J, 4)), dim3(256), st, t.W, t.b, style, out,
                      t.J, t.K, n_utt, t.K, t.ld());
@@ -1130,6 +1132,54 @@ inline int run_style(hipStream_t st, const StyleTable& t, const float* style, in
 inline dim3 rows_grid(const Seg& s, int per_row_work) {
   const long total = (long)s.max_len() * per_row_work;
   return dim3((unsigned)std::min<long>(std::max<long>(1, ceil_div((int)std::min<long>(total, 1 << 30), 256)), 512), s.n_utt);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Launches of the small kernels between the stages (index maps, gathers, broadcasts, one-channel projections): one function per kernel,
+// called by the stages and by the test operators (test_ops.hip.h: stts_op_glue / stts_op_chan_conv), so a test runs the stage's own grid.
+// ------------------------------------------------------------------------------------------------
+inline void launch_embed(hipStream_t st, const long* tokens, const float* emb, int C, int vocab, float* x, int ldx, long R, int* err) {
+  hipLaunchKernelGGL(embed_kernel, dim3((unsigned)std::min<long>(1024, ceil_div((int)(R * C / 4), 256))), dim3(256), 0, st, tokens, emb, C, vocab, sqrtf((float)C), x, ldx, (int)R, err);
+}
+inline void launch_mean_rows(hipStream_t st, const Seg& s, const float* x, int ldx, int C, float* out, int ld_out) {
+  hipLaunchKernelGGL(mean_rows_kernel, dim3(s.n_utt), dim3(256), 0, st, x, ldx, C, s.dev, out, ld_out);
+}
+inline void launch_broadcast_style(hipStream_t st, const Seg& s, const float* style, int ld_style, int C, float* y, int ldy, int col0) {
+  hipLaunchKernelGGL(broadcast_style_kernel, dim3(std::max(1, ceil_div(s.max_len() * C, 256)), s.n_utt), dim3(256), 0, st, style, ld_style, C, y, ldy, col0, s.dev);
+}
+inline void launch_row_utt(hipStream_t st, const Seg& s, int* row_utt) {
+  hipLaunchKernelGGL(row_utt_kernel, dim3(ceil_div(s.max_len(), 256), s.n_utt), dim3(256), 0, st, s.dev, s.n_utt, row_utt);
+}
+inline void launch_frame_token_map(hipStream_t st, int n_utt, const int* dur, const int* tok_off, const int* frm_off, int rep, int* src_row) {
+  hipLaunchKernelGGL(frame_token_map_kernel, dim3(n_utt), dim3(256), 0, st, dur, tok_off, frm_off, rep, src_row);
+}
+inline void launch_local_token(hipStream_t st, const Seg& sf, const Seg& sp, const int* src_row, int* centre) {
+  hipLaunchKernelGGL(local_token_kernel, dim3(ceil_div(sf.max_len(), 256), sf.n_utt), dim3(256), 0, st, src_row, sf.dev, sp.dev, centre);
+}
+// nsets 1: s0 alone; 2: both sets in one launch (grid.y).  x16: 0 = fp32 rows, PREC_BF16 / PREC_F16 = 16-bit rows (ldx in elements).  prof: a record for
+// the profiler (the vocoder's Nyquist bins).
+inline int launch_single_channel_conv(hipStream_t st, const Seg& s, int x16, int nsets, const ChanConvSet& s0, const ChanConvSet& s1, int ldx, int C, int ntaps, int ldy, int ycol,
+                                      bool prof = false) {
+  STTS_CHECK(ntaps >= 1 && ntaps <= kChanTaps && ntaps % 2 == 1, "single-channel conv: kernel size %d (odd, at most %d)", ntaps, kChanTaps);
+  STTS_CHECK((nsets == 1 || nsets == 2) && C > 0 && C % 4 == 0 && ldx % 4 == 0 && ldx >= C, "single-channel conv: one or two sets, C and ldx multiples of 4, ldx >= C");
+  const dim3 cg((unsigned)ceil_div(s.max_len(), 4 * kChanRows), nsets, s.n_utt);
+  if (cg.x == 0) return 0;
+  if (prof) {
+    const size_t cb = (size_t)nsets * s.rows() * (ldx * (x16 ? 2 : 4) + 4);
+    if (x16 == PREC_BF16) STTS_LAUNCH_PROF("single_channel_conv_kernel", cb, single_channel_conv_kernel<PREC_BF16>, cg, dim3(256), st, s0, s1, ldx, C, s.dev, ntaps, ldy, ycol);
+    else if (x16 == PREC_F16) STTS_LAUNCH_PROF("single_channel_conv_kernel", cb, single_channel_conv_kernel<PREC_F16>, cg, dim3(256), st, s0, s1, ldx, C, s.dev, ntaps, ldy, ycol);
+    else STTS_LAUNCH_PROF("single_channel_conv_kernel", cb, single_channel_conv_kernel<0>, cg, dim3(256), st, s0, s1, ldx, C, s.dev, ntaps, ldy, ycol);
+  } else if (x16 == PREC_BF16) {
+    hipLaunchKernelGGL(single_channel_conv_kernel<PREC_BF16>, cg, dim3(256), 0, st, s0, s1, ldx, C, s.dev, ntaps, ldy, ycol);
+  } else if (x16 == PREC_F16) {
+    hipLaunchKernelGGL(single_channel_conv_kernel<PREC_F16>, cg, dim3(256), 0, st, s0, s1, ldx, C, s.dev, ntaps, ldy, ycol);
+  } else {
+    hipLaunchKernelGGL(single_channel_conv_kernel<0>, cg, dim3(256), 0, st, s0, s1, ldx, C, s.dev, ntaps, ldy, ycol);
+  }
+  return 0;
+}
+inline void launch_decoder_front(hipStream_t st, const Seg& s, const FrontArgs& fa) {
+  STTS_LAUNCH_PROF("decoder_front_kernel", (size_t)s.rows() * (fa.c_asr + 2 + fa.ld_enc + 2 * 4) * 4, decoder_front_kernel, rows_grid(s, fa.ld_enc / 4), dim3(256), st, fa, s.dev);
 }
 
 }  // namespace stts
@@ -1364,11 +1414,7 @@ inline int vocoder_body(stts_ctx* c, hipStream_t st, const Seg& s, const float* 
     const int kk = c->amp_out.ntaps;
     STTS_CHECK(kk <= kChanTaps, "output conv kernel size %d > %d", kk, kChanTaps);
     const ChanConvSet sa{headA, c->nyq_w[0], c->nyq_b[0], la}, sp{headP, c->nyq_w[1], c->nyq_b[1], ph};
-    const dim3 cg((unsigned)ceil_div(ml, 4 * kChanRows), 2, s.n_utt);
-    const size_t cb = (size_t)2 * R * (hc * (p16 ? 2 : 4) + 4);
-    if (p16 == PREC_BF16) STTS_LAUNCH_PROF("single_channel_conv_kernel", cb, single_channel_conv_kernel<PREC_BF16>, cg, dim3(256), st, sa, sp, hc, hc, s.dev, kk, ldl, geo.bins - 1);
-    else if (p16 == PREC_F16) STTS_LAUNCH_PROF("single_channel_conv_kernel", cb, single_channel_conv_kernel<PREC_F16>, cg, dim3(256), st, sa, sp, hc, hc, s.dev, kk, ldl, geo.bins - 1);
-    else STTS_LAUNCH_PROF("single_channel_conv_kernel", cb, single_channel_conv_kernel<0>, cg, dim3(256), st, sa, sp, hc, hc, s.dev, kk, ldl, geo.bins - 1);
+    STTS_TRY(launch_single_channel_conv(st, s, p16, 2, sa, sp, hc, hc, kk, ldl, geo.bins - 1, true));
   }
   if (geo.generic) {
     STTS_TRY(launch_istft_geom(st, geo, s.n_utt, s.dev, R, ml, la, ph, ldl, c->hann, c->twiddle64, yw, audio));

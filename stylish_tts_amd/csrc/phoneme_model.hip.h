@@ -358,8 +358,7 @@ inline int text_encoder_forward(stts_ctx* c, hipStream_t st, const TextEncW& W, 
   float* ff = ws.get<float>(R * W.filter);
   STTS_CHECK(ws.ok, "text_encoder_forward: workspace too small");
   STTS_DRY_RETURN(ws);
-  hipLaunchKernelGGL(embed_kernel, dim3((unsigned)std::min<long>(1024, ceil_div((int)(R * C / 4), 256))), dim3(256), 0, st, tokens, W.emb, C, W.tokens,
-                     sqrtf((float)C), x, C, (int)R, c->d_err);
+  launch_embed(st, tokens, W.emb, C, W.tokens, x, C, R, c->d_err);
   // ConvReluNorm prenet (text_encoder.py:79-86): 3 x (conv k5 -> channel LayerNorm eps 1e-4 -> ReLU), + 1x1 proj residual
   const float* cur = x;
   for (int i = 0; i < 3; ++i) {
@@ -415,7 +414,7 @@ inline int text_style_forward(stts_ctx* c, hipStream_t st, const StyleEncW& W, c
     STTS_TRY(launch_conv_gemm(st, b, EPI_STORE, B.pw2.npad, s.n_utt, ml));
     std::swap(h, h2);
   }
-  hipLaunchKernelGGL(mean_rows_kernel, dim3(s.n_utt), dim3(256), 0, st, h, sd, sd, s.dev, style, ld_style);
+  launch_mean_rows(st, s, h, sd, sd, style, ld_style);
   STTS_HIP(hipGetLastError());
   return 0;
 }
@@ -435,7 +434,7 @@ inline int prosody_forward(hipStream_t st, const ProsodyW& W, const Seg& s, cons
   STTS_CHECK(ws.ok, "prosody_forward: workspace too small");
   STTS_DRY_RETURN(ws);
   STTS_HIP(hipMemcpy2DAsync(x, C * sizeof(float), enc, ld_enc * sizeof(float), d * sizeof(float), R, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(broadcast_style_kernel, dim3(std::max(1, ceil_div(s.max_len() * sd, 256)), s.n_utt), dim3(256), 0, st, style, sd, sd, x, C, d, s.dev);
+  launch_broadcast_style(st, s, style, sd, sd, x, C, d);
   for (int i = 0; i < W.n_layers; ++i) {
     const ProsodyW::L& L = W.l[i];
     STTS_TRY(gemm_store(st, s, x, C, 0, L.qkv, qkv, 3 * C, 0));
@@ -472,7 +471,7 @@ inline int duration_forward(stts_ctx* c, PhonemeModel& M, hipStream_t st, const 
     STTS_TRY(prosody());
   }
   STTS_DRY_RETURN(ws);
-  hipLaunchKernelGGL(row_utt_kernel, dim3(ceil_div(s.max_len(), 256), s.n_utt), dim3(256), 0, st, s.dev, s.n_utt, row_utt);
+  launch_row_utt(st, s, row_utt);
   STTS_TRY(text());
   STTS_TRY(text_style());
   STTS_TRY(run_style(st, D.table, style, s.n_utt, sty));
@@ -527,15 +526,15 @@ inline int pitch_energy_forward(stts_ctx* c, PhonemeModel& M, hipStream_t st, co
     STTS_TRY(prosody());
   }
   STTS_DRY_RETURN(ws);
-  hipLaunchKernelGGL(row_utt_kernel, dim3(ceil_div(sp.max_len(), 256), sp.n_utt), dim3(256), 0, st, sp.dev, sp.n_utt, row_utt_p);
-  hipLaunchKernelGGL(row_utt_kernel, dim3(ceil_div(sf.max_len(), 256), sf.n_utt), dim3(256), 0, st, sf.dev, sf.n_utt, row_utt_f);
+  launch_row_utt(st, sp, row_utt_p);
+  launch_row_utt(st, sf, row_utt_f);
   STTS_TRY(run_style(st, P.table, pe_style, sp.n_utt, sty));
   STTS_TRY(prosody());
   // compute_cross (pitch_energy_predictor.py:83-102): base = prosody^T @ alignment == gather by the frame->token map
-  hipLaunchKernelGGL(frame_token_map_kernel, dim3(sp.n_utt), dim3(256), 0, st, dur, sp.dev, sf.dev, 1, src_row);
+  launch_frame_token_map(st, sp.n_utt, dur, sp.dev, sf.dev, 1, src_row);
   hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)std::min<long>(2048, std::max<long>(1, ceil_div((int)(Rf * C / 4), 256)))), dim3(256), 0, st, pros, C,
                      src_row, base, C, 0, C, (int)Rf, sf.rows_dev());
-  hipLaunchKernelGGL(local_token_kernel, dim3(ceil_div(sf.max_len(), 256), sf.n_utt), dim3(256), 0, st, src_row, sf.dev, sp.dev, centre);
+  launch_local_token(st, sf, sp, src_row, centre);
   STTS_TRY(adaptive_ln(st, base, C, C, Rf, row_utt_f, 1e-5f, sty, lds, P.qn.col0, qn, C, sf.rows_dev()));
   STTS_TRY(adaptive_ln(st, pros, C, C, Rp, row_utt_p, 1e-5f, sty, lds, P.kn.col0, kn, C));
   STTS_TRY(gemm_store(st, sf, qn, C, 0, P.q, q, C, 0));
@@ -565,8 +564,7 @@ inline int pitch_energy_forward(stts_ctx* c, PhonemeModel& M, hipStream_t st, co
       cur = bufs[i & 1];
     }
     const ChanConvSet cs{cur, br == 0 ? P.f0_w : P.n_w, br == 0 ? P.f0_b : P.n_b, br == 0 ? f0 : nrg};
-    hipLaunchKernelGGL(single_channel_conv_kernel<0>, dim3((unsigned)ceil_div(sf.max_len(), 4 * kChanRows), 1, sf.n_utt), dim3(256), 0, st, cs, cs, C, C, sf.dev, 1,
-                       1, 0);
+    STTS_TRY(launch_single_channel_conv(st, sf, 0, 1, cs, cs, C, C, 1, 1, 0));
   }
   STTS_HIP(hipGetLastError());
   return 0;

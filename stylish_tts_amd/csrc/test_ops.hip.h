@@ -859,6 +859,115 @@ int stts_op_cfm_source(void* stream, const stts_cfm_source_args* p) {
   API_END
 }
 
+// The small kernels between the stages (index maps, gathers, broadcasts, style projection, decoder front), one launch per call through the launch_* / run_style
+// functions of model.hip.h that the stages call: tests/test_hip_glue_kernels.py.  As above: every check before any launch.
+int stts_op_glue(void* stream, const stts_glue_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p && p->kind >= 0 && p->kind <= 6, "op_glue: null argument, or kind outside 0 - 6");
+  const int kind = p->kind;
+  long R = 0;
+  Seg s{};
+  if (kind != 1 && kind != 2) {
+    STTS_TRY(norm_op_offsets(st, "op_glue", p->n_utt, p->seg_off_host, p->seg_off_dev));
+    s = Seg{p->n_utt, p->seg_off_host, p->seg_off_dev};
+    R = s.rows();
+  }
+  const int C = p->C;
+  if (kind == 0) {  // decoder_front_kernel
+    const int cc = p->c_hidden + p->c_res;
+    STTS_CHECK(p->x && p->x2 && p->x3 && p->y && p->y2 && p->y3, "op_glue: decoder front needs x, x2, x3, y, y2, y3");
+    STTS_CHECK(C > 0 && C % 4 == 0 && p->ldx % 4 == 0 && p->ldy % 4 == 0 && p->ld2 % 4 == 0 && cc % 4 == 0 && p->c_hidden >= 0 && p->c_res >= 0,
+               "op_glue: decoder front moves four columns at a time: C, ldx, ldy, ld2 and c_hidden + c_res are multiples of 4");
+    STTS_CHECK(p->ldy >= C + 4 && p->ld2 >= cc + 4, "op_glue: decoder front needs ldy >= C + 4 and ld2 >= c_hidden + c_res + 4 (the F0 / N quad)");
+    STTS_CHECK(norm_op_fits(R, p->ldx, 0, C, p->x_elems) && R <= p->x2_elems && R <= p->x3_elems && norm_op_fits(R, p->ldy, 0, p->ldy, p->y_elems) &&
+                   norm_op_fits(R, p->ld2, 0, p->ld2, p->y2_elems) && norm_op_fits(R, p->ld2, 0, p->ld2, p->y3_elems),
+               "op_glue: decoder front: a tensor is shorter than its rows");
+    STTS_CHECK((uintptr_t)p->x % 16 == 0 && (uintptr_t)p->y % 16 == 0 && (uintptr_t)p->y2 % 16 == 0 && (uintptr_t)p->y3 % 16 == 0, "op_glue: 16-byte alignment");
+    FrontArgs fa;
+    fa.asr = p->x; fa.ld_asr = p->ldx; fa.pitch = p->x2; fa.energy = p->x3;
+    for (int i = 0; i < 3; ++i) { fa.wf[i] = p->wf[i]; fa.wn[i] = p->wn[i]; }
+    fa.bf = p->bf; fa.bn = p->bn;
+    fa.enc_in = p->y; fa.ld_enc = p->ldy; fa.xa = p->y2; fa.xb = p->y3; fa.ld_x = p->ld2;
+    fa.c_asr = C; fa.c_hidden = p->c_hidden; fa.c_res = p->c_res;
+    if (R > 0) launch_decoder_front(st, s, fa);
+  } else if (kind == 1) {  // run_style: the table is built and padded as the stages' tables are (StyleTable / upload_table)
+    const int n_utt = p->n_utt, J = p->J, K = p->K;
+    STTS_CHECK(n_utt > 0 && J > 0 && K > 0 && p->w_host && p->b_host && p->x && p->y, "op_glue: run_style needs n_utt, J, K, w_host, b_host, x, y");
+    STTS_CHECK(p->ldy == round_up(J, 4) && (long)n_utt * K <= p->x_elems && (long)n_utt * p->ldy <= p->y_elems && (uintptr_t)p->x % 16 == 0,
+               "op_glue: run_style needs x [n_utt, K] (16-byte aligned) and y [n_utt, ldy = J rounded up to 4]");
+    NormOpTemps t(st);
+    PackScope scope(&t.tmp, engine_mode(&t.tmp));
+    StyleTable tab;
+    tab.K = K;
+    tab.J = J;
+    tab.hW.assign(p->w_host, p->w_host + (size_t)J * K);
+    tab.hb.assign(p->b_host, p->b_host + J);
+    STTS_TRY(upload_table(&t.tmp, &tab));
+    STTS_TRY(run_style(st, tab, p->x, n_utt, p->y));
+    STTS_HIP(hipStreamSynchronize(st));
+    return 0;
+  } else if (kind == 2) {  // embed_kernel
+    const long rows = p->n_rows;
+    STTS_CHECK(rows > 0 && C > 0 && C % 4 == 0 && p->J > 0 && p->ldy % 4 == 0 && p->x && p->tokens && p->y && p->err, "op_glue: embed needs n_rows, C %% 4 == 0, J (vocabulary), ldy %% 4 == 0, x, tokens, y, err");
+    STTS_CHECK((long)p->J * C <= p->x_elems && rows <= p->tokens_elems && norm_op_fits(rows, p->ldy, 0, C, p->y_elems) && rows * C < (1L << 31),
+               "op_glue: embed: x [J, C], tokens [n_rows] or y [n_rows, ldy >= C] shorter than that");
+    STTS_CHECK((uintptr_t)p->x % 16 == 0 && (uintptr_t)p->y % 16 == 0, "op_glue: 16-byte alignment");
+    launch_embed(st, reinterpret_cast<const long*>(p->tokens), p->x, C, p->J, p->y, p->ldy, rows, p->err);
+  } else if (kind == 3) {  // mean_rows_kernel
+    STTS_CHECK(C > 0 && p->x && p->y && norm_op_fits(R, p->ldx, 0, C, p->x_elems) && norm_op_fits(p->n_utt, p->ldy, 0, C, p->y_elems),
+               "op_glue: mean_rows needs x [rows, ldx >= C] and y [n_utt, ldy >= C]");
+    launch_mean_rows(st, s, p->x, p->ldx, C, p->y, p->ldy);
+  } else if (kind == 4) {  // broadcast_style_kernel
+    STTS_CHECK(C > 0 && p->x && p->y && norm_op_fits(p->n_utt, p->ldx, 0, C, p->x_elems) && norm_op_fits(R, p->ldy, p->col0, C, p->y_elems),
+               "op_glue: broadcast_style needs x [n_utt, ldx >= C] and y [rows, ldy >= col0 + C]");
+    STTS_CHECK((long)s.max_len() * C < (1L << 31), "op_glue: max_len * C beyond the grid arithmetic");
+    if (R > 0) launch_broadcast_style(st, s, p->x, p->ldx, C, p->y, p->ldy, p->col0);
+  } else if (kind == 5) {  // row_utt_kernel
+    STTS_CHECK(p->iy && R <= p->iy_elems && s.max_len() > 0, "op_glue: row_utt needs iy [rows] and at least one row");
+    launch_row_utt(st, s, p->iy);
+  } else {  // frame_token_map_kernel + local_token_kernel, as pitch_energy_forward chains them
+    STTS_TRY(norm_op_offsets(st, "op_glue (tokens)", p->n_utt, p->tok_off_host, p->tok_off_dev));
+    Seg sp{p->n_utt, p->tok_off_host, p->tok_off_dev};
+    STTS_CHECK(p->dur && p->iy && p->iy2 && p->rep >= 1 && sp.rows() <= p->dur_elems && R <= p->iy_elems && R <= p->iy2_elems && s.max_len() > 0,
+               "op_glue: token map needs dur [tokens], iy / iy2 [frames], rep >= 1 and at least one frame");
+    for (int u = 0; u < p->n_utt; ++u)
+      STTS_CHECK(p->tok_off_host[u + 1] > p->tok_off_host[u] || p->seg_off_host[u + 1] == p->seg_off_host[u], "op_glue: utterance %d has frames but no token", u);
+    launch_frame_token_map(st, p->n_utt, p->dur, sp.dev, s.dev, p->rep, p->iy);
+    launch_local_token(st, s, sp, p->iy, p->iy2);
+  }
+  STTS_HIP(hipGetLastError());
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
+int stts_op_chan_conv(void* stream, const stts_chan_conv_args* p) {
+  API_BEGIN
+  hipStream_t st = (hipStream_t)stream;
+  STTS_CHECK(p, "op_chan_conv: null argument");
+  STTS_TRY(norm_op_offsets(st, "op_chan_conv", p->n_utt, p->seg_off_host, p->seg_off_dev));
+  Seg s{p->n_utt, p->seg_off_host, p->seg_off_dev};
+  const long R = s.rows();
+  const int C = p->C;
+  STTS_CHECK(p->prec16 == 0 || p->prec16 == PREC_BF16 || p->prec16 == PREC_F16, "op_chan_conv: prec16 is 0, STTS_PREC_BF16 or _F16");
+  STTS_CHECK(p->nsets == 1 || p->nsets == 2, "op_chan_conv: one or two sets");
+  STTS_CHECK(R > 0 && C > 0 && p->ntaps >= 1 && p->ycol >= 0 && p->ycol < p->ldy, "op_chan_conv: no rows, or C / ntaps / ycol out of range");
+  STTS_CHECK((long)s.max_len() * p->ldx < (1L << 28), "op_chan_conv: max_len * ldx beyond the kernel's 32-bit byte offsets");
+  auto set_ok = [&](const void* x, long xe, const float* w, long we, const float* y, long ye) {
+    return x && w && y && norm_op_fits(R, p->ldx, 0, C, xe) && (long)p->ntaps * C <= we && (R - 1) * (long)p->ldy + p->ycol + 1 <= ye && (uintptr_t)x % 16 == 0 && (uintptr_t)w % 16 == 0;
+  };
+  STTS_CHECK(set_ok(p->x0, p->x0_elems, p->w0, p->w0_elems, p->y0, p->y0_elems), "op_chan_conv: set 0: x [rows, ldx >= C], w [ntaps, C] (16-byte aligned) or y [rows, ldy] outside its buffer");
+  STTS_CHECK(p->nsets == 1 || set_ok(p->x1, p->x1_elems, p->w1, p->w1_elems, p->y1, p->y1_elems), "op_chan_conv: set 1: x, w or y outside its buffer");
+  const ChanConvSet s0{reinterpret_cast<const float*>(p->x0), p->w0, p->bias0, p->y0};
+  const ChanConvSet s1 = p->nsets == 2 ? ChanConvSet{reinterpret_cast<const float*>(p->x1), p->w1, p->bias1, p->y1} : s0;
+  STTS_TRY(launch_single_channel_conv(st, s, p->prec16, p->nsets, s0, s1, p->ldx, C, p->ntaps, p->ldy, p->ycol));
+  STTS_HIP(hipGetLastError());
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ kernel microbench

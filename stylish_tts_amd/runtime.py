@@ -400,6 +400,27 @@ class HipModel:
         a.curve_off_host, a.curve_off_dev = curves.host_ptr, _ptr(curves.dev)
         _lib.check(self.lib.stts_op_cfm_source(_stream(), C.byref(a)))
 
+    # ------------------------------------------------------------------ the small kernels between the stages (test surface)
+    def op_glue(self, seg: Optional[Segments], tok: Optional[Segments] = None, wf=None, wn=None, **fields):
+        """stts_op_glue (fields of stts_glue_args): kind 0 decoder front (wf / wn: the 3-tap filters), 1 run_style, 2 embed, 3 mean_rows, 4 broadcast_style,
+        5 row_utt, 6 frame_token_map + local_token (seg: frames, tok: tokens)."""
+        keep = []
+        a = self._fill_args(_lib.GlueArgs(), seg, fields, keep)
+        if tok is not None:
+            a.tok_off_host, a.tok_off_dev = tok.host_ptr, _ptr(tok.dev)
+        for i in range(3):
+            if wf is not None:
+                a.wf[i] = float(wf[i])
+            if wn is not None:
+                a.wn[i] = float(wn[i])
+        _lib.check(self.lib.stts_op_glue(_stream(), C.byref(a)))
+
+    def op_chan_conv(self, seg: Segments, **fields):
+        """stts_op_chan_conv (fields of stts_chan_conv_args): the one-channel conv (F0 / N heads, the vocoder's Nyquist bin), one or two sets per launch."""
+        keep = []
+        a = self._fill_args(_lib.ChanConvArgs(), seg, fields, keep)
+        _lib.check(self.lib.stts_op_chan_conv(_stream(), C.byref(a)))
+
     def op_adain_block(self, prefix: str, seg: Segments, x, cin, cout, style):
         y = self._f32(seg.rows, cout)
         ws = self.workspace(seg)
