@@ -886,6 +886,41 @@ int stts_op_chan_conv(void* stream, const stts_chan_conv_args* args);
 int stts_op_adain_block(stts_ctx* ctx, void* stream, const char* prefix, int n_utt, const int32_t* seg_off_host,
                         const int32_t* seg_off_dev, const float* x, int ldx, int cin, int cout, const float* style, float* y, int ldy,
                         void* ws, size_t ws_bytes);
+/* One AdaptiveDecoderBlock, or two chained ones A -> B (B reads [y_A | constant columns]), in any form the block plan can take at any row count: the caller
+ * sets the thresholds and flags of the plan (csrc/adain_block.hip.h BlockSwitches; the environment is not read for them) and what it offers, and gets back
+ * every block's output and the plan that ran.  Weights named `prefix` + reference keys, packed in the context's precision on first use.
+ *   x [rows, ldx >= cin padded as the precision packs it (32; 64 in the 16-bit modes)], style [n_utt, style_dim], ws: workspace of stts_frame_workspace_bytes.
+ *   blocks[i].y [rows, ldy >= cout]: the block's output.  Two blocks: blocks[0].y is B's input, so its ldy covers B's padded channels and the CALLER has
+ *   filled its columns [cout_A, cin_B) with the constant columns and the rest with zeros; the operator runs the one statistics pass over them, hands
+ *   their table to the bridge and rounds them into 16-bit rows, as Decoder.forward does.
+ *   blocks[i].y16 (optional, 16-bit modes) [rows, ldy16]: y rounded to the mode's format; blocks[0].y16 of a pair has ldy16 == ldy and serves as B's rounded input.
+ *   offer_wino: Winograd scratch; offer_stats: buffers for statistics the producers leave behind; offer_rows16: 16-bit scratch for the rounded inputs;
+ *   offer_side: a second stream with fork / join events (owned by the operator) for the learned shortcuts; defer: a folded conv2's split-K reduce may be
+ *   left to the next statistics launch (finished on its own after the last block); force_tile: tile of the direct contractions (0: the plan's).
+ *   plan_out (host, 8 + 16 * nblocks integers): {wino, sc_out, rows16, wino_stats, stats, bridge_w, side, 0} of the chain plan, then per block {conv1, conv2,
+ *   rows16, norm1, norm2, next_norm1, take_pending, defer_conv2, shortcut, cast_x16, y16, affine_serial, bridge_w, force_tile, pending, 0} (the enums of BlockPlan, in
+ *   their order; pending: the split-K factor of the reduce conv2 left to the chain, 0 if none).  A negative fold_rows / fold16_rows / rows16 / sc_side_min_rows: the engine's own.  Written before the block's launches, so a refused or failed call still shows what was planned up to there. */
+typedef struct stts_adain_chain_block {
+  const char* prefix;
+  float* y;
+  uint16_t* y16;
+  int64_t y_elems, y16_elems;
+  int32_t cin, cout, ldy, ldy16;
+} stts_adain_chain_block;
+typedef struct stts_adain_chain_args {
+  const int32_t* seg_off_host;
+  const int32_t* seg_off_dev;
+  const float* x;
+  const float* style;
+  void* ws;
+  int32_t* plan_out;
+  int64_t x_elems, style_elems, ws_bytes;
+  int32_t n_utt, nblocks, ldx;
+  int32_t fold_rows, fold16_rows, rows16, sc_side_min_rows, affine_serial, no_wino_conv2sc, no_stat_fuse, no_wino_stats, bridge;
+  int32_t offer_wino, offer_stats, offer_rows16, offer_side, defer, force_tile;
+  stts_adain_chain_block blocks[2];
+} stts_adain_chain_args;
+int stts_op_adain_chain(stts_ctx* ctx, void* stream, const stts_adain_chain_args* args);
 /* Multi-head scaled-dot-product attention on packed sequences (MultiHeadAttention.attention, models/text_encoder.py:233-277;
  * models/xut/attention.py): q [q rows, heads * kc], k / v [k rows, heads * kc], o [q rows, heads * kc]; utterance u's queries see its
  * own keys only.  band_centre (optional, [q rows] int32) + window: the pitch/energy predictor's inverted band mask.

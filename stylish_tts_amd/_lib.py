@@ -83,6 +83,18 @@ class AdainArgs(C.Structure):
                        (_I32, "ld_gb gcol0 ld_aff ldy rb act out16"))
 
 
+class AdainChainBlock(C.Structure):
+    """include/stylish_hip.h: stts_adain_chain_block (test surface)."""
+    _fields_ = _fields((C.c_char_p, "prefix"), (_P, "y y16"), (_I64, "y_elems y16_elems"), (_I32, "cin cout ldy ldy16"))
+
+
+class AdainChainArgs(C.Structure):
+    """include/stylish_hip.h: stts_adain_chain_args (test surface)."""
+    _fields_ = (_fields((_P, "seg_off_host seg_off_dev x style ws plan_out"), (_I64, "x_elems style_elems ws_bytes"), (_I32, "n_utt nblocks ldx"),
+                        (_I32, "fold_rows fold16_rows rows16 sc_side_min_rows affine_serial no_wino_conv2sc no_stat_fuse no_wino_stats bridge"),
+                        (_I32, "offer_wino offer_stats offer_rows16 offer_side defer force_tile")) + [("blocks", AdainChainBlock * 2)])
+
+
 class WinoStatArgs(C.Structure):
     """include/stylish_hip.h: stts_wino_stat_args (test surface)."""
     _fields_ = _fields((_P, "seg_off_host seg_off_dev x w_host bias_host y stat"), (_I64, "x_elems y_elems stat_elems"),
@@ -268,6 +280,7 @@ TEST_SIGNATURES = {
     "stts_op_glue": (_I, [_P, C.POINTER(GlueArgs)]),
     "stts_op_chan_conv": (_I, [_P, C.POINTER(ChanConvArgs)]),
     "stts_op_adain_block": (_I, [_P, _P, C.c_char_p, _I, _P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _SZ]),
+    "stts_op_adain_chain": (_I, [_P, _P, C.POINTER(AdainChainArgs)]),
     "stts_op_attention": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I]),
     "stts_op_wavlm_l1": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "stts_op_stft_geom": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I]),

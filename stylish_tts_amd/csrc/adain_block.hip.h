@@ -10,6 +10,7 @@ namespace stts {
 struct BlockSwitches {
   // read ONCE per process
   long fold_rows;         // STTS_FOLD_ROWS: batches up to this many rows fold AdaIN into the consuming contraction's staging; above it the fp32 convs run in Winograd form
+  long fold16_rows;       // the same limit in the 16-bit operand modes (no environment switch: 4 096, measured at that size only; tests move it through stts_op_adain_chain)
   long rows16;            // STTS_ROWS16: rows from which the 16-bit operand modes keep contraction inputs as 16-bit rows in HBM
   long sc_side_min_rows;  // STTS_SC_SIDE_MIN_ROWS: rows from which the decoder's learned shortcuts run on the side lane
   bool affine_serial;     // STTS_AFFINE_SERIAL: the one-thread-per-channel merge of the chunk statistics (adain_affine_kernel)
@@ -21,13 +22,15 @@ struct BlockSwitches {
   bool x3_presplit;       // STTS_X3_PRESPLIT: pre-split input planes, a layout the bridge does not write
 };
 // Measured thresholds.  rows16 (B = 4 x 3 s; bf16, 3-s utterances: B = 1: 827 vs 739 utt/s without / with 16-bit rows, B = 2: 1 424 vs 1 313, B = 4: 2 272 vs
-// 2 304, B = 8: 3 442 vs 3 522).  sc_side_min_rows (3-s utterances, same box, alternated): B = 16: 5.82 -> 5.74 ms per step (+1.4 %); B = 8: 3.505 -> 3.52
+// 2 304, B = 8: 3 442 vs 3 522).  (The B = 4 pair dates from when 3 840 .. 4 096 rows planned 16-bit rows under folded
+// contractions and timed a wrong result.  With the window folded on fp32 rows, B = 4 x 3 s runs at 2 509 / 2 525 utt/s in
+// bf16 and 2 549 / 2 524 in f16: bench.py --batch 4, 30 steps, two runs each.)  sc_side_min_rows (3-s utterances, same box, alternated): B = 16: 5.82 -> 5.74 ms per step (+1.4 %); B = 8: 3.505 -> 3.52
 // (-0.5 %), B = 4: 2.39 -> 2.42 (-1.3 %): below ~12 000 rows the two cross-queue waits per block cost what the overlap gains.
 inline BlockSwitches block_switches() {
   static const BlockSwitches once = [] {
     auto num = [](const char* name, long unset) { return getenv(name) ? atol(getenv(name)) : unset; };
     auto set = [](const char* name) { return getenv(name) != nullptr; };
-    return BlockSwitches{num("STTS_FOLD_ROWS", 2500), num("STTS_ROWS16", 3840), num("STTS_SC_SIDE_MIN_ROWS", 12000), set("STTS_AFFINE_SERIAL"), set("STTS_NO_WINO_CONV2SC"),
+    return BlockSwitches{num("STTS_FOLD_ROWS", 2500), 4096, num("STTS_ROWS16", 3840), num("STTS_SC_SIDE_MIN_ROWS", 12000), set("STTS_AFFINE_SERIAL"), set("STTS_NO_WINO_CONV2SC"),
                          set("STTS_NO_STAT_FUSE"), set("STTS_NO_WINO_STATS"), -1, false};
   }();
   BlockSwitches sw = once;
@@ -142,7 +145,8 @@ inline ChainPlan plan_adain_chain(const Seg& s, int prec, const AdainBlockW* blo
   // conv1 of every block in Winograd form once the batch is large enough to be throughput-bound (B = 1: 35 vs 30 us)
   p.wino = R > sw.fold_rows && blocks[probe].w1.ready;
   p.sc_out = p.wino && blocks[probe].sc.W;
-  p.rows16 = offer.rows16 && R >= sw.rows16 && prec != PREC_F32 && blocks[probe].cout % 8 == 0;
+  // (as plan_adain_block: a folded block keeps fp32 rows, so up to fold16_rows nothing reads the 16-bit copies and the chain carves and casts none)
+  p.rows16 = offer.rows16 && R >= sw.rows16 && R > sw.fold16_rows && prec != PREC_F32 && blocks[probe].cout % 8 == 0;
   p.wino_stats = offer.stats && prec == PREC_F32 && p.wino && !sw.no_wino_stats;
   p.stats = (p.rows16 && !sw.no_stat_fuse) || p.wino_stats;
   p.side = offer.side_lane && p.sc_out && R >= sw.sc_side_min_rows;
@@ -243,7 +247,7 @@ inline BlockPlan plan_adain_block(const AdainBlockW& B, const Seg& s, const Bloc
   BlockPlan p;
   const int prec = B.conv1.prec;
   const long rows = s.rows();
-  const bool fold = rows <= (prec == PREC_F32 ? sw.fold_rows : 4096);  // (16-bit modes: measured at 4 096 only)
+  const bool fold = rows <= (prec == PREC_F32 ? sw.fold_rows : sw.fold16_rows);
   const bool wino = !fold && io.wino && *io.wino && force_tile == 0;
   const bool wino1 = wino && B.w1.ready;
   // (learned shortcut: conv2 in Winograd form + the 1x1 shortcut as a contraction of its own, added as the Winograd conv's residual)
@@ -254,11 +258,10 @@ inline BlockPlan plan_adain_block(const AdainBlockW& B, const Seg& s, const Bloc
   p.bridge_w = wstats ? ch.bridge_w : 0;
   // 16-bit operand modes, large batches: the normalised activations are WRITTEN as 16-bit rows (act1 / act2 reinterpreted), so the contractions stage half
   // the bytes and convert nothing; a learned shortcut reads a rounded copy of x (xs16).
-  // NOTE the window rows16 <= rows <= 4 096 of the 16-bit modes: this does not ask for !fold, so both hold there.  The folded contractions then keep fp32 rows
-  // (no apply pass writes 16-bit ones), but a learned shortcut is still conv2's second K segment ON THE 16-BIT COPY xs16, and Y16_EPILOGUE asks a contraction
-  // for the rounded y that only its 16-bit-row form writes.  Kept as it is here (the launches are the parent's); the fix is `&& !fold` on the next line.
-  p.rows16 = (rows >= sw.rows16 && prec != PREC_F32 && force_tile == 0 && (!B.sc.W || io.xs16) && io.ldx % 8 == 0) ? prec : 0;
-  const bool fuse = ch.stats && p.rows16 && !fold && !wino1 && !wino2;  // statistics from the epilogues of conv_gemm16_kernel, where it runs
+  // Not while the block folds (rows16 <= rows <= fold16_rows, 3 840 .. 4 096 rows with the defaults): no apply pass writes 16-bit rows there, and the folded
+  // contraction (conv_gemm_f32<..., XAFF>) stages fp32 rows in every segment, so the shortcut segment reads x and a rounded y comes from a cast pass.
+  p.rows16 = (rows >= sw.rows16 && !fold && prec != PREC_F32 && force_tile == 0 && (!B.sc.W || io.xs16) && io.ldx % 8 == 0) ? prec : 0;
+  const bool fuse = ch.stats && p.rows16 && !wino1 && !wino2;  // statistics from the epilogues of conv_gemm16_kernel, where it runs
 
   p.take_pending = fold;
   p.affine_serial = sw.affine_serial;
@@ -445,6 +448,36 @@ inline int adain_block(hipStream_t st, const Seg& s, const AdainBlockW& B, const
   return run_adain_block(st, s, B, plan_adain_block(B, s, io, ch, 0, sw), io, ch);
 }
 
+// The constant input columns of chained blocks: block i + 1 reads [y_i | constant columns], the same columns for every block of the chain (the decoder's
+// [asr_res | F0 | N]).  The statistics of a block's input come out of the previous block's conv2 (its `hidden` columns) and, for the constant columns, from ONE
+// statistics pass here; the bridge reads that pass's table as BlockChain::cst; 16-bit rows hold the columns rounded once.  decoder_forward and the test operator
+// stts_op_adain_chain share this.
+struct ConstColumns {
+  const float* x = nullptr;  // a row buffer that holds them: columns [hidden, ccat) of rows `ld` wide
+  int ld = 0, hidden = 0, ccat = 0;
+  float* ss_in = nullptr;    // the chain's statistics of a block's input, out_ld columns per row
+  int out_ld = 0;
+  bool ready = false;
+  void offer_bridge(BlockChain& ch) const {
+    ch.cst = ss_in;
+    ch.cst_ld = out_ld;
+  }
+  // (once, as soon as a block has left statistics of its output: whichever block that is, the constant columns must be there before the next norm1 merges them;
+  //  bridged: the first block's second bridge already merges them)
+  int stats(hipStream_t st, const Seg& s, const BlockChain& ch, bool bridged) {
+    if (!(ch.out_ready || bridged) || ready) return 0;
+    STTS_CHECK(hidden % 32 == 0, "adain chain: the blocks' width %d must be a multiple of 32", hidden);
+    launch_adain_partial(st, s, x + hidden, ld, ccat - hidden, ss_in + hidden, out_ld, ch.chunk_rows);
+    ready = true;
+    return 0;
+  }
+  // the rounded copy of the constant columns of `src` (from the 8-aligned column at or below `hidden`, pad columns included) into the 16-bit rows `dst`
+  void cast_tail(hipStream_t st, int prec, const float* src, unsigned short* dst, long rows) const {
+    const int ctail = hidden & ~7;
+    launch_cast_rows(st, prec, src + ctail, ld, ccat - ctail, dst + ctail, ld, rows, ld - ctail);
+  }
+};
+
 // ------------------------------------------------------------------------------------------------
 // stage: Decoder.forward (models/decoder.py:47-60)
 // ------------------------------------------------------------------------------------------------
@@ -495,33 +528,17 @@ inline int decoder_forward(stts_ctx* c, hipStream_t st, const Seg& s, const floa
     a.N = d.dec_residual; a.bias = c->asr_res.bias; a.Y = dst; a.ldy = ldcat; a.ycol0 = d.dec_hidden;
     STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, c->asr_res.npad, s.n_utt, s.max_len()));
   }
-  const int ctail = d.dec_hidden & ~7, ntail = ldcat - ctail;  // constant columns (from the 8-aligned column at or below dec_hidden)
-  auto cast_tail = [&](const float* src, unsigned short* dst) {
-    launch_cast_rows(st, c->prec, src + ctail, ldcat, ccat - ctail, dst + ctail, ldcat, R, ntail);
-  };
-  // The statistics of a block's input come out of the previous block's conv2 (its 512 hidden columns) and, for the constant columns [asr_res | F0 | N]
-  // that every decode block sees, from ONE statistics pass here.  With the bridge, hbuf, ss_mid and the hidden columns of ss_in are unused.
+  // (xa and xb hold the same constant columns.  With the bridge, hbuf, ss_mid and the hidden columns of ss_in are unused.)
   BlockChain chain(plan, ss_mid);
   chain.defer = true;
   const int out_ld = round_up(ccat, 32);
+  ConstColumns cst;
+  cst.x = xa; cst.ld = ldcat; cst.hidden = d.dec_hidden; cst.ccat = ccat; cst.ss_in = ss_in; cst.out_ld = out_ld;
   if (plan.bridge_w) {
-    chain.cst = ss_in;
-    chain.cst_ld = out_ld;
+    cst.offer_bridge(chain);
     wino.mp_kc = c->dec[1].w1.planes.kc;  // (the scratch is sized by this conv)
-  }
-  bool const_ready = false;
-  // (once, as soon as a block has left statistics of its output: whichever block that is, the constant columns must be there before the next norm1 merges them;
-  //  xa and xb hold the same constant columns)
-  auto const_columns = [&]() -> int {
-    if (!(chain.out_ready || plan.bridge_w) || const_ready) return 0;
-    STTS_CHECK(d.dec_hidden % 32 == 0, "decoder_forward: hidden_dim must be a multiple of 32");
-    launch_adain_partial(st, s, xa + d.dec_hidden, ldcat, ccat - d.dec_hidden, ss_in + d.dec_hidden, out_ld, chain.chunk_rows);
-    const_ready = true;
-    return 0;
-  };
-  if (plan.bridge_w) {  // (block 0's second bridge already merges them)
     STTS_CHECK(c->dec[0].cout == d.dec_hidden, "decoder_forward: the blocks' width %d is not hidden_dim %d", c->dec[0].cout, d.dec_hidden);
-    STTS_TRY(const_columns());
+    STTS_TRY(cst.stats(st, s, chain, true));
   }
   io.style = sty; io.ld_style = c->dec_style.ld();
   io.wino = &wino;
@@ -531,10 +548,10 @@ inline int decoder_forward(stts_ctx* c, hipStream_t st, const Seg& s, const floa
   chain.link(nullptr, false, ss_in, out_ld, plan.bridge_w ? &c->dec[1] : nullptr);
   STTS_TRY(adain_block(st, s, c->dec[0], io, chain, sw));
   if (plan.rows16) {
-    cast_tail(xa, xs16a);
-    cast_tail(xb, xs16b);
+    cst.cast_tail(st, c->prec, xa, xs16a, R);
+    cst.cast_tail(st, c->prec, xb, xs16b, R);
   }
-  STTS_TRY(const_columns());
+  STTS_TRY(cst.stats(st, s, chain, plan.bridge_w != 0));
   float* cur = xa;
   float* nxt = xb;
   unsigned short* cur16 = xs16a;
@@ -547,7 +564,7 @@ inline int decoder_forward(stts_ctx* c, hipStream_t st, const Seg& s, const floa
   }
   auto blocks = [&]() -> int {
     for (int i = 1; i <= 4; ++i) {
-      STTS_TRY(const_columns());
+      STTS_TRY(cst.stats(st, s, chain, plan.bridge_w != 0));
       io.x = cur; io.ldx = ldcat;
       io.y = i == 4 ? x_out : nxt; io.ldy = i == 4 ? ld_x : ldcat;
       io.xs16 = cur16; io.xs16_ready = plan.rows16; io.y16 = i == 4 ? nullptr : nxt16;

@@ -272,6 +272,165 @@ int stts_op_adain_block(stts_ctx* c, void* stream, const char* prefix, int n_utt
   API_END
 }
 
+// One block, or two chained ones, under the caller's BlockSwitches and offers (include/stylish_hip.h).  The walk is decoder_forward's: chain plan, the carving,
+// the constant columns (ConstColumns), block A, the rounded tail, block B, the chain's pending reduce.  Every buffer is checked before anything is launched.
+int stts_op_adain_chain(stts_ctx* c, void* stream, const stts_adain_chain_args* p) {
+  API_BEGIN
+  STTS_CHECK(c && p && p->seg_off_host && p->seg_off_dev && p->x && p->style && p->ws && p->plan_out && p->n_utt > 0, "op_adain_chain: null / empty argument");
+  STTS_CHECK(p->nblocks == 1 || p->nblocks == 2, "op_adain_chain: one or two blocks");
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = p->nblocks;
+  for (int i = 0; i < nb; ++i) STTS_CHECK(p->blocks[i].prefix && p->blocks[i].y && p->blocks[i].cin > 0 && p->blocks[i].cout > 0, "op_adain_chain: block %d: null / empty argument", i);
+  std::string key = "chain:";
+  for (int i = 0; i < nb; ++i) key += std::string(p->blocks[i].prefix) + "|";
+  if (!c->op_tables.count(key)) {  // the blocks of a chain share one style table (the bridge reads the next block's norm1 from this block's)
+    auto tab = std::make_unique<StyleTable>();
+    std::unique_ptr<AdainBlockW> blk[2];
+    PackScope scope(c, {c->prec, true, c->prec != PREC_F32 ? 64 : 32, 0});  // (the frame path's packing: input channels padded to conv_gemm16_kernel's K tile in the 16-bit modes)
+    for (int i = 0; i < nb; ++i) {
+      blk[i] = std::make_unique<AdainBlockW>();
+      STTS_TRY(pack_adain_block(c, p->blocks[i].prefix, p->blocks[i].cin, p->blocks[i].cout, tab.get(), blk[i].get()));
+    }
+    STTS_TRY(upload_table(c, tab.get()));
+    for (int i = 0; i < nb; ++i) c->op_blocks[key + std::to_string(i)] = std::move(blk[i]);
+    c->op_tables[key] = std::move(tab);
+  }
+  AdainBlockW B[2];
+  for (int i = 0; i < nb; ++i) {
+    B[i] = *c->op_blocks[key + std::to_string(i)];
+    STTS_CHECK(B[i].cin == p->blocks[i].cin && B[i].cout == p->blocks[i].cout, "op_adain_chain: block %d was packed as %d -> %d", i, B[i].cin, B[i].cout);
+  }
+  const StyleTable& T = *c->op_tables[key];
+  const int prec = B[0].conv1.prec;
+  Seg s{p->n_utt, p->seg_off_host, p->seg_off_dev};
+  const long R = s.rows();
+  STTS_CHECK(R > 0, "op_adain_chain: no rows");
+  // ---- the caller's buffers
+  STTS_CHECK(p->ldx >= B[0].kcin && p->ldx % 4 == 0 && R * p->ldx <= p->x_elems, "op_adain_chain: x must be [rows, ldx >= %d, a multiple of 4]", B[0].kcin);
+  STTS_CHECK((long)p->n_utt * T.K <= p->style_elems, "op_adain_chain: style must be [n_utt, %d]", T.K);
+  for (int i = 0; i < nb; ++i) {
+    const stts_adain_chain_block& b = p->blocks[i];
+    STTS_CHECK(b.ldy >= b.cout && b.ldy % 4 == 0 && R * b.ldy <= b.y_elems, "op_adain_chain: block %d: y must be [rows, ldy >= cout, a multiple of 4]", i);
+    STTS_CHECK(!b.y16 || (prec != PREC_F32 && b.cout % 8 == 0 && b.ldy16 >= b.cout && b.ldy16 % 8 == 0 && R * b.ldy16 <= b.y16_elems),
+               "op_adain_chain: block %d: y16 needs a 16-bit mode, cout and ldy16 multiples of 8, [rows, ldy16 >= cout]", i);
+  }
+  if (nb == 2) {
+    STTS_CHECK(B[1].cin >= B[0].cout && p->blocks[0].ldy >= B[1].kcin, "op_adain_chain: block 1 reads [y_0 | constant columns]: cin %d >= cout %d, ldy_0 >= %d", B[1].cin, B[0].cout, B[1].kcin);
+    STTS_CHECK(!p->blocks[0].y16 || p->blocks[0].ldy16 == p->blocks[0].ldy, "op_adain_chain: the rounded copy of y_0 is block 1's rounded input: ldy16 == ldy");
+  }
+  // ---- switches and offers
+  BlockSwitches sw = block_switches();  // (x3_presplit: per call, as everywhere)
+  // (a negative threshold: the engine's own, block_switches())
+  if (p->fold_rows >= 0) sw.fold_rows = p->fold_rows;
+  if (p->fold16_rows >= 0) sw.fold16_rows = p->fold16_rows;
+  if (p->rows16 >= 0) sw.rows16 = p->rows16;
+  if (p->sc_side_min_rows >= 0) sw.sc_side_min_rows = p->sc_side_min_rows;
+  sw.affine_serial = p->affine_serial != 0; sw.no_wino_conv2sc = p->no_wino_conv2sc != 0; sw.no_stat_fuse = p->no_stat_fuse != 0; sw.no_wino_stats = p->no_wino_stats != 0;
+  sw.bridge = p->bridge;
+  const int probe = nb - 1;  // (the wider input)
+  ChainOffer offer{p->offer_stats != 0, p->offer_rows16 != 0, true, p->offer_side != 0};
+  const bool scratch = p->offer_wino != 0 && p->force_tile == 0;  // (without it plan_adain_block keeps every conv a direct contraction, whatever the chain plan carved for)
+  const ChainPlan plan = plan_adain_chain(s, prec, B, nb, probe, offer, sw);
+  int32_t* out = p->plan_out;
+  const int32_t cp[8] = {plan.wino && scratch, plan.sc_out, plan.rows16, plan.wino_stats, plan.stats, plan.bridge_w, plan.side, 0};
+  std::copy(cp, cp + 8, out);
+  std::fill(out + 8, out + 8 + 16 * nb, -1);
+  // ---- the carving (decoder_forward's)
+  int ldwide = p->ldx, cwide = 0;
+  for (int i = 0; i < nb; ++i) {
+    ldwide = std::max({ldwide, B[i].kcin, B[i].cout, (int)p->blocks[i].ldy});
+    cwide = std::max(cwide, B[i].cout);
+  }
+  Arena ws(p->ws, (size_t)p->ws_bytes);
+  BlockIO io;
+  io.act1 = ws.get<float>(R * ldwide);
+  io.hbuf = ws.get<float>(R * cwide);
+  io.act2 = ws.get<float>(R * cwide);
+  io.ss = ws.get<float>(adain_part_floats(s, ldwide));
+  float* ss_in = ws.get<float>(adain_part_floats(s, ldwide, kWinoStatChunk));
+  float* ss_mid = ws.get<float>(adain_part_floats(s, ldwide, kWinoStatChunk));
+  float* sty = ws.get<float>((size_t)s.n_utt * T.ld());
+  WinoScratch wino;
+  if (plan.wino && scratch) {
+    size_t floats = 0;
+    for (int i = 0; i < nb; ++i) floats = std::max({floats, wino_scratch_floats(s, B[i].w1), B[i].w2.ready ? wino_scratch_floats(s, B[i].w2) : 0});
+    wino.p = ws.get<float>(floats);
+  }
+  float* sc_out = plan.sc_out ? ws.get<float>(R * cwide) : nullptr;
+  // (16-bit scratch wherever the caller offers it, so that a block plan that disagrees with the chain plan would show; only the chain plan's rows16 rounds the tail)
+  unsigned short* xs16a = p->offer_rows16 ? ws.get<unsigned short>(R * ldwide) : nullptr;
+  unsigned short* xs16b = p->offer_rows16 ? ws.get<unsigned short>(R * ldwide) : nullptr;
+  STTS_CHECK(ws.ok, "op_adain_chain: workspace too small");
+  struct Lane {  // the side lane: created and destroyed here, after both streams have drained
+    hipStream_t main, stream = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    ~Lane() {
+      (void)hipStreamSynchronize(main);
+      if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+      if (fork) (void)hipEventDestroy(fork);
+      if (join) (void)hipEventDestroy(join);
+    }
+  } lane{st};
+  SideWork side;
+  if (plan.side) {
+    STTS_HIP(hipStreamCreateWithFlags(&lane.stream, hipStreamNonBlocking));
+    STTS_HIP(hipEventCreateWithFlags(&lane.fork, hipEventDisableTiming));
+    STTS_HIP(hipEventCreateWithFlags(&lane.join, hipEventDisableTiming));
+    side.stream = lane.stream; side.fork = lane.fork; side.join = lane.join; side.out = sc_out;
+    io.side = &side;
+  }
+  STTS_TRY(run_style(st, T, p->style, s.n_utt, sty));
+  io.style = sty; io.ld_style = T.ld();
+  io.wino = &wino;
+  BlockChain chain(plan, ss_mid);
+  chain.defer = p->defer != 0;
+  ConstColumns cst;
+  if (nb == 2) {
+    cst.x = p->blocks[0].y; cst.ld = p->blocks[0].ldy; cst.hidden = B[0].cout; cst.ccat = B[1].cin; cst.ss_in = ss_in; cst.out_ld = round_up(B[1].cin, 32);
+  }
+  if (plan.bridge_w) {
+    wino.mp_kc = B[probe].w1.planes.kc;
+    if (nb == 2) {
+      cst.offer_bridge(chain);
+      STTS_TRY(cst.stats(st, s, chain, true));
+    }
+  }
+  auto block = [&](int i) -> int {
+    const BlockPlan bp = plan_adain_block(B[i], s, io, chain, p->force_tile, sw);
+    const int32_t v[16] = {bp.conv1, bp.conv2, bp.rows16, bp.norm1, bp.norm2, bp.next_norm1, bp.take_pending, bp.defer_conv2, bp.shortcut, bp.cast_x16, bp.y16, bp.affine_serial,
+                           bp.bridge_w, bp.force_tile, 0, 0};
+    std::copy(v, v + 16, out + 8 + 16 * i);
+    STTS_TRY(run_adain_block(st, s, B[i], bp, io, chain));
+    out[8 + 16 * i + 14] = chain.pend.src.partial ? chain.pend.src.ksplit : 0;  // what conv2 left pending: its split-K factor
+    return 0;
+  };
+  auto blocks = [&]() -> int {
+    io.x = p->x; io.ldx = p->ldx; io.y = p->blocks[0].y; io.ldy = p->blocks[0].ldy;
+    io.xs16 = xs16b; io.y16 = p->blocks[0].y16; io.ldy16 = p->blocks[0].ldy16;
+    // (a single block leaves the statistics of y as if a block of its own width followed)
+    chain.link(nullptr, false, offer.stats ? ss_in : nullptr, nb == 2 ? cst.out_ld : round_up(B[0].cout, 32), plan.bridge_w && nb == 2 ? &B[1] : nullptr);
+    STTS_TRY(block(0));
+    if (nb == 1) return 0;
+    unsigned short* x16 = p->blocks[0].y16 ? p->blocks[0].y16 : xs16a;
+    if (plan.rows16 && x16) cst.cast_tail(st, prec, p->blocks[0].y, x16, R);
+    STTS_TRY(cst.stats(st, s, chain, plan.bridge_w != 0));
+    io.x = p->blocks[0].y; io.ldx = p->blocks[0].ldy; io.y = p->blocks[1].y; io.ldy = p->blocks[1].ldy;
+    io.xs16 = x16; io.xs16_ready = plan.rows16 && p->blocks[0].y16; io.y16 = p->blocks[1].y16; io.ldy16 = p->blocks[1].ldy16;
+    chain.link(ss_in, chain.out_ready, nullptr, cst.out_ld, nullptr);
+    return block(1);
+  };
+  int rc = blocks();
+  if (rc && plan.side) {  // an error path may have left a shortcut running on the side lane
+    (void)hipEventRecord(side.join, side.stream);
+    (void)hipStreamWaitEvent(st, side.join, 0);
+  }
+  if (rc) return rc;
+  STTS_TRY(chain.finish(st));
+  STTS_HIP(hipStreamSynchronize(st));
+  return 0;
+  API_END
+}
+
 int stts_op_attention(void* stream, int n_utt, const int32_t* q_off_host, const int32_t* q_off_dev, const int32_t* k_off_host,
                       const int32_t* k_off_dev, const float* q, const float* k, const float* v, float* o, int heads, int kc,
                       const int32_t* band_centre, int window, int kernel) {

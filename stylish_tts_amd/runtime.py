@@ -428,6 +428,40 @@ class HipModel:
                                                 cout, _ptr(style), _ptr(y), cout, _ptr(ws), ws.numel()))
         return y
 
+    BLOCK_PLAN_FIELDS = ("conv1", "conv2", "rows16", "norm1", "norm2", "next_norm1", "take_pending", "defer_conv2", "shortcut", "cast_x16", "y16", "affine_serial",
+                         "bridge_w", "force_tile", "pending")
+    CHAIN_PLAN_FIELDS = ("wino", "sc_out", "rows16", "wino_stats", "stats", "bridge_w", "side")
+
+    def op_adain_chain(self, seg: Segments, x, style, blocks, *, fold_rows=-1, fold16_rows=-1, rows16=-1, sc_side_min_rows=-1, affine_serial=False,
+                       no_wino_conv2sc=False, no_stat_fuse=False, no_wino_stats=False, bridge=0, wino=False, stats=False, xs16=False, side=False, defer=False,
+                       force_tile=0):
+        """stts_op_adain_chain: one AdaptiveDecoderBlock or two chained ones under the caller's plan thresholds (-1: the engine's own) and offers.
+        blocks: one or two dicts {prefix, cin, cout, y [rows, ldy] fp32, y16 (optional) [rows, ldy16] int16}, written INTO the caller's tensors (of a pair,
+        blocks[0]["y"] already holds the constant columns).  Returns (chain plan, [block plans]) as dicts of integers (csrc/adain_block.hip.h)."""
+        a = _lib.AdainChainArgs()
+        ws = self.workspace(seg)
+        plan = (C.c_int32 * (8 + 16 * len(blocks)))()
+        assert x.dtype == torch.float32 and x.is_contiguous() and style.dtype == torch.float32 and style.is_contiguous()
+        a.seg_off_host, a.seg_off_dev, a.n_utt, a.nblocks = seg.host_ptr, _ptr(seg.dev), seg.n, len(blocks)
+        a.x, a.x_elems, a.ldx, a.style, a.style_elems = _ptr(x), x.numel(), x.shape[1], _ptr(style), style.numel()
+        a.ws, a.ws_bytes, a.plan_out = _ptr(ws), ws.numel(), C.cast(plan, C.c_void_p)
+        a.fold_rows, a.fold16_rows, a.rows16, a.sc_side_min_rows = fold_rows, fold16_rows, rows16, sc_side_min_rows
+        a.affine_serial, a.no_wino_conv2sc, a.no_stat_fuse, a.no_wino_stats, a.bridge = int(affine_serial), int(no_wino_conv2sc), int(no_stat_fuse), int(no_wino_stats), bridge
+        a.offer_wino, a.offer_stats, a.offer_rows16, a.offer_side, a.defer, a.force_tile = int(wino), int(stats), int(xs16), int(side), int(defer), force_tile
+        for i, b in enumerate(blocks):
+            y, y16 = b["y"], b.get("y16")
+            assert y.dtype == torch.float32 and y.is_contiguous() and y.is_cuda and (y16 is None or (y16.dtype == torch.int16 and y16.is_contiguous() and y16.is_cuda))
+            o = a.blocks[i]
+            o.prefix, o.cin, o.cout = b["prefix"].encode(), b["cin"], b["cout"]
+            o.y, o.y_elems, o.ldy = _ptr(y), y.numel(), y.shape[1]
+            if y16 is not None:
+                o.y16, o.y16_elems, o.ldy16 = _ptr(y16), y16.numel(), y16.shape[1]
+        rc = self.lib.stts_op_adain_chain(self.ctx, _stream(), C.byref(a))
+        v = list(plan)
+        self.last_chain_plan = (dict(zip(self.CHAIN_PLAN_FIELDS, v[:8])), [dict(zip(self.BLOCK_PLAN_FIELDS, v[8 + 16 * i : 24 + 16 * i])) for i in range(len(blocks))])
+        _lib.check(rc)
+        return self.last_chain_plan
+
     def op_attention(self, seg_q: Segments, seg_k: Segments, q, k, v, heads: int, kc: int, band_centre=None, window: int = 0, kernel: int = 0):
         """Packed multi-head attention (test surface): q [q rows, heads * kc], k / v [k rows, heads * kc] -> [q rows, heads * kc]."""
         o = self._f32(seg_q.rows, heads * kc)

@@ -784,6 +784,36 @@ static void block_section(stts_ctx* c, int prec, const Widths& wd, const stts_mo
       });
     }
   }
+  {  // stts_op_adain_chain: encode -> decode.0 at 300 / 301 / 500 / 501 rows with the thresholds brought down to them (fp32: fold up to 300 rows; 16-bit modes:
+     // 16-bit rows from 300 rows, folded up to 500 - the window of the defaults at 3 840 .. 4 096 rows), everything offered; `blockplan` = the plan it returns
+    const int cin = d.inter_dim + 2, ccat = d.dec_hidden + d.dec_residual + 2, al = f32 ? 32 : 64;
+    const int ldx = (cin + al - 1) / al * al, ldcat = (ccat + al - 1) / al * al;
+    for (int rows : {300, 301, 500, 501}) {
+      const std::vector<int> lens = {rows - 143, 143};
+      const std::vector<int32_t> off = offsets(lens);
+      Workspace ws(stts_frame_workspace_bytes(c, rows, 2, lens[0]));
+      auto x = buf((size_t)rows * ldx), style = buf(2 * 64), ya = buf((size_t)rows * ldcat), yb = buf((size_t)rows * d.dec_hidden);
+      std::vector<uint16_t> y16((size_t)rows * ldcat);
+      int32_t plan[8 + 32] = {};
+      stts_adain_chain_args a;
+      memset(&a, 0, sizeof(a));
+      a.seg_off_host = a.seg_off_dev = off.data();
+      a.x = x.data(); a.x_elems = (int64_t)x.size(); a.ldx = ldx; a.style = style.data(); a.style_elems = (int64_t)style.size();
+      a.ws = ws.p; a.ws_bytes = (int64_t)ws.bytes; a.plan_out = plan; a.n_utt = 2; a.nblocks = 2;
+      a.fold_rows = 300; a.fold16_rows = 500; a.rows16 = 300; a.sc_side_min_rows = 12000; a.bridge = 0;
+      a.offer_wino = a.offer_stats = a.offer_rows16 = a.offer_side = a.defer = 1;
+      a.blocks[0].prefix = "speech_predictor.decoder.encode"; a.blocks[0].cin = cin; a.blocks[0].cout = d.dec_hidden;
+      a.blocks[0].y = ya.data(); a.blocks[0].y_elems = (int64_t)ya.size(); a.blocks[0].ldy = ldcat;
+      if (!f32) { a.blocks[0].y16 = y16.data(); a.blocks[0].y16_elems = (int64_t)y16.size(); a.blocks[0].ldy16 = ldcat; }
+      a.blocks[1].prefix = "speech_predictor.decoder.decode.0"; a.blocks[1].cin = ccat; a.blocks[1].cout = d.dec_hidden;
+      a.blocks[1].y = yb.data(); a.blocks[1].y_elems = (int64_t)yb.size(); a.blocks[1].ldy = d.dec_hidden;
+      const std::string what = "chain_" + std::to_string(rows) + "rows";
+      block_case(prec, what, "-", [&] { return stts_op_adain_chain(c, nullptr, &a); });
+      printf("blockplan %d %s :", prec, what.c_str());
+      for (int v : plan) printf(" %d", v);
+      printf("\n");
+    }
+  }
   if (!phoneme_rate) return;
   // the pitch/energy predictor's two branches of three blocks (always fp32 operands): three utterances of 2 500 and of 2 501 frames
   for (int last : {840, 841}) {

@@ -85,6 +85,7 @@ BLOCK_CASES = ([(p, f"dec_1x{n}", "-") for p in (0, 3) for n in (300, 2500, 2501
                + [(p, f"dec_{b}", sw) for p in (0, 3) for b in BRIDGE_ON + BRIDGE_OFF + (BRIDGE_TOO_LONG,) for sw in _BRIDGE]
                + [(p, f"dec_{c}", "-") for p in (1, 2) for c in ("1x300", "3839rows", "3840rows", "4096rows", "4097rows", "110utt", "100utt")]
                + [(0, f"frame_{b}x960", sw) for b in (12, 13) for sw in _BRIDGE[:2]] + [(p, c, "-") for p in (0, 1, 2, 3) for c in ("op_1x300", "op_2x2049")]
+               + [(p, f"chain_{r}rows", "-") for p in (0, 1, 2, 3) for r in (300, 301, 500, 501)]
                + [(p, c, "-") for p in (0, 2, 3) for c in ("pe_2500frames", "pe_2501frames", "hubert_353frames", "hubert_2600frames")])
 # the block's process-wide switches (tests/asan/build_and_run.py BLOCK_SETTINGS): setting -> the (precision, case, switches) whose trace it must change and those it
 # must leave alone.  STTS_FOLD_ROWS=0 forces the Winograd form and STTS_SC_SIDE_MIN_ROWS=0 the side lane, so what they leave alone is the unforced choice pinned.
@@ -118,6 +119,27 @@ def check_blocktraces(stdout):
     for p in (1, 2):  # 4 400 rows: conv_gemm16_kernel with the statistics from its epilogues; 3 960 rows: folded, no apply pass
         assert "conv_gemm16_kernel<" in block[(p, "dec_110utt", "-")] and "conv_gemm16_kernel<" not in block[(p, "dec_100utt", "-")], p
         assert "adain_apply_kernel" in block[(p, "dec_4097rows", "-")] and "adain_apply_kernel" not in block[(p, "dec_4096rows", "-")], p
+        # 3 840 .. 4 096 rows: folded means fp32 rows throughout, so nothing is cast to 16-bit rows there (no rounded copy of x for the shortcuts, no rounded y);
+        # from 4 097 rows on the blocks read and write them
+        for rows in (3839, 3840, 4096):
+            assert "cast_rows_kernel" not in block[(p, f"dec_{rows}rows", "-")], (p, rows)
+        assert "cast_rows_kernel" in block[(p, "dec_4097rows", "-")], p
+    # stts_op_adain_chain's returned plans (8 integers of the chain plan, 16 per block: conv1, conv2, rows16, ... shortcut at 8, cast_x16 at 9, y16 at 10), with
+    # fold_rows = 300, the 16-bit fold limit at 500 and 16-bit rows from 300: a block is folded on fp32 rows with the shortcut a segment on x, or it runs
+    # on 16-bit rows throughout - never 16-bit rows under folded contractions
+    plans = {(int(p), c): [int(v) for v in t.split()] for p, c, t in re.findall(r"^blockplan (\d) (\S+) :(.*)$", stdout, re.M)}
+    assert sorted(plans) == sorted((p, f"chain_{r}rows") for p in (0, 1, 2, 3) for r in (300, 301, 500, 501)), sorted(plans)
+    for (p, c), v in plans.items():
+        rows, chain, blk = int(c[6:-4]), v[:8], [v[8:24], v[24:40]]
+        for b in blk:
+            assert b[2] == 0 or (b[0] != 0 and b[1] != 0), (p, c, "16-bit rows under a folded contraction", b)
+        if p in (0, 3):
+            assert [b[0] for b in blk] == ([0, 0] if rows <= 300 else [2, 2]) and chain[2] == 0, (p, c, v)  # CONV_FOLD | CONV_WINO
+        else:
+            folded = rows <= 500
+            assert [b[:3] for b in blk] == ([[0, 0, 0]] * 2 if folded else [[1, 1, p]] * 2), (p, c, v)  # CONV_FOLD on fp32 rows | CONV_APPLY on 16-bit rows
+            assert chain[2] == (0 if folded else 1) and [b[8] for b in blk] == [1, 1], (p, c, v)         # the chain plan agrees; SC_SEGMENT
+            assert blk[0][10] == (2 if folded else 1) and blk[1][9] == 0, (p, c, v)                       # y16: a cast pass | conv2's epilogue; B's copy is there
     per_setting = {}
     for sw, p, c, s, t in re.findall(r"^\[(STTS_\w+=\d+)\] blocktrace (\d) (\S+) (\S+) : (.*)$", stdout, re.M):
         per_setting.setdefault(sw, {})[(int(p), c, s)] = t

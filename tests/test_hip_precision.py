@@ -138,6 +138,8 @@ TOL = {"bf16": (8e-3, 1.2e-2), "f16": (1.2e-3, 1.5e-3)}  # measured: bf16 3.8e-3
 @pytest.mark.parametrize("prec", ["bf16", "f16"])
 def test_frame_path_16bit_ragged_batch(cfg, weights, rounded_oracle, prec):
     """cfg3 / cfg5 arithmetic on a mixed-length batch: decoder -> prior/flow -> vocoder with 16-bit matrix-core operands."""
+    import block64
+
     from stylish_tts_amd.runtime import HipModel
 
     hip = HipModel(cfg, 0, precision=prec)
@@ -168,6 +170,14 @@ def test_frame_path_16bit_ragged_batch(cfg, weights, rounded_oracle, prec):
         O = rounded_oracle(prec)
         xd = O.decoder_forward(p["asr"], p["pitch"], p["energy"], p["style"], w)
         ex = np.abs(x_np[s.host[i] : s.host[i + 1], :512].T - xd[0]).max() / np.abs(xd).max()
+        # the decoder against float64 with the same rounding points, at the bars of tests/test_hip_block_forms.py's decoder cases (block64.py: BOUNDS, FLIPS)
+        # ex against the bound of tests/test_hip_block_forms.py's decoder cases: the decoder is held to FOUR x the rounded oracle's own error e against float64 with
+        # the same rounding points (block64.decoder64), and the oracle is e away from that, so against the oracle it may be (FOUR + 1) e
+        want, bars, _, e = block64.decoder_reference(p["asr"], p["pitch"], p["energy"], p["style"], w, prec)
+        rx = block64.ratios(x_np[s.host[i] : s.host[i + 1], :512], want, [L], bars)
+        print(prec, "decoder utterance", i, "vs the rounded oracle", ex, "bound", (block64.FOUR + 1) * e, "; vs float64 / bars", rx)
+        assert ex <= (block64.FOUR + 1) * e, (prec, i, ex, e)
+        assert block64.within(rx), (prec, i, rx)
         a_r, _, _ = O.frame_path(p["asr"], p["pitch"], p["energy"], p["style"], nz, w, branch_hint=hint)
         O = rounded_oracle(None)
         a_f, _, _ = O.frame_path(p["asr"], p["pitch"], p["energy"], p["style"], nz, w, branch_hint=hint)
