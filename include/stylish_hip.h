@@ -72,7 +72,8 @@ enum {
   STTS_W_SSL = 16384,        /* hubert.model.* = AdaptiveHubert (finalized by stts_ssl_finalize, not part of STTS_W_ALL)      train/models/ssl.py:16-31 */
   STTS_W_RMVPE = 32768,      /* rmvpe.* = the RMVPE pitch extractor E2E0 (finalized by stts_rmvpe_finalize, not part of STTS_W_ALL) train/dataprep/rmvpe/model.py:49-86 */
   STTS_W_ALIGNER = 65536,    /* text_aligner.* = the TDNN CTC aligner (finalized by stts_aligner_finalize, not part of STTS_W_ALL)           train/models/text_aligner.py */
-  STTS_W_WAVLM = 131072      /* wavlm.* = transformers' WavLMModel, the network of the "slm" distance (finalized by stts_wavlm_finalize, not part of STTS_W_ALL) train/losses.py:408-426 */
+  STTS_W_WAVLM = 131072,     /* wavlm.* = transformers' WavLMModel, the network of the "slm" distance (finalized by stts_wavlm_finalize, not part of STTS_W_ALL) train/losses.py:408-426 */
+  STTS_W_POSTERIOR = 262144  /* speech_predictor.posterior_encoder.* (stts_finalize_weights; not part of STTS_W_ALL)                       models/flow.py:234-293 */
 };
 int stts_finalize_weights(stts_ctx* ctx, int which);
 /* Operand precision of the FRAME-RATE Conv1d / Linear contractions (call before the first stts_finalize_weights).
@@ -151,6 +152,28 @@ int stts_harmonic_stft(stts_ctx* ctx, void* stream, int n_utt, const int32_t* se
 int stts_vocoder_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev,
                          const float* mel, int ld_mel, const float* style, const float* har_spec, const float* har_phase, int ld_har,
                          float* audio_out, float* logamp_out, float* phase_out, int ld_lp, void* ws, size_t ws_bytes);
+
+/* PosteriorEncoder.forward (models/flow.py:282-293) [+ post_flow, models/speech_predictor.py:109]: a recording -> z ~ q(z | audio), the
+ * latent that copy-synthesis vocodes.  Component STTS_W_POSTERIOR (keys "speech_predictor.posterior_encoder.*", either weight-norm flavour;
+ * 12 layers, hidden 128, k = 3 at model.yml; dilation 1 only); fp32 arithmetic whatever stts_set_precision says.
+ *   audio [75*rows] packed (h = hop_length / 4 samples per row), or NULL: har_spec / har_phase [rows, ld_har] are read as given (columns from
+ *   n_fft/2 + 1 up to the packed input width - the bins rounded up to 32 - must be finite); with audio they are WRITTEN: the vocoder's STFT of
+ *   the recording, its last frame dropped (flow.py:283-286).  ld_har: a multiple of 4, >= the bins rounded up to 32 (stts_har_ld fits).
+ *   style [n_utt, 64], or NULL = the reference's g=None (no conditioning).  noise [rows,128] ~ N(0,1): the one draw (flow.py:292).
+ *   z_out / mean_out / logstd_out [rows,128]: any of them optional.  mel_out [rows, ld_mel >= 512] (optional) = post_flow(z): needs STTS_W_FLOW.
+ *   x0_out / wn_out [rows,128] (optional taps): cat[pre_spec, pre_phase] and the WaveNet's output.
+ * Utterances are ragged and packed, each its own sequence with zero padding at its ends (the reference at B = 1).  seg_flags must be 0: capacity
+ * segments are refused, as are an utterance too short for the STFT's reflect padding (from audio), a small ld_har, mel_out without STTS_W_FLOW and
+ * a small workspace - each with stts_last_error set and nothing launched.  The WaveNet runs one fused launch per layer (wn_post_kernel) or as plain
+ * contractions; STTS_POST_WN (read per call) = 0 | 16 | 32 | 64 forces the generic form or the fused one on that block height.
+ * PARITY NOTE: as stts_harmonic_stft's - from audio, frame 0's negative-real bins are +-pi by rounding noise and pre_phase is linear in the
+ * phase; tests adopt the reference's branch at those bins (oracle.align_branch) before they compare. */
+int stts_posterior_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, const float* audio,
+                           float* har_spec, float* har_phase, int ld_har, const float* style, const float* noise, float* z_out, float* mean_out,
+                           float* logstd_out, float* mel_out, int ld_mel, float* x0_out, float* wn_out, void* ws, size_t ws_bytes, int seg_flags);
+/* Workspace stts_posterior_forward accepts for `rows` rows in `n_utt` utterances, the longest having `max_len` (a dry run of its own carving;
+ * 0 before STTS_W_POSTERIOR is finalized). */
+size_t stts_posterior_workspace_bytes(const stts_ctx* ctx, int64_t rows, int n_utt, int max_len);
 
 /* Utterance offsets of a frame-rate call may be CAPACITY SEGMENTS (seg_flags & STTS_SEG_CAPACITY): the host array then holds
  * upper bounds (cumulative capacities - every buffer, workspace and grid is sized by them), the device array the real offsets,
@@ -942,6 +965,13 @@ int stts_op_stft_geom(void* stream, int n_utt, const int32_t* seg_off_host, cons
                       float* spec, float* phase, int ld, int generic);
 int stts_op_istft_geom(void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, int n_fft, int win, int h, const float* logamp,
                        const float* phase, int ld, float* audio, int generic);
+/* WaveNet layer `layer` of the finalized posterior encoder (STTS_W_POSTERIOR) alone: h_in, out_in [rows, hidden], cond [n_utt, ld_cond] (the
+ * cond_layer rows; layer i reads columns [i * 2 hidden, (i + 1) * 2 hidden)) -> h_out, out_out [rows, hidden] (other buffers than the inputs).
+ * form: 0 = plain contractions, 16 | 32 | 64 = wn_post_kernel on that block height.  out_acc 0: out = skip (what layer 0 does), else out_in + skip.
+ * The last layer leaves h alone (h_out = h_in).  ws: rows * hidden floats of scratch. */
+int stts_op_posterior_layer(stts_ctx* ctx, void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, int layer, int form,
+                            int out_acc, const float* h_in, const float* out_in, const float* cond, int ld_cond, float* h_out, float* out_out,
+                            void* ws, size_t ws_bytes);
 /* Tuning aid (tools/gemm_bench.py): average time of `iters` back-to-back contraction launches on synthetic data.
  * tile: 0 = the launcher's own choice; tune bits: 128 bf16 operands, 256 fp16 operands; only in a library built with
  * -DSTTS_GEMM_TRACE: 2/4/8/16 K-loop ablations (results invalid, timing only), 64 block-timeline trace. */

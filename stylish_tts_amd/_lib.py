@@ -188,6 +188,8 @@ SIGNATURES = {
     "stts_harmonic_stft": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _SZ]),
     "stts_vocoder_forward": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _SZ]),
     "stts_frame_path": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _SZ, _I]),
+    "stts_posterior_forward": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _SZ, _I]),
+    "stts_posterior_workspace_bytes": (_SZ, [_P, _I64, _I, _I]),
     "stts_frame_offsets": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "stts_phoneme_workspace_bytes": (_SZ, [_P, _I64, _I64, _I, _I, _I]),
     "stts_text_encoder_forward": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P, _SZ]),
@@ -285,6 +287,7 @@ TEST_SIGNATURES = {
     "stts_op_wavlm_l1": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     "stts_op_stft_geom": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I]),
     "stts_op_istft_geom": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I]),
+    "stts_op_posterior_layer": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _SZ]),
 }
 
 _lib = None

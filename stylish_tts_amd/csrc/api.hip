@@ -13,6 +13,7 @@
 #include "log_mel.hip.h"
 #include "resample.hip.h"
 #include "val_scores.hip.h"
+#include "posterior.hip.h"
 
 using namespace stts;
 
@@ -136,6 +137,17 @@ int stts_finalize_weights(stts_ctx* c, int which) {
     PackScope scope(c, {PREC_F32, false, 32, STTS_W_CFM_PITCH_NET});
     STTS_TRY(finalize_cfm_pitch_net(c, static_cast<CfmPitchNetW*>(c->cfm_pitch.get())));
     c->ready |= STTS_W_CFM_PITCH_NET;
+  }
+  if (which & STTS_W_POSTERIOR) {
+    if (!c->posterior) c->posterior = std::make_shared<PostW>();
+    if (!c->hann) {  // the STFT geometry and its tables (context lifetime), as a frame-path finalize sets them up
+      PackScope tables(c, {c->prec, true, c->prec != PREC_F32 ? 64 : 32, 0});
+      STTS_TRY(finalize_frame(c, 0));
+    }
+    // fp32 whatever the precision; the contractions around the WaveNet in the split-fp32 form where the engine allows it
+    PackScope scope(c, {PREC_F32, true, 32, STTS_W_POSTERIOR});
+    STTS_TRY(finalize_posterior(c, static_cast<PostW*>(c->posterior.get())));
+    c->ready |= STTS_W_POSTERIOR;
   }
   STTS_HIP(hipDeviceSynchronize());
   return 0;
@@ -1342,6 +1354,67 @@ int stts_cfm_pitch_forward_taps(stts_ctx* c, void* stream, int n_utt, const int3
                          ws_bytes);
   API_END
 }
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ PosteriorEncoder (posterior.hip.h)
+extern "C" {
+
+size_t stts_posterior_workspace_bytes(const stts_ctx* c, int64_t rows, int n_utt, int max_len) {
+  if (!c || !c->posterior || !(c->ready & STTS_W_POSTERIOR) || rows <= 0 || n_utt <= 0) return 0;
+  const SynthSeg syn(rows, n_utt, max_len);
+  return dry_run_bytes([&](Arena a) {
+    PostIO io{};
+    (void)posterior_forward(const_cast<stts_ctx*>(c), nullptr, syn.seg(), io, a);
+  });
+}
+
+int stts_posterior_forward(stts_ctx* c, void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, const float* audio, float* har_spec,
+                           float* har_phase, int ld_har, const float* style, const float* noise, float* z_out, float* mean_out, float* logstd_out, float* mel_out,
+                           int ld_mel, float* x0_out, float* wn_out, void* ws, size_t ws_bytes, int seg_flags) {
+  API_BEGIN
+  READY_CHECK(c->posterior, STTS_W_POSTERIOR);
+  STTS_TRY(seg_ok(n_utt, seg_off_host, seg_off_dev));
+  Seg s{n_utt, seg_off_host, seg_off_dev};
+  s.cap = (seg_flags & STTS_SEG_CAPACITY) != 0;
+  const PostIO io{audio, har_spec, har_phase, ld_har, style, noise, z_out, mean_out, logstd_out, mel_out, ld_mel, x0_out, wn_out};
+  STTS_TRY(posterior_check(c, s, io));
+  Arena a(ws, ws_bytes);
+  return posterior_forward(c, st, s, io, a);
+  API_END
+}
+
+#ifdef STTS_TEST_OPS
+int stts_op_posterior_layer(stts_ctx* c, void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, int layer, int form, int out_acc,
+                            const float* h_in, const float* out_in, const float* cond, int ld_cond, float* h_out, float* out_out, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  READY_CHECK(c->posterior, STTS_W_POSTERIOR);
+  STTS_TRY(seg_ok(n_utt, seg_off_host, seg_off_dev));
+  const PostW& P = *static_cast<const PostW*>(c->posterior.get());
+  const Seg s{n_utt, seg_off_host, seg_off_dev};
+  const int H = P.hidden;
+  STTS_CHECK(layer >= 0 && layer < P.n_layers, "op_posterior_layer: layer %d of %d", layer, P.n_layers);
+  STTS_CHECK(form == 0 || ((form == 16 || form == 32 || form == 64) && P.fused), "op_posterior_layer: form %d is not built for this encoder", form);
+  STTS_CHECK(h_in && out_in && cond && h_out && out_out && h_out != h_in && out_out != out_in, "op_posterior_layer: null or aliased buffers");
+  STTS_CHECK(ld_cond % 4 == 0 && ld_cond >= 2 * H * P.n_layers, "op_posterior_layer: ld_cond %d < %d", ld_cond, 2 * H * P.n_layers);
+  for (const void* ptr : {(const void*)h_in, (const void*)out_in, (const void*)cond, (const void*)h_out, (const void*)out_out})
+    STTS_CHECK((uintptr_t)ptr % 16 == 0, "op_posterior_layer: buffers must be 16-byte aligned");
+  Arena a(ws, ws_bytes);
+  float* acts = a.get<float>((size_t)s.rows() * H);
+  STTS_CHECK(a.ok, "op_posterior_layer: workspace too small");
+  const size_t bytes = (size_t)s.rows() * H * sizeof(float);
+  const bool last = layer == P.n_layers - 1, fused = form != 0;
+  STTS_HIP(hipMemcpyAsync(out_out, out_in, bytes, hipMemcpyDeviceToDevice, st));
+  // the fused form writes h into another buffer (h_out); the generic one and the last layer work on a copy
+  if (!fused || last) STTS_HIP(hipMemcpyAsync(h_out, h_in, bytes, hipMemcpyDeviceToDevice, st));
+  float* after = nullptr;
+  const PostPlan plan{fused, form};
+  if (fused) STTS_TRY(posterior_layer(c, st, s, P, plan, layer, out_acc != 0, const_cast<float*>(h_in), h_out, out_out, acts, cond, ld_cond, &after));
+  else STTS_TRY(posterior_layer(c, st, s, P, plan, layer, out_acc != 0, h_out, nullptr, out_out, acts, cond, ld_cond, &after));
+  return 0;
+  API_END
+}
+#endif
 
 }  // extern "C"
 

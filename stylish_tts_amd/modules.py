@@ -24,17 +24,19 @@ Reference classes mirrored (paths relative to /root/reference/src/stylish_tts/tr
   MultiSpectrogram            train/multi_spectrogram.py:25-81
   MultiResolutionSTFTLoss     train/losses.py:14-35 (forward values; fused from the audio behind one MultiSpectrogram.forward call's lists, else on the tensors)
   MagPhaseLoss                train/losses.py:38-154 (forward values; leaves pred.phase unmodified)
+  PosteriorEncoder            models/flow.py:234-293 (+ FlowStatistics, utils.py:357-360)
 
 Differences, all additive: forward() of the stochastic modules takes an optional ``noise`` dict with the three draws
 the reference takes from the global torch generator (``prior_noise`` [B,128,4T], ``src_noise`` [B,1,300T],
 ``init_phase`` [1,1]); when omitted they are drawn with torch on the device.  Weights live in a flat store keyed by
 the reference's state_dict names (both weight-norm flavours), so ``load_state_dict`` accepts reference checkpoints;
-the training-only ``posterior_encoder.*`` keys are ignored.  There is no CPU path: forward() needs the GPU library.
+``posterior_encoder.*`` keys never enter a shim's own store: SpeechPredictor builds a PosteriorEncoder from a complete set (copy-synthesis,
+``forward(audio_gt=...)``), every other case ignores them.  There is no CPU path: forward() needs the GPU library.
 """
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -51,6 +53,7 @@ W_SSL = 16384  # hubert.model.* (AdaptiveHubert; finalized by stts_ssl_finalize)
 W_RMVPE = 32768  # rmvpe.* (RmvpePitchExtractor; finalized by stts_rmvpe_finalize)
 W_ALIGNER = 65536  # text_aligner.* (TextAligner; finalized by stts_aligner_finalize)
 W_WAVLM = 131072  # wavlm.* (WavLM; finalized by stts_wavlm_finalize)
+W_POSTERIOR = 262144  # speech_predictor.posterior_encoder.* (PosteriorEncoder; outside STTS_W_ALL)
 
 _ENGINES: Dict[int, HipModel] = {}
 
@@ -62,8 +65,16 @@ def get_engine(cfg=None, device: int = 0) -> HipModel:
     return _ENGINES[device]
 
 
+class FlowStatistics(NamedTuple):
+    """utils.py:357-360: a latent and the Gaussian it was drawn from, each [B, C, T]."""
+
+    z: torch.Tensor
+    mean: torch.Tensor
+    logstd: torch.Tensor
+
+
 class DecoderPrediction:
-    """utils.py:363-382 (inference fields only)."""
+    """utils.py:363-382 (inference fields; copy-synthesis fills mel_stats)."""
 
     def __init__(self, *, audio, magnitude, phase):
         self.audio, self.magnitude, self.phase = audio, magnitude, phase
@@ -347,16 +358,158 @@ class Generator(HipModule):
                                  phase=rep(eng.to_channel_major(ph, B, self.n_bins, T4)))
 
 
+class PosteriorEncoder(HipModule):
+    """models/flow.py:234-293: recording -> (z, mean, logstd), z ~ q(z | audio).  The reference's constructor; SpeechPredictor builds it with
+    out = hidden = decoder.hidden_dim // 4, kernel 3, dilation 1, 12 layers, hop_length // 4 and style_dim conditioning
+    (models/speech_predictor.py:39-49).  The STFT is the engine's (the vocoder's geometry), so n_fft / hop_length / win_length must be the
+    config's; dilation_rate must be 1 (the reference never builds another)."""
+
+    module_name, key_prefix, components = "speech_predictor", "posterior_encoder.", W_POSTERIOR
+
+    def __init__(self, out_channels, hidden_channels, kernel_size, dilation_rate, n_layers, n_fft, hop_length, win_length, gin_channels=0, cfg=None, engine=None):
+        cfg = cfg or load_model_config()
+        if dilation_rate != 1:
+            raise ValueError(f"PosteriorEncoder: dilation_rate {dilation_rate} is not built (the reference uses 1)")
+        if (n_fft, win_length, hop_length) != (cfg.n_fft, cfg.win_length, cfg.hop_length // 4):
+            raise ValueError(f"PosteriorEncoder: STFT geometry {(n_fft, win_length, hop_length)} is not the engine's {(cfg.n_fft, cfg.win_length, cfg.hop_length // 4)}")
+        if gin_channels not in (0, cfg.style_dim):
+            raise ValueError(f"PosteriorEncoder: gin_channels {gin_channels} must be 0 or style_dim {cfg.style_dim}")
+        if kernel_size % 2 != 1 or hidden_channels % 32 or out_channels % 4:
+            raise ValueError("PosteriorEncoder: kernel_size must be odd, hidden_channels a multiple of 32, out_channels a multiple of 4")
+        super().__init__(params.posterior_encoder_spec(cfg, "", hidden_channels, out_channels, kernel_size, n_layers, gin_channels), cfg, engine)
+        self.out_channels, self.hidden_channels, self.gin_channels, self.hop = out_channels, hidden_channels, gin_channels, hop_length
+
+    @classmethod
+    def from_config(cls, cfg=None, engine=None):
+        """As SpeechPredictor.__init__ builds it (models/speech_predictor.py:39-49)."""
+        cfg = cfg or load_model_config()
+        fh = cfg.decoder.hidden_dim // 4
+        return cls(fh, fh, 3, 1, 12, cfg.n_fft, cfg.hop_length // 4, cfg.win_length, gin_channels=cfg.style_dim, cfg=cfg, engine=engine)
+
+    def packed(self, seg: Segments, audio, style=None, noise=None, **kw):
+        """Packed rows: audio [hop * rows] (seg at the vocoder-frame rate), style [n_utt, 64] or None, noise [rows, out] (drawn when omitted)
+        -> HipModel.posterior's dict."""
+        eng = self.engine
+        if noise is None:
+            noise = torch.randn(seg.rows, self.out_channels, device=eng.device)
+        return eng.posterior(seg, audio=audio, style=style, noise=noise, **kw)
+
+    def forward(self, x, g=None, noise=None):
+        eng = self.engine
+        x = _f(torch.as_tensor(x), eng.device)
+        if x.dim() == 3:
+            x = x[:, 0]
+        B, S = x.shape
+        if S % self.hop:
+            raise ValueError(f"PosteriorEncoder: {S} samples are not a multiple of the hop {self.hop}")
+        T4 = S // self.hop
+        seg = Segments([T4] * B, eng.device)
+        style = None if g is None else _f(torch.as_tensor(g), eng.device).reshape(B, -1)
+        nz = None if noise is None else _f(torch.as_tensor(noise), eng.device).transpose(1, 2).reshape(B * T4, self.out_channels).contiguous()
+        o = self.packed(seg, x.reshape(-1), style, nz)
+        eng.check_status()
+        return tuple(eng.to_channel_major(o[k], B, self.out_channels, T4) for k in ("z", "mean", "logstd"))
+
+
 class SpeechPredictor(HipModule):
     module_name, components = "speech_predictor", W_DECODER | W_FLOW | W_GENERATOR | W_SPEECH_TEXT
 
     def __init__(self, model_config=None, engine=None):
         cfg = model_config if model_config is not None else load_model_config()
         super().__init__(params.speech_predictor_spec(cfg), cfg, engine)
+        self.__dict__["_posterior"] = None  # (not a registered sub-module: state_dict() keeps the inference inventory)
+
+    @property
+    def has_posterior(self) -> bool:
+        return self._posterior is not None
+
+    @property
+    def posterior(self) -> Optional[PosteriorEncoder]:
+        return self._posterior
+
+    def attach_posterior(self, module: Optional[PosteriorEncoder]):
+        """Use `module` for forward(audio_gt=...) (None detaches).  Its weights stay its own: state_dict() here is unchanged."""
+        if module is not None and not isinstance(module, PosteriorEncoder):
+            raise TypeError("attach_posterior: a modules.PosteriorEncoder is expected")
+        self.__dict__["_posterior"] = module
+        return self
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        res = super().load_state_dict(state_dict, strict, assign)
+        # a complete, correctly shaped posterior_encoder.* set builds the posterior; anything less is ignored as before
+        want = params.posterior_encoder_spec(self.cfg)
+        try:
+            ok = all(n in state_dict and tuple(torch.as_tensor(state_dict[n]).shape) == tuple(sh) for n, sh, _ in want)
+        except Exception:  # noqa: BLE001 - an entry that is no tensor: malformed, ignored
+            ok = False
+        if ok:
+            pe = PosteriorEncoder.from_config(self.cfg, self._engine)
+            pe.load_state_dict({n[len(pe.key_prefix):]: state_dict[n] for n, _, _ in want})
+            self.attach_posterior(pe)
+        return res
+
+    def _resynthesize(self, texts, text_lengths, alignment, pitch, energy, audio_gt, noise):
+        """forward(audio_gt=...): text encoder + style -> posterior(audio_gt | style) -> post_flow -> harmonic source + vocoder."""
+        eng = self.engine
+        pe = self._posterior
+        if pe._engine is None:
+            pe._engine = eng
+        if pe._engine is not eng:
+            raise RuntimeError("forward(audio_gt=...): the attached PosteriorEncoder is bound to another engine than this SpeechPredictor; build it with engine=<the "
+                               "speech predictor's engine> (or with none)")
+        pe.engine  # noqa: B018 - binds (packs) the posterior's weights
+        # `energy` is not read: in the reference it feeds the decoder, which this path does not run (the vocoder takes mel, style and pitch)
+        toks, sp = _pack_tokens(texts, text_lengths, eng.device)
+        _, T = _durations_from_alignment(alignment, sp.lengths, eng.device)
+        st = Segments(T, eng.device)
+        st4 = st.scaled(4)
+        B = sp.n
+        h, nb, fh = self.cfg.hop_length // 4, self.cfg.n_fft // 2 + 1, self.cfg.decoder.hidden_dim // 4
+        waves = list(audio_gt) if isinstance(audio_gt, (list, tuple)) else [w for w in torch.as_tensor(audio_gt)]
+        waves = [_f(torch.as_tensor(w), eng.device).reshape(-1) for w in waves]
+        if len(waves) != B:
+            raise ValueError(f"audio_gt holds {len(waves)} recordings for {B} texts")
+        for b in range(B):
+            if waves[b].numel() < 4 * h * T[b]:
+                raise ValueError(f"audio_gt[{b}] has {waves[b].numel()} samples, the alignment needs {4 * h * T[b]}")
+        wave = torch.cat([waves[b][: 4 * h * T[b]] for b in range(B)]).contiguous()
+        enc = eng.text_encoder(1, sp, toks)
+        style = eng.text_style(1, sp, enc)
+        pk = lambda t: torch.cat([_f(t, eng.device)[b, : T[b]] for b in range(B)])  # noqa: E731
+        p4 = eng.upsample4(st, st4, pk(pitch))
+        nz = noise or dict(draw_noise(B, 4 * max(T), eng.device, flow_dim=fh, h=h), posterior_noise=torch.randn(B, fh, 4 * max(T), device=eng.device))
+        qn = _f(torch.as_tensor(nz["posterior_noise"]), eng.device)
+        sn = _f(torch.as_tensor(nz["src_noise"]), eng.device)
+        qn_tm = torch.cat([qn[b, :, : 4 * T[b]].t() for b in range(B)]).contiguous()
+        sn_flat = torch.cat([sn[b, 0, : 4 * h * T[b]] for b in range(B)]).contiguous()
+        ip = _f(torch.as_tensor(nz["init_phase"]), eng.device).reshape(-1)
+        o = eng.posterior(st4, audio=wave, style=style, noise=qn_tm, mel=True)
+        spec, phase = eng.harmonic_stft(st4, p4, sn_flat, ip, batch_scope=True)
+        audio, la, ph = eng.vocoder(st4, o["mel"], style, spec, phase, return_spec=True)
+        eng.check_status()
+        if len(set(T)) == 1:
+            T4 = 4 * T[0]
+            rep = lambda t: torch.cat([t, t[:, :, -1:]], dim=2)  # noqa: E731
+            pred = DecoderPrediction(audio=audio.reshape(B, 1, h * T4), magnitude=rep(eng.to_channel_major(la, B, nb, T4)),
+                                     phase=rep(eng.to_channel_major(ph, B, nb, T4)))
+            pred.mel_stats = FlowStatistics(*(eng.to_channel_major(o[k], B, fh, T4) for k in ("z", "mean", "logstd")))
+            return pred
+        pred = DecoderPrediction(audio=[audio[h * st4.host[b] : h * st4.host[b + 1]] for b in range(B)], magnitude=None, phase=None)
+        rows = lambda t, b: t[st4.host[b] : st4.host[b + 1]].t().unsqueeze(0).contiguous()  # noqa: E731
+        pred.mel_stats = [FlowStatistics(*(rows(o[k], b) for k in ("z", "mean", "logstd"))) for b in range(B)]
+        return pred
 
     def forward(self, texts, text_lengths, alignment, pitch, energy, audio_gt=None, noise=None, return_spectra=True):
+        """audio_gt (copy-synthesis; [B, 300 T], [B, 1, 300 T] or a list of recordings for a ragged batch) needs a posterior (has_posterior): the
+        vocoder then runs on post_flow(z_mel), z_mel ~ q(z | audio_gt, style); decoder and reverse flow are not run.  The prediction carries
+        mel_stats = FlowStatistics(z, mean, logstd) (a list per utterance for a ragged batch); text_stats, text2mel_stats and mel2text_stats
+        stay None (they need the decoder, the reverse flow's statistics and the forward flow).  The noise dict then holds posterior_noise
+        [B, 128, 4 T] in place of prior_noise."""
         if audio_gt is not None:
-            raise NotImplementedError("audio_gt (posterior encoder, training only: speech_predictor.py:103-110) is outside the inference hot path")
+            if not self.has_posterior:
+                raise NotImplementedError("audio_gt needs the posterior encoder: load a state_dict that holds the complete posterior_encoder.* set, "
+                                          "or attach_posterior(modules.PosteriorEncoder)")
+            return self._resynthesize(texts, text_lengths, alignment, pitch, energy, audio_gt, noise)
         eng = self.engine
         toks, sp = _pack_tokens(texts, text_lengths, eng.device)
         dur, T = _durations_from_alignment(alignment, sp.lengths, eng.device)

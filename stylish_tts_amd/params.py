@@ -250,6 +250,40 @@ def speech_predictor_spec(cfg) -> Spec:
     return s
 
 
+def posterior_encoder_spec(cfg, p: str = "posterior_encoder.", hidden=None, out_channels=None, kernel_size: int = 3, n_layers: int = 12,
+                           gin_channels=None) -> Spec:
+    """PosteriorEncoder (models/flow.py:234-293) as SpeechPredictor builds it (models/speech_predictor.py:39-49): keys under
+    ``speech_predictor.`` + ``p``, registration order (WN: in_layers, res_skip_layers, cond_layer; legacy weight_g/_v keys).  It is kept out
+    of ``speech_predictor_spec``: the posterior's weights live in their own shim (modules.PosteriorEncoder).  gin_channels 0: no cond_layer."""
+    h = cfg.decoder.hidden_dim // 4 if hidden is None else hidden
+    oc = h if out_channels is None else out_channels
+    gin = cfg.style_dim if gin_channels is None else gin_channels
+    nbin = cfg.n_fft // 2 + 1
+    s: Spec = _conv(p + "pre_spec", h // 2, nbin, 1) + _conv(p + "pre_phase", h // 2, nbin, 1)
+    for i in range(n_layers):
+        s += [
+            (p + f"enc.in_layers.{i}.bias", (2 * h,), "b"),
+            (p + f"enc.in_layers.{i}.weight_g", (2 * h, 1, 1), "wn_g"),
+            (p + f"enc.in_layers.{i}.weight_v", (2 * h, h, kernel_size), "wn_v"),
+        ]
+    for i in range(n_layers):
+        rs = 2 * h if i < n_layers - 1 else h
+        s += [
+            (p + f"enc.res_skip_layers.{i}.bias", (rs,), "b"),
+            (p + f"enc.res_skip_layers.{i}.weight_g", (rs, 1), "wn_g_half"),
+            (p + f"enc.res_skip_layers.{i}.weight_v", (rs, h), "wn_v"),
+        ]
+    if gin:
+        s += [
+            (p + "enc.cond_layer.bias", (2 * h * n_layers,), "b"),
+            (p + "enc.cond_layer.weight_g", (2 * h * n_layers, 1), "wn_g_half"),
+            (p + "enc.cond_layer.weight_v", (2 * h * n_layers, gin), "wn_v"),
+        ]
+    s += [(p + "proj_mean.weight", (oc, h), "w_small"), (p + "proj_mean.bias", (oc,), "b")]
+    s += [(p + "proj_logstd.weight", (oc, h), "w_tiny"), (p + "proj_logstd.bias", (oc,), "b_tiny")]
+    return s
+
+
 def encoder_spec(p: str, c: int, filter_channels: int, kernel_size: int, n: int) -> Spec:
     """The transformer Encoder (models/text_encoder.py:332-393), registration order."""
     s: Spec = []

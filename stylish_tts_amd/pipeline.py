@@ -107,6 +107,53 @@ class Synthesizer:
     def __call__(self, token_lists: Sequence[Sequence[int]], noise: Optional[Dict[str, torch.Tensor]] = None, return_details: bool = False):
         return self._run(token_lists, noise, return_details, self._lane)
 
+    @torch.no_grad()
+    def resynthesize(self, token_lists: Sequence[Sequence[int]], recordings, alignments_or_durations, pitch, noise: Optional[Dict[str, torch.Tensor]] = None):
+        """Copy-synthesis (the reference's SpeechPredictor.forward with audio_gt, models/speech_predictor.py:104-118): the recording's posterior latent
+        z ~ q(z | recording, style) through post_flow and the vocoder; the text gives the style only, so the result tells how good the vocoder half of a
+        checkpoint is.  recordings: 1-D waveforms at the model's sample rate, at least hop_length samples per mel frame of the alignment;
+        alignments_or_durations: per utterance the integer durations [tokens] or the 0/1 alignment matrix [tokens, frames]; pitch: per utterance
+        the F0 curve [frames] (mel-frame rate, as validate_acoustic takes it from the data set).  The energy curve of the reference's call feeds the
+        decoder only, which this path does not run, so none is taken.  noise: packed draws posterior_noise [rows, 128], src_noise [rows * hop / 4],
+        init_phase [1] (rows = 4 x the mel frames).  Needs W_POSTERIOR finalized next to the speech predictor.  -> waveforms, one per utterance."""
+        eng, dev = self.eng, self.eng.device
+        L = [len(t) for t in token_lists]
+        if not (len(recordings) == len(alignments_or_durations) == len(pitch) == len(L)):
+            raise ValueError("resynthesize: token_lists, recordings, alignments_or_durations and pitch must have one entry per utterance")
+        durs = []
+        for b, a in enumerate(alignments_or_durations):
+            a = torch.as_tensor(a)
+            d = a.sum(dim=1).round() if a.dim() == 2 else a
+            if d.numel() != L[b]:
+                raise ValueError(f"utterance {b}: {d.numel()} durations for {L[b]} tokens")
+            durs.append([int(v) for v in d.tolist()])
+        T = [sum(d) for d in durs]
+        st = Segments(T, dev)
+        st4 = st.scaled(4)
+        R, h = st4.rows, eng.hop4
+        if int(eng.lib.stts_posterior_workspace_bytes(eng.ctx, R, st4.n, st4.max_len)) == 0:
+            raise RuntimeError("resynthesize needs the posterior encoder: load speech_predictor.posterior_encoder.* and finalize W_POSTERIOR")
+        waves = [torch.as_tensor(w).to(device=dev, dtype=torch.float32).reshape(-1) for w in recordings]
+        for b, w in enumerate(waves):
+            if w.numel() < 4 * h * T[b]:
+                raise ValueError(f"recording {b} has {w.numel()} samples, its alignment needs {4 * h * T[b]}")
+        wave = torch.cat([w[: 4 * h * T[b]] for b, w in enumerate(waves)]).contiguous()
+        f0 = torch.cat([torch.as_tensor(p).to(device=dev, dtype=torch.float32).reshape(-1)[: T[b]] for b, p in enumerate(pitch)]).contiguous()
+        if f0.numel() != st.rows:
+            raise ValueError("resynthesize: a pitch curve is shorter than its alignment")
+        toks = torch.tensor([int(v) for t in token_lists for v in t], dtype=torch.int64, device=dev)
+        sp = Segments(L, dev)
+        style = eng.text_style(1, sp, eng.text_encoder(1, sp, toks))
+        p4 = eng.upsample4(st, st4, f0)
+        if noise is None:
+            noise = dict(posterior_noise=torch.randn(R, self.cfg.decoder.hidden_dim // 4, device=dev), src_noise=torch.randn(R * h, device=dev),
+                         init_phase=torch.rand(1, device=dev))
+        o = eng.posterior(st4, audio=wave, style=style, noise=noise["posterior_noise"], mel=True, stats=False)
+        spec, phase = eng.harmonic_stft(st4, p4, noise["src_noise"], noise["init_phase"], batch_scope=False)
+        audio = eng.vocoder(st4, o["mel"], style, spec, phase)
+        eng.check_status()
+        return [audio[h * int(st4.host[b]) : h * int(st4.host[b + 1])] for b in range(len(L))]
+
     host_syncs_per_call = 0  # reads of device data by the host between the duration predictor and the frame path
 
     def stage_times(self, token_lists, noise=None) -> Dict[str, float]:

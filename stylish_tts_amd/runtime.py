@@ -217,7 +217,50 @@ class HipModel:
                                             _ptr(audio), _ptr(ws), ws.numel(), seg.flags))
         return audio
 
+    def posterior(self, seg: Segments, audio=None, spectra=None, style=None, noise=None, taps=False, mel=False, stats=True):
+        """PosteriorEncoder.forward on packed rows (stts_posterior_forward; needs W_POSTERIOR, and W_FLOW for mel=True).  audio [hop4 * rows]
+        packed, or spectra = (har_spec, har_phase) as [rows, >= n_bins] rows (copied into zero-padded [rows, har_ld] buffers).  style
+        [n_utt, 64] or None (the reference's g=None); noise [rows, 128].  -> dict: z, mean, logstd [rows, 128] (stats=False: z only),
+        har_spec / har_phase [rows, har_ld] (what the call read or wrote), mel [rows, hidden_dim] = post_flow(z) when mel=True, and with
+        taps=True x0 (cat[pre_spec, pre_phase]) and wn (the WaveNet's output)."""
+        if (audio is None) == (spectra is None):
+            raise ValueError("posterior: give exactly one of audio and spectra")
+        if noise is None:
+            raise ValueError("posterior: noise [rows, 128] is required")
+        fh, dh = self.cfg.decoder.hidden_dim // 4, self.cfg.decoder.hidden_dim
+        if audio is not None:
+            spec, phase = self._f32(seg.rows, self.har_ld), self._f32(seg.rows, self.har_ld)
+        else:
+            spec, phase = (torch.zeros(seg.rows, self.har_ld, dtype=torch.float32, device=self.device) for _ in range(2))
+            for dst, src in zip((spec, phase), spectra):
+                dst[:, : self.n_bins] = src[:, : self.n_bins]
+        o = dict(z=self._f32(seg.rows, fh), har_spec=spec, har_phase=phase)
+        if stats:
+            o.update(mean=self._f32(seg.rows, fh), logstd=self._f32(seg.rows, fh))
+        if mel:
+            o["mel"] = self._f32(seg.rows, dh)
+        if taps:
+            o.update(x0=self._f32(seg.rows, fh), wn=self._f32(seg.rows, fh))
+        ws = self._grow(self._ws, int(self.lib.stts_posterior_workspace_bytes(self.ctx, seg.rows, seg.n, seg.max_len)))
+        _lib.check(self.lib.stts_posterior_forward(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(audio), _ptr(spec), _ptr(phase), self.har_ld,
+                                                   _ptr(style), _ptr(noise), _ptr(o["z"]), _ptr(o.get("mean")), _ptr(o.get("logstd")), _ptr(o.get("mel")), dh,
+                                                   _ptr(o.get("x0")), _ptr(o.get("wn")), _ptr(ws), ws.numel(), seg.flags))
+        return o
+
     # ------------------------------------------------------------------ layout bridge + single ops
+    def op_posterior_layer(self, seg: Segments, layer: int, h, out, cond, form: int = 0, out_acc: Optional[bool] = None, pad_rows: int = 0):
+        """WaveNet layer `layer` of the finalized posterior encoder alone (test surface): h, out [rows, 128], cond [n_utt, ld] -> (h', out').
+        form: 0 = plain contractions, 16 | 32 | 64 = wn_post_kernel on that block height.  pad_rows: canary rows (NaN) behind the outputs."""
+        H = h.shape[1]
+        h_out = torch.full((seg.rows + pad_rows, H), float("nan"), dtype=torch.float32, device=self.device)
+        o_out = torch.full((seg.rows + pad_rows, H), float("nan"), dtype=torch.float32, device=self.device)
+        ws = self._f32(seg.rows * H + 64)
+        acc = layer > 0 if out_acc is None else out_acc
+        _lib.check(self.lib.stts_op_posterior_layer(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), layer, form, int(acc), _ptr(h), _ptr(out),
+                                                    _ptr(cond), cond.shape[1], _ptr(h_out), _ptr(o_out), _ptr(ws), ws.numel() * 4))
+        return h_out, o_out
+
+
     def to_time_major(self, x_bct: torch.Tensor, ld: Optional[int] = None) -> torch.Tensor:
         B, Cc, T = x_bct.shape
         ld = ld or ((Cc + 31) // 32 * 32)

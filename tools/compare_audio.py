@@ -16,6 +16,16 @@ Prints the score per resolution, their mean, the worst utterance and the wavefor
 files resampled from --sample-rate to 16 kHz on the engine) from the LOCAL WavLM checkpoint directory DIR (config.json + model.safetensors or
 pytorch_model.bin; nothing is downloaded, no weights ship with the engine).  ``--slm synthetic`` runs the base network with the engine's synthetic
 weights: the arithmetic of the score, not a perceptual number.
+
+    python tools/compare_audio.py recordings.npy [resynth_out.npy] --resynth JOB.npz --checkpoint DIR [--lengths ...] [--slm DIR]
+
+--resynth JOB.npz resynthesises the recordings of A on the engine and scores the result against them in the same command (copy-synthesis,
+pipeline.Synthesizer.resynthesize: the posterior encoder's latent of each recording through post_flow and the vocoder - how good the vocoder half
+of a checkpoint is, with the text half taken out of the question).  JOB.npz holds, for the utterances of A in order: ``tokens`` (all token ids, one
+after the other), ``token_lengths`` [utterances], ``durations`` (mel frames per token, one per token) and ``pitch`` (Hz per mel frame, one after the
+other); a recording must hold at least hop_length samples per mel frame and is cut to that.  --checkpoint is the reference's accelerate checkpoint
+directory or a packed safetensors file (checkpoint.py) whose speech_predictor holds the posterior_encoder.* keys; ``synthetic`` runs the synthetic
+weights.  With a second file name the resynthesised waveforms are also written there (one flat row; their lengths are printed).
 """
 from __future__ import annotations
 
@@ -45,14 +55,47 @@ def utterances(a: np.ndarray, lengths):
     return [row for row in a]
 
 
+def resynthesize(eng, recordings, job, checkpoint):
+    """-> (the recordings cut to their alignments, the resynthesised waveforms), numpy rows."""
+    import torch
+
+    from stylish_tts_amd import checkpoint as ckpt
+    from stylish_tts_amd import modules, pipeline
+
+    sp = modules.SpeechPredictor(eng.cfg, engine=eng)
+    if checkpoint == "synthetic":
+        sp.load_synthetic(0).attach_posterior(modules.PosteriorEncoder.from_config(eng.cfg, engine=eng).load_synthetic(0))
+    else:
+        sds = ckpt.load_accelerate_checkpoint(checkpoint, ("speech_predictor",)) if os.path.isdir(checkpoint) else ckpt.load_packed(checkpoint)
+        sp.load_state_dict(sds["speech_predictor"])
+    if not sp.has_posterior:
+        raise SystemExit("the checkpoint's speech_predictor holds no complete posterior_encoder.* set")
+    sp.engine, sp.posterior.engine  # noqa: B018 - packs both
+    tl = np.asarray(job["token_lengths"], np.int64)
+    to = np.concatenate([[0], np.cumsum(tl)])
+    if len(tl) != len(recordings):
+        raise SystemExit(f"the job describes {len(tl)} utterances, A holds {len(recordings)}")
+    toks = [[int(v) for v in job["tokens"][to[i] : to[i + 1]]] for i in range(len(tl))]
+    durs = [[int(v) for v in job["durations"][to[i] : to[i + 1]]] for i in range(len(tl))]
+    fo = np.concatenate([[0], np.cumsum([sum(d) for d in durs])])
+    f0 = [torch.from_numpy(np.asarray(job["pitch"][fo[i] : fo[i + 1]], np.float32)) for i in range(len(tl))]
+    out = pipeline.Synthesizer(eng).resynthesize(toks, [torch.from_numpy(w) for w in recordings], durs, f0)
+    out = [w.cpu().numpy() for w in out]
+    return [r[: w.size] for r, w in zip(recordings, out)], out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("a", help="the target waveforms (.npy)")
-    ap.add_argument("b", help="the waveforms scored against them (.npy)")
+    ap.add_argument("b", nargs="?", default=None, help="the waveforms scored against them (.npy); with --resynth: where the resynthesised waveforms are written (optional)")
     ap.add_argument("--sample-rate", type=int, default=None, help="of both files (default: the model config's)")
     ap.add_argument("--lengths", default="", help="comma-separated sample counts of the utterances in a flat file")
     ap.add_argument("--slm", default=None, metavar="DIR", help="also print the WavLM distance, from this local checkpoint directory ('synthetic': synthetic weights)")
+    ap.add_argument("--resynth", default=None, metavar="JOB.npz", help="resynthesise A's recordings (tokens, token_lengths, durations, pitch) and score the result against them")
+    ap.add_argument("--checkpoint", default="synthetic", help="with --resynth: checkpoint directory or packed file holding speech_predictor with posterior_encoder.* ('synthetic')")
     args = ap.parse_args()
+    if args.b is None and args.resynth is None:
+        ap.error("give B, or --resynth JOB.npz")
     import torch
 
     from stylish_tts_amd import val_scores
@@ -61,9 +104,16 @@ def main():
     from stylish_tts_amd.runtime import HipModel, Segments
 
     lengths = [int(v) for v in args.lengths.split(",") if v]
-    A, B = utterances(np.load(args.a), lengths), utterances(np.load(args.b), lengths)
-    val_scores.check_pair([w.size for w in A], [w.size for w in B])
+    A = utterances(np.load(args.a), lengths)
     eng = HipModel(load_model_config(), 0)
+    if args.resynth:
+        A, B = resynthesize(eng, A, np.load(args.resynth), args.checkpoint)
+        print("resynthesised lengths:", ",".join(str(w.size) for w in B))
+        if args.b:
+            np.save(args.b, np.concatenate(B))
+    else:
+        B = utterances(np.load(args.b), lengths)
+    val_scores.check_pair([w.size for w in A], [w.size for w in B])
     sr = eng.cfg.sample_rate if args.sample_rate is None else args.sample_rate
     seg = Segments([w.size for w in A], eng.device)
     sums = eng.mel_sums(seg, torch.from_numpy(np.concatenate(A)), torch.from_numpy(np.concatenate(B)), sample_rate=sr)
