@@ -52,14 +52,7 @@ int stts_ctx_create(const stts_model_dims* dims, int device, stts_ctx** out) {
 void stts_ctx_destroy(stts_ctx* c) {
   if (!c) return;
   for (void* p : c->allocs) (void)hipFree(p);
-  for (auto& kv : c->side_lanes) {
-    if (kv.second.fork) (void)hipEventDestroy(kv.second.fork);
-    if (kv.second.join) (void)hipEventDestroy(kv.second.join);
-    if (kv.second.stream) (void)hipStreamDestroy(kv.second.stream);
-    if (kv.second.fork2) (void)hipEventDestroy(kv.second.fork2);
-    if (kv.second.join2) (void)hipEventDestroy(kv.second.join2);
-    if (kv.second.stream2) (void)hipStreamDestroy(kv.second.stream2);
-  }
+  for (auto& kv : c->side_lanes) release_side_lane(kv.second);
   delete c;
 }
 

@@ -1183,49 +1183,7 @@ inline void launch_decoder_front(hipStream_t st, const Seg& s, const FrontArgs& 
   STTS_LAUNCH_PROF("decoder_front_kernel", (size_t)s.rows() * (fa.c_asr + 2 + fa.ld_enc + 2 * 4) * 4, decoder_front_kernel, rows_grid(s, fa.ld_enc / 4), dim3(256), st, fa, s.dev);
 }
 
-}  // namespace stts
-
-#include "adain_block.hip.h"
-#include "flow.hip.h"
-
-namespace stts {
-
-
-// ------------------------------------------------------------------------------------------------
-// stage: harmonic source + STFT (models/generator.py:247-315, :32-44, :406-410)
-// ------------------------------------------------------------------------------------------------
-inline int harmonic_stft(stts_ctx* c, hipStream_t st, const Seg& s, const float* pitch, const float* noise, const float* init_phase,
-                         int batch_scope, float* prior_out, float* har_spec, float* har_phase, int ld, Arena& ws, int out16 = 0) {
-  const long R = s.rows();
-  double* prefix = ws.get<double>(R);
-  float* stats = ws.get<float>(2 * s.n_utt);
-  const SignalGeom& g = c->geom;
-  float* sig = prior_out ? prior_out : ws.get<float>(R * g.h);
-  STTS_CHECK(ws.ok, "harmonic_stft: workspace too small");
-  if (g.generic) STTS_CHECK(ld >= g.bins, "harmonic_stft: row stride %d < %d bins", ld, g.bins);
-  else STTS_CHECK(ld >= kBins && ld <= 64 * ((kBins + 63) / 64), "harmonic_stft: row stride %d outside [%d, %d]", ld, kBins, 64 * ((kBins + 63) / 64));
-  STTS_DRY_RETURN(ws);
-  if (!s.cap)  // (capacity segments: pcph_kernel checks the real lengths and raises the device error word 4)
-    for (int u = 0; u < s.n_utt; ++u)
-      STTS_CHECK((long)(s.host[u + 1] - s.host[u]) * g.h > g.n_fft / 2, "utterance %d too short for reflect padding (%d frames; need > %d samples)", u,
-                 s.host[u + 1] - s.host[u], g.n_fft / 2);
-  if (g.generic) {
-    STTS_TRY(launch_pcph_geom(st, g, s.n_utt, s.dev, R, s.max_len(), pitch, noise, init_phase, batch_scope, prefix, stats, sig, c->d_err));
-    STTS_TRY(launch_stft_geom(st, g, s.n_utt, s.dev, R, s.max_len(), sig, c->hann, c->twiddle64, har_spec, har_phase, ld, out16));
-    STTS_HIP(hipGetLastError());
-    return 0;
-  }
-  STTS_LAUNCH_PROF("pcph_prep_kernel", (size_t)R * 12, pcph_prep_kernel, dim3(s.n_utt), dim3(256), st, pitch, s.dev, prefix, stats);
-  STTS_LAUNCH_PROF("pcph_kernel", (size_t)R * kHop * 8, pcph_kernel, dim3(std::min(1024, ceil_div(s.max_len() * kHop, 256)), s.n_utt), dim3(256), st, pitch, s.dev, s.n_utt,
-                     prefix, stats, noise, init_phase, batch_scope, sig, c->d_err);
-  STTS_LAUNCH_PROF("stft_kernel", (size_t)R * (kHop + 2 * kBins) * 4, stft_kernel, dim3((s.max_len() + kFftWaves - 1) / kFftWaves, s.n_utt), dim3(64 * kFftWaves), st, sig, s.dev, c->hann, c->twiddle64, har_spec, har_phase, ld, out16);
-  STTS_HIP(hipGetLastError());
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// stage: vocoder body + iSTFT (models/generator.py:412-433)
-// ------------------------------------------------------------------------------------------------
+// row LayerNorm (plain or adaptive, one or two outputs): the vocoder, the ConvNeXt block, the phoneme-rate stages and the test operators
 inline int ln_launch(hipStream_t st, const float* X, int ldx, int C, long n_rows, const int* row_utt, float eps, int adaptive, int nout,
                      const LnOut& o0, const LnOut& o1, int act, const LnIn& in = LnIn{}, const int* n_rows_dev = nullptr) {
   STTS_LAUNCH_PROF("row_layernorm_kernel", (size_t)n_rows * C * (1 + nout) * 4, row_layernorm_kernel, dim3((unsigned)ceil_div((int)n_rows, 4)), dim3(256), st, X, ldx, C, (int)n_rows, row_utt, eps,
@@ -1233,344 +1191,11 @@ inline int ln_launch(hipStream_t st, const float* X, int ldx, int C, long n_rows
   STTS_HIP(hipGetLastError());
   return 0;
 }
-
-// Scratch of convnext_block_forward: dw / nrm [rows, h], U [rows, inter], part [n_utt * ss_stride, inter] (GRN sums of squares per 32-row
-// sub-tile, ss_stride >= ceil(max_len / 32)), gscale [n_utt, inter], w2u [n_utt, pw2.npad * inter] (per-utterance GRN-scaled pwconv2),
-// row_utt [rows] (read only when the block does not fit dwconv_ln_kernel).
-struct ConvNextScratch {
-  float *dw, *nrm, *U, *part;
-  int ss_stride;
-  float *gscale, *w2u;
-  const int* row_utt;
-};
-
-// One ConvNeXtBlock with an AdaptiveLayerNorm (models/generator.py:441-499) over packed rows: nxt = cur + block(cur, style).  sty / lds:
-// the block's style table rows (its norm slot); p16: the 16-bit operand mode of the frame path (0: fp32).  Used by the vocoder
-// (vocoder_body) and by CfmPitchPredictor (cfm_pitch.hip.h).
-inline int convnext_block_forward(hipStream_t st, const Seg& s, const ConvNextW& B, int h, int inter, const float* sty, int lds, int p16, const float* cur,
-                                  float* nxt, const ConvNextScratch& sc) {
-  const long R = s.rows();
-  const int ml = s.max_len();
-  float *dw = sc.dw, *nrm = sc.nrm, *U = sc.U, *part = sc.part, *gscale = sc.gscale, *w2u = sc.w2u;
-  const int ss_stride = sc.ss_stride;
-  const int* row_utt = sc.row_utt;
-  if (h <= kDwLnMaxC && h % 4 == 0 && (B.K == 3 || B.K == 7 || B.K == 15 || B.K == 31)) {
-    // depthwise conv + adaptive LayerNorm in one launch (the [rows, h] intermediate never reaches HBM)
-    // (32-row blocks for the long kernels - half the halo re-reads, two blocks per CU - measured no faster at B = 64: 64 vs 58 us)
-    const dim3 fg(ceil_div(ml, 16), s.n_utt);
-    const size_t fb = (size_t)R * h * (4 + (p16 ? 2 : 4));
-#define STTS_DWLN(KK) STTS_LAUNCH_PROF("dwconv_ln_kernel", fb, (dwconv_ln_kernel<KK, 16>), fg, dim3(256), st, cur, h, h, s.dev, B.dw_wt, B.dw_b, 1e-6f, sty, lds, B.norm.col0, nrm, h, p16)
-    if (B.K == 3) STTS_DWLN(3);
-    else if (B.K == 7) STTS_DWLN(7);
-    else if (B.K == 15) STTS_DWLN(15);
-    else STTS_DWLN(31);
-#undef STTS_DWLN
-  } else {
-    STTS_CHECK(row_utt, "convnext_block_forward: this block needs the row -> utterance table");
-    STTS_LAUNCH_PROF("dwconv_kernel", (size_t)R * h * 2 * 4, (dwconv_kernel<31>), dim3(ceil_div(h, 64), ceil_div(ml, 64), s.n_utt), dim3(256), st, cur, h, dw, h, h, s.dev, B.dw_wt,
-                       B.dw_b, B.K, (int)ACT_NONE);
-    LnOut o0{nrm, h, 0, sty, nullptr, lds, B.norm.col0, p16}, o1{};
-    STTS_TRY(ln_launch(st, dw, h, h, R, row_utt, 1e-6f, 1, 1, o0, o1, ACT_NONE, LnIn{}, s.rows_dev()));
-  }
-  GemmArgs a = gemm_args(s);
-  set_seg(a, 0, nrm, h, 0, B.pw1);
-  a.N = inter; a.bias = B.pw1.bias; a.act = ACT_SILU;
-  a.x16 = p16 != 0;
-  if (p16) { a.Y = nullptr; a.Y16 = reinterpret_cast<unsigned short*>(U); a.ldy16 = inter; }  // GRN's sums of squares come from the fp32 values
-  else { a.Y = U; a.ldy = inter; }
-  a.sumsq_part = part; a.ld_ss = inter; a.ss_stride = ss_stride;
-  STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, B.pw1.npad, s.n_utt, ml));
-  STTS_LAUNCH_PROF("grn_gx_kernel", (size_t)s.n_utt * ss_stride * inter * 4, grn_gx_kernel, dim3(ceil_div(inter, 32), s.n_utt), dim3(256), st, part, inter, ss_stride, s.dev, inter, gscale, inter);
-  GemmArgs b = gemm_args(s);
-  set_seg(b, 0, U, inter, 0, B.pw2);
-  if (B.pw2.prec == PREC_F32 && B.pw2.w16_plane > 0 && x3_enabled()) {
-    // split fp32: GRN's per-(utterance, channel) factor scales the ACTIVATION while pwconv2's tile is staged (the contraction's input affine with
-    // slope 1) instead of a per-utterance copy of the weight: the shared split planes of W stay valid and the scale_weight pass is gone
-    hipLaunchKernelGGL(grn_xaff_kernel, dim3(s.n_utt), dim3(256), 0, st, gscale, inter, B.grn_gamma, w2u, B.pw2.kc, inter);
-    b.xaff = w2u;
-    b.ld_xaff = B.pw2.kc;
-    b.xaff_slope = 1.0f;
-    static const bool no_scale_only = getenv("STTS_XAFF_GENERAL") != nullptr;  // experiments: the general scale / shift / slope form
-    b.xaff_scale_only = B.pw2.kc == inter && !no_scale_only;  // (no pad column: every staged value is a written one)
-  } else {
-    launch_scale_weight(st, dim3(128, s.n_utt), B.pw2.prec, B.pw2.W, gscale, inter, B.grn_gamma, w2u, B.pw2.npad, B.pw2.kc);
-    b.seg[0].W = w2u;
-    b.seg[0].W16 = reinterpret_cast<const unsigned short*>(w2u);
-    b.seg[0].w16_plane = 0;
-    b.seg[0].w_utt_stride = (long)B.pw2.npad * B.pw2.kc;
-  }
-  b.x16 = p16 != 0;
-  b.N = h; b.bias = B.pw2.bias; b.Y = nxt; b.ldy = h; b.R = cur; b.ldr = h;
-  STTS_TRY(launch_conv_gemm(st, b, EPI_STORE, B.pw2.npad, s.n_utt, ml));
-  return 0;
-}
-
-// prior convs (generator.py:412-413) write straight into the concat slots [h, h+hp) of the two head inputs.  The two
-// convs are independent (and independent of decoder/flow), so the caller may put them on different streams.
-inline bool vocoder_rows16(const stts_ctx* c, long rows) { return c->prec != PREC_F32 && rows >= rows16_threshold(); }
-
-// 16-bit operand modes, large batches: the head inputs are 16-bit row buffers (`head` reinterpreted, [rows, hc] elements) and
-// the conv reads a rounded copy of har (har16: scratch of rows * ld_har elements).
-inline int prior_conv(stts_ctx* c, hipStream_t st, const Seg& s, int which, const float* har, int ld_har, float* head, WinoScratch* wino = nullptr,
-                      unsigned short* har16 = nullptr, bool har_is16 = false) {
-  const int h = c->d.gen_hidden, hp = h / 2, hc = h + hp;
-  const PackedConv& w = which == 0 ? c->amp_prior : c->phase_prior;
-  if (wino && *wino && c->wino_prior[which].ready)  // k = 7 in Winograd F(6,7) form: 12 instead of 42 multiplies per 6 outputs
-    return run_winograd(st, s, har, ld_har, c->wino_prior[which], head + h, hc, ACT_NONE, nullptr, 0, 1.0f, *wino);
-  GemmArgs a = gemm_args(s);
-  set_seg(a, 0, har, ld_har, 0, w);
-  a.N = hp; a.bias = w.bias;
-  if (vocoder_rows16(c, s.rows())) {
-    STTS_CHECK((har16 || har_is16) && ld_har % 8 == 0, "prior_conv: 16-bit mode needs the rounded-copy scratch");
-    if (!har_is16) launch_cast_rows(st, c->prec, har, ld_har, c->geom.bins, har16, ld_har, s.rows());
-    a.seg[0].X = har_is16 ? har : reinterpret_cast<const float*>(har16);
-    a.x16 = 1;
-    a.Y = nullptr; a.Y16 = reinterpret_cast<unsigned short*>(head); a.ldy16 = hc; a.ycol16 = h;
-  } else {
-    a.Y = head; a.ldy = hc; a.ycol0 = h;
-  }
-  return launch_conv_gemm(st, a, EPI_STORE, w.npad, s.n_utt, s.max_len());
-}
-
-// everything after the prior convs: projector, ConvNeXt blocks, heads, output convs, iSTFT (generator.py:414-433).
-// headA / headP [rows, 768]: columns [512, 768) already hold logamp_prior / phase_prior.
-inline int vocoder_body(stts_ctx* c, hipStream_t st, const Seg& s, const float* mel, int ld_mel, const float* style, float* headA, float* headP,
-                        float* audio, float* logamp_out, float* phase_out, int ld_lp, Arena& ws, const unsigned short* mel16_in = nullptr) {
-  // mel16_in: [rows, round_up(gen_input, 32)] mel already rounded to the operand precision by its producer (frame_path)
-  const stts_model_dims& d = c->d;
-  const long R = s.rows();
-  const int h = d.gen_hidden, hp = h / 2, hc = h + hp, inter = d.gen_inter, ml = s.max_len();
-  const SignalGeom& geo = c->geom;
-  const int ldlp = round_up(geo.bins, 32);
-  float* xa = ws.get<float>(R * h);
-  float* xb = ws.get<float>(R * h);
-  float* dw = ws.get<float>(R * h);
-  float* nrm = ws.get<float>(R * h);
-  float* U = ws.get<float>(R * inter);
-  const int ss_stride = ceil_div(ml, 128) * 4;
-  float* part = ws.get<float>((size_t)s.n_utt * ss_stride * inter);
-  float* gscale = ws.get<float>((size_t)s.n_utt * inter);
-  float* w2u = ws.get<float>((size_t)s.n_utt * c->cnx[0].pw2.npad * inter);
-  float* sty = ws.get<float>((size_t)s.n_utt * c->gen_style.ld());
-  int* row_utt = ws.get<int>(R);
-  float* la = logamp_out ? logamp_out : ws.get<float>(R * ldlp);
-  float* ph = phase_out ? phase_out : ws.get<float>(R * ldlp);
-  const int ldl = logamp_out ? ld_lp : ldlp;
-  // 16-bit operand modes: every contraction input of the body is a 16-bit row buffer written by its producer (LayerNorm
-  // outputs, the SiLU output of pwconv1, the head inputs) - nrm / U / headA / headP are reinterpreted; mel gets a rounded copy
-  // (from rows16_threshold() rows on: below that the contractions are latency-bound one-round launches and the extra copies cost more
-  //  than the staging they save)
-  const int p16 = (c->prec != PREC_F32 && vocoder_rows16(c, R)) ? c->prec : 0;
-  unsigned short* mel16 = (p16 && !mel16_in) ? ws.get<unsigned short>(R * round_up(d.gen_input, 32)) : nullptr;
-  float* yw = ws.get<float>((R + s.n_utt) * geo.win);
-  WinoScratch wino;
-  if (c->wino_out[0].ready && c->wino_out[1].ready) wino.p = ws.get<float>(wino_scratch_floats(s, c->wino_out[0]));
-  STTS_CHECK(ws.ok, "vocoder: workspace too small");
-  STTS_DRY_RETURN(ws);
-  STTS_CHECK(!logamp_out == !phase_out, "logamp_out and phase_out must be given together");
-  const int lds = c->gen_style.ld();
-  STTS_TRY(run_style(st, c->gen_style, style, s.n_utt, sty));
-  STTS_LAUNCH_PROF("row_utt_kernel", (size_t)R * 4, row_utt_kernel, dim3(ceil_div(ml, 256), s.n_utt), dim3(256), st, s.dev, s.n_utt, row_utt);
-  // projector over cat[mel, logamp_prior, phase_prior] as three K segments (generator.py:414)
-  {
-    GemmArgs a = gemm_args(s);
-    if (p16) {
-      const int ldm16 = round_up(d.gen_input, 32);
-      if (!mel16_in) launch_cast_rows(st, p16, mel, ld_mel, d.gen_input, mel16, ldm16, R);
-      set_seg(a, 0, reinterpret_cast<const float*>(mel16_in ? mel16_in : mel16), ldm16, 0, c->proj_mel);
-      a.x16 = 1;
-    } else {
-      set_seg(a, 0, mel, ld_mel, 0, c->proj_mel);
-    }
-    set_seg(a, 1, headA, hc, h, c->proj_la);
-    set_seg(a, 2, headP, hc, h, c->proj_ph);
-    a.N = h; a.bias = c->proj_mel.bias; a.Y = xa; a.ldy = h;
-    STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, c->proj_mel.npad, s.n_utt, ml));
-  }
-  float* cur = xa;
-  float* nxt = xb;
-  const ConvNextScratch cs{dw, nrm, U, part, ss_stride, gscale, w2u, row_utt};
-  for (int i = 0; i < 4; ++i) {
-    STTS_TRY(convnext_block_forward(st, s, c->cnx[i], h, inter, sty, lds, p16, cur, nxt, cs));
-    std::swap(cur, nxt);
-  }
-  // two AdaLN heads (eps 1e-5) into columns [0,512) of the head inputs (generator.py:417-423)
-  {
-    LnOut o0{headA, hc, 0, sty, nullptr, lds, c->head_amp.col0, p16}, o1{headP, hc, 0, sty, nullptr, lds, c->head_phase.col0, p16};
-    STTS_TRY(ln_launch(st, cur, h, h, R, row_utt, 1e-5f, 1, 2, o0, o1, ACT_NONE, LnIn{}, s.rows_dev()));
-  }
-  {
-    GemmArgs a = gemm_args(s);
-    set_seg(a, 0, headA, hc, 0, c->amp_out);
-    a.x16 = p16 != 0;
-    a.N = geo.bins - 1; a.bias = c->amp_out.bias; a.Y = la; a.ldy = ldl;
-    if (wino) STTS_TRY(run_winograd(st, s, headA, hc, c->wino_out[0], la, ldl, ACT_NONE, nullptr, 0, 1.0f, wino));
-    else STTS_TRY(launch_conv_gemm(st, a, EPI_STORE, c->amp_out.npad, s.n_utt, ml));
-    GemmArgs b = gemm_args(s);
-    set_seg(b, 0, headP, hc, 0, c->phase_out);
-    b.x16 = p16 != 0;
-    b.N = geo.bins - 1; b.bias = c->phase_out.bias; b.Y = ph; b.ldy = ldl;
-    if (wino) STTS_TRY(run_winograd(st, s, headP, hc, c->wino_out[1], ph, ldl, ACT_NONE, nullptr, 0, 1.0f, wino));
-    else STTS_TRY(launch_conv_gemm(st, b, EPI_STORE, c->phase_out.npad, s.n_utt, ml));
-    const int kk = c->amp_out.ntaps;
-    STTS_CHECK(kk <= kChanTaps, "output conv kernel size %d > %d", kk, kChanTaps);
-    const ChanConvSet sa{headA, c->nyq_w[0], c->nyq_b[0], la}, sp{headP, c->nyq_w[1], c->nyq_b[1], ph};
-    STTS_TRY(launch_single_channel_conv(st, s, p16, 2, sa, sp, hc, hc, kk, ldl, geo.bins - 1, true));
-  }
-  if (geo.generic) {
-    STTS_TRY(launch_istft_geom(st, geo, s.n_utt, s.dev, R, ml, la, ph, ldl, c->hann, c->twiddle64, yw, audio));
-    STTS_HIP(hipGetLastError());
-    return 0;
-  }
-  STTS_LAUNCH_PROF("istft_frames_kernel", (size_t)R * 2 * kBins * 4, istft_frames_kernel, dim3((ml + 1 + kFftWaves - 1) / kFftWaves, s.n_utt), dim3(64 * kFftWaves), st, la, ph, ldl, s.dev, c->hann, c->twiddle64, yw);
-  STTS_LAUNCH_PROF("istft_ola_kernel", (size_t)R * kHop * 4, istft_ola_kernel, dim3(std::min(1024, ceil_div(ml * kHop, 256)), s.n_utt), dim3(256), st, yw, s.dev, c->hann, audio);
-  STTS_HIP(hipGetLastError());
-  return 0;
-}
-
-inline int vocoder_forward(stts_ctx* c, hipStream_t st, const Seg& s, const float* mel, int ld_mel, const float* style, const float* har_spec,
-                           const float* har_phase, int ld_har, float* audio, float* logamp_out, float* phase_out, int ld_lp, Arena& ws) {
-  const long R = s.rows();
-  const int hc = c->d.gen_hidden + c->d.gen_hidden / 2;
-  float* headA = ws.get<float>(R * hc);
-  float* headP = ws.get<float>(R * hc);
-  STTS_CHECK(ws.ok, "vocoder_forward: workspace too small");
-  {
-    Arena tmp = ws.rest();  // released again before vocoder_body carves its own buffers
-    WinoScratch wino;
-    if (c->wino_prior[0].ready) wino.p = tmp.get<float>(wino_scratch_floats(s, c->wino_prior[0]));
-    unsigned short* har16 = c->prec != PREC_F32 ? tmp.get<unsigned short>(R * ld_har) : nullptr;
-    STTS_CHECK(tmp.ok, "vocoder_forward: workspace too small");
-    if (dry_run().on) {
-      dry_run().peak = std::max(dry_run().peak, tmp.offset0 + tmp.used);
-    } else {
-      STTS_TRY(prior_conv(c, st, s, 0, har_spec, ld_har, headA, &wino, har16));
-      STTS_TRY(prior_conv(c, st, s, 1, har_phase, ld_har, headP, &wino, har16));
-      }
-  }
-  return vocoder_body(c, st, s, mel, ld_mel, style, headA, headP, audio, logamp_out, phase_out, ld_lp, ws);
-}
-
-// row stride of the harmonic spectra: the prior convs' packed input width (1056; 1088 in the 16-bit modes)
-inline int har_ld(const stts_ctx* c) { return std::max(round_up(c->d.n_fft / 2 + 1, 32), c->amp_prior.kc); }
-
-inline int frame_path(stts_ctx* c, hipStream_t st, const Seg& s, const float* asr, int ld_asr, const float* pitch, const float* energy,
-                      const float* style, const float* prior_noise, const float* src_noise, const float* init_phase, int batch_scope,
-                      float* audio, void* wsp, size_t ws_bytes) {
-  const long R = s.rows();
-  Arena top(wsp, ws_bytes);
-  const int ldh = har_ld(c), hc = c->d.gen_hidden + c->d.gen_hidden / 2, dh = c->d.dec_hidden;
-  float* x = top.get<float>(R * dh);
-  float* mel = top.get<float>(R * dh);
-  float* hs = top.get<float>(R * ldh);
-  float* hp = top.get<float>(R * ldh);
-  float* headA = top.get<float>(R * hc);
-  float* headP = top.get<float>(R * hc);
-  const int ldm16 = round_up(c->d.gen_input, 32);
-  unsigned short* mel16 = (c->prec != PREC_F32 && vocoder_rows16(c, R) && c->d.gen_input == dh) ? top.get<unsigned short>(R * ldm16) : nullptr;
-  const size_t side_bytes = (size_t)R * (sizeof(double) + c->geom.h * sizeof(float)) + 4096 + 8 * s.n_utt;
-  const size_t side_off = top.used;
-  char* side_ws = top.get<char>(side_bytes);
-  // (side stream, below: the prior convs then need scratch of their own - the decoder uses the stage region at the same time)
-  static const long side_min_rows = getenv("STTS_SIDE_MIN_ROWS") ? atol(getenv("STTS_SIDE_MIN_ROWS")) : 3000;
-  const bool side_cfg = c->prec == PREC_F32 && R > side_min_rows && c->wino_prior[0].ready;
-  float* side_scratch = side_cfg ? top.get<float>(wino_scratch_floats(s, c->wino_prior[0])) : nullptr;
-  STTS_CHECK(top.ok, "frame_path: workspace too small");
-  auto stage = [&]() { return top.rest(); };  // (nothing more is carved from `top`: every stage starts at the same mark)
-  // Measured: running the (independent) source -> STFT -> prior-conv chain on side streams next to decoder/flow gains
-  // < 1 % at B = 8 (7.51 vs 7.57 ms/step): the decoder GEMMs already fill the chip, so the stages stay on one stream.
-  // 16-bit operand modes, large batches: the spectra are only read by the prior convs, so the STFT writes them as 16-bit rows
-  const int h16 = vocoder_rows16(c, R) ? c->prec : 0;
-  // fp32, large batches: the source -> STFT -> prior-conv chain (independent of decoder and flow until the vocoder) runs on a SIDE STREAM of the caller's
-  // stream (fork / join events; the prior convs' scratch is its own region, carved above): it fills the chip while the decoder runs its small
-  // bandwidth-bound kernels.  Same kernels, same results; same-box A/B (3-s utterances): B = 8: 4.43 -> 4.38 ms per step (+1.2 %), B = 4: 2.91 -> 2.86
-  // (+1.6 %), B = 2: +0.8 %, B = 1: 1.76 -> 1.78 (the two cross-queue waits cost more than the overlap gains: off below 3 000 rows; STTS_SIDE_MIN_ROWS).
-  // (Round 1, when the step took 7.5 ms and the prior convs were direct contractions, the same experiment gained < 1 %.)  Not while the per-launch profiler is on (its events belong to one stream),
-  // not in the 16-bit modes (the persistent contraction kernel of the decoder and that of the prior convs would fight for the same CUs).
-  const bool side_off_env = getenv("STTS_NO_SIDE_STREAM") != nullptr;  // experiments / tests (read per call)
-  // (not while the caller's stream is being captured into a graph: the lane's stream and events are created on first use, which a capture may not allow)
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  if (side_scratch && !side_off_env) (void)hipStreamIsCapturing(st, &capturing);
-  if (side_scratch && !dry_run().on && !gemm_profiler().on && !side_off_env && capturing == hipStreamCaptureStatusNone) {
-    stts_ctx::SideLane lane;
-    {
-      std::lock_guard<std::mutex> lock(c->side_mu);
-      stts_ctx::SideLane& l = c->side_lanes[st];
-      if (!l.stream) {
-        STTS_HIP(hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
-        STTS_HIP(hipEventCreateWithFlags(&l.fork, hipEventDisableTiming));
-        STTS_HIP(hipEventCreateWithFlags(&l.join, hipEventDisableTiming));
-        STTS_HIP(hipStreamCreateWithFlags(&l.stream2, hipStreamNonBlocking));
-        STTS_HIP(hipEventCreateWithFlags(&l.fork2, hipEventDisableTiming));
-        STTS_HIP(hipEventCreateWithFlags(&l.join2, hipEventDisableTiming));
-      }
-      lane = l;
-    }
-    STTS_HIP(hipEventRecord(lane.fork, st));
-    STTS_HIP(hipStreamWaitEvent(lane.stream, lane.fork, 0));
-    // Whatever fails from here on, the caller's stream joins the side stream before this call returns: work that is still running there reads and
-    // writes the caller's workspace, which the caller is free to reuse (in stream order) as soon as it has the status.
-    auto forked = [&]() -> int {
-      { Arena a(side_ws, side_bytes, side_off); STTS_TRY(harmonic_stft(c, lane.stream, s, pitch, src_noise, init_phase, batch_scope, nullptr, hs, hp, ldh, a, h16)); }
-      WinoScratch wino;
-      wino.p = side_scratch;
-      STTS_TRY(prior_conv(c, lane.stream, s, 0, hs, ldh, headA, &wino, nullptr, h16 != 0));
-      STTS_TRY(prior_conv(c, lane.stream, s, 1, hp, ldh, headP, &wino, nullptr, h16 != 0));
-      return 0;
-    };
-    int rc = forked();
-    STTS_HIP(hipEventRecord(lane.join, lane.stream));
-    if (rc == 0) {
-      auto main_part = [&]() -> int {
-        SideWork sw;
-        sw.stream = lane.stream2; sw.fork = lane.fork2; sw.join = lane.join2;
-        { Arena a = stage(); STTS_TRY(decoder_forward(c, st, s, asr, ld_asr, pitch, energy, style, x, dh, a, &sw)); }
-        { Arena a = stage(); STTS_TRY(prior_flow_forward(c, st, s, x, dh, style, prior_noise, mel, dh, nullptr, nullptr, a, mel16, ldm16)); }
-        return 0;
-      };
-      rc = main_part();
-    }
-    STTS_HIP(hipStreamWaitEvent(st, lane.join, 0));
-    if (rc) return rc;
-    { Arena a = stage(); STTS_TRY(vocoder_body(c, st, s, mel, dh, style, headA, headP, audio, nullptr, nullptr, 0, a, mel16)); }
-    return 0;
-  }
-  { Arena a(side_ws, side_bytes, side_off); STTS_TRY(harmonic_stft(c, st, s, pitch, src_noise, init_phase, batch_scope, nullptr, hs, hp, ldh, a, h16)); }
-  {
-    Arena a = stage();
-    WinoScratch wino;
-    if (c->wino_prior[0].ready) wino.p = a.get<float>(wino_scratch_floats(s, c->wino_prior[0]));
-    STTS_CHECK(a.ok, "frame_path: workspace too small");
-    if (dry_run().on) {
-      dry_run().peak = std::max(dry_run().peak, a.offset0 + a.used);
-    } else {
-      STTS_TRY(prior_conv(c, st, s, 0, hs, ldh, headA, &wino, nullptr, h16 != 0));
-      STTS_TRY(prior_conv(c, st, s, 1, hp, ldh, headP, &wino, nullptr, h16 != 0));
-      }
-  }
-  { Arena a = stage(); STTS_TRY(decoder_forward(c, st, s, asr, ld_asr, pitch, energy, style, x, dh, a)); }
-  { Arena a = stage(); STTS_TRY(prior_flow_forward(c, st, s, x, dh, style, prior_noise, mel, dh, nullptr, nullptr, a, mel16, ldm16)); }
-  { Arena a = stage(); STTS_TRY(vocoder_body(c, st, s, mel, dh, style, headA, headP, audio, nullptr, nullptr, 0, a, mel16)); }
-  return 0;
-}
-
-// Bytes of caller-owned workspace that every frame-rate entry point accepts for a batch of `R` rows in `n_utt` utterances,
-// the longest `max_len` rows: a dry run of the stages themselves (dry_run_bytes), so the bound follows the model dims and
-// whatever the stages really request.  Weights must be finalized (which convs have a Winograd form decides their scratch).
-inline size_t frame_workspace_bytes(const stts_ctx* cc, int64_t R, int n_utt, int max_len) {
-  stts_ctx* c = const_cast<stts_ctx*>(cc);
-  if (R <= 0 || n_utt <= 0 || max_len <= 0) return 0;
-  const SynthSeg syn(R, n_utt, max_len);
-  const Seg s = syn.seg();
-  return dry_run_bytes([&](Arena a) {
-    (void)frame_path(c, nullptr, s, nullptr, c->d.inter_dim, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, a.base, a.cap);
-    // the staged entry points start their carving at offset 0; vocoder_forward with its own head buffers is the largest of them
-    Arena v = a, d = a;
-    (void)vocoder_forward(c, nullptr, s, nullptr, c->d.dec_hidden, nullptr, nullptr, nullptr, har_ld(c), nullptr, nullptr, nullptr, 0, v);
-    (void)decoder_forward(c, nullptr, s, nullptr, c->d.inter_dim, nullptr, nullptr, nullptr, nullptr, c->d.dec_hidden, d);
-  });
-}
-
 }  // namespace stts
+
+#include "adain_block.hip.h"
+#include "flow.hip.h"
+#include "vocoder.hip.h"
+#include "frame_path.hip.h"
 
 #include "phoneme_model.hip.h"

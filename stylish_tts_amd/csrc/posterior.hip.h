@@ -1,6 +1,6 @@
 // The posterior encoder (models/flow.py:234-293): recording -> STFT -> pre_spec | pre_phase -> 12-layer WaveNet (flow.py:17-88, k = 3) ->
 // proj_mean | proj_logstd -> z = mean + noise * exp(logstd) [-> post_flow].  Component STTS_W_POSTERIOR, keys "speech_predictor.posterior_encoder.*".
-// Included by api.hip after model.hip.h (context, packers, contraction launchers, harmonic stage).  plan_posterior() chooses the WaveNet form of a
+// Included by api.hip after model.hip.h (context, packers, contraction launchers; vocoder.hip.h: launch_stft).  plan_posterior() chooses the WaveNet form of a
 // call, posterior_forward() walks the stage.  fp32 whatever the engine's precision.
 //
 // wn_post_kernel<RT, LAST>: one WaveNet layer in one launch, the structure of wn_fused_kernel's direct form (wn_fused.hip.h, M = 1) with TAPS = 3, PAD = 1 and
@@ -430,13 +430,7 @@ inline int posterior_forward(stts_ctx* c, hipStream_t st, const Seg& s, const Po
                  s.host[u + 1] - s.host[u], g.n_fft / 2);
   const PostPlan plan = plan_posterior(c, s);
   // 1. STFT of the recording, the last frame dropped (flow.py:283-286): the harmonic stage's kernels on `audio`
-  if (io.audio) {
-    if (g.generic) STTS_TRY(launch_stft_geom(st, g, s.n_utt, s.dev, R, ml, io.audio, c->hann, c->twiddle64, io.har_spec, io.har_phase, io.ld_har, 0));
-    else
-      STTS_LAUNCH_PROF("stft_kernel", (size_t)R * (kHop + 2 * kBins) * 4, stft_kernel, dim3((ml + kFftWaves - 1) / kFftWaves, s.n_utt), dim3(64 * kFftWaves), st, io.audio, s.dev,
-                       c->hann, c->twiddle64, io.har_spec, io.har_phase, io.ld_har, 0);
-    STTS_HIP(hipGetLastError());
-  }
+  if (io.audio) STTS_TRY(launch_stft(c, st, s, io.audio, io.har_spec, io.har_phase, io.ld_har, 0));
   // 2. x0 = cat[pre_spec(har_spec), pre_phase(har_phase)] (flow.py:288): two contractions into the column halves of one buffer
   for (int q = 0; q < 2; ++q) {
     const PackedConv& w = q == 0 ? P.pre_spec : P.pre_phase;

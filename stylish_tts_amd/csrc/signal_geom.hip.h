@@ -356,7 +356,7 @@ inline void signal_tables(int n_fft, int win, std::vector<float>* hann, std::vec
   for (int i = 0; i < n_fft / 2; ++i) (*tw64)[i] = make_double2(cos(2.0 * M_PI * i / n_fft), -sin(2.0 * M_PI * i / n_fft));
 }
 
-// launchers of the run-time-geometry path (the same stream / argument conventions as the specialised launches in model.hip.h)
+// launchers of the run-time-geometry path (the same stream / argument conventions as the specialised launches in vocoder.hip.h)
 // (utterances: n_utt, device row offsets seg, R rows in all, the longest ml rows)
 inline int launch_pcph_geom(hipStream_t st, const SignalGeom& g, int n_utt, const int* seg, long R, int ml, const float* pitch, const float* noise,
                             const float* init_phase, int batch_scope, double* prefix, float* stats, float* sig, int* err) {

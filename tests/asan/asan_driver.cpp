@@ -17,6 +17,8 @@
 // split-accumulate and couple epilogues.
 // The AdaptiveDecoderBlock chains the same way: `blocktrace <precision> <case> <switches> : <trace>` per case of block_section below, in all four precisions;
 // `asan_driver <weights> block` prints those lines only (fp32 and bf16), for one process per setting of the block's process-wide switches.
+// The vocoder and the frame path the same way: `frametrace <precision> <call>_<rows> <switches> : <workspace bytes> | <launches on the caller's stream>+<on any other> | <trace>`
+// per case of frametrace_section below, in every precision the frame path is walked in.
 // `asan_driver <weights> gemm` prints the gemmtrace lines only (no finalize): the STTS_* switches of the contractions are read once per process, so
 // tests/asan/build_and_run.py starts one process per setting.
 #include <algorithm>
@@ -35,6 +37,7 @@ extern "C" long stts_stub_launch_count();
 extern "C" uint64_t stts_stub_digest();
 extern "C" void stts_stub_trace_begin();
 extern "C" const char* stts_stub_trace_end();
+extern "C" long stts_stub_trace_side_count();
 
 #define CK(expr)                                                                  \
   do {                                                                            \
@@ -126,6 +129,48 @@ static int frame_case(stts_ctx* c, const std::vector<int>& lens, const char* wha
   launchtrace(what, stts_stub_trace_end());
   printf("  %-44s rows %8ld  workspace %8.1f MB  %ld launches per frame-path call\n", what, R, wsb / 1048576.0, fused);
   return 0;
+}
+
+// One stts_frame_path call and one stts_vocoder_forward call over utterances of `lens` rows, each traced on its own:
+// `frametrace <precision> <call>_<rows> <switches> : <stts_frame_workspace_bytes> | <launches on the caller's (null) stream>+<launches on any other stream> | <trace>`.
+// switches: "-" or "STTS_NO_SIDE_STREAM=1" (read per call).  The shapes sit on the two thresholds of the frame path and the vocoder: 3 000 rows (the side
+// stream of the source -> STFT -> prior-conv chain, fp32) and 3 840 rows (16-bit rows in the 16-bit modes).
+static int frametrace_case(stts_ctx* c, const std::vector<int>& lens, const char* switches) {
+  const int n = (int)lens.size();
+  const std::vector<int32_t> off = offsets(lens);
+  const long R = off[n];
+  const int ml = *std::max_element(lens.begin(), lens.end());
+  const size_t wsb = stts_frame_workspace_bytes(c, R, n, ml);
+  std::vector<char> ws(wsb);
+  auto asr = buf(R * 128), pitch = buf(R), energy = buf(R), style = buf((size_t)n * 64), pn = buf(R * 128), sn = buf(R * 75), ph = buf(1), audio = buf(R * 75);
+  auto mel = buf(R * 512), hs = buf(R * 1088), hp = buf(R * 1088);
+  unsetenv("STTS_NO_SIDE_STREAM");
+  if (strcmp(switches, "-") != 0) setenv("STTS_NO_SIDE_STREAM", strchr(switches, '=') + 1, 1);
+  auto line = [&](const char* call, long launched) {
+    const char* trace = stts_stub_trace_end();  // (the counts are read after the trace has ended and before the next one begins)
+    const long side = stts_stub_trace_side_count();
+    printf("frametrace %d %s_%ld %s : %zu | %ld+%ld | %s\n", g_prec, call, R, switches, wsb, launched - side, side, trace);
+  };
+  stts_stub_trace_begin();
+  long before = stts_stub_launch_count();
+  int rc = stts_frame_path(c, nullptr, n, off.data(), off.data(), asr.data(), 128, pitch.data(), energy.data(), style.data(), pn.data(), sn.data(), ph.data(), 0,
+                           audio.data(), ws.data(), wsb, 0);
+  line("frame_path", stts_stub_launch_count() - before);
+  if (rc == 0) {
+    stts_stub_trace_begin();
+    before = stts_stub_launch_count();
+    rc = stts_vocoder_forward(c, nullptr, n, off.data(), off.data(), mel.data(), 512, style.data(), hs.data(), hp.data(), 1088, audio.data(), nullptr, nullptr, 0,
+                              ws.data(), wsb);
+    line("vocoder_forward", stts_stub_launch_count() - before);
+  }
+  unsetenv("STTS_NO_SIDE_STREAM");
+  if (rc != 0) fprintf(stderr, "FAILED frametrace %ld rows %s: %s\n", R, switches, stts_last_error());
+  return rc != 0;
+}
+static int frametrace_section(stts_ctx* c) {
+  for (const char* sw : {"-", "STTS_NO_SIDE_STREAM=1"})
+    if (frametrace_case(c, {1000, 1000, 1000}, sw) || frametrace_case(c, {1000, 1000, 1001}, sw)) return 1;
+  return frametrace_case(c, {1280, 1280, 1279}, "-") || frametrace_case(c, {1280, 1280, 1280}, "-");
 }
 
 // One stts_prior_flow_forward call under `switches` ("NAME=value,NAME=value" or "-"; every other STTS_WN_* switch unset), traced.  want_z: pass a
@@ -987,6 +1032,7 @@ int main(int argc, char** argv) {
         if (frame_case(c, lens, "cfg4: 256 utterances of 0.25-10 s")) return 1;
       }
       if (frame_case(c, std::vector<int>(64, 3200), "cfg5 per GPU: 64 x 10 s")) return 1;
+      if (frametrace_section(c)) return 1;
       if (phoneme_case(c, std::vector<int>(64, 50), std::vector<int>(64, 240), "cfg3: 64 x 50 tokens")) return 1;
       if (phoneme_case(c, {510, 2, 160}, {1020, 4, 800}, "token-count extremes")) return 1;
       // skewed batches: the per-utterance statistics buffers grow with (utterances x longest utterance).  256 utterances, one of 4 000 frames; and 24 with

@@ -6,6 +6,8 @@
 // Device allocations are zero-filled and recorded, so that stts_stub_digest() can say what the packers wrote.
 // Between stts_stub_trace_begin() and stts_stub_trace_end() every launch is also written down by name (the device name
 // __hipRegisterFunction was given for the host handle, demangled), grid and block: which kernels the launch planning chose, as text.
+// stts_stub_trace_side_count(): how many launches of the trace went to a stream other than the null one (the driver's caller stream is null, so these
+// are the launches the library put on a stream of its own).
 #include <hip/hip_runtime.h>
 
 #include <cxxabi.h>
@@ -66,7 +68,7 @@ static std::string short_name(const char* mangled) {
 static struct {
   bool on = false;
   std::string text, last;
-  long run = 0;
+  long run = 0, side = 0;
   void flush() {
     if (run) text += (text.empty() ? "" : " | ") + std::to_string(run) + "x " + last;
     run = 0;
@@ -75,8 +77,9 @@ static struct {
 extern "C" void stts_stub_trace_begin() {
   g_trace.on = true;
   g_trace.text.clear();
-  g_trace.run = 0;
+  g_trace.run = g_trace.side = 0;
 }
+extern "C" long stts_stub_trace_side_count() { return g_trace.side; }
 extern "C" const char* stts_stub_trace_end() {
   g_trace.flush();
   g_trace.on = false;
@@ -164,7 +167,7 @@ hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) {
   *ms = 0.001f;
   return hipSuccess;
 }
-hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void**, size_t, hipStream_t) {
+hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void**, size_t, hipStream_t st) {
   // what a real launch would reject
   if (grid.x == 0 || grid.y == 0 || grid.z == 0 || block.x * block.y * block.z == 0 || block.x * block.y * block.z > 1024 || grid.y > 65535 || grid.z > 65535) {
     fprintf(stderr, "hip_stub: invalid launch configuration grid (%u,%u,%u) block (%u,%u,%u)\n", grid.x, grid.y, grid.z, block.x, block.y, block.z);
@@ -179,6 +182,7 @@ hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void**, size_t,
     if (entry != g_trace.last) g_trace.flush();
     g_trace.last = entry;
     ++g_trace.run;
+    g_trace.side += st != nullptr;
   }
   return hipSuccess;
 }

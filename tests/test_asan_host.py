@@ -30,7 +30,12 @@ same shape.  build_and_run.py repeats the gemmtrace cases under each experiment 
 And for the AdaptiveDecoderBlock chains (csrc/adain_block.hip.h plan_adain_chain / plan_adain_block): `blocktrace <precision> <case> <switches> : <trace>` of the decoder, the
 frame path, the pitch/energy predictors and stts_op_adain_block on the batch shapes around every threshold of the plan (2 500 rows fold -> Winograd, 96 .. 384 bridge
 blocks, 3 840 / 4 096 rows in the 16-bit modes, 12 000 rows for the side lane), under STTS_ADAIN_BRIDGE (read per call) and, one process per setting, under the block's
-process-wide switches.  The unforced trace must equal the forced one on its side of a threshold and differ from it on the other (check_blocktraces)."""
+process-wide switches.  The unforced trace must equal the forced one on its side of a threshold and differ from it on the other (check_blocktraces).
+
+And for the vocoder and the frame path: `frametrace <precision> <call>_<rows> <switches> : <stts_frame_workspace_bytes> | <launches on the caller's stream>+<launches on
+any other stream> | <trace>` of one stts_frame_path and one stts_vocoder_forward call on the two thresholds this code owns: 3 000 rows against 3 001 (fp32: the source ->
+STFT -> prior-conv chain goes to a side stream above), with and without STTS_NO_SIDE_STREAM (read per call), and 3 839 rows against 3 840 (16-bit rows in the 16-bit
+modes) (check_frametraces)."""
 import os
 import re
 import shutil
@@ -153,6 +158,34 @@ def check_blocktraces(stdout):
     assert len({tuple(sorted(f.items())) for f in per_setting.values()}) == len(per_setting)  # (the settings differ from one another)
 
 
+# frametrace cases: (precision, call_rows, switches); tests/asan/asan_driver.cpp frametrace_section has the shapes
+_NO_SIDE = "STTS_NO_SIDE_STREAM=1"
+FRAME_CASES = ([(p, f"{call}_{rows}", sw) for p in (0, 2) for call in ("frame_path", "vocoder_forward") for rows in (3000, 3001) for sw in ("-", _NO_SIDE)]
+               + [(p, f"{call}_{rows}", "-") for p in (0, 2) for call in ("frame_path", "vocoder_forward") for rows in (3839, 3840)])
+
+
+def check_frametraces(stdout):
+    """The frametrace lines of a driver run: every case there; the side stream taken above 3 000 rows in fp32 only, and not under the switch, with the same kernels in
+    the same order either way; 16-bit rows in the vocoder from 3 840 rows on."""
+    frame = {(int(p), c, sw): (int(b), int(m), int(s), t) for p, c, sw, b, m, s, t in
+             re.findall(r"^frametrace (\d) (\S+) (\S+) : (\d+) \| (\d+)\+(\d+) \| (.*)$", stdout, re.M)}
+    assert sorted(frame) == sorted(FRAME_CASES), sorted(frame)
+    assert not [k for k, v in frame.items() if v[0] == 0 or v[1] == 0 or not v[3].strip()], frame
+    on, below, off = frame[(0, "frame_path_3001", "-")], frame[(0, "frame_path_3000", "-")], frame[(0, "frame_path_3001", _NO_SIDE)]
+    assert on[2] > 0 and below[2] == 0 and off[2] == 0, (on[:3], below[:3], off[:3])
+    assert on[3] == off[3] and on[1] + on[2] == off[1] and on[0] == off[0], (on, off)  # same kernels, same order, same workspace
+    # nothing else leaves the caller's stream: only stts_frame_path, only fp32, only above 3 000 rows
+    assert sorted(k for k, v in frame.items() if v[2]) == [(0, f"frame_path_{rows}", "-") for rows in (3001, 3839, 3840)], frame
+    for k in FRAME_CASES:  # the switch changes nothing else
+        if k[2] == _NO_SIDE and k != (0, "frame_path_3001", _NO_SIDE):
+            assert frame[k] == frame[(k[0], k[1], "-")], k
+    # 3 840 rows: the 16-bit modes run the vocoder on 16-bit rows (mel gets a rounded copy; the prior convs read a rounded copy of the spectra), fp32 does not
+    lo, hi = frame[(2, "vocoder_forward_3839", "-")][3], frame[(2, "vocoder_forward_3840", "-")][3]
+    assert lo != hi and "cast_rows_kernel" in hi and "cast_rows_kernel" not in lo, (lo, hi)
+    assert frame[(2, "frame_path_3839", "-")][3] != frame[(2, "frame_path_3840", "-")][3]
+    assert "cast_rows_kernel" not in frame[(0, "vocoder_forward_3840", "-")][3]
+
+
 LAUNCH_CASES = [(p, c) for p in (0, 2) for c in ("cfg2:_8_x_3_s", "B_=_1_x_3_s", "short_ragged_utterances", "cfg5_per_GPU:_64_x_10_s", "cfg3:_64_x_50_tokens",
                                                  "token-count_extremes")] + [(0, "cfg4:_256_utterances_of_0.25-10_s")]
 
@@ -249,6 +282,7 @@ def test_host_side_under_asan_ubsan(tmp_path):
     refused = [k for k in cfm if k.startswith("refuse_")]
     assert sorted(refused) == ["refuse_elem", "refuse_rms_adaln", "refuse_rope", "refuse_small", "refuse_source"] and all(cfm[k].strip() == "error" for k in refused), cfm
     check_blocktraces(r.stdout)
+    check_frametraces(r.stdout)
     # every switch setting ran every case
     per_setting = {}
     for sw in re.findall(r"^\[(STTS_\w+=\d+)\] gemmtrace ", r.stdout, re.M):

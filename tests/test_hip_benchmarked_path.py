@@ -73,7 +73,7 @@ def test_cfg2_batch8_reproduces_the_reference_waveform(hip, B):
     g = load_golden("frame_path_3s")
     T4 = 960
     s = segs([T4] * B)
-    assert s.rows > 2500  # model.hip.h fold_rows(): the large-batch branches (run_adain_block `fold` off, decoder convs in Winograd form)
+    assert s.rows > 2500  # adain_block.hip.h fold_rows(): the large-batch branches (run_adain_block `fold` off, decoder convs in Winograd form)
     tile_rows = lambda a: dev(np.tile(a, (B, 1)))  # noqa: E731
     asr = tile_rows(synth.normal("g3.asr", (1, 128, T4))[0].T)
     pitch = dev(np.tile(synth.pitch_curve("g3.pitch", 1, T4)[0], B))
@@ -218,7 +218,7 @@ def test_side_stream_equals_single_stream(hip, monkeypatch, lens):
     from stylish_tts_amd import synth
 
     B = len(lens)
-    assert sum(lens) > 3000  # model.hip.h frame_path: side_min_rows
+    assert sum(lens) > 3000  # frame_path.hip.h plan_frame: side_min_rows
     s = segs(lens)
     asr = dev(np.concatenate([synth.normal(f"side.asr{b}", (t, 128)) for b, t in enumerate(lens)]))
     pitch = dev(np.concatenate([synth.pitch_curve(f"side.pitch{b}", 1, t)[0] for b, t in enumerate(lens)]))
@@ -252,7 +252,7 @@ def test_ragged_decoder_on_the_winograd_statistics_path_vs_the_oracle(hip, weigh
     from stylish_tts_amd import synth
 
     lens = [997, 13, 1201, 613, 25]
-    assert sum(lens) > 2500  # model.hip.h fold_rows(): the Winograd branch
+    assert sum(lens) > 2500  # adain_block.hip.h fold_rows(): the Winograd branch
     B = len(lens)
     s = segs(lens)
     asr_h = [synth.normal(f"wst.asr{b}", (t, 128)) for b, t in enumerate(lens)]
