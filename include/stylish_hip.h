@@ -73,7 +73,8 @@ enum {
   STTS_W_RMVPE = 32768,      /* rmvpe.* = the RMVPE pitch extractor E2E0 (finalized by stts_rmvpe_finalize, not part of STTS_W_ALL) train/dataprep/rmvpe/model.py:49-86 */
   STTS_W_ALIGNER = 65536,    /* text_aligner.* = the TDNN CTC aligner (finalized by stts_aligner_finalize, not part of STTS_W_ALL)           train/models/text_aligner.py */
   STTS_W_WAVLM = 131072,     /* wavlm.* = transformers' WavLMModel, the network of the "slm" distance (finalized by stts_wavlm_finalize, not part of STTS_W_ALL) train/losses.py:408-426 */
-  STTS_W_POSTERIOR = 262144  /* speech_predictor.posterior_encoder.* (stts_finalize_weights; not part of STTS_W_ALL)                       models/flow.py:234-293 */
+  STTS_W_POSTERIOR = 262144, /* speech_predictor.posterior_encoder.* (stts_finalize_weights; not part of STTS_W_ALL)                       models/flow.py:234-293 */
+  STTS_W_FLOW_STATS = 524288 /* speech_predictor.flow.flows.* + prior_encoder.* packed again in fp32 for the flow statistics (stts_finalize_weights; not part of STTS_W_ALL) */
 };
 int stts_finalize_weights(stts_ctx* ctx, int which);
 /* Operand precision of the FRAME-RATE Conv1d / Linear contractions (call before the first stts_finalize_weights).
@@ -174,6 +175,36 @@ int stts_posterior_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t
 /* Workspace stts_posterior_forward accepts for `rows` rows in `n_utt` utterances, the longest having `max_len` (a dry run of its own carving;
  * 0 before STTS_W_POSTERIOR is finalized). */
 size_t stts_posterior_workspace_bytes(const stts_ctx* ctx, int64_t rows, int n_utt, int max_len);
+
+/* Flow statistics: ResidualCouplingBlock.forward in both directions with the reference's three streams (models/flow.py:132-151, :196-218), the
+ * prior with its three outputs (:311-315) and the sums behind kl_text / kl_audio (train/losses.py:157-222).  Component STTS_W_FLOW_STATS packs
+ * its own fp32 copy of the already loaded keys "speech_predictor.flow.flows.{0,2,..,14}.*" (either weight-norm flavour) and
+ * "speech_predictor.prior_encoder.*"; it may be finalized alone, before or after STTS_W_FLOW, with the same results bit for bit, and is fp32
+ * whatever stts_set_precision says (validation numbers).
+ *   z_in / mean_in / logstd_in [rows,128], style [n_utt,64] -> z_out / mean_out / logstd_out [rows,128] (other buffers than the inputs).
+ *   reverse 0: layers 0 .. 7, each followed by a Flip:   z1 = m + z1 exp(s),    mean1 = m + mean1 exp(s),    logstd1 += s
+ *   reverse 1: Flip, layer 7, ..., Flip, layer 0:        z1 = (z1 - m) exp(-s), mean1 = (mean1 - m) exp(-s), logstd1 -= s
+ *   with m, s = proj_mean, proj_logstd of the WaveNet's output on the z stream's other half.  Layer f reads half f & 1 and updates the other; the
+ *   half it reads leaves the layer bit-identical; after eight layers the halves are in their natural order.
+ * Utterances are ragged and packed, each its own sequence with zero padding at its ends (the reference at B = 1, z_mask = 1).  Refused with
+ * stts_last_error set and nothing launched: capacity segments (seg_flags must be 0), a small workspace, outputs that alias inputs, a missing component.
+ * A coupling layer runs as plain contractions and one row kernel for the coupling (the generic form, any width) or as wn_stats_kernel, one fused launch
+ * per WaveNet layer (width 128); STTS_FSTAT_WN (read per call) = 0 | 16 | 32 | 64 forces the generic form or the fused one on that block height. */
+int stts_flow_stats_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, int reverse, const float* z_in,
+                            const float* mean_in, const float* logstd_in, const float* style, float* z_out, float* mean_out, float* logstd_out, void* ws,
+                            size_t ws_bytes, int seg_flags);
+/* Workspace stts_flow_stats_forward accepts (a dry run of its own carving, exact: one byte less is refused; 0 before STTS_W_FLOW_STATS is finalized). */
+size_t stts_flow_stats_workspace_bytes(const stts_ctx* ctx, int64_t rows, int n_utt, int max_len);
+/* PriorEncoder.forward with all three outputs: x [rows, ld_x >= 512] (the decoder's output), noise [rows,128] ~ N(0,1) -> mean_out, logstd_out and
+ * z_out = mean + noise exp(logstd), each [rows,128].  Needs no workspace.  Refusals as above, and an ld_x that does not cover the packed input width. */
+int stts_prior_stats_forward(stts_ctx* ctx, void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, const float* x, int ld_x,
+                             const float* noise, float* z_out, float* mean_out, float* logstd_out, void* ws, size_t ws_bytes, int seg_flags);
+/* sums[u] (device double [n_utt]) = utterance u's sum over rows and the C channels of the KL term, accumulated in fp64 from the fp32 rows [rows, ld]
+ * on, in a fixed order, no atomics.  kind 0 = kl_loss(z_p = a, logs_q = b, m_p = c, logs_p = d): d - b - 0.5 + 0.5 (a - c)^2 exp(-2 d); kind 1 =
+ * kl_loss_normal(m_q = a, ...): d - b - 0.5 + 0.5 (exp(2 b) + (a - c)^2) exp(-2 d).  The reference's score is sum(sums) / rows (its mask sums to
+ * B T, not B T C).  ws: rows doubles (rounded up to 256 bytes). */
+int stts_val_kl_sums(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, int kind, const float* a, const float* b,
+                     const float* c, const float* d, int ld, int C, double* sums, void* ws, size_t ws_bytes);
 
 /* Utterance offsets of a frame-rate call may be CAPACITY SEGMENTS (seg_flags & STTS_SEG_CAPACITY): the host array then holds
  * upper bounds (cumulative capacities - every buffer, workspace and grid is sized by them), the device array the real offsets,
@@ -972,6 +1003,13 @@ int stts_op_istft_geom(void* stream, int n_utt, const int32_t* seg_off_host, con
 int stts_op_posterior_layer(stts_ctx* ctx, void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, int layer, int form,
                             int out_acc, const float* h_in, const float* out_in, const float* cond, int ld_cond, float* h_out, float* out_out,
                             void* ws, size_t ws_bytes);
+/* Coupling layer `layer` of the flow statistics (STTS_W_FLOW_STATS) alone, in the direction `reverse`: three streams [rows,128] and style [n_utt,64]
+ * in, three streams out (other buffers).  form: 0 = the generic form, 16 | 32 | 64 = wn_stats_kernel on that block height.  h0_out [rows,128]: the next
+ * coupling layer's h_0 = pre(z') where the form produces it (a fused form, and a next layer exists: f + 1 forward, f - 1 in reverse); otherwise left
+ * untouched (may be NULL).  ws: stts_flow_stats_workspace_bytes. */
+int stts_op_flow_stats_layer(stts_ctx* ctx, void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, int layer, int reverse, int form,
+                             const float* z_in, const float* mean_in, const float* logstd_in, const float* style, float* z_out, float* mean_out,
+                             float* logstd_out, float* h0_out, void* ws, size_t ws_bytes);
 /* Tuning aid (tools/gemm_bench.py): average time of `iters` back-to-back contraction launches on synthetic data.
  * tile: 0 = the launcher's own choice; tune bits: 128 bf16 operands, 256 fp16 operands; only in a library built with
  * -DSTTS_GEMM_TRACE: 2/4/8/16 K-loop ablations (results invalid, timing only), 64 block-timeline trace. */

@@ -190,6 +190,10 @@ SIGNATURES = {
     "stts_frame_path": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _SZ, _I]),
     "stts_posterior_forward": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _SZ, _I]),
     "stts_posterior_workspace_bytes": (_SZ, [_P, _I64, _I, _I]),
+    "stts_flow_stats_forward": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I]),
+    "stts_flow_stats_workspace_bytes": (_SZ, [_P, _I64, _I, _I]),
+    "stts_prior_stats_forward": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _I]),
+    "stts_val_kl_sums": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _SZ]),
     "stts_frame_offsets": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "stts_phoneme_workspace_bytes": (_SZ, [_P, _I64, _I64, _I, _I, _I]),
     "stts_text_encoder_forward": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _P, _SZ]),
@@ -288,6 +292,7 @@ TEST_SIGNATURES = {
     "stts_op_stft_geom": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I]),
     "stts_op_istft_geom": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _I]),
     "stts_op_posterior_layer": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _SZ]),
+    "stts_op_flow_stats_layer": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ]),
 }
 
 _lib = None

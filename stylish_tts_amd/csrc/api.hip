@@ -17,6 +17,10 @@
 
 using namespace stts;
 
+namespace stts {
+int finalize_flow_stats_component(stts_ctx* c);  // flow_stats.hip.h is included at the end of this file (its kernels are the code object's last)
+}
+
 #define API_BEGIN try {
 #define API_END                                                         \
   }                                                                     \
@@ -142,6 +146,7 @@ int stts_finalize_weights(stts_ctx* c, int which) {
     STTS_TRY(finalize_posterior(c, static_cast<PostW*>(c->posterior.get())));
     c->ready |= STTS_W_POSTERIOR;
   }
+  if (which & STTS_W_FLOW_STATS) STTS_TRY(finalize_flow_stats_component(c));
   STTS_HIP(hipDeviceSynchronize());
   return 0;
   API_END
@@ -1415,3 +1420,112 @@ int stts_op_posterior_layer(stts_ctx* c, void* stream, int n_utt, const int32_t*
 #ifdef STTS_TEST_OPS  // single-layer test operators + the contraction micro-benchmark (not part of the product surface)
 #include "test_ops.hip.h"
 #endif
+
+// ------------------------------------------------------------------------------------------------ flow statistics (flow_stats.hip.h)
+#include "flow_stats.hip.h"
+
+namespace stts {
+int finalize_flow_stats_component(stts_ctx* c) {
+  if (!c->flow_stats) c->flow_stats = std::make_shared<FStatW>();
+  // fp32 whatever the precision; the contractions in the split-fp32 form where the engine allows it
+  PackScope scope(c, {PREC_F32, true, 32, STTS_W_FLOW_STATS});
+  STTS_TRY(finalize_flow_stats(c, static_cast<FStatW*>(c->flow_stats.get())));
+  c->ready |= STTS_W_FLOW_STATS;
+  return 0;
+}
+}  // namespace stts
+
+extern "C" {
+
+size_t stts_flow_stats_workspace_bytes(const stts_ctx* c, int64_t rows, int n_utt, int max_len) {
+  if (!c || !c->flow_stats || !(c->ready & STTS_W_FLOW_STATS) || rows <= 0 || n_utt <= 0) return 0;
+  const SynthSeg syn(rows, n_utt, max_len);
+  // exactly what the stage carves (dry_run_bytes adds 4 KiB of slack for stages whose sub-arenas round on their own; this one carves from one arena,
+  // every piece a multiple of 256 bytes): one byte less is refused
+  return dry_run_bytes([&](Arena a) {
+    FStatIO io{};
+    (void)flow_stats_forward(const_cast<stts_ctx*>(c), nullptr, syn.seg(), io, a);
+  }) - 4096;
+}
+
+int stts_flow_stats_forward(stts_ctx* c, void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, int reverse, const float* z_in,
+                            const float* mean_in, const float* logstd_in, const float* style, float* z_out, float* mean_out, float* logstd_out, void* ws, size_t ws_bytes,
+                            int seg_flags) {
+  API_BEGIN
+  READY_CHECK(c->flow_stats, STTS_W_FLOW_STATS);
+  STTS_TRY(seg_ok(n_utt, seg_off_host, seg_off_dev));
+  Seg s{n_utt, seg_off_host, seg_off_dev};
+  s.cap = (seg_flags & STTS_SEG_CAPACITY) != 0;
+  const FStatIO io{reverse, z_in, mean_in, logstd_in, style, z_out, mean_out, logstd_out};
+  STTS_TRY(flow_stats_check(c, s, io));
+  Arena a(ws, ws_bytes);
+  return flow_stats_forward(c, st, s, io, a);
+  API_END
+}
+
+int stts_prior_stats_forward(stts_ctx* c, void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, const float* x, int ld_x, const float* noise,
+                             float* z_out, float* mean_out, float* logstd_out, void* ws, size_t ws_bytes, int seg_flags) {
+  API_BEGIN
+  READY_CHECK(c->flow_stats, STTS_W_FLOW_STATS);
+  STTS_TRY(seg_ok(n_utt, seg_off_host, seg_off_dev));
+  Seg s{n_utt, seg_off_host, seg_off_dev};
+  STTS_CHECK(!(seg_flags & STTS_SEG_CAPACITY), "the flow statistics take plain segments (no STTS_SEG_CAPACITY)");
+  const FStatW& P = *static_cast<const FStatW*>(c->flow_stats.get());
+  STTS_CHECK(x && noise && z_out && mean_out && logstd_out, "prior_stats_forward: null argument");
+  STTS_CHECK(ld_x % 4 == 0 && ld_x >= P.in_ch, "prior_stats_forward: ld_x %d must be a multiple of 4 covering the %d columns the packer built", ld_x, P.in_ch);
+  for (const void* ptr : {(const void*)x, (const void*)noise, (const void*)z_out, (const void*)mean_out, (const void*)logstd_out})
+    STTS_CHECK((uintptr_t)ptr % 16 == 0, "prior_stats_forward: buffers must be 16-byte aligned");
+  Arena a(ws, ws_bytes);
+  return prior_stats_forward(c, st, s, x, ld_x, noise, z_out, mean_out, logstd_out, a);
+  API_END
+}
+
+int stts_val_kl_sums(stts_ctx* c, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, int kind, const float* a, const float* b, const float* cc,
+                     const float* d, int ld, int C, double* sums, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  STTS_CHECK(c, "null ctx");
+  STTS_HIP(hipSetDevice(c->device));
+  STTS_TRY(seg_ok(n_utt, off_host, off_dev));
+  STTS_CHECK(kind == 0 || kind == 1, "val_kl_sums: kind must be 0 (kl_loss) or 1 (kl_loss_normal)");
+  STTS_CHECK(a && b && cc && d && sums, "val_kl_sums: null argument");
+  STTS_CHECK(C > 0 && ld >= C, "val_kl_sums: ld %d < C %d", ld, C);
+  const Seg s{n_utt, off_host, off_dev};
+  Arena ar(ws, ws_bytes);
+  return val_kl_sums((hipStream_t)stream, s, kind, a, b, cc, d, ld, C, sums, ar);
+  API_END
+}
+
+#ifdef STTS_TEST_OPS
+int stts_op_flow_stats_layer(stts_ctx* c, void* stream, int n_utt, const int32_t* seg_off_host, const int32_t* seg_off_dev, int layer, int reverse, int form,
+                             const float* z_in, const float* mean_in, const float* logstd_in, const float* style, float* z_out, float* mean_out, float* logstd_out,
+                             float* h0_out, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  READY_CHECK(c->flow_stats, STTS_W_FLOW_STATS);
+  STTS_TRY(seg_ok(n_utt, seg_off_host, seg_off_dev));
+  const Seg s{n_utt, seg_off_host, seg_off_dev};
+  const FStatW& P = *static_cast<const FStatW*>(c->flow_stats.get());
+  STTS_CHECK(layer >= 0 && layer < 8, "op_flow_stats_layer: layer %d of 8", layer);
+  STTS_CHECK(form == 0 || ((form == 16 || form == 32 || form == 64) && P.fused), "op_flow_stats_layer: form %d is not built for this flow", form);
+  const FStatIO io{reverse, z_in, mean_in, logstd_in, style, z_out, mean_out, logstd_out};
+  STTS_TRY(flow_stats_check(c, s, io));
+  STTS_CHECK(!h0_out || (uintptr_t)h0_out % 16 == 0, "op_flow_stats_layer: buffers must be 16-byte aligned");
+  Arena a(ws, ws_bytes);
+  const FStatBufs b = flow_stats_carve(P, s, a);
+  STTS_CHECK(a.ok, "op_flow_stats_layer: workspace too small");
+  const size_t bytes = (size_t)s.rows() * P.fh * sizeof(float);
+  STTS_HIP(hipMemcpyAsync(z_out, z_in, bytes, hipMemcpyDeviceToDevice, st));
+  STTS_HIP(hipMemcpyAsync(mean_out, mean_in, bytes, hipMemcpyDeviceToDevice, st));
+  STTS_HIP(hipMemcpyAsync(logstd_out, logstd_in, bytes, hipMemcpyDeviceToDevice, st));
+  STTS_TRY(run_style(st, P.cond, style, n_utt, b.cond));
+  if (form == 0) return flow_stats_layer(st, s, P, layer, reverse, z_out, mean_out, logstd_out, b);  // (runs its own `pre`; hands back no next h_0)
+  const int next = reverse ? layer - 1 : (layer < 7 ? layer + 1 : -1);
+  float* h = b.hf;
+  STTS_TRY(flow_stats_pre(st, s, P, layer, z_out, h));
+  STTS_TRY(flow_stats_layer_fused(st, s, P, form, layer, next, reverse, z_out, mean_out, logstd_out, b, &h));
+  if (next >= 0 && h0_out) STTS_HIP(hipMemcpyAsync(h0_out, h, bytes, hipMemcpyDeviceToDevice, st));
+  return 0;
+  API_END
+}
+#endif
+
+}  // extern "C"

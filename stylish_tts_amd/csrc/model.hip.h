@@ -210,6 +210,7 @@ struct stts_ctx {
   std::shared_ptr<void> aligner;    // stts::AlW (aligner.hip.h)
   std::shared_ptr<void> wavlm;      // stts::WavlmW (wavlm.hip.h)
   std::shared_ptr<void> posterior;  // stts::PostW (posterior.hip.h)
+  std::shared_ptr<void> flow_stats; // stts::FStatW (flow_stats.hip.h)
   // log-mel front end (log_mel.hip.h): window, twiddles and mel filters per (n_fft, win_length, n_mels, sample_rate), context lifetime
   std::map<std::array<int, 4>, std::shared_ptr<void>> log_mel;  // stts::LogMelTables
   std::mutex log_mel_mu;

@@ -54,6 +54,7 @@ W_RMVPE = 32768  # rmvpe.* (RmvpePitchExtractor; finalized by stts_rmvpe_finaliz
 W_ALIGNER = 65536  # text_aligner.* (TextAligner; finalized by stts_aligner_finalize)
 W_WAVLM = 131072  # wavlm.* (WavLM; finalized by stts_wavlm_finalize)
 W_POSTERIOR = 262144  # speech_predictor.posterior_encoder.* (PosteriorEncoder; outside STTS_W_ALL)
+W_FLOW_STATS = 524288  # speech_predictor.flow.* + prior_encoder.* packed again in fp32 for the flow statistics (outside STTS_W_ALL)
 
 _ENGINES: Dict[int, HipModel] = {}
 
@@ -74,7 +75,7 @@ class FlowStatistics(NamedTuple):
 
 
 class DecoderPrediction:
-    """utils.py:363-382 (inference fields; copy-synthesis fills mel_stats)."""
+    """utils.py:363-382 (inference fields; copy-synthesis fills mel_stats, and with flow_stats=True the other three statistics)."""
 
     def __init__(self, *, audio, magnitude, phase):
         self.audio, self.magnitude, self.phase = audio, magnitude, phase
@@ -448,8 +449,25 @@ class SpeechPredictor(HipModule):
             self.attach_posterior(pe)
         return res
 
-    def _resynthesize(self, texts, text_lengths, alignment, pitch, energy, audio_gt, noise):
-        """forward(audio_gt=...): text encoder + style -> posterior(audio_gt | style) -> post_flow -> harmonic source + vocoder."""
+    def _bind(self):
+        eng = self._engine
+        owners = eng.__dict__.setdefault("_owners", {})
+        bits = [1 << i for i in range(self.components.bit_length()) if self.components >> i & 1]
+        rebinding = self._dirty or any(owners.get(b) is not self for b in bits)
+        super()._bind()
+        if rebinding:  # the flow statistics' packing is of the weights loaded before: packed again on their next use
+            owners.pop(W_FLOW_STATS, None)
+
+    def _bind_flow_stats(self, eng: HipModel):
+        """W_FLOW_STATS is finalized lazily, on the first forward(flow_stats=True) after this shim's weights were (re)bound."""
+        owners = eng.__dict__.setdefault("_owners", {})
+        if owners.get(W_FLOW_STATS) is not self:
+            eng.finalize(W_FLOW_STATS)
+            owners[W_FLOW_STATS] = self
+
+    def _resynthesize(self, texts, text_lengths, alignment, pitch, energy, audio_gt, noise, flow_stats=False):
+        """forward(audio_gt=...): text encoder + style -> posterior(audio_gt | style) -> post_flow -> harmonic source + vocoder.  flow_stats: also
+        decoder -> prior (text_stats) -> reverse flow (text2mel_stats), and the forward flow of the posterior's statistics (mel2text_stats)."""
         eng = self.engine
         pe = self._posterior
         if pe._engine is None:
@@ -458,9 +476,9 @@ class SpeechPredictor(HipModule):
             raise RuntimeError("forward(audio_gt=...): the attached PosteriorEncoder is bound to another engine than this SpeechPredictor; build it with engine=<the "
                                "speech predictor's engine> (or with none)")
         pe.engine  # noqa: B018 - binds (packs) the posterior's weights
-        # `energy` is not read: in the reference it feeds the decoder, which this path does not run (the vocoder takes mel, style and pitch)
+        # `energy` is read with flow_stats only: it feeds the decoder, which copy-synthesis alone does not run (the vocoder takes mel, style and pitch)
         toks, sp = _pack_tokens(texts, text_lengths, eng.device)
-        _, T = _durations_from_alignment(alignment, sp.lengths, eng.device)
+        dur, T = _durations_from_alignment(alignment, sp.lengths, eng.device)
         st = Segments(T, eng.device)
         st4 = st.scaled(4)
         B = sp.n
@@ -486,30 +504,49 @@ class SpeechPredictor(HipModule):
         o = eng.posterior(st4, audio=wave, style=style, noise=qn_tm, mel=True)
         spec, phase = eng.harmonic_stft(st4, p4, sn_flat, ip, batch_scope=True)
         audio, la, ph = eng.vocoder(st4, o["mel"], style, spec, phase, return_spec=True)
+        stats = dict(mel_stats=o)
+        if flow_stats:
+            if "prior_noise" not in nz:
+                raise ValueError("forward(flow_stats=True): the noise dict needs prior_noise [B, 128, 4 T] (the prior's draw) next to posterior_noise")
+            self._bind_flow_stats(eng)
+            pn = _f(torch.as_tensor(nz["prior_noise"]), eng.device)
+            pn_tm = torch.cat([pn[b, :, : 4 * T[b]].t() for b in range(B)]).contiguous()
+            asr = eng.length_regulate(sp, st4, dur, 4, enc, self.cfg.inter_dim)
+            x = eng.decoder(st4, asr, p4, eng.upsample4(st, st4, pk(energy)), style)
+            text = eng.prior_stats(st4, x, pn_tm)
+            stats.update(text_stats=text, text2mel_stats=eng.flow_stats(st4, text["z"], text["mean"], text["logstd"], style, reverse=True),
+                         mel2text_stats=eng.flow_stats(st4, o["z"], o["mean"], o["logstd"], style, reverse=False))
         eng.check_status()
         if len(set(T)) == 1:
             T4 = 4 * T[0]
             rep = lambda t: torch.cat([t, t[:, :, -1:]], dim=2)  # noqa: E731
             pred = DecoderPrediction(audio=audio.reshape(B, 1, h * T4), magnitude=rep(eng.to_channel_major(la, B, nb, T4)),
                                      phase=rep(eng.to_channel_major(ph, B, nb, T4)))
-            pred.mel_stats = FlowStatistics(*(eng.to_channel_major(o[k], B, fh, T4) for k in ("z", "mean", "logstd")))
+            for name, d in stats.items():
+                setattr(pred, name, FlowStatistics(*(eng.to_channel_major(d[k], B, fh, T4) for k in ("z", "mean", "logstd"))))
             return pred
         pred = DecoderPrediction(audio=[audio[h * st4.host[b] : h * st4.host[b + 1]] for b in range(B)], magnitude=None, phase=None)
         rows = lambda t, b: t[st4.host[b] : st4.host[b + 1]].t().unsqueeze(0).contiguous()  # noqa: E731
-        pred.mel_stats = [FlowStatistics(*(rows(o[k], b) for k in ("z", "mean", "logstd"))) for b in range(B)]
+        for name, d in stats.items():
+            setattr(pred, name, [FlowStatistics(*(rows(d[k], b) for k in ("z", "mean", "logstd"))) for b in range(B)])
         return pred
 
-    def forward(self, texts, text_lengths, alignment, pitch, energy, audio_gt=None, noise=None, return_spectra=True):
+    def forward(self, texts, text_lengths, alignment, pitch, energy, audio_gt=None, noise=None, return_spectra=True, flow_stats=False):
         """audio_gt (copy-synthesis; [B, 300 T], [B, 1, 300 T] or a list of recordings for a ragged batch) needs a posterior (has_posterior): the
         vocoder then runs on post_flow(z_mel), z_mel ~ q(z | audio_gt, style); decoder and reverse flow are not run.  The prediction carries
         mel_stats = FlowStatistics(z, mean, logstd) (a list per utterance for a ragged batch); text_stats, text2mel_stats and mel2text_stats
-        stay None (they need the decoder, the reverse flow's statistics and the forward flow).  The noise dict then holds posterior_noise
-        [B, 128, 4 T] in place of prior_noise."""
+        stay None.  The noise dict then holds posterior_noise [B, 128, 4 T] in place of prior_noise.
+        flow_stats=True (with audio_gt): additionally the decoder, the prior with its three outputs (noise key prior_noise, next to
+        posterior_noise), the reverse flow of the prior's statistics and the forward flow of the posterior's - all four FlowStatistics of the
+        reference's training forward (speech_predictor.py:99-128), what NormalizingFlowLoss reads.  audio, magnitude, phase and mel_stats are
+        the bits of the flow_stats=False call with the same noise."""
+        if flow_stats and audio_gt is None:
+            raise NotImplementedError("flow_stats=True needs audio_gt: the mel and mel2text statistics come from the posterior encoder of a recording")
         if audio_gt is not None:
             if not self.has_posterior:
                 raise NotImplementedError("audio_gt needs the posterior encoder: load a state_dict that holds the complete posterior_encoder.* set, "
                                           "or attach_posterior(modules.PosteriorEncoder)")
-            return self._resynthesize(texts, text_lengths, alignment, pitch, energy, audio_gt, noise)
+            return self._resynthesize(texts, text_lengths, alignment, pitch, energy, audio_gt, noise, flow_stats)
         eng = self.engine
         toks, sp = _pack_tokens(texts, text_lengths, eng.device)
         dur, T = _durations_from_alignment(alignment, sp.lengths, eng.device)
@@ -540,6 +577,64 @@ class SpeechPredictor(HipModule):
             return DecoderPrediction(audio=audio.reshape(B, 1, h * T4), magnitude=rep(eng.to_channel_major(la, B, nb, T4)),
                                      phase=rep(eng.to_channel_major(ph, B, nb, T4)))
         return DecoderPrediction(audio=[audio[h * st4.host[b] : h * st4.host[b + 1]] for b in range(B)], magnitude=None, phase=None)
+
+
+def _stat_rows(stats, dev):
+    """FlowStatistics of [B, C, T] tensors, or a list of per-utterance ones ([1, C, T_b]) -> ({z, mean, logstd} packed time-major rows, lengths)."""
+    items = stats if isinstance(stats, (list, tuple)) and not isinstance(stats, FlowStatistics) else [stats]
+    lengths = [int(t.z.shape[2]) for t in items for _ in range(t.z.shape[0])]
+    rows = {k: torch.cat([_f(getattr(t, k), dev).transpose(1, 2).reshape(-1, t.z.shape[1]) for t in items]).contiguous() for k in ("z", "mean", "logstd")}
+    return rows, lengths
+
+
+def flow_kl_sums(eng: HipModel, pred):
+    """The sums behind NormalizingFlowLoss's two scores (train/losses.py:205-222) of a prediction that carries all four FlowStatistics
+    -> (device double [2, B]: kl_text, kl_audio per utterance; lengths [B])."""
+    text, L = _stat_rows(pred.text_stats, eng.device)
+    t2m, _ = _stat_rows(pred.text2mel_stats, eng.device)
+    mel, _ = _stat_rows(pred.mel_stats, eng.device)
+    m2t, _ = _stat_rows(pred.mel2text_stats, eng.device)
+    seg = Segments(L, eng.device)
+    return torch.stack([eng.kl_sums(seg, 0, m2t["z"], m2t["logstd"], text["mean"], text["logstd"]),
+                        eng.kl_sums(seg, 1, t2m["mean"], t2m["logstd"], mel["mean"], mel["logstd"])]), L
+
+
+def flow_kl_score(sums, lengths):
+    """host numbers [B] of one score -> (sum / rows: the reference's mask sums to B T, not B T C; every utterance's own value)."""
+    tot = 0.0
+    for v in sums:
+        tot += v
+    return tot / sum(lengths), [v / n for v, n in zip(sums, lengths)]
+
+
+def has_flow_stats(pred) -> bool:
+    return all(getattr(pred, k, None) is not None for k in ("text_stats", "text2mel_stats", "mel_stats", "mel2text_stats"))
+
+
+class NormalizingFlowLoss(torch.nn.Module):
+    """train/losses.py:205-222 as validation numbers: kl_text = kl_loss(z_mel2text, logstd_mel2text, mean_text, logstd_text) and kl_audio =
+    kl_loss_normal(mean_text2mel, logstd_text2mel, mean_mel, logstd_mel) of a prediction from SpeechPredictor.forward(audio_gt=, flow_stats=True),
+    summed in fp64 on the engine (stts_val_kl_sums).  No gradients."""
+
+    def __init__(self, cfg=None, engine: Optional[HipModel] = None):
+        super().__init__()
+        self.cfg, self._engine = cfg, engine
+
+    def scores(self, pred) -> dict:
+        if not has_flow_stats(pred):
+            raise ValueError("NormalizingFlowLoss: the prediction carries no flow statistics (SpeechPredictor.forward(audio_gt=..., flow_stats=True) fills them)")
+        eng = self._engine if self._engine is not None else get_engine(self.cfg)
+        sums, L = flow_kl_sums(eng, pred)
+        host = sums.cpu().tolist()
+        out = {}
+        for name, row in zip(("kl_text", "kl_audio"), host):
+            out[name], out[name + "_utt"] = flow_kl_score(row, L)
+        return out
+
+    def forward(self, pred, log):
+        sc = self.scores(pred)
+        log.add_loss("kl_text", torch.tensor(sc["kl_text"], dtype=torch.float64))
+        log.add_loss("kl_audio", torch.tensor(sc["kl_audio"], dtype=torch.float64))
 
 
 class STFT(torch.nn.Module):

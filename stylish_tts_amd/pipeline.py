@@ -448,10 +448,12 @@ def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, predictio
                  time-major rows (logamp_rows, phase_rows[, Segments]) of ``HipModel.vocoder(return_spec=True)``, whose last row of every utterance is
                  repeated like the reference's replicate padding; phase_terms the three means "phase" adds up
       pitch, energy  smooth_l1_loss (beta 1, mean) of the pairs (predicted, recorded) given as ``pitch`` / ``energy``
+      kl_text, kl_audio  when ``prediction`` carries all four FlowStatistics (SpeechPredictor.forward(audio_gt=, flow_stats=True)): the two scores of
+                 NormalizingFlowLoss (the values of ``modules.NormalizingFlowLoss.scores``); kl_text_utt / kl_audio_utt every utterance's own value
       slm        with ``slm``: a modules.WavLMLoss - the mean absolute difference of WavLM's hidden states of the recordings and the synthesised
                  waveforms (the value of ``slm(audio_gt, audio)``, bit for bit); slm_utt every utterance's own value
     ValueError naming the utterance whose lengths do not agree, or the geometry rule a length breaks."""
-    from .modules import MagPhaseLoss, _magphase_sums, _pack_waves, _wave_batch, magphase_score, mel_score
+    from .modules import MagPhaseLoss, _magphase_sums, _pack_waves, _wave_batch, flow_kl_score, flow_kl_sums, has_flow_stats, magphase_score, mel_score
 
     eng = engine
     pw, Lp = _wave_batch(audio, lengths)
@@ -482,6 +484,10 @@ def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, predictio
             a, b, L = _curve_pair(pair, name)
             parts.append(eng.smooth_l1_sums(Segments(L, eng.device), _pack_waves(eng, a), _pack_waves(eng, b)))  # [len(L)]
             curves.append((name, len(L), sum(L)))
+    kl_len = None
+    if prediction is not None and has_flow_stats(prediction):
+        kl, kl_len = flow_kl_sums(eng, prediction)  # [2, B]
+        parts.append(kl)
     if slm is not None:
         slm.wavlm._engine = slm.wavlm._engine or eng
         s_sums, s_fr = slm.sums(gw, pw)  # [B, states] float64, [B] int32
@@ -500,6 +506,11 @@ def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, predictio
             tot += v
         out[name] = tot / n
         at += n_utt
+    if kl_len is not None:
+        nk = len(kl_len)
+        for j, name in enumerate(("kl_text", "kl_audio")):
+            out[name], out[name + "_utt"] = flow_kl_score(host[at + j * nk : at + (j + 1) * nk], kl_len)
+        at += 2 * nk
     if slm is not None:
         from . import wavlm
 

@@ -247,6 +247,48 @@ class HipModel:
                                                    _ptr(o.get("x0")), _ptr(o.get("wn")), _ptr(ws), ws.numel(), seg.flags))
         return o
 
+    # ------------------------------------------------------------------ flow statistics (needs W_FLOW_STATS)
+    def flow_stats_workspace_bytes(self, seg: Segments) -> int:
+        """What stts_flow_stats_forward carves for this batch (0 before W_FLOW_STATS is finalized)."""
+        return int(self.lib.stts_flow_stats_workspace_bytes(self.ctx, seg.rows, seg.n, seg.max_len))
+
+    def flow_stats(self, seg: Segments, z, mean, logstd, style, reverse: bool):
+        """ResidualCouplingBlock.forward with the three streams (stts_flow_stats_forward): z, mean, logstd [rows, 128], style [n_utt, 64]
+        -> dict z, mean, logstd [rows, 128] (new buffers).  reverse=False is the forward direction (mel -> text), True the reverse one."""
+        o = {k: self._f32(seg.rows, z.shape[1]) for k in ("z", "mean", "logstd")}
+        ws = self._grow(self._ws, self.flow_stats_workspace_bytes(seg))
+        _lib.check(self.lib.stts_flow_stats_forward(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), int(bool(reverse)), _ptr(z), _ptr(mean), _ptr(logstd),
+                                                    _ptr(style), _ptr(o["z"]), _ptr(o["mean"]), _ptr(o["logstd"]), _ptr(ws), ws.numel(), seg.flags))
+        return o
+
+    def prior_stats(self, seg: Segments, x, noise):
+        """PriorEncoder.forward with all three outputs (stts_prior_stats_forward): x [rows, ld >= 512] (the decoder's output), noise [rows, 128]
+        -> dict z = mean + noise exp(logstd), mean, logstd [rows, 128]."""
+        fh = self.cfg.decoder.hidden_dim // 4
+        o = {k: self._f32(seg.rows, fh) for k in ("z", "mean", "logstd")}
+        _lib.check(self.lib.stts_prior_stats_forward(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(x), x.shape[1], _ptr(noise), _ptr(o["z"]),
+                                                     _ptr(o["mean"]), _ptr(o["logstd"]), None, 0, seg.flags))
+        return o
+
+    def kl_sums(self, seg: Segments, kind: int, a, b, c, d):
+        """Per-utterance fp64 sums of the KL term over rows and channels (stts_val_kl_sums) -> device double [n_utt].  kind 0 = kl_loss(z_p=a,
+        logs_q=b, m_p=c, logs_p=d), 1 = kl_loss_normal(m_q=a, ...); the reference's score is sums.sum() / rows."""
+        sums = torch.empty(seg.n, dtype=torch.float64, device=self.device)
+        ws = torch.empty(seg.rows + 32, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.stts_val_kl_sums(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), kind, _ptr(a), _ptr(b), _ptr(c), _ptr(d), a.shape[1], a.shape[1],
+                                             _ptr(sums), _ptr(ws), ws.numel() * 8))
+        return sums
+
+    def op_flow_stats_layer(self, seg: Segments, layer: int, z, mean, logstd, style, reverse: bool, form: int = 0, pad_rows: int = 0):
+        """Coupling layer `layer` of the flow statistics alone (test surface) -> (z', mean', logstd', h0): h0 = the next coupling layer's pre(z') where
+        the form produces it (a fused form with a next layer; NaN otherwise).  form: 0 = plain contractions, 16 | 32 | 64 = wn_stats_kernel on that
+        block height.  pad_rows: canary rows (NaN) behind the outputs."""
+        outs = [torch.full((seg.rows + pad_rows, z.shape[1]), float("nan"), dtype=torch.float32, device=self.device) for _ in range(4)]
+        ws = torch.empty(self.flow_stats_workspace_bytes(seg), dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.stts_op_flow_stats_layer(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), layer, int(bool(reverse)), form, _ptr(z), _ptr(mean),
+                                                     _ptr(logstd), _ptr(style), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]), _ptr(ws), ws.numel()))
+        return tuple(outs)
+
     # ------------------------------------------------------------------ layout bridge + single ops
     def op_posterior_layer(self, seg: Segments, layer: int, h, out, cond, form: int = 0, out_acc: Optional[bool] = None, pad_rows: int = 0):
         """WaveNet layer `layer` of the finalized posterior encoder alone (test surface): h, out [rows, 128], cond [n_utt, ld] -> (h', out').

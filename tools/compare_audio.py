@@ -26,6 +26,9 @@ after the other), ``token_lengths`` [utterances], ``durations`` (mel frames per 
 other); a recording must hold at least hop_length samples per mel frame and is cut to that.  --checkpoint is the reference's accelerate checkpoint
 directory or a packed safetensors file (checkpoint.py) whose speech_predictor holds the posterior_encoder.* keys; ``synthetic`` runs the synthetic
 weights.  With a second file name the resynthesised waveforms are also written there (one flat row; their lengths are printed).
+When JOB.npz also holds ``energy`` (per mel frame, like ``pitch``) the command prints kl_text and kl_audio as well - NormalizingFlowLoss's two scores
+(train/losses.py:205-222) from SpeechPredictor.forward(audio_gt=, flow_stats=True): how well the text prior and the audio posterior of the checkpoint
+meet in latent space, the flow half of the question the mel score leaves open.
 """
 from __future__ import annotations
 
@@ -55,8 +58,28 @@ def utterances(a: np.ndarray, lengths):
     return [row for row in a]
 
 
+def flow_scores(sp, toks, durs, f0, energy, recordings):
+    """kl_text / kl_audio of the batch: the module's training forward on padded tensors (a ragged batch comes back as lists per utterance)."""
+    import torch
+
+    from stylish_tts_amd import modules
+
+    B, P, T = len(toks), max(len(t) for t in toks), max(sum(d) for d in durs)
+    texts, al = torch.zeros(B, P, dtype=torch.int64), torch.zeros(B, P, T)
+    pitch, en = torch.zeros(B, T), torch.zeros(B, T)
+    for b in range(B):
+        texts[b, : len(toks[b])] = torch.tensor(toks[b])
+        t0 = 0
+        for p_, d in enumerate(durs[b]):
+            al[b, p_, t0 : t0 + d] = 1
+            t0 += d
+        pitch[b, :t0], en[b, :t0] = f0[b], energy[b]
+    pred = sp(texts, torch.tensor([len(t) for t in toks]), al, pitch, en, audio_gt=[torch.from_numpy(w) for w in recordings], flow_stats=True)
+    return modules.NormalizingFlowLoss(sp.cfg, engine=sp.engine).scores(pred)
+
+
 def resynthesize(eng, recordings, job, checkpoint):
-    """-> (the recordings cut to their alignments, the resynthesised waveforms), numpy rows."""
+    """-> (the recordings cut to their alignments, the resynthesised waveforms, the KL scores or None), numpy rows."""
     import torch
 
     from stylish_tts_amd import checkpoint as ckpt
@@ -81,7 +104,11 @@ def resynthesize(eng, recordings, job, checkpoint):
     f0 = [torch.from_numpy(np.asarray(job["pitch"][fo[i] : fo[i + 1]], np.float32)) for i in range(len(tl))]
     out = pipeline.Synthesizer(eng).resynthesize(toks, [torch.from_numpy(w) for w in recordings], durs, f0)
     out = [w.cpu().numpy() for w in out]
-    return [r[: w.size] for r, w in zip(recordings, out)], out
+    kl = None
+    if "energy" in job:
+        en = [torch.from_numpy(np.asarray(job["energy"][fo[i] : fo[i + 1]], np.float32)) for i in range(len(tl))]
+        kl = flow_scores(sp, toks, durs, f0, en, recordings)
+    return [r[: w.size] for r, w in zip(recordings, out)], out, kl
 
 
 def main():
@@ -107,7 +134,7 @@ def main():
     A = utterances(np.load(args.a), lengths)
     eng = HipModel(load_model_config(), 0)
     if args.resynth:
-        A, B = resynthesize(eng, A, np.load(args.resynth), args.checkpoint)
+        A, B, kl = resynthesize(eng, A, np.load(args.resynth), args.checkpoint)
         print("resynthesised lengths:", ",".join(str(w.size) for w in B))
         if args.b:
             np.save(args.b, np.concatenate(B))
@@ -119,19 +146,23 @@ def main():
     sums = eng.mel_sums(seg, torch.from_numpy(np.concatenate(A)), torch.from_numpy(np.concatenate(B)), sample_rate=sr)
     mel, mel_r, mel_utt = mel_score(sums.cpu().tolist())
     extra = {}
+    if args.resynth and kl is not None:
+        extra.update(kl_text=kl["kl_text"], kl_audio=kl["kl_audio"])
     if args.slm:
         from stylish_tts_amd import modules
 
         net = modules.WavLM(engine=eng).load_synthetic(0) if args.slm == "synthetic" else modules.WavLM(model_path=args.slm, engine=eng)
         slm, slm_utt = modules.WavLMLoss(net, sr).scores([torch.from_numpy(w) for w in A], [torch.from_numpy(w) for w in B])
-        extra = dict(slm=slm, slm_utt_max=max(slm_utt))
+        extra.update(slm=slm, slm_utt_max=max(slm_utt))
     eng.close()
     for (fft, hop, window), v in zip((val_scores.as_tuple(r) for r in val_scores.resolutions), mel_r):
         print(f"mel at fft {fft:4d} hop {hop:3d} window {window:4d}: {v:.6e}")
     worst = int(np.argmax(mel_utt))
     max_abs = max(float(np.abs(x - y).max()) for x, y in zip(A, B))
     print(f"mel: {mel:.6e}   worst utterance {worst}: {mel_utt[worst]:.6e}   waveform max-abs difference: {max_abs:.3e}")
-    if extra:
+    if "kl_text" in extra:
+        print(f"kl_text: {extra['kl_text']:.6e}   kl_audio: {extra['kl_audio']:.6e}")
+    if "slm" in extra:
         print(f"slm: {extra['slm']:.6e}   worst utterance: {extra['slm_utt_max']:.6e}")
     print(json.dumps(dict(mel=mel, mel_r=mel_r, mel_utt_max=mel_utt[worst], utterances=len(A), sample_rate=sr, max_abs=max_abs, **extra)))
 
