@@ -435,6 +435,21 @@ size_t stts_ctc_align_workspace_bytes(int n_utt, const int32_t* t_off_host, cons
 int stts_ctc_align(void* stream, int n_utt, const int32_t* t_off_host, const int32_t* t_off_dev, const int32_t* p_off_host, const int32_t* p_off_dev,
                    const float* log_probs, int ld, int classes, int blank, const int32_t* targets, int path_given, int32_t* path, float* scores,
                    int32_t* durations, float* left, float* right, void* ws, size_t ws_bytes);
+/* The CTC negative log-likelihood (what the reference takes from k2.ctc_loss, here the exact sum over ALL paths, unpruned): the same states and
+ * jumps as stts_ctc_align over the log semiring, in fp64 from the fp32 log_probs; nll [n_utt] (fp64) = -log of the summed path probabilities, +inf
+ * (never NaN) where (T, targets) has no path.  log_priors (null, or [classes] fp64): every emission becomes log_probs[t][c] - prior_scale *
+ * log_priors[c] (CTCLossWithLabelPriors' "train" branch) without a second log-prob tensor.  Same refusals as stts_ctc_align; no workspace; an
+ * utterance's value does not depend on the batch around it. */
+int stts_ctc_nll(void* stream, int n_utt, const int32_t* t_off_host, const int32_t* t_off_dev, const int32_t* p_off_host, const int32_t* p_off_dev,
+                 const float* log_probs, int ld, int classes, int blank, const int32_t* targets, const double* log_priors, double prior_scale, double* nll);
+/* sums [n_utt] (fp64) = each utterance's sum of exp(scores[t]) over the path log-probs stts_ctc_align writes, added in a fixed order, no atomics
+ * (validate_alignment's "confidence" = sum of the sums / frames; align_text's per-file score = sums[u] / T_u). */
+int stts_ctc_confidence_sums(void* stream, int n_utt, const int32_t* t_off_host, const int32_t* t_off_dev, const float* scores, double* sums);
+/* log_sums [classes] (fp64) = logsumexp over every frame of the batch of log_probs[t][c] (CTCLossWithLabelPriors' log_batch_priors_sum,
+ * train/losses.py:563-580): (max, sum) partials of 64-row chunks in ws, merged in chunk order; an all -inf column gives -inf. */
+size_t stts_ctc_prior_sums_workspace_bytes(int n_utt, const int32_t* t_off_host, int classes);
+int stts_ctc_prior_sums(void* stream, int n_utt, const int32_t* t_off_host, const int32_t* t_off_dev, const float* log_probs, int ld, int classes,
+                        double* log_sums, void* ws, size_t ws_bytes);
 
 /* ---- HuBERT voice conversion (the reference's hubert_acoustic models, train/stage_type.py:907-1015).  Inputs are HuBERT features at the
  * mel-frame rate as packed time-major rows feats [rows_T, ld_feats] (ld_feats a multiple of 4 covering hubert.hidden_dim padded to 32, pad
@@ -570,6 +585,16 @@ int stts_val_magphase_sums(stts_ctx* ctx, void* stream, int n_utt, const int32_t
  * vectors a and b, utterance u = values [off[u], off[u+1]), at least one; added in a fixed order. */
 int stts_val_smooth_l1_sums(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* a, const float* b,
                             double* sums);
+/* The same for l1_loss / mse_loss: sums [n_utt] (fp64) = each utterance's sum of |a - b| (kind 0) or (a - b)^2 (kind 1). */
+int stts_val_diff_sums(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* a, const float* b, int kind,
+                       double* sums);
+/* The sums of DurationLoss / CDW_CCELoss (train/losses.py:429-476, alpha = 2) over packed token rows logits [sum P, ld >= classes] (fp32),
+ * 2 <= classes <= 64, targets [sum P] int32 classes (clamped to [0, classes - 1]), weight [classes] fp32.  With sm / lsm the row's softmax and
+ * log-softmax in fp64, t = the row's target and d[t][c] = min(|t - c|, 7)^2, sums [n_utt][3] (fp64) =
+ *   sum_p lsm[p][t] * w[t],   sum_p w[t],   sum_p sum_c log(1 - sm[p][c] + 1e-9) * (d[t][c] / sum_c d[t][c])
+ * added in a fixed order.  The reference's numbers: duration_ce = mean_u -s0 / (s1 + 1e-9), duration = mean_u -100 * s2 / P_u. */
+int stts_val_duration_sums(stts_ctx* ctx, void* stream, int n_utt, const int32_t* p_off_host, const int32_t* p_off_dev, const float* logits, int ld,
+                           int classes, const int32_t* targets, const float* weight, double* sums);
 
 /* ---- Windowed-sinc sample-rate conversion: torchaudio.transforms.Resample(orig_freq, new_freq, resampling_method, lowpass_filter_width, rolloff,
  * beta) / functional.resample from their published definition, with the float64 result as the target:

@@ -242,6 +242,10 @@ SIGNATURES = {
     "stts_aligner_tap_floats": (_I64, [_P, _I, _P]),
     "stts_ctc_align_workspace_bytes": (_SZ, [_I, _P, _P]),
     "stts_ctc_align": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
+    "stts_ctc_nll": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, C.c_double, _P]),
+    "stts_ctc_confidence_sums": (_I, [_P, _I, _P, _P, _P, _P]),
+    "stts_ctc_prior_sums_workspace_bytes": (_SZ, [_I, _P, _I]),
+    "stts_ctc_prior_sums": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _SZ]),
     "stts_log_mel_forward": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_double, C.c_double, _P, _I, _P, _P]),
     "stts_log_mel_stats": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "stts_log_mel_filters": (_I, [_I, _I, _I, _P, _P]),
@@ -250,6 +254,8 @@ SIGNATURES = {
     "stts_val_mel_sums": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "stts_val_magphase_sums": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "stts_val_smooth_l1_sums": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
+    "stts_val_diff_sums": (_I, [_P, _P, _I, _P, _P, _P, _P, _I, _P]),
+    "stts_val_duration_sums": (_I, [_P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
     "stts_resample_geometry": (_I, [_I, _I, _I, C.c_double, _P, _P, _P, _P]),
     "stts_resample_out_length": (_I64, [_I64, _I, _I]),
     "stts_resample_tile": (_I, [_I, _I]),

@@ -9,6 +9,8 @@
 //   output layer  Linear hidden -> classes, then log_softmax over the classes, one wave per row                 : conv_gemm_f32, aligner_log_softmax_kernel
 //   alignment     Viterbi over the 2 P + 1 CTC states, one workgroup per utterance                              : ctc_viterbi_kernel
 //   durations     per-token frame counts and torch_align's boundary probabilities from a label path             : ctc_durations_kernel
+//   likelihood    the CTC negative log-likelihood (the same states over the log semiring, fp64), optional priors  : ctc_forward_kernel
+//   sums          sum of exp(path log-probs) per utterance; per-class logsumexp over the batch's frames           : ctc_confidence_kernel, ctc_prior_*_kernel
 // Everything is fp32 whatever stts_set_precision chose.  The contractions run the split-fp32 form (the f32 matrix cores on an STTS_PREC_F32_NATIVE
 // engine), always on the 128 x 128 tile whose 16 waves are 8 positions x 2 K-groups and never cut over blocks - ssl.hip.h gives the reasons: two
 // accumulator chains of K / 2 round less than one of K (K = 1920 in the TDNN layers), and one tile for every call makes an utterance's rows the
@@ -231,6 +233,106 @@ __global__ void __launch_bounds__(kCtcThreads) ctc_durations_kernel(const float*
   }
 }
 
+// ------------------------------------------------------------------------------------------------ CTC likelihood and the sums beside it
+// log(exp(a) + exp(b) + exp(c)) in fp64: m + log(sum exp(x - m)) with m the largest; -inf when all three are -inf (no inf - inf is ever formed:
+// a - m with a = -inf and m finite is -inf, whose exp is 0).
+__device__ __forceinline__ double ctc_lse3(double a, double b, double c) {
+  const double m = fmax(a, fmax(b, c));
+  if (m == -INFINITY) return -INFINITY;
+  return m + log(exp(a - m) + exp(b - m) + exp(c - m));
+}
+
+// CTC negative log-likelihood of one utterance: the Viterbi kernel's skeleton (thread s owns state s, the previous frame's row in LDS, double
+// buffered, one barrier per frame, the next frame's emission gathered before the barrier) over the log semiring, in fp64:
+//   alpha[t][s] = lse(alpha[t-1][s], alpha[t-1][s-1], alpha[t-1][s-2] if the jump is allowed) + e[t][s]
+//   e[t][s] = lp[t][label(s)] - prior_scale * log_priors[label(s)]   (log_priors may be null)
+//   nll[u] = -lse(alpha[T-1][2P], alpha[T-1][2P-1]); +inf when no path exists.
+// No back pointers, no workspace.  Token ids are clamped to [0, V - 1]; a thread past the utterance's states only meets the barriers.  An
+// utterance whose P is outside [1, kCtcMaxTokens] or whose T < 1 is left alone (the entry point refuses it).  grid n_utt, block 1024.
+__global__ void __launch_bounds__(kCtcThreads) STTS_NO_PK ctc_forward_kernel(const float* __restrict__ lp, int ld, int V, int blank, const int* __restrict__ t_off,
+                                                                             const int* __restrict__ p_off, const int* __restrict__ targets,
+                                                                             const double* __restrict__ log_priors, double prior_scale, double* __restrict__ nll) {
+  __shared__ double al[2][kCtcThreads];
+  __shared__ int tok[kCtcMaxTokens + 2];
+  const int u = blockIdx.x, s = threadIdx.x;
+  const int t0 = t_off[u], T = t_off[u + 1] - t0, q0 = p_off[u], P = p_off[u + 1] - q0;
+  if (P < 1 || P > kCtcMaxTokens || T < 1) return;
+  const int S = 2 * P + 1;
+  for (int i = s; i < P; i += kCtcThreads) tok[i] = min(max(targets[q0 + i], 0), V - 1);
+  __syncthreads();
+  const bool live = s < S;
+  const int label = (live && (s & 1)) ? tok[s >> 1] : blank;
+  const bool skip = live && (s & 1) && s >= 3 && tok[s >> 1] != tok[(s >> 1) - 1];
+  const double pc = log_priors ? prior_scale * log_priors[label] : 0.0;
+  const float* col = lp + (long)t0 * ld + label;
+  double e = live ? (double)col[0] - pc : 0.0;
+  al[0][s] = (live && s < 2) ? e : -INFINITY;
+  for (int t = 1; t < T; ++t) {
+    e = live ? (double)col[(long)t * ld] - pc : 0.0;  // in flight across the barrier
+    __syncthreads();
+    if (live) {
+      const double* prev = al[(t - 1) & 1];
+      const double a = ctc_lse3(prev[s], s >= 1 ? prev[s - 1] : -INFINITY, skip ? prev[s - 2] : -INFINITY);
+      al[t & 1][s] = a == -INFINITY ? -INFINITY : a + e;
+    }
+  }
+  __syncthreads();
+  if (s == 0) {
+    const double* last = al[(T - 1) & 1];
+    const double a = ctc_lse3(last[S - 1], last[S - 2], -INFINITY);
+    nll[u] = a == -INFINITY ? INFINITY : -a;
+  }
+}
+
+// sums[u] = sum over the utterance's frames of exp(scores[t]) in fp64 (scores: the path log-probs ctc_durations_kernel writes): thread i takes
+// frames i, i + 256, ... in order, a fixed tree joins the 256 sums.  grid n_utt, block 256.
+__global__ void __launch_bounds__(256) STTS_NO_PK ctc_confidence_kernel(const float* __restrict__ scores, const int* __restrict__ t_off, double* __restrict__ sums) {
+  __shared__ double acc[256];
+  const int u = blockIdx.x;
+  const long lo = t_off[u], n = t_off[u + 1] - lo;
+  double s = 0.0;
+  for (long i = threadIdx.x; i < n; i += 256) s += exp((double)scores[lo + i]);
+  acc[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) acc[threadIdx.x] += acc[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) sums[u] = acc[0];
+}
+
+// Per-class logsumexp over all frames of the batch (losses.py:563-580), two launches.  (1) chunk k = rows [k * kCtcPriorChunk, ..): thread c walks
+// class c down the chunk's rows (a wave reads consecutive classes of one row), part[k][c] = (max, sum of exp(x - max)) in fp64; an all -inf
+// column gives (-inf, 0).  (2) thread c merges the chunks of class c in chunk order: M = the largest max, sum_k s_k exp(m_k - M), M + log of it.
+constexpr int kCtcPriorChunk = 64;
+
+__global__ void __launch_bounds__(256) STTS_NO_PK ctc_prior_part_kernel(const float* __restrict__ lp, int ld, int V, long R, double* __restrict__ part) {
+  const long r0 = (long)blockIdx.x * kCtcPriorChunk, r1 = r0 + kCtcPriorChunk < R ? r0 + kCtcPriorChunk : R;
+  for (int c = threadIdx.x; c < V; c += 256) {
+    double m = -INFINITY;
+    for (long r = r0; r < r1; ++r) m = fmax(m, (double)lp[r * ld + c]);
+    double s = 0.0;
+    if (m != -INFINITY)
+      for (long r = r0; r < r1; ++r) s += exp((double)lp[r * ld + c] - m);
+    part[2 * ((long)blockIdx.x * V + c)] = m;
+    part[2 * ((long)blockIdx.x * V + c) + 1] = s;
+  }
+}
+
+__global__ void __launch_bounds__(256) STTS_NO_PK ctc_prior_merge_kernel(const double* __restrict__ part, int n_chunks, int V, double* __restrict__ log_sums) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= V) return;
+  double M = -INFINITY;
+  for (int k = 0; k < n_chunks; ++k) M = fmax(M, part[2 * ((long)k * V + c)]);
+  double s = 0.0;
+  if (M != -INFINITY)
+    for (int k = 0; k < n_chunks; ++k) {
+      const double m = part[2 * ((long)k * V + c)];
+      if (m != -INFINITY) s += part[2 * ((long)k * V + c) + 1] * exp(m - M);
+    }
+  log_sums[c] = M == -INFINITY ? -INFINITY : M + log(s);
+}
+
 // ------------------------------------------------------------------------------------------------ packing
 inline int finalize_aligner(stts_ctx* c, const AlDims& d, AlW* M) {
   *M = AlW();
@@ -360,6 +462,24 @@ inline int ctc_align(hipStream_t st, int n_utt, const int* t_off_dev, const int*
                      int path_given, int* path, float* scores, int* dur, float* left, float* right, unsigned char* bp) {
   if (!path_given) hipLaunchKernelGGL(ctc_viterbi_kernel, dim3(n_utt), dim3(kCtcThreads), 0, st, lp, ld, V, blank, t_off_dev, p_off_dev, targets, bp, path);
   hipLaunchKernelGGL(ctc_durations_kernel, dim3(n_utt), dim3(kCtcThreads), 0, st, lp, ld, V, blank, t_off_dev, p_off_dev, targets, path, scores, dur, left, right);
+  STTS_HIP(hipGetLastError());
+  return 0;
+}
+
+inline int ctc_nll(hipStream_t st, int n_utt, const int* t_off_dev, const int* p_off_dev, const float* lp, int ld, int V, int blank, const int* targets,
+                   const double* log_priors, double prior_scale, double* nll) {
+  hipLaunchKernelGGL(ctc_forward_kernel, dim3(n_utt), dim3(kCtcThreads), 0, st, lp, ld, V, blank, t_off_dev, p_off_dev, targets, log_priors, prior_scale, nll);
+  STTS_HIP(hipGetLastError());
+  return 0;
+}
+
+inline int ctc_prior_chunks(long rows) { return (int)((rows + kCtcPriorChunk - 1) / kCtcPriorChunk); }
+inline size_t ctc_prior_workspace_bytes(long rows, int V) { return (size_t)ctc_prior_chunks(rows) * V * 2 * sizeof(double); }
+
+inline int ctc_prior_sums(hipStream_t st, long rows, const float* lp, int ld, int V, double* log_sums, double* part) {
+  const int n_chunks = ctc_prior_chunks(rows);
+  hipLaunchKernelGGL(ctc_prior_part_kernel, dim3(n_chunks), dim3(256), 0, st, lp, ld, V, rows, part);
+  hipLaunchKernelGGL(ctc_prior_merge_kernel, dim3(ceil_div(V, 256)), dim3(256), 0, st, part, n_chunks, V, log_sums);
   STTS_HIP(hipGetLastError());
   return 0;
 }

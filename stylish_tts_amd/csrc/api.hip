@@ -835,12 +835,12 @@ int stts_aligner_forward_taps(stts_ctx* c, void* stream, int n_utt, const int32_
   API_END
 }
 
-static int ctc_check_offsets(int n_utt, const int32_t* t_off_host, const int32_t* p_off_host) {
-  STTS_CHECK(n_utt > 0 && t_off_host && p_off_host && t_off_host[0] == 0 && p_off_host[0] == 0, "ctc_align: bad offsets");
+static int ctc_check_offsets(int n_utt, const int32_t* t_off_host, const int32_t* p_off_host, const char* what = "ctc_align") {
+  STTS_CHECK(n_utt > 0 && t_off_host && p_off_host && t_off_host[0] == 0 && p_off_host[0] == 0, "%s: bad offsets", what);
   for (int u = 0; u < n_utt; ++u) {
     const long T = (long)t_off_host[u + 1] - t_off_host[u], P = (long)p_off_host[u + 1] - p_off_host[u];
-    STTS_CHECK(T >= 1, "ctc_align: utterance %d has no frames", u);
-    STTS_CHECK(P >= 1 && P <= kCtcMaxTokens, "ctc_align: utterance %d has %ld tokens, outside [1, %d]", u, P, kCtcMaxTokens);
+    STTS_CHECK(T >= 1, "%s: utterance %d has no frames", what, u);
+    STTS_CHECK(P >= 1 && P <= kCtcMaxTokens, "%s: utterance %d has %ld tokens, outside [1, %d]", what, u, P, kCtcMaxTokens);
   }
   return 0;
 }
@@ -860,6 +860,51 @@ int stts_ctc_align(void* stream, int n_utt, const int32_t* t_off_host, const int
   STTS_CHECK(path_given || (ws && ws_bytes >= ctc_workspace_bytes(n_utt, t_off_host, p_off_host)), "ctc_align: workspace too small (stts_ctc_align_workspace_bytes)");
   return ctc_align((hipStream_t)stream, n_utt, t_off_dev, p_off_dev, log_probs, ld, classes, blank, targets, path_given, path, scores, durations, left, right,
                    (unsigned char*)ws);
+  API_END
+}
+
+int stts_ctc_nll(void* stream, int n_utt, const int32_t* t_off_host, const int32_t* t_off_dev, const int32_t* p_off_host, const int32_t* p_off_dev,
+                 const float* log_probs, int ld, int classes, int blank, const int32_t* targets, const double* log_priors, double prior_scale, double* nll) {
+  API_BEGIN
+  STTS_CHECK(t_off_dev && p_off_dev && log_probs && targets && nll, "ctc_nll: null argument");
+  STTS_TRY(ctc_check_offsets(n_utt, t_off_host, p_off_host, "ctc_nll"));
+  STTS_CHECK(classes >= 2 && ld >= classes && blank >= 0 && blank < classes, "ctc_nll: %d classes in rows of %d, blank %d", classes, ld, blank);
+  STTS_CHECK(std::isfinite(prior_scale), "ctc_nll: prior_scale is not finite");
+  return ctc_nll((hipStream_t)stream, n_utt, t_off_dev, p_off_dev, log_probs, ld, classes, blank, targets, log_priors, prior_scale, nll);
+  API_END
+}
+
+// frame offsets alone: at least one frame per utterance
+static int ctc_check_frames(const char* what, int n_utt, const int32_t* t_off_host) {
+  STTS_CHECK(n_utt > 0 && n_utt <= 65535 && t_off_host && t_off_host[0] == 0, "%s: bad offsets", what);
+  for (int u = 0; u < n_utt; ++u) STTS_CHECK(t_off_host[u + 1] > t_off_host[u], "%s: utterance %d has no frames", what, u);
+  return 0;
+}
+
+int stts_ctc_confidence_sums(void* stream, int n_utt, const int32_t* t_off_host, const int32_t* t_off_dev, const float* scores, double* sums) {
+  API_BEGIN
+  STTS_TRY(ctc_check_frames("ctc_confidence_sums", n_utt, t_off_host));
+  STTS_CHECK(t_off_dev && scores && sums, "ctc_confidence_sums: null argument");
+  hipLaunchKernelGGL(ctc_confidence_kernel, dim3(n_utt), dim3(256), 0, (hipStream_t)stream, scores, t_off_dev, sums);
+  STTS_HIP(hipGetLastError());
+  return 0;
+  API_END
+}
+
+size_t stts_ctc_prior_sums_workspace_bytes(int n_utt, const int32_t* t_off_host, int classes) {
+  if (classes < 1 || ctc_check_frames("ctc_prior_sums", n_utt, t_off_host) != 0) return 0;
+  return ctc_prior_workspace_bytes(t_off_host[n_utt], classes);
+}
+
+int stts_ctc_prior_sums(void* stream, int n_utt, const int32_t* t_off_host, const int32_t* t_off_dev, const float* log_probs, int ld, int classes,
+                        double* log_sums, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  STTS_TRY(ctc_check_frames("ctc_prior_sums", n_utt, t_off_host));
+  STTS_CHECK(t_off_dev && log_probs && log_sums, "ctc_prior_sums: null argument");
+  STTS_CHECK(classes >= 1 && ld >= classes, "ctc_prior_sums: %d classes in rows of %d", classes, ld);
+  STTS_CHECK(ws && ws_bytes >= ctc_prior_workspace_bytes(t_off_host[n_utt], classes) && (uintptr_t)ws % 8 == 0,
+             "ctc_prior_sums: workspace too small (stts_ctc_prior_sums_workspace_bytes)");
+  return ctc_prior_sums((hipStream_t)stream, t_off_host[n_utt], log_probs, ld, classes, log_sums, (double*)ws);
   API_END
 }
 
@@ -1148,6 +1193,35 @@ int stts_val_smooth_l1_sums(stts_ctx* c, void* stream, int n_utt, const int32_t*
   STTS_CHECK(c && off_dev && a && b && sums, "val_smooth_l1_sums: null argument");
   STTS_HIP(hipSetDevice(c->device));
   hipLaunchKernelGGL(val_smooth_l1_kernel, dim3(n_utt), dim3(256), 0, (hipStream_t)stream, a, b, off_dev, sums);
+  STTS_HIP(hipGetLastError());
+  return 0;
+  API_END
+}
+
+int stts_val_diff_sums(stts_ctx* c, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* a, const float* b, int kind,
+                       double* sums) {
+  API_BEGIN
+  STTS_CHECK(n_utt > 0 && n_utt <= 65535 && off_host && off_host[0] == 0, "val_diff_sums: bad offsets");
+  for (int u = 0; u < n_utt; ++u) STTS_CHECK(off_host[u + 1] > off_host[u], "val_diff_sums: utterance %d has no values", u);
+  STTS_CHECK(c && off_dev && a && b && sums, "val_diff_sums: null argument");
+  STTS_CHECK(kind == 0 || kind == 1, "val_diff_sums: kind must be 0 (absolute) or 1 (squared), got %d", kind);
+  STTS_HIP(hipSetDevice(c->device));
+  if (kind == 0) hipLaunchKernelGGL(val_diff_kernel<0>, dim3(n_utt), dim3(256), 0, (hipStream_t)stream, a, b, off_dev, sums);
+  else hipLaunchKernelGGL(val_diff_kernel<1>, dim3(n_utt), dim3(256), 0, (hipStream_t)stream, a, b, off_dev, sums);
+  STTS_HIP(hipGetLastError());
+  return 0;
+  API_END
+}
+
+int stts_val_duration_sums(stts_ctx* c, void* stream, int n_utt, const int32_t* p_off_host, const int32_t* p_off_dev, const float* logits, int ld, int classes,
+                           const int32_t* targets, const float* weight, double* sums) {
+  API_BEGIN
+  STTS_CHECK(n_utt > 0 && n_utt <= 65535 && p_off_host && p_off_host[0] == 0, "val_duration_sums: bad offsets");
+  for (int u = 0; u < n_utt; ++u) STTS_CHECK(p_off_host[u + 1] > p_off_host[u], "val_duration_sums: utterance %d has no tokens", u);
+  STTS_CHECK(classes >= 2 && classes <= 64 && ld >= classes, "val_duration_sums: %d classes in rows of %d; one lane per class takes 2 to 64", classes, ld);
+  STTS_CHECK(c && p_off_dev && logits && targets && weight && sums, "val_duration_sums: null argument");
+  STTS_HIP(hipSetDevice(c->device));
+  hipLaunchKernelGGL(val_duration_kernel, dim3(n_utt), dim3(256), 0, (hipStream_t)stream, logits, ld, classes, targets, weight, p_off_dev, sums);
   STTS_HIP(hipGetLastError());
   return 0;
   API_END

@@ -1,5 +1,7 @@
 // Validation scores of the reference's validate_* functions (train/stage_type.py): MultiSpectrogram (train/multi_spectrogram.py) feeding
-// MultiResolutionSTFTLoss ("mel", train/losses.py:14-35), MagPhaseLoss ("mag" / "phase", losses.py:38-154) and smooth_l1_loss ("pitch" / "energy").
+// MultiResolutionSTFTLoss ("mel", train/losses.py:14-35), MagPhaseLoss ("mag" / "phase", losses.py:38-154) and smooth_l1_loss ("pitch" / "energy");
+// at the end of the kernels the sums of DurationLoss ("duration_ce" / "duration", losses.py:429-476) and of l1_loss / mse_loss ("linear_pitch",
+// "mel_l2", "normed_pitch_l2").
 //   calculate_single, per resolution (fft, hop, window): X = torch.stft(audio, fft, hop, window, periodic Hann(window)) (center=True, reflect,
 //   one-sided, unnormalised); fft_mag = |X|; phase = (fft_mag > 1e-3) * angle(X); mag = log1p(MelScale(128, sample_rate, fft / 2 + 1)(fft_mag))
 //   (HTK, norm None, f_min 0, f_max sample_rate / 2: the filters of log_mel.hip.h).
@@ -322,6 +324,68 @@ __global__ void __launch_bounds__(256) STTS_NO_PK val_smooth_l1_kernel(const flo
     __syncthreads();
   }
   if (threadIdx.x == 0) sums[u] = acc[0];
+}
+
+// The sibling of val_smooth_l1_kernel for mse_loss / l1_loss: sums[u] = sum of |a - b| (KIND 0) or of (a - b)^2 (KIND 1) in fp64, same order.
+template <int KIND>
+__global__ void __launch_bounds__(256) STTS_NO_PK val_diff_kernel(const float* __restrict__ a, const float* __restrict__ b, const int* __restrict__ off,
+                                                                  double* __restrict__ sums) {
+  __shared__ double acc[256];
+  const int u = blockIdx.x;
+  const long lo = off[u], n = off[u + 1] - lo;
+  double s = 0.0;
+  for (long i = threadIdx.x; i < n; i += 256) {
+    const double d = (double)a[lo + i] - (double)b[lo + i];
+    s += KIND == 0 ? fabs(d) : d * d;
+  }
+  acc[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) acc[threadIdx.x] += acc[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) sums[u] = acc[0];
+}
+
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// The sums of CDW_CCELoss (train/losses.py:429-459, alpha = 2) over one utterance's token rows.  One wave per row, lane c = class c < C <= 64:
+// softmax and log-softmax in fp64 from the fp32 logits, t = the row's target class clamped to [0, C - 1], d[t][c] = min(|t - c|, 7)^2:
+//   sums[u][0] = sum_p lsm[p][t] * w[t]      sums[u][1] = sum_p w[t]      sums[u][2] = sum_p sum_c log(1 - sm[p][c] + 1e-9) * (d[t][c] / sum_c d[t][c])
+// Wave w of the block's four takes rows w, w + 4, ... in order; the four waves' sums are joined in wave order.  grid n_utt, block 256.
+__global__ void __launch_bounds__(256) STTS_NO_PK val_duration_kernel(const float* __restrict__ logits, int ld, int C, const int* __restrict__ targets,
+                                                                      const float* __restrict__ weight, const int* __restrict__ p_off, double* __restrict__ sums) {
+  __shared__ double acc[4][3];
+  const int u = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long lo = p_off[u], n = p_off[u + 1] - lo;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  for (long p = wv; p < n; p += 4) {
+    const double x = lane < C ? (double)logits[(lo + p) * ld + lane] : -INFINITY;
+    const double m = wave_max_f64(x);
+    const double ex = lane < C ? exp(x - m) : 0.0;
+    const double tot = wave_sum_f64(ex);
+    const double lsm = (x - m) - log(tot), sm = ex / tot;
+    const int t = min(max(targets[lo + p], 0), C - 1);
+    const int k = min(abs(t - lane), 7);
+    const double d = lane < C ? (double)(k * k) : 0.0;
+    const double D = wave_sum_f64(d);
+    const double cdw = lane < C ? log((1.0 - sm) + 1e-9) * (d / D) : 0.0;
+    const double w = (double)weight[t];
+    s0 += __shfl(lsm, t, 64) * w;
+    s1 += w;
+    s2 += wave_sum_f64(cdw);
+  }
+  if (lane == 0) {
+    acc[wv][0] = s0;
+    acc[wv][1] = s1;
+    acc[wv][2] = s2;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) sums[3 * u + threadIdx.x] = ((acc[0][threadIdx.x] + acc[1][threadIdx.x]) + acc[2][threadIdx.x]) + acc[3][threadIdx.x];
 }
 
 // ------------------------------------------------------------------------------------------------ host side

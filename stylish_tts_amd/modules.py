@@ -35,6 +35,7 @@ the reference's state_dict names (both weight-norm flavours), so ``load_state_di
 """
 from __future__ import annotations
 
+import math
 from collections import OrderedDict
 from typing import Dict, NamedTuple, Optional
 
@@ -261,12 +262,29 @@ class DurationPredictor(HipModule):
         return out
 
 
+# the frames a duration class stands for, and the class of a duration of 0 .. 50 frames (utils.py:391-450)
+_CLASS_TO_DUR = [1, 2, 3, 4, 5, 6, 7, 9, 12, 15, 18, 22, 27, 32, 38, 46]
+_DUR_TO_CLASS = [0, 0, 1, 2, 3, 4, 5, 6] + [7] * 3 + [8] * 3 + [9] * 3 + [10] * 3 + [11] * 5 + [12] * 5 + [13] * 5 + [14] * 7 + [15] * 9
+
+
 class DurationProcessor(torch.nn.Module):
-    """utils.py:385-494: logits [P,16] -> 0/1 alignment [P,T]."""
+    """utils.py:385-494: logits [P,16] -> 0/1 alignment [P,T]; dur_to_class / align_to_class: the host tables of the duration targets."""
 
     def __init__(self, class_count, max_dur):
         super().__init__()
         self.class_count, self.max_dur = class_count, max_dur
+        # utils.py:391-450, host tables (kept out of state_dict: the shim's keys stay as they were)
+        self.register_buffer("class_to_dur_table", torch.tensor(_CLASS_TO_DUR, dtype=torch.float32), persistent=False)
+        self.register_buffer("dur_to_class_table", torch.tensor(_DUR_TO_CLASS, dtype=torch.float32), persistent=False)
+
+    def dur_to_class(self, durs):
+        """utils.py:459-461: durations clamped to [1, max_dur] -> their class (a float tensor, like the reference's table)."""
+        durs = torch.as_tensor(durs).clamp(min=1, max=self.max_dur)
+        return self.dur_to_class_table.to(durs.device)[durs.long()]
+
+    def align_to_class(self, alignment):
+        """utils.py:463-466: a 0/1 alignment [.., P, T] -> the duration class of every token."""
+        return self.dur_to_class(torch.as_tensor(alignment).sum(dim=-1).clamp(min=1, max=50))
 
     def prediction_to_duration(self, pred, text_length=None):
         from . import _lib
@@ -987,6 +1005,173 @@ class MagPhaseLoss(torch.nn.Module):
         mag, phase, _ = self.scores(pred, gt)
         log.add_loss("mag", torch.tensor(mag, dtype=torch.float64))
         log.add_loss("phase", torch.tensor(phase, dtype=torch.float64))
+
+
+# ------------------------------------------------------------------------------------------------ alignment, duration and CFM scores
+class _EngineUser(torch.nn.Module):
+    def __init__(self, engine=None, cfg=None):
+        super().__init__()
+        self._engine, self._cfg = engine, cfg
+
+    @property
+    def engine(self) -> HipModel:
+        if self._engine is None:
+            self._engine = get_engine(self._cfg, 0)
+        return self._engine
+
+
+def duration_score(sums, lengths):
+    """sums [B, 3] (HipModel.duration_sums, on the host), token counts [B] -> (duration_ce, duration, [ce_utt], [cdw_utt]): CDW_CCELoss' two values
+    of every utterance, ce_u = -s0 / (s1 + 1e-9) and cdw_u = -100 s2 / P_u, and DurationLoss.forward's means over the utterances."""
+    ce = [-float(s[0]) / (float(s[1]) + 1e-9) for s in sums]
+    cdw = [-100.0 * float(s[2]) / float(n) for s, n in zip(sums, lengths)]
+    return sum(ce) / len(ce), sum(cdw) / len(cdw), ce, cdw
+
+
+class CDW_CCELoss(_EngineUser):
+    """train/losses.py:429-459 on the engine: forward(pred [N, C], target [N]) -> (-ce.sum(), -100 cdw.sum()) of one utterance as fp32 tensors,
+    from the fp64 sums of HipModel.duration_sums.  The distance weights are built for ``alpha`` = 2 (what DurationLoss constructs); another
+    alpha raises.  ``weight=None`` raises ValueError in forward (the reference calls exit(1) there)."""
+
+    def __init__(self, classes, *, alpha=1.0, weight=None, engine=None, cfg=None):
+        super().__init__(engine, cfg)
+        self.classes, self.alpha = int(classes), float(alpha)
+        self.custom_weight = None if weight is None else torch.as_tensor(weight).detach().to(torch.float32).reshape(-1)
+        if self.custom_weight is not None and self.custom_weight.numel() != self.classes:
+            raise ValueError(f"{self.custom_weight.numel()} class weights for {self.classes} classes")
+
+    def sums(self, pred, target, lengths=None):
+        """pred [sum P, C] packed rows, target [sum P], lengths [B] (default: one utterance) -> [B, 3] float64 on the device; nothing is read back."""
+        if self.custom_weight is None:
+            raise ValueError("CDW_CCELoss needs class weights (weight=None is the branch in which the reference exits)")
+        if self.alpha != 2.0:
+            raise NotImplementedError(f"CDW_CCELoss: the engine builds the distance weights of alpha = 2, not {self.alpha}")
+        pred = torch.as_tensor(pred)
+        if pred.dim() != 2 or pred.shape[1] != self.classes:
+            raise ValueError(f"pred must be [N, {self.classes}], got {tuple(pred.shape)}")
+        eng = self.engine
+        L = [pred.shape[0]] if lengths is None else [int(v) for v in lengths]
+        return eng.duration_sums(Segments(L, eng.device), pred, torch.as_tensor(target).reshape(-1), self.custom_weight)
+
+    def forward(self, pred, target):
+        s = self.sums(pred, target)[0]
+        n = torch.as_tensor(pred).shape[0]
+        return (-s[0] / (s[1] + 1e-9)).to(torch.float32), (-100.0 * s[2] / n).to(torch.float32)
+
+
+class DurationLoss(_EngineUser):
+    """train/losses.py:462-476 on the engine: forward(pred [B, P, C] logits, gt [B, P] duration classes, text_length [B]) -> (loss_ce, loss_cdw),
+    the means over the utterances of CDW_CCELoss(alpha = 2) on every utterance's own tokens; one launch for the batch."""
+
+    def __init__(self, *, class_count, weight, engine=None, cfg=None):
+        super().__init__(engine, cfg)
+        self.loss = CDW_CCELoss(class_count, alpha=2, weight=weight, engine=engine, cfg=cfg)
+
+    def sums(self, pred, gt, text_length):
+        """(sums [B, 3] float64 on the device, the token counts); nothing is read back beyond text_length."""
+        pred, gt = torch.as_tensor(pred), torch.as_tensor(gt)
+        L = [int(v) for v in torch.as_tensor(text_length).tolist()]
+        if pred.dim() != 3 or gt.dim() != 2 or pred.shape[0] != len(L) or gt.shape[0] != len(L) or any(n < 1 or n > pred.shape[1] or n > gt.shape[1] for n in L):
+            raise ValueError(f"pred {tuple(pred.shape)} / gt {tuple(gt.shape)} do not fit text lengths {L}")
+        self.loss._engine = self.loss._engine or self.engine
+        rows = torch.cat([pred[b, : L[b]] for b in range(len(L))])
+        tg = torch.cat([gt[b, : L[b]] for b in range(len(L))]).long()
+        return self.loss.sums(rows, tg, L), L
+
+    def scores(self, pred, gt, text_length):
+        """dict(duration_ce, duration, duration_ce_utt, duration_utt) as Python numbers; one host read."""
+        s, L = self.sums(pred, gt, text_length)
+        ce, cdw, ce_u, cdw_u = duration_score(s.cpu().tolist(), L)
+        return dict(duration_ce=ce, duration=cdw, duration_ce_utt=ce_u, duration_utt=cdw_u)
+
+    def forward(self, pred, gt, text_length):
+        s, L = self.sums(pred, gt, text_length)
+        n = torch.tensor(L, dtype=torch.float64, device=s.device)
+        ce, cdw = -s[:, 0] / (s[:, 1] + 1e-9), -100.0 * s[:, 2] / n
+        return ce.mean().to(torch.float32), cdw.mean().to(torch.float32)
+
+
+def align_loss_value(nll_utt, frame_lengths, token_lengths, loss=None):
+    """CTCLossWithLabelPriors.forward's reduction on the host, from per-utterance float64 values: fp32 roundings of the values, then
+    ``loss.reduction`` ("mean" without a loss: the mean of float32(nll_u) / P_u) and ``loss.reference_pairing``, in fp32 like the tensor form."""
+    reduction = "mean" if loss is None else loss.reduction
+    v = np.asarray(nll_utt, np.float64).astype(np.float32)
+    if loss is not None and loss.reference_pairing:
+        v = v[sorted(range(len(v)), key=lambda i: -int(frame_lengths[i]))]
+    if reduction == "none":
+        return [float(x) for x in v]
+    if reduction == "sum":
+        return float(torch.from_numpy(v).sum())
+    return float((torch.from_numpy(v) / torch.tensor([float(n) for n in token_lengths], dtype=torch.float32)).mean())
+
+
+class CTCLossWithLabelPriors(_EngineUser):
+    """train/losses.py:508-639 on the engine: the CTC loss of log_probs [T, N, C] (already log-softmaxed) against padded targets [N, P], with the
+    label priors of the "train" step accumulated and applied as the reference does.  Two stated deviations: (1) the likelihood is exact - k2
+    prunes its lattice with output_beam = 10; (2) the reference hands k2 a batch sorted by frame count but the UNSORTED target_lengths, so its
+    "mean" divides an utterance's likelihood by another utterance's token count unless the batch was sorted already (read from the code, k2 not
+    run); here every utterance is paired with its own length, and ``reference_pairing=True`` reproduces the reference's pairing (stable
+    descending sort by frame count) from the per-utterance values.  on_train_epoch_end() takes no accelerator: one process."""
+
+    prior_threshold = -12.0
+
+    def __init__(self, prior_scaling_factor=0.0, blank=0, reduction="mean", engine=None, cfg=None, reference_pairing=False):
+        super().__init__(engine, cfg)
+        if reduction not in ("none", "sum", "mean"):
+            raise ValueError(f"reduction must be 'none', 'sum' or 'mean', got {reduction!r}")
+        self.blank, self.reduction, self.reference_pairing = int(blank), reduction, bool(reference_pairing)
+        self.log_priors = None      # [1, 1, C] float64 on the device, like the reference's shape
+        self.log_priors_sum = None  # [1, C]
+        self.num_samples = 0
+        self.prior_scaling_factor = prior_scaling_factor
+
+    def _pack(self, log_probs, targets, input_lengths, target_lengths):
+        log_probs, targets = torch.as_tensor(log_probs), torch.as_tensor(targets)
+        TL = [int(v) for v in torch.as_tensor(input_lengths).tolist()]
+        PL = [int(v) for v in torch.as_tensor(target_lengths).tolist()]
+        if log_probs.dim() != 3 or targets.dim() != 2 or not (log_probs.shape[1] == targets.shape[0] == len(TL) == len(PL)):
+            raise ValueError(f"log_probs {tuple(log_probs.shape)} [T, N, C] and targets {tuple(targets.shape)} [N, P] do not fit {len(TL)} / {len(PL)} lengths")
+        if any(n < 1 or n > log_probs.shape[0] for n in TL) or any(n < 1 or n > targets.shape[1] for n in PL):
+            raise ValueError(f"input_lengths {TL} / target_lengths {PL} do not fit {log_probs.shape[0]} frames and {targets.shape[1]} tokens")
+        eng = self.engine
+        lp = _f(log_probs, eng.device)
+        rows = torch.cat([lp[: TL[b], b] for b in range(len(TL))]).contiguous()
+        tg = torch.cat([targets[b, : PL[b]] for b in range(len(PL))]).to(device=eng.device, dtype=torch.int32)
+        return rows, tg, Segments(TL, eng.device), Segments(PL, eng.device)
+
+    def nll(self, log_probs, targets, input_lengths, target_lengths, step_type="train"):
+        """The per-utterance negative log-likelihoods [N] float64 on the device (+inf where no path exists).  step_type "train" accumulates the
+        label priors of this batch and applies the current ones, as forward does."""
+        rows, tg, seg_t, seg_p = self._pack(log_probs, targets, input_lengths, target_lengths)
+        eng = self.engine
+        priors = None
+        if step_type == "train":
+            batch = eng.ctc_prior_sums(seg_t, rows)[None]  # [1, C]
+            self.num_samples += seg_t.rows
+            self.log_priors_sum = batch if self.log_priors_sum is None else torch.logaddexp(self.log_priors_sum, batch)
+            if self.log_priors is not None and self.prior_scaling_factor > 0:
+                priors = self.log_priors
+        return eng.ctc_nll(seg_t, rows, seg_p, tg, self.blank, log_priors=priors, prior_scale=float(self.prior_scaling_factor) if priors is not None else 0.0)
+
+    def forward(self, log_probs, targets, input_lengths, target_lengths, step_type="train"):
+        nll = self.nll(log_probs, targets, input_lengths, target_lengths, step_type).to(torch.float32)
+        TL = [int(v) for v in torch.as_tensor(input_lengths).tolist()]
+        P = torch.as_tensor(target_lengths).to(device=nll.device, dtype=torch.float32)
+        if self.reference_pairing:  # the reference's order of the values: sorted by frame count, longest first, ties in batch order
+            order = sorted(range(len(TL)), key=lambda i: -TL[i])
+            nll = nll[torch.tensor(order, device=nll.device)]
+        if self.reduction == "none":
+            return nll
+        if self.reduction == "sum":
+            return nll.sum()
+        return (nll / P).mean()
+
+    def on_train_epoch_end(self, train=None):
+        if self.log_priors_sum is not None:
+            new = self.log_priors_sum[None] - math.log(self.num_samples + 1e-9)
+            self.log_priors = torch.clamp(new, min=self.prior_threshold)
+            self.log_priors_sum = None
+            self.num_samples = 0
 
 
 class Resample(torch.nn.Module):
@@ -1954,6 +2139,51 @@ class TextAligner(HipModule):
         front._engine = eng
         rows, seg = front.packed(wave, Ls, frames="drop_last", mean=mel_stats[0], std=mel_stats[1])
         return self._align_rows(eng.text_aligner(seg, rows), seg, toks, PL)
+
+    def _score_rows(self, lp, seg, toks, PL, loss):
+        """One ctc_align, one ctc_nll, one confidence launch on the log-prob rows, one host read."""
+        eng = self.engine
+        seg_p = Segments(PL, eng.device)
+        tg = torch.tensor([v for tk in toks for v in tk], dtype=torch.int32, device=eng.device)
+        r = eng.ctc_align(seg, lp, seg_p, tg, self.blank)
+        if loss is not None and loss.blank != self.blank:
+            raise ValueError(f"the loss has blank {loss.blank}, the aligner {self.blank}")
+        nll = eng.ctc_nll(seg, lp, seg_p, tg, self.blank)  # step_type "eval": no label priors
+        conf = eng.ctc_confidence_sums(seg, r["scores"])
+        host = torch.cat([nll, conf]).cpu().tolist()  # the one host read
+        B = seg.n
+        nll_utt, conf_sum = host[:B], host[B:]
+        return dict(align_loss=align_loss_value(nll_utt, seg.lengths, PL, loss), nll_utt=nll_utt, confidence=sum(conf_sum) / float(seg.rows),
+                    confidence_utt=[conf_sum[b] / float(seg.lengths[b]) for b in range(B)])
+
+    def alignment_scores(self, mels, mel_lengths, texts, text_lengths, loss: Optional["CTCLossWithLabelPriors"] = None):
+        """What validate_alignment logs about a batch (train/stage_type.py:79-111) and align_text's per-file score (align_text.py:155): mels
+        [B, T, n_mels] normalised log-mel, texts [B, P] -> dict of Python numbers:
+          align_loss      the loss' "eval" value: ``loss.reduction`` and pairing over the fp32 per-utterance values (default: "mean", every
+                          utterance with its own token count)
+          nll_utt         every utterance's CTC negative log-likelihood (float64, exact over all paths)
+          confidence      the total of exp(scores) over the total number of frames, scores the Viterbi path's log-probs
+          confidence_utt  every utterance's mean of exp(scores): the number a dataset is filtered by
+        One aligner forward, one ctc_align, one ctc_nll, one confidence launch, one host read."""
+        L = self._lengths(mels, mel_lengths)
+        toks, PL = self._check_texts(L, texts, text_lengths)
+        lp, seg = self.packed(mels, L)
+        return self._score_rows(lp, seg, toks, PL, loss)
+
+    def alignment_scores_audio(self, wave, sample_lengths, texts, text_lengths, loss: Optional["CTCLossWithLabelPriors"] = None, mel_stats=(-4.0, 4.0),
+                               front: Optional["LogMelSpectrogram"] = None):
+        """alignment_scores() from recordings, through the front end of align_audio."""
+        if front is None:
+            front = LogMelSpectrogram.from_config(self.cfg, self.n_mels, mean=mel_stats[0], std=mel_stats[1], frames="drop_last")
+        if front.n_mels != self.n_mels:
+            raise ValueError(f"the front end has {front.n_mels} mel bins, the aligner takes {self.n_mels}")
+        Ls = front._lengths(wave, sample_lengths)
+        L = front.frame_counts(Ls, "drop_last")
+        toks, PL = self._check_texts(L, texts, text_lengths)
+        eng = self.engine
+        front._engine = eng
+        rows, seg = front.packed(wave, Ls, frames="drop_last", mean=mel_stats[0], std=mel_stats[1])
+        return self._score_rows(eng.text_aligner(seg, rows), seg, toks, PL, loss)
 
 
 def build_inference_modules(cfg=None, engine=None, synthetic_seed: Optional[int] = None, hubert: bool = False, mel_style: bool = False,

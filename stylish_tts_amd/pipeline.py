@@ -436,8 +436,42 @@ def _curve_pair(pair, what):
     return a, b, La
 
 
+def _value_pair(pair, what):
+    """(predicted, target) tensors [B, ...] or lists of tensors of any shape -> (list of 1-D predicted, list of 1-D target, their sizes)."""
+    if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+        raise ValueError(f"{what} must be a pair (predicted, target)")
+    out = []
+    for x in pair:
+        if isinstance(x, (list, tuple)):
+            out.append([torch.as_tensor(v).reshape(-1) for v in x])
+        else:
+            x = torch.as_tensor(x)
+            out.append([x.reshape(-1)] if x.dim() < 2 else [x[b].reshape(-1) for b in range(x.shape[0])])
+    La, Lb = [int(v.numel()) for v in out[0]], [int(v.numel()) for v in out[1]]
+    if La != Lb or not La or min(La) < 1:
+        raise ValueError(f"{what}: the predictions have {La} values, the targets {Lb}")
+    return out[0], out[1], La
+
+
 @torch.no_grad()
-def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, prediction=None, pitch=None, energy=None, slm=None) -> dict:
+def duration_scores(engine: HipModel, logits, alignment_or_durations, text_lengths, weight) -> dict:
+    """What validate_duration logs (train/stage_type.py:514-520): logits [B, P, C] of the duration predictor, the batch's 0/1 alignment [B, P, T] or
+    its durations [B, P] in frames, text_lengths [B], weight [C] the class weights of DurationLoss -> dict(duration_ce, duration,
+    duration_ce_utt, duration_utt) of Python numbers: DurationLoss.forward's two values and every utterance's own, from the fp64 sums of one
+    launch, read from the device once."""
+    from .modules import DurationLoss, DurationProcessor
+
+    logits, x = torch.as_tensor(logits), torch.as_tensor(alignment_or_durations)
+    if logits.dim() != 3 or x.dim() not in (2, 3) or x.shape[:2] != logits.shape[:2]:
+        raise ValueError(f"logits {tuple(logits.shape)} [B, P, C] do not fit an alignment [B, P, T] / durations [B, P] of shape {tuple(x.shape)}")
+    proc = DurationProcessor(logits.shape[2], 50)
+    classes = proc.align_to_class(x.cpu()) if x.dim() == 3 else proc.dur_to_class(x.cpu())
+    return DurationLoss(class_count=logits.shape[2], weight=weight, engine=engine).scores(logits, classes, text_lengths)
+
+
+@torch.no_grad()
+def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, prediction=None, pitch=None, energy=None, slm=None, mel_l2=None, normed_pitch_l2=None,
+                      linear_pitch=None) -> dict:
     """What the reference's validate_* functions log about a batch (train/stage_type.py), on the engine's fused kernels (nothing is materialised):
     audio / audio_gt: the synthesised waveforms and the recordings, [B, samples], [B, 1, samples] or lists of 1-D tensors (``lengths`` [B] cuts a
     padded batch).  -> dict of Python numbers, read from the device once:
@@ -452,6 +486,9 @@ def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, predictio
                  NormalizingFlowLoss (the values of ``modules.NormalizingFlowLoss.scores``); kl_text_utt / kl_audio_utt every utterance's own value
       slm        with ``slm``: a modules.WavLMLoss - the mean absolute difference of WavLM's hidden states of the recordings and the synthesised
                  waveforms (the value of ``slm(audio_gt, audio)``, bit for bit); slm_utt every utterance's own value
+      mel_l2, normed_pitch_l2, linear_pitch  with the pair (predicted, target) given under that name (tensors [B, ...] or lists of tensors): what
+                 validate_cfm_mel / validate_cfm_pitch log, F.mse_loss (the two *_l2) and F.l1_loss (linear_pitch) over the batch, from fp64 sums;
+                 <name>_utt every utterance's own mean
     ValueError naming the utterance whose lengths do not agree, or the geometry rule a length breaks."""
     from .modules import MagPhaseLoss, _magphase_sums, _pack_waves, _wave_batch, flow_kl_score, flow_kl_sums, has_flow_stats, magphase_score, mel_score
 
@@ -492,6 +529,12 @@ def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, predictio
         slm.wavlm._engine = slm.wavlm._engine or eng
         s_sums, s_fr = slm.sums(gw, pw)  # [B, states] float64, [B] int32
         parts += [s_sums, s_fr.to(torch.float64)]
+    diffs = []
+    for name, pair, kind in (("mel_l2", mel_l2, "l2"), ("normed_pitch_l2", normed_pitch_l2, "l2"), ("linear_pitch", linear_pitch, "l1")):
+        if pair is not None:
+            a, b, L = _value_pair(pair, name)
+            diffs.append((name, L, eng.diff_sums(Segments(L, eng.device), _pack_waves(eng, a), _pack_waves(eng, b), kind)))  # [len(L)]
+    parts += [d[2] for d in diffs]  # behind everything else: the offsets of the other parts stay where they were
     host = torch.cat([p.reshape(-1) for p in parts]).cpu().tolist()  # the one host read
     at = 2 * R * B
     mel, mel_r, mel_utt = mel_score([[host[2 * (r * B + u) : 2 * (r * B + u) + 2] for u in range(B)] for r in range(R)])
@@ -517,4 +560,11 @@ def validation_scores(engine: HipModel, audio, audio_gt, lengths=None, predictio
         ns = slm.wavlm.n_states
         fr = [int(v) for v in host[at + ns * B : at + ns * B + B]]
         out["slm"], out["slm_utt"] = wavlm.score([host[at + ns * u : at + ns * u + ns] for u in range(B)], fr, slm.wavlm.hidden)
+    at = len(host) - sum(len(L) for _, L, _ in diffs)
+    for name, L, _ in diffs:
+        tot = 0.0
+        for v in host[at : at + len(L)]:
+            tot += v
+        out[name], out[name + "_utt"] = tot / sum(L), [v / n for v, n in zip(host[at : at + len(L)], L)]
+        at += len(L)
     return out

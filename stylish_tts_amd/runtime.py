@@ -1129,3 +1129,87 @@ class HipModel:
                                            int(blank), _ptr(tg), 1 if given else 0, _ptr(p), _ptr(out["scores"]), _ptr(out["durations"]), _ptr(out["left"]),
                                            _ptr(out["right"]), _ptr(ws), 0 if ws is None else ws.numel()))
         return out
+
+    def _log_prob_rows(self, seg_t: Segments, log_probs: torch.Tensor, classes: Optional[int]):
+        lp = log_probs.to(self.device, torch.float32).contiguous()
+        if lp.dim() != 2 or lp.shape[0] != seg_t.rows:
+            raise ValueError(f"log-probs of shape {tuple(lp.shape)}, the offsets describe {seg_t.rows} frames")
+        V = lp.shape[1] if classes is None else int(classes)
+        if not 1 <= V <= lp.shape[1]:
+            raise ValueError(f"{V} classes in rows of {lp.shape[1]}")
+        return lp, V
+
+    def ctc_nll(self, seg_t: Segments, log_probs: torch.Tensor, seg_p: Segments, targets: torch.Tensor, blank: int, log_priors: Optional[torch.Tensor] = None,
+                prior_scale: float = 0.0, classes: Optional[int] = None) -> torch.Tensor:
+        """[B] float64 on the device: every utterance's CTC negative log-likelihood, the exact sum over all paths in fp64 (include/stylish_hip.h,
+        stts_ctc_nll); +inf where no path exists.  log_probs [sum T, ld] with frame offsets seg_t (``classes`` <= ld columns count, default all),
+        targets [sum P] with token offsets seg_p.  ``log_priors`` [classes]: every emission is log_probs - prior_scale * log_priors.  Nothing is
+        read back by the host."""
+        if seg_t.n != seg_p.n:
+            raise ValueError(f"{seg_t.n} utterances of frames but {seg_p.n} of tokens")
+        lp, V = self._log_prob_rows(seg_t, log_probs, classes)
+        tg = targets.to(self.device, torch.int32).contiguous()
+        if tg.dim() != 1 or tg.numel() != seg_p.rows:
+            raise ValueError(f"{tg.numel()} targets, the offsets describe {seg_p.rows}")
+        pr = None
+        if log_priors is not None:
+            pr = log_priors.to(self.device, torch.float64).reshape(-1).contiguous()
+            if pr.numel() != V:
+                raise ValueError(f"{pr.numel()} label priors for {V} classes")
+        nll = torch.empty(seg_t.n, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.stts_ctc_nll(_stream(), seg_t.n, seg_t.host_ptr, _ptr(seg_t.dev), seg_p.host_ptr, _ptr(seg_p.dev), _ptr(lp), lp.shape[1], V, int(blank),
+                                         _ptr(tg), _ptr(pr), float(prior_scale), _ptr(nll)))
+        return nll
+
+    def ctc_confidence_sums(self, seg_t: Segments, scores: torch.Tensor) -> torch.Tensor:
+        """[B] float64 on the device: each utterance's sum of exp(scores[t]) over the path log-probs of ctc_align (include/stylish_hip.h,
+        stts_ctc_confidence_sums), added in a fixed order.  Nothing is read back by the host."""
+        sc = self._packed_wave(seg_t, scores, "scores")
+        sums = torch.empty(seg_t.n, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.stts_ctc_confidence_sums(_stream(), seg_t.n, seg_t.host_ptr, _ptr(seg_t.dev), _ptr(sc), _ptr(sums)))
+        return sums
+
+    def ctc_prior_sums(self, seg_t: Segments, log_probs: torch.Tensor, classes: Optional[int] = None) -> torch.Tensor:
+        """[classes] float64 on the device: logsumexp of every class over all frames of the batch (include/stylish_hip.h, stts_ctc_prior_sums):
+        chunk partials merged in chunk order.  Nothing is read back by the host."""
+        lp, V = self._log_prob_rows(seg_t, log_probs, classes)
+        need = int(self.lib.stts_ctc_prior_sums_workspace_bytes(seg_t.n, seg_t.host_ptr, V)) or 256  # 0: bad offsets - the entry point names them
+        ws = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+        out = torch.empty(V, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.stts_ctc_prior_sums(_stream(), seg_t.n, seg_t.host_ptr, _ptr(seg_t.dev), _ptr(lp), lp.shape[1], V, _ptr(out), _ptr(ws), ws.numel() * 8))
+        return out
+
+    def duration_sums(self, seg_p: Segments, logits: torch.Tensor, targets: torch.Tensor, weight: torch.Tensor, classes: Optional[int] = None) -> torch.Tensor:
+        """[B, 3] float64 on the device: the sums of DurationLoss / CDW_CCELoss over packed token rows logits [sum P, ld] (``classes`` <= min(ld, 64)
+        columns count, default all), targets [sum P] classes, weight [classes] (include/stylish_hip.h, stts_val_duration_sums).  Nothing is read
+        back by the host."""
+        lg = logits.to(self.device, torch.float32).contiguous()
+        if lg.dim() != 2 or lg.shape[0] != seg_p.rows:
+            raise ValueError(f"logits of shape {tuple(lg.shape)}, the offsets describe {seg_p.rows} tokens")
+        V = lg.shape[1] if classes is None else int(classes)
+        if not 2 <= V <= min(64, lg.shape[1]):
+            raise ValueError(f"{V} classes in rows of {lg.shape[1]}: 2 to 64 are built")
+        tg = targets.to(self.device, torch.int32).contiguous()
+        if tg.dim() != 1 or tg.numel() != seg_p.rows:
+            raise ValueError(f"{tg.numel()} targets, the offsets describe {seg_p.rows}")
+        w = weight.to(self.device, torch.float32).reshape(-1).contiguous()
+        if w.numel() != V:
+            raise ValueError(f"{w.numel()} class weights for {V} classes")
+        if min(seg_p.lengths) < 1:
+            raise ValueError(f"utterance {seg_p.lengths.index(min(seg_p.lengths))} has no tokens")
+        sums = torch.empty(seg_p.n, 3, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.stts_val_duration_sums(self.ctx, _stream(), seg_p.n, seg_p.host_ptr, _ptr(seg_p.dev), _ptr(lg), lg.shape[1], V, _ptr(tg), _ptr(w),
+                                                   _ptr(sums)))
+        return sums
+
+    def diff_sums(self, seg: Segments, a: torch.Tensor, b: torch.Tensor, kind: str) -> torch.Tensor:
+        """[B] float64 on the device: each utterance's sum of |a - b| (kind "l1") or (a - b)^2 (kind "l2") over the packed fp32 vectors a and b,
+        added in a fixed order (include/stylish_hip.h, stts_val_diff_sums).  The reference's l1_loss / mse_loss is sums.sum() / seg.rows."""
+        if kind not in ("l1", "l2"):
+            raise ValueError(f"kind must be 'l1' or 'l2', got {kind!r}")
+        a, b = self._packed_wave(seg, a, "vector a"), self._packed_wave(seg, b, "vector b")
+        if min(seg.lengths) < 1:
+            raise ValueError(f"utterance {seg.lengths.index(min(seg.lengths))} has no values")
+        sums = torch.empty(seg.n, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.stts_val_diff_sums(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(a), _ptr(b), 1 if kind == "l2" else 0, _ptr(sums)))
+        return sums
