@@ -396,6 +396,22 @@ int stts_rmvpe_mel(stts_ctx* ctx, void* stream, int n_utt, const int32_t* sample
                    const int32_t* mel_off_dev, const float* wave, const float* mel_basis, const int32_t* band, float* mel_out, int ld_mel, float* mel_lin);
 /* to_local_average_f0 of a salience [n_rows, ld >= 360] -> f0 [n_rows] (no weights needed) */
 int stts_rmvpe_decode(stts_ctx* ctx, void* stream, int64_t n_rows, const float* salience, int ld, float thred, float* f0_out);
+/* The same local average around a GIVEN centre bin per row (center [n_rows] int32 on the device, clamped to [0, 360)); f0 is 0 where the row's
+ * largest salience is below thred.  With center = the row's first argmax the result equals stts_rmvpe_decode's bit for bit. */
+int stts_rmvpe_decode_at(stts_ctx* ctx, void* stream, int64_t n_rows, const float* salience, int ld, const int32_t* center, float thred, float* f0_out);
+/* to_viterbi_f0 (rmvpe/utils.py:134-150): the best path through the 360 classes of every utterance's salience rows [off[u], off[u + 1]) (at least
+ * one frame each; no weights needed), one workgroup per utterance, fp64.  Objective: e[t][j] = log(s[t][j] / sum_j s[t][j] + eps), sum, quotient and
+ * log in fp64 (a NaN or negative salience counts as 0; a frame whose sum is 0 or not finite gets p = 0 everywhere); v[0][j] = e[0][j] +
+ * log(1 / 360 + eps); v[t][j] = e[t][j] + max_i (v[t - 1][i] + lt[i][j]); every argmax takes the lowest index among equals.  lt comes from the
+ * caller in band form, fp64 on the device: lt_band[j][k] = lt[j - 29 + k][j] for k < 59 (-inf where that predecessor does not exist), and lt_out =
+ * the one value of every lt[i][j] with |i - j| > 29.  A jump across the band is allowed at that cost: a state scans the rest of the row exactly when
+ * max_i v[t - 1][i] + lt_out reaches its band maximum, so the result is the optimum of the full 360 x 360 recursion.  Outputs (each may be null,
+ * not all): path_out [rows] int32, logp_out [n_utt] fp64 = the path's score, f0_out [rows] = stts_rmvpe_decode_at around the path.  An utterance's
+ * outputs are the same bit for bit alone and in any batch.  The stated deviation from the reference: it normalises and takes logs in fp32. */
+size_t stts_rmvpe_viterbi_workspace_bytes(int n_utt, const int32_t* off_host);
+int stts_rmvpe_viterbi(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* salience, int ld,
+                       const double* lt_band, double lt_out, double eps, float thred, int32_t* path_out, double* logp_out, float* f0_out, void* ws,
+                       size_t ws_bytes);
 /* F.interpolate(mode="linear", align_corners=True) of every utterance's curve from its frames (off_in) to the frames of off_out, on the device */
 int stts_rmvpe_resample(stts_ctx* ctx, void* stream, int n_utt, const int32_t* off_in_dev, const int32_t* off_out_host, const int32_t* off_out_dev,
                         const float* f0_in, float* f0_out);

@@ -234,6 +234,9 @@ SIGNATURES = {
     "stts_rmvpe_tap_floats": (_I64, [_P, _I, _P]),
     "stts_rmvpe_mel": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "stts_rmvpe_decode": (_I, [_P, _P, _I64, _P, _I, C.c_float, _P]),
+    "stts_rmvpe_decode_at": (_I, [_P, _P, _I64, _P, _I, _P, C.c_float, _P]),
+    "stts_rmvpe_viterbi_workspace_bytes": (_SZ, [_I, _P]),
+    "stts_rmvpe_viterbi": (_I, [_P, _P, _I, _P, _P, _P, _I, _P, C.c_double, C.c_double, C.c_float, _P, _P, _P, _P, _SZ]),
     "stts_rmvpe_resample": (_I, [_P, _P, _I, _P, _P, _P, _P, _P]),
     "stts_aligner_finalize": (_I, [_P, _P]),
     "stts_aligner_workspace_bytes": (_SZ, [_P, _I, _P]),

@@ -9,6 +9,7 @@
 #include "ssl.hip.h"
 #include "wavlm.hip.h"
 #include "rmvpe.hip.h"
+#include "rmvpe_viterbi.hip.h"
 #include "aligner.hip.h"
 #include "log_mel.hip.h"
 #include "resample.hip.h"
@@ -1021,6 +1022,43 @@ int stts_rmvpe_decode(stts_ctx* c, void* stream, int64_t n_rows, const float* sa
   hipLaunchKernelGGL(rv_decode_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, salience, ld, (long)n_rows, thred, f0_out);
   STTS_HIP(hipGetLastError());
   return 0;
+  API_END
+}
+
+int stts_rmvpe_decode_at(stts_ctx* c, void* stream, int64_t n_rows, const float* salience, int ld, const int32_t* center, float thred, float* f0_out) {
+  API_BEGIN
+  STTS_CHECK(c && n_rows > 0 && salience && center && f0_out && ld >= kRvClasses && std::isfinite(thred), "rmvpe_decode_at: bad argument");
+  STTS_HIP(hipSetDevice(c->device));
+  hipLaunchKernelGGL(rv_decode_at_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, salience, ld, (long)n_rows, center, thred, f0_out);
+  STTS_HIP(hipGetLastError());
+  return 0;
+  API_END
+}
+
+// at least one frame per utterance (the path search needs no padding, unlike the network)
+static int rmvpe_viterbi_check_offsets(int n_utt, const int32_t* off_host) {
+  STTS_CHECK(n_utt > 0 && off_host && off_host[0] == 0, "rmvpe_viterbi: bad frame offsets");
+  for (int u = 0; u < n_utt; ++u) STTS_CHECK(off_host[u + 1] > off_host[u], "rmvpe_viterbi: utterance %d has no frames", u);
+  return 0;
+}
+
+size_t stts_rmvpe_viterbi_workspace_bytes(int n_utt, const int32_t* off_host) {
+  if (rmvpe_viterbi_check_offsets(n_utt, off_host) != 0) return 0;
+  return rmvpe_viterbi_workspace_bytes(n_utt, off_host);
+}
+
+int stts_rmvpe_viterbi(stts_ctx* c, void* stream, int n_utt, const int32_t* off_host, const int32_t* off_dev, const float* salience, int ld, const double* lt_band,
+                       double lt_out, double eps, float thred, int32_t* path_out, double* logp_out, float* f0_out, void* ws, size_t ws_bytes) {
+  API_BEGIN
+  STTS_CHECK(c && off_dev && salience && ws && (path_out || logp_out || f0_out), "rmvpe_viterbi: null argument");
+  STTS_CHECK(lt_band, "rmvpe_viterbi: null transition table");
+  STTS_TRY(rmvpe_viterbi_check_offsets(n_utt, off_host));
+  STTS_CHECK(ld >= kRvClasses, "rmvpe_viterbi: ld %d < 360 classes", ld);
+  STTS_CHECK(std::isfinite(thred) && std::isfinite(lt_out) && eps > 0.0 && std::isfinite(eps), "rmvpe_viterbi: thred, lt_out and eps must be finite, eps positive");
+  STTS_CHECK((uintptr_t)ws % 16 == 0, "rmvpe_viterbi: the workspace must be 16-byte aligned");
+  STTS_HIP(hipSetDevice(c->device));
+  Arena a(ws, ws_bytes);
+  return rmvpe_viterbi((hipStream_t)stream, n_utt, off_host, off_dev, salience, ld, lt_band, lt_out, eps, thred, path_out, logp_out, f0_out, a);
   API_END
 }
 

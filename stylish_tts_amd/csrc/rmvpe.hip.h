@@ -190,6 +190,21 @@ __global__ void __launch_bounds__(256) STTS_NO_PK rv_crop_kernel(const float* __
   }
 }
 
+// The local average of to_local_average_f0 around the centre bin c (0 <= c < 360) of one salience row s, `best` the row's largest value: shared by the
+// argmax decode below and the decode around a given centre (rmvpe_viterbi.hip.h), which therefore agree bit for bit where the centres do.
+__device__ __forceinline__ float rv_local_average(const float* __restrict__ s, int c, float best, float thred) {
+  const int a = max(0, c - 4), b = min(kRvClasses, c + 5);
+  double ps = 0.0, wsum = 0.0;
+  for (int i = a; i < b; ++i) {
+    const float cents = (float)(20 * i) + 1997.3794084376191f;  // the reference's mapping is an fp32 tensor
+    ps += (double)s[i] * (double)cents;
+    wsum += (double)s[i];
+  }
+  const double cents = ps / (wsum + (wsum == 0.0 ? 1.0 : 0.0));
+  const float v = (float)(10.0 * exp2(cents / 1200.0));
+  return best < thred ? 0.f : v;
+}
+
 // to_local_average_f0: one wave per frame.  c = the first argmax bin; the salience-weighted mean of 20 i + 1997.379... cents over [c - 4, c + 5) clipped to
 // [0, 360); f0 = 10 * 2^(cents / 1200), 0 where the frame's maximum is below thred.  The nine-term sums and the power run in double (one lane).
 __global__ void __launch_bounds__(256) STTS_NO_PK rv_decode_kernel(const float* __restrict__ S, int ld, long rows, float thred, float* __restrict__ f0) {
@@ -217,16 +232,7 @@ __global__ void __launch_bounds__(256) STTS_NO_PK rv_decode_kernel(const float* 
   }
   if (lane != 0) return;
   if (bi >= kRvClasses) bi = 0;  // a row of NaNs
-  const int a = max(0, bi - 4), b = min(kRvClasses, bi + 5);
-  double ps = 0.0, wsum = 0.0;
-  for (int i = a; i < b; ++i) {
-    const float cents = (float)(20 * i) + 1997.3794084376191f;  // the reference's mapping is an fp32 tensor
-    ps += (double)s[i] * (double)cents;
-    wsum += (double)s[i];
-  }
-  const double cents = ps / (wsum + (wsum == 0.0 ? 1.0 : 0.0));
-  const float v = (float)(10.0 * exp2(cents / 1200.0));
-  f0[row] = best < thred ? 0.f : v;
+  f0[row] = rv_local_average(s, bi, best, thred);
 }
 
 // F.interpolate(mode="linear", align_corners=True) of every utterance's curve from its L frames to its n frames; positions in double

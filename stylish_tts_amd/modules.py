@@ -1914,31 +1914,73 @@ class RmvpePitchExtractor(HipModule):
         h, _ = eng.rmvpe(seg, self._pack_mel(mel, L), f0=False)
         return self._unpack(h, seg)
 
-    def decode(self, hidden, thred: float = 0.03, use_viterbi: bool = False):
-        """salience [B, T, 360] (or [T, 360]) -> f0 [B, T] in Hz, 0 on unvoiced frames."""
-        if use_viterbi:
-            raise NotImplementedError("RMVPE's Viterbi decoding is not built (its reference needs a sequence decoder whose parity is unpinned); use_viterbi=False is")
-        eng = self.engine
-        h = _f(hidden, eng.device)
-        if h.dim() not in (2, 3) or h.shape[-1] != 360:
-            raise ValueError(f"salience must be [B, T, 360], got shape {tuple(h.shape)}")
-        return eng.rmvpe_decode(h.reshape(-1, 360), thred).reshape(h.shape[:-1])
+    DECODERS = ("argmax", "viterbi")
 
-    def packed(self, mel, lengths=None, frames=None, thred: float = 0.03, return_segments: bool = False):
-        """Packed f0 rows [sum frames] on the device (100 frames / s, or resampled to ``frames`` per utterance), as the engine's stages take curves."""
+    @classmethod
+    def _decoder(cls, decoder: str, use_viterbi: bool = False) -> bool:
+        """True for decoder="viterbi".  The reference's own flag, use_viterbi=True, stays refused: it promises librosa's decoder, whose floating point
+        is not pinned here; the engine's exact Viterbi decode of the same objective is asked for by its own name, decoder="viterbi"."""
+        if use_viterbi:
+            raise NotImplementedError('use_viterbi=True (the reference\'s librosa decoder, bit parity unpinned) is not built; decoder="viterbi" is the '
+                                      "engine's exact Viterbi decode of the same objective")
+        if decoder not in cls.DECODERS:
+            raise ValueError(f"decoder must be one of {cls.DECODERS}, got {decoder!r}")
+        return decoder == "viterbi"
+
+    def decode(self, hidden, thred: float = 0.03, use_viterbi: bool = False, decoder: str = "argmax", lengths=None, return_path: bool = False):
+        """salience [B, T, 360] (or [T, 360]) -> f0 [B, T] in Hz, 0 on unvoiced frames.  decoder="viterbi": the objective of the reference's
+        to_viterbi_f0 solved exactly - the local average around the best path through the 360 classes (HipModel.rmvpe_viterbi), every utterance on its
+        own ``lengths`` frames (default: all T), zeros past them; return_path=True also returns the path [B, T] int32.  use_viterbi=True raises
+        NotImplementedError as before (_decoder)."""
+        viterbi = self._decoder(decoder, use_viterbi)
+        if hidden.dim() not in (2, 3) or hidden.shape[-1] != 360 or hidden.shape[-2] < 1:
+            raise ValueError(f"salience must be [B, T, 360], got shape {tuple(hidden.shape)}")
+        if not viterbi:
+            if lengths is not None or return_path:
+                raise ValueError('lengths and return_path belong to decoder="viterbi"')
+            eng = self.engine
+            h = _f(hidden, eng.device)
+            return eng.rmvpe_decode(h.reshape(-1, 360), thred).reshape(h.shape[:-1])
+        B, T = (1, hidden.shape[0]) if hidden.dim() == 2 else hidden.shape[:2]
+        L = [T] * B if lengths is None else [int(v) for v in torch.as_tensor(lengths).tolist()]
+        if len(L) != B or any(n < 1 or n > T for n in L):
+            raise ValueError(f"lengths {L} do not fit a batch of {B} x {T} frames (at least one frame each)")
+        eng = self.engine
+        h = _f(hidden, eng.device).reshape(B, T, 360)
+        seg = Segments(L, eng.device)
+        rows = h.reshape(-1, 360) if all(n == T for n in L) else torch.cat([h[b, : L[b]] for b in range(B)])
+        f0, path = eng.rmvpe_viterbi(seg, rows, thred, path=True)
+        f0, path = self._unpack(f0, seg), self._unpack(path, seg)
+        if hidden.dim() == 2:
+            f0, path = f0[0], path[0]
+        return (f0, path) if return_path else f0
+
+    def _viterbi_f0(self, seg: Segments, mel_rows, thred):
+        """The network's salience and the Viterbi decode at its 100 frames / s."""
+        eng = self.engine
+        h, _ = eng.rmvpe(seg, mel_rows, thred, f0=False)
+        return eng.rmvpe_viterbi(seg, h, thred)
+
+    def packed(self, mel, lengths=None, frames=None, thred: float = 0.03, return_segments: bool = False, decoder: str = "argmax"):
+        """Packed f0 rows [sum frames] on the device (100 frames / s, or resampled to ``frames`` per utterance), as the engine's stages take curves.
+        decoder="viterbi": the Viterbi decode of the salience (before any resampling)."""
+        use_viterbi = self._decoder(decoder)
         L = self._mel_lengths(mel, lengths)
         Fr = self._frames(frames, len(L))
         eng = self.engine
         seg = Segments(L, eng.device)
-        _, f0 = eng.rmvpe(seg, self._pack_mel(mel, L), thred, hidden=False)
+        if use_viterbi:
+            f0 = self._viterbi_f0(seg, self._pack_mel(mel, L), thred)
+        else:
+            _, f0 = eng.rmvpe(seg, self._pack_mel(mel, L), thred, hidden=False)
         if Fr is not None:
             seg_o = Segments(Fr, eng.device)
             f0, seg = eng.rmvpe_resample(seg, f0, seg_o), seg_o
         return (f0, seg) if return_segments else f0
 
-    def forward(self, mel, lengths=None, frames=None, thred: float = 0.03):
+    def forward(self, mel, lengths=None, frames=None, thred: float = 0.03, decoder: str = "argmax"):
         """mel [B, 128, T] -> f0 [B, T] (or [B, max frames] after the linear resampling to ``frames``)."""
-        f0, seg = self.packed(mel, lengths, frames, thred, return_segments=True)
+        f0, seg = self.packed(mel, lengths, frames, thred, return_segments=True, decoder=decoder)
         return self._unpack(f0, seg)
 
     RESAMPLE_WIDTH = 128  # the lowpass_filter_width of the reference's resampler (inference.py:55-57)
@@ -1985,10 +2027,12 @@ class RmvpePitchExtractor(HipModule):
         return self._unpack(rows, seg).transpose(1, 2).contiguous()
 
     def packed_from_audio(self, wave, sample_lengths=None, frames=None, thred: Optional[float] = None, sample_rate: int = 16000, return_segments: bool = False,
-                          resample: bool = False):
+                          resample: bool = False, decoder: str = "argmax"):
         """Packed f0 rows [sum frames] on the device from audio [B, samples] at 16 kHz (resample=True: at ``sample_rate``, converted on the engine
-        first); thred None: ``self.thred``."""
+        first); thred None: ``self.thred``.  decoder="viterbi": the Viterbi decode of the salience (before any resampling to ``frames``)."""
         from . import rmvpe
+
+        use_viterbi = self._decoder(decoder)
 
         thred = self.thred if thred is None else thred
 
@@ -1997,19 +2041,22 @@ class RmvpePitchExtractor(HipModule):
         rows, seg = self.mel_packed(wave, sample_lengths, sample_rate, resample=resample)
         Fr = self._frames(frames, seg.n)
         eng = self.engine
-        _, f0 = eng.rmvpe(seg, rows, thred, hidden=False)
+        if use_viterbi:
+            f0 = self._viterbi_f0(seg, rows, thred)
+        else:
+            _, f0 = eng.rmvpe(seg, rows, thred, hidden=False)
         if Fr is not None:
             seg_o = Segments(Fr, eng.device)
             f0, seg = eng.rmvpe_resample(seg, f0, seg_o), seg_o
         return (f0, seg) if return_segments else f0
 
     def infer_from_audio(self, wave16k, sample_lengths=None, frames=None, thred: float = 0.03, sample_rate: int = 16000, use_viterbi: bool = False,
-                         resample: bool = False):
+                         resample: bool = False, decoder: str = "argmax"):
         """wave [B, samples] at 16 kHz -> f0 [B, T] (T = samples // 160 + 1, or ``frames`` after the linear resampling).  resample=True with another
-        ``sample_rate`` is the reference's infer_from_audio: its width-128 resampler to 16 kHz runs first."""
-        if use_viterbi:
-            raise NotImplementedError("RMVPE's Viterbi decoding is not built; use_viterbi=False is")
-        f0, seg = self.packed_from_audio(wave16k, sample_lengths, frames, thred, sample_rate, return_segments=True, resample=resample)
+        ``sample_rate`` is the reference's infer_from_audio: its width-128 resampler to 16 kHz runs first.  decoder="viterbi": the Viterbi decode;
+        use_viterbi=True raises NotImplementedError as before (_decoder)."""
+        self._decoder(decoder, use_viterbi)
+        f0, seg = self.packed_from_audio(wave16k, sample_lengths, frames, thred, sample_rate, return_segments=True, resample=resample, decoder=decoder)
         return self._unpack(f0, seg)
 
 

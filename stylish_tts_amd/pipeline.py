@@ -373,14 +373,15 @@ class VoiceConverter:
         return waves
 
     @torch.no_grad()
-    def convert_audio(self, wave, sample_lengths, frames, spk_emb, ssl=None, pitch_extractor=None, sample_rate=None, **kw):
+    def convert_audio(self, wave, sample_lengths, frames, spk_emb, ssl=None, pitch_extractor=None, sample_rate=None, decoder: str = "argmax", **kw):
         """Voice conversion from audio: wave [B, samples] at hubert.sr (zero padded past sample_lengths[b]), frames [B] = the mel-frame count
         of every utterance (the reference's time_dim; an argument, so the host reads nothing back) -> HuBERT features on the engine
         (``ssl``: the modules.AdaptiveHubert bound to this engine, or the one among this converter's modules) written as the packed rows
         convert() consumes, then convert() with the same keywords (pitch, energy, noise, ref_mel, ref_wave, energy_wave, ...).
         pitch_extractor (a modules.RmvpePitchExtractor; the audio must be at its 16 kHz): the source's own F0 is extracted on the engine and
         resampled to ``frames``.  Without ref_mel it becomes the pitch (energy from HubertPitchEnergyPredictor unless given); with ref_mel it
-        gives the voicing flags uv = (f0 == 0), formed on the device, unless uv is given.  The host reads nothing back.
+        gives the voicing flags uv = (f0 == 0), formed on the device, unless uv is given.  The host reads nothing back.  decoder="viterbi": that F0
+        is the extractor's Viterbi decode (the objective of to_viterbi_f0: no one-frame octave jumps), found at its 100 frames / s before the resampling.
         sample_rate: the rate of ``wave`` where it is not hubert.sr.  The content encoder then gets torchaudio's default (width-6) resampling of it
         and the pitch extractor the reference's width-128 one, each from the original recording, on the engine.  At the model's sample rate the
         same ``wave`` may also be passed as ref_wave / energy_wave: one recording in, at one rate."""
@@ -404,10 +405,11 @@ class VoiceConverter:
         feats = ssl.packed(wave, T, sample_lengths) if sample_rate is None else ssl.packed(wave, T, sample_lengths, sample_rate=int(sample_rate))
         if pitch_extractor is not None:
             pitch_extractor._engine = pitch_extractor._engine or self.eng
+            vk = {} if decoder == "argmax" else dict(decoder=decoder)  # the default call stays what it was
             if sample_rate is None:
-                f0 = pitch_extractor.packed_from_audio(wave, sample_lengths, T)
+                f0 = pitch_extractor.packed_from_audio(wave, sample_lengths, T, **vk)
             else:
-                f0 = pitch_extractor.packed_from_audio(wave, sample_lengths, T, sample_rate=int(sample_rate), resample=True)
+                f0 = pitch_extractor.packed_from_audio(wave, sample_lengths, T, sample_rate=int(sample_rate), resample=True, **vk)
             if kw.get("ref_mel") is not None or kw.get("ref_wave") is not None:
                 if kw.get("uv") is None:
                     kw["_packed_uv"] = (f0 == 0).to(torch.float32)

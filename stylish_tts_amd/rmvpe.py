@@ -66,6 +66,36 @@ def mel_frames(samples: int) -> int:
     return samples // HOP + 1
 
 
+# ------------------------------------------------------------------------------------------------ Viterbi decoding (rmvpe/utils.py:134-150)
+VITERBI_BAND = 29          # max(30 - |i - j|, 0) is nonzero for |i - j| <= 29
+VITERBI_EPS = 2.0 ** -126  # the smallest normal fp32: what the reference's sequence decoder adds inside every logarithm of an fp32 input
+_VITERBI_TABLES = None
+
+
+def viterbi_transition() -> np.ndarray:
+    """[360, 360] float64: lt[i][j] = log(A[i][j] + eps), A = w / w.sum(axis=1) with w[i][j] = max(30 - |i - j|, 0) (to_viterbi_f0's transition)."""
+    idx = np.arange(N_CLASS)
+    w = np.maximum(30 - np.abs(idx[:, None] - idx[None, :]), 0).astype(np.float64)
+    return np.log(w / w.sum(axis=1, keepdims=True) + VITERBI_EPS)
+
+
+def viterbi_tables():
+    """(lt_band [360, 59] float64, lt_out, eps): the transition log-probabilities in the form stts_rmvpe_viterbi reads.  lt_band[j][k] =
+    lt[j - 29 + k][j], -inf where that predecessor does not exist; lt_out = log(eps), the value of every lt[i][j] outside the band.  Built once."""
+    global _VITERBI_TABLES
+    if _VITERBI_TABLES is None:
+        lt = viterbi_transition()
+        band = np.full((N_CLASS, 2 * VITERBI_BAND + 1), -np.inf, np.float64)
+        for j in range(N_CLASS):
+            lo, hi = max(0, j - VITERBI_BAND), min(N_CLASS, j + VITERBI_BAND + 1)
+            band[j, lo - (j - VITERBI_BAND) : hi - (j - VITERBI_BAND)] = lt[lo:hi, j]
+        band.setflags(write=False)
+        out = float(lt[0, N_CLASS - 1])  # read from the matrix itself: the same bits as every other out-of-band entry
+        assert (lt[np.abs(np.arange(N_CLASS)[:, None] - np.arange(N_CLASS)[None, :]) > VITERBI_BAND] == out).all()
+        _VITERBI_TABLES = (band, out, VITERBI_EPS)
+    return _VITERBI_TABLES
+
+
 # ------------------------------------------------------------------------------------------------ mel filter bank
 def _hz_to_mel_htk(f):
     return 2595.0 * np.log10(1.0 + np.asarray(f, np.float64) / 700.0)

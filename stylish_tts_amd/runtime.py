@@ -105,6 +105,8 @@ class HipModel:
         self._cpws: Dict[int, torch.Tensor] = {}
         self._sslws: Dict[int, torch.Tensor] = {}
         self._rvws: Dict[int, torch.Tensor] = {}
+        self._rvvws: Dict[int, torch.Tensor] = {}
+        self._rv_lt = None  # the Viterbi decode's transition table on this device
         self._alws: Dict[int, torch.Tensor] = {}
         self._ctcws: Dict[int, torch.Tensor] = {}
         self._ws_lock = threading.Lock()
@@ -870,14 +872,43 @@ class HipModel:
                                            _ptr(band), _ptr(out), 128, _ptr(lin)))
         return (out, seg_m, lin) if linear else (out, seg_m)
 
-    def rmvpe_decode(self, salience: torch.Tensor, thred: float = 0.03) -> torch.Tensor:
-        """salience [rows, 360] -> f0 [rows] in Hz (to_local_average_f0; include/stylish_hip.h, stts_rmvpe_decode)."""
+    def rmvpe_decode(self, salience: torch.Tensor, thred: float = 0.03, center: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """salience [rows, 360] -> f0 [rows] in Hz (to_local_average_f0; include/stylish_hip.h, stts_rmvpe_decode).  ``center`` [rows] int: the local
+        average around these bins, not around every row's argmax (stts_rmvpe_decode_at)."""
         s = salience.to(self.device, torch.float32).contiguous()
         if s.dim() != 2 or s.shape[1] != 360 or s.shape[0] < 1:
             raise ValueError(f"salience must be [rows, 360], got shape {tuple(s.shape)}")
         out = self._f32(s.shape[0])
-        _lib.check(self.lib.stts_rmvpe_decode(self.ctx, _stream(), s.shape[0], _ptr(s), 360, float(thred), _ptr(out)))
+        if center is None:
+            _lib.check(self.lib.stts_rmvpe_decode(self.ctx, _stream(), s.shape[0], _ptr(s), 360, float(thred), _ptr(out)))
+            return out
+        c = center.to(self.device, torch.int32).contiguous()
+        if c.dim() != 1 or c.numel() != s.shape[0]:
+            raise ValueError(f"{c.numel()} centres for {s.shape[0]} rows")
+        _lib.check(self.lib.stts_rmvpe_decode_at(self.ctx, _stream(), s.shape[0], _ptr(s), 360, _ptr(c), float(thred), _ptr(out)))
         return out
+
+    def rmvpe_viterbi(self, seg: Segments, salience: torch.Tensor, thred: float = 0.03, path: bool = False, logp: bool = False):
+        """to_viterbi_f0 on the device (include/stylish_hip.h, stts_rmvpe_viterbi): salience [rows, 360] packed rows with frame offsets seg (at least one
+        frame each) -> f0 [rows] in Hz around the best path through the 360 classes; path=True / logp=True append the path [rows] int32 and its score
+        [B] float64.  Nothing is read back by the host."""
+        from . import rmvpe
+
+        s = salience.to(self.device, torch.float32).contiguous()
+        if s.dim() != 2 or s.shape[1] != 360 or s.shape[0] != seg.rows:
+            raise ValueError(f"salience of shape {tuple(s.shape)}, the offsets describe {seg.rows} rows of 360 classes")
+        band, lt_out, eps = rmvpe.viterbi_tables()
+        if self._rv_lt is None:
+            self._rv_lt = torch.from_numpy(band.copy()).to(self.device)
+        need = int(self.lib.stts_rmvpe_viterbi_workspace_bytes(seg.n, seg.host_ptr)) or 256  # 0: an empty utterance - the entry point names it
+        ws = self._grow(self._rvvws, need)
+        f0 = self._f32(seg.rows)
+        p = torch.empty(seg.rows, dtype=torch.int32, device=self.device) if path else None
+        lp = torch.empty(seg.n, dtype=torch.float64, device=self.device) if logp else None
+        _lib.check(self.lib.stts_rmvpe_viterbi(self.ctx, _stream(), seg.n, seg.host_ptr, _ptr(seg.dev), _ptr(s), 360, _ptr(self._rv_lt), lt_out, eps, float(thred),
+                                               _ptr(p), _ptr(lp), _ptr(f0), _ptr(ws), ws.numel()))
+        out = (f0,) + ((p,) if path else ()) + ((lp,) if logp else ())
+        return out[0] if len(out) == 1 else out
 
     def rmvpe_resample(self, seg_in: Segments, f0: torch.Tensor, seg_out: Segments) -> torch.Tensor:
         """Packed curves at seg_in's frames -> packed curves at seg_out's frames, linear with align_corners=True, on the device."""
